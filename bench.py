@@ -9,10 +9,13 @@ point, computed in FP64 by the hand-written HIP kernels behind the C ABI
 HBM before the timed region; the timed region is kernel launch(es) + (N > 1) the RCCL
 all-gather that assembles the grid on every rank.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.  `value` = grid points of the full grid / step time (whole job).
+Prints ONE JSON line on rank 0.  `value` = grid points of the full grid / step time (whole job).  A plain run sets up,
+warms up, times the K steps and prints the line; --full adds what takes work of its own: the oracle spot check
+(`selfcheck`), the roofline figures, the one-shot API timings (`oneshot`) and the CPU baseline (`cpu_baseline`).
+--dump-outputs DIR writes the grids of the last timed step to DIR (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -40,14 +43,20 @@ FP64_VALU_PEAK_TFLOPS = 78.6   # 256 CU x 4 SIMD x 16 lanes x 2 x 2.4 GHz (no MF
 # image list needs 3 subtractions + |d|^2 = 8 flops per pair; SURVEY's 47 is the reference's brute-force routine
 # (two 3x3 mat-vecs + wrap) and is only reported alongside for continuity with round 1.
 PREWARM_STEPS = 3          # untimed launches of the set-up phase (clock ramp-up), in addition to --warmup
+DUMP_POINTS = 1 << 19      # grid points per grid written by --dump-outputs: 8 channels x 2^19 x 4 B = 16 MiB per grid
+DUMP_SEED = 1234           # the sample of a larger grid is the same from run to run and from build to build
 F_DIST, F_DIST_SURVEY, F_LJ, F_BUCK, F_EWALD = 8.0, 47.0, 50.0, 95.0, 140.0
 
 
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
+    ap.add_argument("--warmup", type=int, default=2, help="untimed steps after the set-up phase's own")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the grids of the last timed step to DIR/<grid>.npy (float32) and their point indices to DIR/points.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: oracle spot check, roofline figures, one-shot API timings, CPU baseline")
     ap.add_argument("--mode", choices=("fused", "vdw", "coulomb"), default="fused")
     ap.add_argument("--probe", default="Ar", help="probe atom of the VdW grid (Ar: LJ; Na: Buckingham + hard sphere)")
     ap.add_argument("--algo", choices=("auto", "bruteforce", "culled"), default="auto")
@@ -59,15 +68,38 @@ def parse_args():
     ap.add_argument("--chunks", type=int, default=8,
                     help="x-chunks per rank pipelined with the all-gather (N > 1); 8 from the exchange model of profiles/r02_rank_emulation.txt")
     ap.add_argument("--n", "--dims", dest="n", type=int, default=255, help="dims per axis (odd); grid has (n+1)^3 points")
-    ap.add_argument("--cpu-rows", type=int, default=-1, help="y-rows per x-plane the CPU baseline times, one plane per thread (-1 = auto ~12 s, 0 = skip)")
-    ap.add_argument("--no-check", action="store_true", help="skip the built-in oracle spot check")
-    ap.add_argument("--no-oneshot", action="store_true", help="skip the one-shot API timings (N = 1: ceg_grid_vdw / ceg_grid_coulomb / ceg_grids_multi into host arrays)")
+    ap.add_argument("--cpu-rows", type=int, default=-1, help="--full: y-rows per x-plane the CPU baseline times, one plane per thread (-1 = auto ~12 s, 0 = skip)")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the built-in oracle spot check")
+    ap.add_argument("--no-oneshot", action="store_true", help="--full: skip the one-shot API timings (N = 1: ceg_grid_vdw / ceg_grid_coulomb / ceg_grids_multi into host arrays)")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="torch.distributed backend; gloo is a rehearsal aid: several ranks may then share one GPU "
                          "(device = LOCAL_RANK mod device count), which RCCL refuses")
     ap.add_argument("--force-exchange", action="store_true",
                     help="N = 1 only: run the N > 1 code path (RCCL group of one rank, chunked build, collectives issued) -- a rehearsal")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(dirpath, grids: dict) -> None:
+    """--dump-outputs: the [8, nx, ny, nz] float32 grids the timed path computed, as DIR/<name>.npy of shape [8, K] -- the values
+    at K grid points, the same K points for every grid -- and DIR/points.npy, their flat C-order indices into (nx, ny, nz) as
+    float64, ascending.  K = every point when the grid has at most DUMP_POINTS of them, else a sample of DUMP_POINTS points
+    drawn with DUMP_SEED (2 grids of 256^3: 38 MB in all)."""
+    shapes = {tuple(g.shape) for g in grids.values()}
+    assert len(shapes) == 1, shapes
+    npts = int(np.prod(shapes.pop()[1:]))
+    if npts <= DUMP_POINTS:
+        idx = np.arange(npts, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(npts, size=DUMP_POINTS, replace=False))
+    out = Path(dirpath)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, g in grids.items():
+        ti = torch.from_numpy(idx).to(g.device)
+        np.save(out / f"{name}.npy", g.reshape(8, -1)[:, ti].cpu().numpy().astype(np.float32, copy=False))
+    np.save(out / "points.npy", idx.astype(np.float64))
 
 
 # the sources that determine the instruction stream of the grid-build kernels (k_culled / k_bruteforce) and the tables they read:
@@ -479,10 +511,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kern_ms = float(t[0]), float(t[1])
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: t for k, t in (("vdw", full_v), ("coulomb", full_c)) if t is not None})
+
     # built-in spot check against the oracle (a block of this rank's result), after timing
     check = None
     selfcheck_failed = False
-    if not args.no_check and rank == 0:
+    if args.full and not args.no_check and rank == 0:
         from oracle import oracle as O
         from oracle.compare import compare_grids
         from ceg_hip import grids as G
@@ -532,48 +567,6 @@ def main():
         ms = elapsed / max(args.steps, 1) * 1e3
         value = npts / (ms * 1e-3)
         ngrids = int(need_v) + int(need_c)
-        # algorithmic (compulsory) HBM bytes per launch: 32 B per point per grid written + the
-        # image/atom table read once (32 B position+charge, 4 B kind)  -- SURVEY §8d
-        slab_pts = n_local * ny * nz
-        nlaunch = cyc.nchunks if cyc is not None else 1
-        alg_bytes = 32.0 * slab_pts * ngrids + 36.0 * max(plan.num_images, w.natoms)
-        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
-        # counted minimum work (exact on a sample of the grid points): in-cutoff pairs and, of those, the ones whose kind
-        # has a VdW rule for this probe -- Si/Al carry no Ar rule and do no VdW work
-        pw = W.count_pair_work(w)
-        n_in = pw["in_cutoff_per_point"]
-        n_vdw = pw["lj_per_point"] + pw["buckingham_per_point"] + pw["other_vdw_per_point"]
-        f_vdw = pw["lj_per_point"] * F_LJ + (pw["buckingham_per_point"] + pw["other_vdw_per_point"]) * F_BUCK
-        per_point = ((n_in if need_c else n_vdw) * F_DIST + (f_vdw if need_v else 0.0) + (n_in * F_EWALD if need_c else 0.0))
-        min_flops = slab_pts * per_point
-        survey_flops = slab_pts * 310.0 * ((F_DIST_SURVEY + F_LJ if need_v else 0.0) + (F_DIST_SURVEY + F_EWALD if need_c else 0.0)
-                                           - (F_DIST_SURVEY if (need_v and need_c) else 0.0))
-        nominal_tflops = min_flops / (kern_ms * 1e-3) / 1e12
-        # Executed work, convention-free: FP64 VALU instructions of one launch by class (rocprofv3 PMC passes of this very command,
-        # scripts/pmc.sh -> profiles/pmc_summary.json) -> flops = (ADD + MUL + TRANS + 2 FMA) x 64 lanes x measured lane
-        # utilisation.  The instruction counts of a launch are a property of (library, workload), not of the box or the run, so they
-        # may be divided by the kernel time measured HERE; the record is only used when it was taken on this library (sha256 of
-        # the kernel sources).  Everything that comes from that file sits under "pmc" with its provenance.
-        pmc_key = f"{args.mode}/{args.probe}/{args.n}/{world}"
-        pmc = load_pmc_record(pmc_key)
-        if pmc is None and world > 1:
-            # no profile of the N-rank run: the one-GPU record of the same workload, its per-launch totals scaled to this rank's
-            # share of the x-planes (every rank runs the same kernel on 1/N of the planes)
-            one = load_pmc_record(f"{args.mode}/{args.probe}/{args.n}/1")
-            if one:
-                share = n_local / float(nx)
-                for k in ("hbm_bytes_per_launch", "fp64_flops_per_launch", "fp64_insts_per_launch", "gpu_cycles_per_launch"):
-                    if k in one:
-                        one[k] = one[k] * share
-                one["scaled_from"] = f"{args.mode}/{args.probe}/{args.n}/1 x {share:.4f} (this rank's share of the x-planes; per STEP, i.e. over all its chunk launches)"
-                one.pop("kernel_ms_in_profile", None)
-                pmc = one
-        traffic = pmc.get("hbm_bytes_per_launch") if pmc else None
-        exec_flops = pmc.get("fp64_flops_per_launch") if pmc else None
-        exec_tflops = exec_flops / (kern_ms * 1e-3) / 1e12 if exec_flops else None
-        frac_issue = pmc.get("frac_issue") if pmc else None
-        eff_clock = (pmc["gpu_cycles_per_launch"] / (pmc["kernel_ms_in_profile"] * 1e-3) / 1e9
-                     if pmc and pmc.get("gpu_cycles_per_launch") and pmc.get("kernel_ms_in_profile") else None)
         transport = "RCCL" if args.backend == "nccl" else "gloo (rehearsal)"
         out = {
             "metric": "grid-points/sec", "value": value, "unit": "grid-points/s",
@@ -584,50 +577,93 @@ def main():
                        "lattice_images": plan.num_images, "grids_per_step": ngrids, "mode": args.mode,
                        "algo": "culled" if (algo != _abi.ALGO_BRUTEFORCE and plan.can_cull) else "bruteforce",
                        "parallelism": (f"block-cyclic x-chunks over {world} GPUs ({cyc.nchunks} chunks of {cyc.m} planes per rank), each chunk all-gathered over {transport} ({gather_mode}) while the next is computed" if cyc is not None
-                                       else f"x-slab sharding over {world} GPU(s)" + (f", {transport} all-gather of slabs" if world > 1 else ""))},
+                                       else f"x-slab sharding over {world} GPU(s)" + (f", {transport} all-gather of slabs" if world > 1 else ""))}
+        }
+        if args.full:
+            # algorithmic (compulsory) HBM bytes per launch: 32 B per point per grid written + the
+            # image/atom table read once (32 B position+charge, 4 B kind)  -- SURVEY §8d
+            slab_pts = n_local * ny * nz
+            nlaunch = cyc.nchunks if cyc is not None else 1
+            alg_bytes = 32.0 * slab_pts * ngrids + 36.0 * max(plan.num_images, w.natoms)
+            achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+            # counted minimum work (exact on a sample of the grid points): in-cutoff pairs and, of those, the ones whose kind
+            # has a VdW rule for this probe -- Si/Al carry no Ar rule and do no VdW work
+            pw = W.count_pair_work(w)
+            n_in = pw["in_cutoff_per_point"]
+            n_vdw = pw["lj_per_point"] + pw["buckingham_per_point"] + pw["other_vdw_per_point"]
+            f_vdw = pw["lj_per_point"] * F_LJ + (pw["buckingham_per_point"] + pw["other_vdw_per_point"]) * F_BUCK
+            per_point = ((n_in if need_c else n_vdw) * F_DIST + (f_vdw if need_v else 0.0) + (n_in * F_EWALD if need_c else 0.0))
+            min_flops = slab_pts * per_point
+            survey_flops = slab_pts * 310.0 * ((F_DIST_SURVEY + F_LJ if need_v else 0.0) + (F_DIST_SURVEY + F_EWALD if need_c else 0.0)
+                                               - (F_DIST_SURVEY if (need_v and need_c) else 0.0))
+            nominal_tflops = min_flops / (kern_ms * 1e-3) / 1e12
+            # Executed work, convention-free: FP64 VALU instructions of one launch by class (rocprofv3 PMC passes of this very command,
+            # scripts/pmc.sh -> profiles/pmc_summary.json) -> flops = (ADD + MUL + TRANS + 2 FMA) x 64 lanes x measured lane
+            # utilisation.  The instruction counts of a launch are a property of (library, workload), not of the box or the run, so they
+            # may be divided by the kernel time measured HERE; the record is only used when it was taken on this library (sha256 of
+            # the kernel sources).  Everything that comes from that file sits under "pmc" with its provenance.
+            pmc_key = f"{args.mode}/{args.probe}/{args.n}/{world}"
+            pmc = load_pmc_record(pmc_key)
+            if pmc is None and world > 1:
+                # no profile of the N-rank run: the one-GPU record of the same workload, its per-launch totals scaled to this rank's
+                # share of the x-planes (every rank runs the same kernel on 1/N of the planes)
+                one = load_pmc_record(f"{args.mode}/{args.probe}/{args.n}/1")
+                if one:
+                    share = n_local / float(nx)
+                    for k in ("hbm_bytes_per_launch", "fp64_flops_per_launch", "fp64_insts_per_launch", "gpu_cycles_per_launch"):
+                        if k in one:
+                            one[k] = one[k] * share
+                    one["scaled_from"] = f"{args.mode}/{args.probe}/{args.n}/1 x {share:.4f} (this rank's share of the x-planes; per STEP, i.e. over all its chunk launches)"
+                    one.pop("kernel_ms_in_profile", None)
+                    pmc = one
+            traffic = pmc.get("hbm_bytes_per_launch") if pmc else None
+            exec_flops = pmc.get("fp64_flops_per_launch") if pmc else None
+            exec_tflops = exec_flops / (kern_ms * 1e-3) / 1e12 if exec_flops else None
+            frac_issue = pmc.get("frac_issue") if pmc else None
+            eff_clock = (pmc["gpu_cycles_per_launch"] / (pmc["kernel_ms_in_profile"] * 1e-3) / 1e9
+                         if pmc and pmc.get("gpu_cycles_per_launch") and pmc.get("kernel_ms_in_profile") else None)
             # neither HBM nor MFMA bounds this path (FP64 vector ALU does); `roofline` is the binding
             # one -- minimum-work flops / t against the FP64 vector peak -- and the HBM view sits alongside
-            "roofline": {"bound": "valu_fp64", "achieved": exec_tflops, "peak": FP64_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": (exec_tflops / FP64_VALU_PEAK_TFLOPS) if exec_tflops else None, "traffic": traffic,
-                         "frac_executed": (exec_tflops / FP64_VALU_PEAK_TFLOPS) if exec_tflops else None,
-                         "frac_stale": bool(pmc and pmc.get("stale")),
-                         "frac_issue": frac_issue,
-                         "frac_nominal": nominal_tflops / FP64_VALU_PEAK_TFLOPS,
-                         "kernel": f"k_culled<{args.mode}>" if plan.can_cull and algo != _abi.ALGO_BRUTEFORCE else f"k_bruteforce<{args.mode}>",
-                         "kernel_ms": kern_ms, "launches_per_step": nlaunch,
-                         "executed_fp64_flops_per_launch": exec_flops, "effective_clock_ghz_in_profile": eff_clock,
-                         "pmc": pmc,
-                         "nominal": {"achieved": nominal_tflops, "algorithmic_flops": min_flops,
-                                     "counted_work": dict(pw, flops_per_point=per_point, f_dist=F_DIST, f_lj=F_LJ, f_buckingham=F_BUCK, f_ewald=F_EWALD),
-                                     "frac_survey_convention": survey_flops / (kern_ms * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS,
-                                     "note": "counted minimum work in SURVEY 8d's nominal flops (LJ 50, Buckingham 95, Ewald 140 incl. exp = 20, "
-                                             "erfc = 40; distance from an image list 8): a work RATE for comparing algorithms, not a hardware "
-                                             "fraction -- the kernel evaluates r^2-indexed tables and executes far fewer flops per pair"},
-                         "pair_checks_per_s": slab_pts * float(w.natoms) / (kern_ms * 1e-3),
-                         "flops": "frac = frac_executed = executed FP64 flops of one launch (PMC: (ADD_F64 + MUL_F64 + TRANS_F64 + 2 FMA_F64) x 64 x "
-                                  "lane utilisation, instruction counts of THIS library on THIS workload from profiles/pmc_summary.json) / kernel "
-                                  "time measured in this run / peak; frac_issue = VALU issue utilisation x lane utilisation of the profiled "
-                                  "run (share of lane-issue slots doing work); frac_nominal = counted minimum work in nominal flops / time / peak "
-                                  "(round 2's headline; kept for continuity); peak = 256 CU x 4 SIMD x 16 lanes x 2 x 2.4 GHz "
-                                  "(FP64 MFMA has the same peak on MI355X; no MFMA is used)",
-                         "note": "the contract's bound enum is hbm|mfma; this path is an FP64 pairwise reduction bound by the vector ALU "
-                                 "(>= 1e3 flop per compulsory HBM byte), see roofline_hbm for the byte view"},
-            "roofline_hbm": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "algorithmic_bytes": alg_bytes,
-                             "measured_GBps": (traffic / (kern_ms * 1e-3) / 1e9) if traffic else None,
-                             "traffic_source": (pmc or {}).get("source"),
-                             "note": "algorithmic bytes (32 B/point/grid written once + 36 B/image) over the kernel time; ~1 % by construction; "
-                                     "measured_GBps = PMC traffic of the profiled run (WRITE_SIZE + 2 x FETCH_SIZE, profiles/pmc_summary.json) "
-                                     "over this run's kernel time"},
-            "selfcheck": check,
-        }
+            out["roofline"] = {"bound": "valu_fp64", "achieved": exec_tflops, "peak": FP64_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                               "frac": (exec_tflops / FP64_VALU_PEAK_TFLOPS) if exec_tflops else None, "traffic": traffic,
+                               "frac_executed": (exec_tflops / FP64_VALU_PEAK_TFLOPS) if exec_tflops else None,
+                               "frac_stale": bool(pmc and pmc.get("stale")),
+                               "frac_issue": frac_issue,
+                               "frac_nominal": nominal_tflops / FP64_VALU_PEAK_TFLOPS,
+                               "kernel": f"k_culled<{args.mode}>" if plan.can_cull and algo != _abi.ALGO_BRUTEFORCE else f"k_bruteforce<{args.mode}>",
+                               "kernel_ms": kern_ms, "launches_per_step": nlaunch,
+                               "executed_fp64_flops_per_launch": exec_flops, "effective_clock_ghz_in_profile": eff_clock,
+                               "pmc": pmc,
+                               "nominal": {"achieved": nominal_tflops, "algorithmic_flops": min_flops,
+                                           "counted_work": dict(pw, flops_per_point=per_point, f_dist=F_DIST, f_lj=F_LJ, f_buckingham=F_BUCK, f_ewald=F_EWALD),
+                                           "frac_survey_convention": survey_flops / (kern_ms * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS,
+                                           "note": "counted minimum work in SURVEY 8d's nominal flops (LJ 50, Buckingham 95, Ewald 140 incl. exp = 20, "
+                                                   "erfc = 40; distance from an image list 8): a work RATE for comparing algorithms, not a hardware "
+                                                   "fraction -- the kernel evaluates r^2-indexed tables and executes far fewer flops per pair"},
+                               "pair_checks_per_s": slab_pts * float(w.natoms) / (kern_ms * 1e-3),
+                               "flops": "frac = frac_executed = executed FP64 flops of one launch (PMC: (ADD_F64 + MUL_F64 + TRANS_F64 + 2 FMA_F64) x 64 x "
+                                        "lane utilisation, instruction counts of THIS library on THIS workload from profiles/pmc_summary.json) / kernel "
+                                        "time measured in this run / peak; frac_issue = VALU issue utilisation x lane utilisation of the profiled "
+                                        "run (share of lane-issue slots doing work); frac_nominal = counted minimum work in nominal flops / time / peak "
+                                        "(round 2's headline; kept for continuity); peak = 256 CU x 4 SIMD x 16 lanes x 2 x 2.4 GHz "
+                                        "(FP64 MFMA has the same peak on MI355X; no MFMA is used)",
+                               "note": "the contract's bound enum is hbm|mfma; this path is an FP64 pairwise reduction bound by the vector ALU "
+                                       "(>= 1e3 flop per compulsory HBM byte), see roofline_hbm for the byte view"}
+            out["roofline_hbm"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                   "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "algorithmic_bytes": alg_bytes,
+                                   "measured_GBps": (traffic / (kern_ms * 1e-3) / 1e9) if traffic else None,
+                                   "traffic_source": (pmc or {}).get("source"),
+                                   "note": "algorithmic bytes (32 B/point/grid written once + 36 B/image) over the kernel time; ~1 % by construction; "
+                                           "measured_GBps = PMC traffic of the profiled run (WRITE_SIZE + 2 x FETCH_SIZE, profiles/pmc_summary.json) "
+                                           "over this run's kernel time"}
+            out["selfcheck"] = check
         if multi:
             # gather time reported separately.  compute_ms = span of this rank's kernels
             # (max over ranks); what is left of the step is the part of the exchange that was not hidden
             out["exchange"] = {"compute_ms": kern_ms, "exposed_ms": max(0.0, ms - kern_ms),
                                "mode": gather_mode if (cyc is not None or fallback_reason) else "slab", "autotune_ms": autotune, "fallback_reason": fallback_reason,
                                "bytes_gathered_per_rank": 32.0 * npts * ngrids * (world - 1) / world, "backend": "nccl (RCCL over xGMI)" if args.backend == "nccl" else "gloo (rehearsal)"}
-        if world == 1 and not args.force_exchange and not args.no_oneshot:
+        if args.full and world == 1 and not args.force_exchange and not args.no_oneshot:
             # the timed buffers are no longer needed: give the one-shot pipelines the card (they keep their own device slab)
             del full_v, full_c, loc_v, loc_c, fulls, locs
             torch.cuda.empty_cache()
@@ -635,7 +671,7 @@ def main():
                 out["oneshot"] = oneshot_record(w)
             except Exception as exc:          # noqa: BLE001 -- a failure here must not cost the line
                 out["oneshot"] = {"error": repr(exc)}
-        if world == 1 and args.cpu_rows != 0:
+        if args.full and world == 1 and args.cpu_rows != 0:
             out["cpu_baseline"] = cpu_baseline(w, args.mode, args.cpu_rows)
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     plan.close()

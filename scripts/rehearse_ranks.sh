@@ -7,7 +7,7 @@ run() {   # nranks dims extra...
   n=$1; d=$2; shift 2
   port=$((port+1))
   out=$(timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $port \
-        bench.py --gpus $n --backend gloo --dims $d --steps 2 --warmup 1 --cpu-rows 0 "$@" 2>/dev/null | tail -1)
+        bench.py --full --gpus $n --backend gloo --dims $d --steps 2 --warmup 1 --cpu-rows 0 "$@" 2>/dev/null | tail -1)
   python - "$n" "$d" "$*" "$out" <<'PY'
 import sys, json
 n, d, extra, line = sys.argv[1:5]

@@ -6,7 +6,7 @@ for lib in crystalenergygrids.jl_amd/csrc/libceg_hip.so build_variants/*.so; do
   for mp in "$@"; do
     read -r mode probe <<< "$mp"; probe=${probe:-Ar}
     echo "== $lib $mode $probe"
-    CEG_HIP_LIB=$PWD/$lib timeout -k 10 300 python bench.py --steps 5 --warmup 2 --cpu-rows 0 --mode $mode --probe $probe 2>&1 | python -c "
+    CEG_HIP_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --cpu-rows 0 --mode $mode --probe $probe 2>&1 | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

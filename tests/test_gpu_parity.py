@@ -1040,7 +1040,7 @@ def test_image_list_built_on_the_device(hip_lib, monkeypatch, case):
 
 
 def test_bench_line_and_exchange_rehearsal(hip_lib):
-    """bench.py as the driver runs it: exactly ONE line on stdout, valid JSON with the contract's keys, the
+    """bench.py --full: exactly ONE line on stdout, valid JSON with the contract's keys, the
     roofline / cpu_baseline objects, and -- with --force-exchange -- the N > 1 code path (RCCL group, chunked
     build, collectives on the side stream) ending in a grid that passes the oracle spot check."""
     import json
@@ -1052,7 +1052,7 @@ def test_bench_line_and_exchange_rehearsal(hip_lib):
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
-        r = subprocess.run([sys.executable, str(root / "bench.py"), "--n", "63", "--steps", "2", "--warmup", "1", "--cpu-rows", "1"] + extra,
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--full", "--n", "63", "--steps", "2", "--warmup", "1", "--cpu-rows", "1"] + extra,
                            capture_output=True, text=True, timeout=600, env={**os.environ, "MASTER_PORT": str(port)})
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -1084,6 +1084,46 @@ def test_bench_line_and_exchange_rehearsal(hip_lib):
                     assert one[fn][route]["best_ms"] > 0 and len(one[fn][route]["ms"]) == one["reps"], (fn, route)
 
 
+def test_bench_plain_run_and_dumped_outputs(hip_lib, oracle, tmp_path):
+    """A plain bench.py run (no --full): ONE line with the contract's keys and none of what --full adds, `steps` timed steps;
+    --dump-outputs writes the grids of the last timed step -- at 64^3 every point -- which match the oracle, and a second run
+    with the same arguments writes the same values bit for bit."""
+    import json
+    import subprocess
+    import sys
+    root = Path(__file__).resolve().parent.parent
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--n", "63", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+            assert key in d, key
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+        assert d["value"] == pytest.approx(64 ** 3 / (d["ms_per_step"] * 1e-3))
+        assert not {"roofline", "roofline_hbm", "selfcheck", "oneshot", "cpu_baseline"} & set(d), sorted(d)
+        assert sorted(p.name for p in out.iterdir()) == ["coulomb.npy", "points.npy", "vdw.npy"]
+        dumps.append({n: np.load(out / f"{n}.npy") for n in ("vdw", "coulomb", "points")})
+    a, b = dumps
+    assert a["points"].dtype == np.float64 and np.array_equal(a["points"], np.arange(64 ** 3))
+    for name in ("vdw", "coulomb"):
+        assert a[name].dtype == np.float32 and a[name].shape == (8, 64 ** 3)
+        assert np.array_equal(a[name].view(np.int32), b[name].view(np.int32)), name
+    w = W.roofline_workload("Ar", 63)
+    scratch = np.empty((8, 64, 64, 64), dtype=np.float32)
+    for i0, i1 in ((0, 2), (31, 33), (62, 64)):
+        lam, thr = G.vdw_scaling()
+        ref, _ = oracle.grid_vdw(w.probe_vdw, w.cset, lam, thr, i0, i1, out=scratch)
+        compare_grids(a["vdw"].reshape(8, 64, 64, 64)[:, i0:i1], ref[:, i0:i1], f"dumped vdw planes {i0}:{i1}")
+        lam, thr = G.coulomb_scaling()
+        ref, _ = oracle.grid_coulomb(w.probe_coulomb, w.alpha, w.cset, lam, thr, i0, i1, out=scratch)
+        compare_grids(a["coulomb"].reshape(8, 64, 64, 64)[:, i0:i1], ref[:, i0:i1], f"dumped coulomb planes {i0}:{i1}")
+
+
 def test_bench_full_size_exchange_rehearsal(hip_lib):
     """The N > 1 code path of the benchmark AT THE BENCHMARK'S SIZE on one card: 256^3 x 11 664 atoms, the
     default 8 block-cyclic chunks of 32 planes, an RCCL group of one rank with the collectives forced on (side-stream
@@ -1098,7 +1138,7 @@ def test_bench_full_size_exchange_rehearsal(hip_lib):
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-rows", "0", "--force-exchange"],
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--cpu-rows", "0", "--force-exchange"],
                        capture_output=True, text=True, timeout=900, env={**os.environ, "MASTER_PORT": str(port)})
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip()][0])
@@ -1195,7 +1235,7 @@ def test_bench_two_and_three_ranks_on_one_gpu(hip_lib):
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nranks}", "--master-addr", "127.0.0.1",
-               "--master-port", str(port), str(root / "bench.py"), "--gpus", str(nranks), "--backend", "gloo", "--dims", str(dims),
+               "--master-port", str(port), str(root / "bench.py"), "--full", "--gpus", str(nranks), "--backend", "gloo", "--dims", str(dims),
                "--steps", "2", "--warmup", "1", "--cpu-rows", "0"] + (["--gather", "auto"] if mode == "staged" else [])
         # (--gather auto is opt-in since round 3; one of its candidates is made to raise: it must be skipped, not fatal.  "fallback": the
         #  pipelined exchange itself raises in its guarded first step -> contiguous slabs + one all-gather per channel, still a valid line)

@@ -423,6 +423,35 @@ def test_bench_cpu_baseline_leg(monkeypatch):
         assert "preallocated" in cb["sample"]
 
 
+def test_bench_dump_outputs_sample(tmp_path):
+    """bench.py --dump-outputs on a grid of more than DUMP_POINTS points: the same seeded sample of DUMP_POINTS distinct points for
+    every grid and every call, the values taken from those points, float32 values and float64 indices, within 64 MB at 256^3."""
+    import importlib.util
+    import torch
+    root = Path(__file__).resolve().parent.parent
+    spec = importlib.util.spec_from_file_location("bench_module", root / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    nx, ny, nz = 96, 90, 85
+    assert nx * ny * nz > bench.DUMP_POINTS
+    g = torch.arange(8 * nx * ny * nz, dtype=torch.float32).reshape(8, nx, ny, nz)
+    for sub in ("a", "b"):
+        bench.dump_outputs(tmp_path / sub, {"vdw": g, "coulomb": -g})
+    names = ("vdw.npy", "coulomb.npy", "points.npy")
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(names)
+    for f in names:
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes(), f
+    pts = np.load(tmp_path / "a" / "points.npy")
+    assert pts.dtype == np.float64 and pts.shape == (bench.DUMP_POINTS,)
+    idx = pts.astype(np.int64)
+    assert np.array_equal(idx, pts) and (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < nx * ny * nz
+    flat = g.numpy().reshape(8, -1)
+    v, c = np.load(tmp_path / "a" / "vdw.npy"), np.load(tmp_path / "a" / "coulomb.npy")
+    assert v.dtype == np.float32 and v.shape == (8, bench.DUMP_POINTS)
+    assert np.array_equal(v, flat[:, idx]) and np.array_equal(c, -flat[:, idx])
+    assert 2 * 8 * 4 * bench.DUMP_POINTS + 8 * bench.DUMP_POINTS <= 64e6          # both grids of the default 256^3 run
+
+
 def test_interpolate_grid_without_derivatives_host_mirror_vs_oracle(oracle):
     """The "no derivatives" branch of interpolate_grid (grids.jl:259-269) in the host mirror and in the oracle: same values where
     the reference's [x, y, z] addressing of its [z, y, x] array stays in bounds, IndexError / NaN where Julia raises BoundsError."""
