@@ -243,18 +243,30 @@ class GpuMonteCarloEnergy:
 class DeviceMonteCarlo:
     """Device-resident energy state of a :class:`ceg_hip.hostmirror.montecarlo.MonteCarloSetup` (``ceg_mc_*``, BASELINE config 5):
     ``movement_energy`` (montecarlo.jl:563-579) of a batch of trial placements in ONE launch, ``update_mc!``
-    (montecarlo.jl:615-628) applied on the device.  The MC driver (proposals, acceptance) stays with the caller."""
+    (montecarlo.jl:615-628) applied on the device.  The MC driver (proposals, acceptance) stays with the caller.
 
-    def __init__(self, mc, device: int = 0):
+    ``grids_from``: another instance on the same device and framework whose grid interpolators this one uses instead of uploading
+    its own (the chains of an isotherm share one framework); the interpolators are released when the last instance using them
+    is closed."""
+
+    def __init__(self, mc, device: int = 0, grids_from: Optional["DeviceMonteCarlo"] = None):
         from .hostmirror.constants import COULOMBIC_CONVERSION_FACTOR
         self._lib = _abi.load_library()
         self.mc = mc
+        self._group = None
         ff = mc.ff
         nk = ff.nkinds
-        self.interp = [GridInterpolator(g, device) if (g is not None and g.ewald_precision == math.inf) else None
-                       for g in (mc.grids if mc.grids else [None] * nk)]
-        has_coulomb = bool(mc.grids) and mc.coulomb.ewald_precision != -math.inf
-        self.coulomb = GridInterpolator(mc.coulomb, device) if has_coulomb else None
+        if grids_from is not None:
+            if len(grids_from.interp) != nk:
+                raise ValueError("grids_from: another force field (number of kinds differs)")
+            self.interp, self.coulomb, self._grid_users = grids_from.interp, grids_from.coulomb, grids_from._grid_users
+        else:
+            self.interp = [GridInterpolator(g, device) if (g is not None and g.ewald_precision == math.inf) else None
+                           for g in (mc.grids if mc.grids else [None] * nk)]
+            has_coulomb = bool(mc.grids) and mc.coulomb.ewald_precision != -math.inf
+            self.coulomb = GridInterpolator(mc.coulomb, device) if has_coulomb else None
+            self._grid_users = [0]
+        self._grid_users[0] += 1
         handles = (C.c_void_p * nk)(*[it._h if it is not None else None for it in self.interp])
         charge = np.ascontiguousarray([0.0 if (k + 1 >= len(mc.charges) or np.isnan(mc.charges[k + 1])) else float(mc.charges[k + 1])
                                        for k in range(nk)], dtype=np.float64)
@@ -406,14 +418,122 @@ class DeviceMonteCarlo:
         return (np.concatenate(host) if host else pos), (re[:nk] + 1j * im[:nk])
 
     def close(self) -> None:
+        if getattr(self, "_group", None) is not None:
+            raise RuntimeError(f"this chain is a member of {self._group!r}: close the group first")
         if getattr(self, "_h", None):
             self._lib.ceg_mc_destroy(self._h)
             self._h = None
-        for it in self.interp:
-            if it is not None:
-                it.close()
-        if self.coulomb is not None:
-            self.coulomb.close()
+            self._grid_users[0] -= 1
+            if self._grid_users[0] == 0:
+                for it in self.interp:
+                    if it is not None:
+                        it.close()
+                if self.coulomb is not None:
+                    self.coulomb.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceMonteCarloGroup:
+    """K :class:`DeviceMonteCarlo` chains on one device stepped in lockstep (``ceg_mc_group_*``): one launch evaluates the trials
+    of every chain, one launch applies every accepted move -- the way ``make_isotherm`` (parameterinputs.jl:316-329) runs one
+    ``run_gcmc`` per pressure, with the launch cost shared by the chains.  The acceptance rule stays with the caller.  While
+    grouped the chains' own methods remain usable (insert, remove, single trials ...) and are ordered with the group calls; the
+    group and its chains are driven from one thread.  Usable as a context manager; ``close()`` gives the chains back."""
+
+    MAX_CHAINS = 256          # CEG_MC_GROUP_MAX
+
+    def __init__(self, chains):
+        self.chains = list(chains)
+        if not self.chains:
+            raise ValueError("a group needs at least one chain")
+        self._lib = self.chains[0]._lib
+        hs = (C.c_void_p * len(self.chains))(*[c._h for c in self.chains])
+        g = C.c_void_p()
+        _abi.check(self._lib, self._lib.ceg_mc_group_create(C.byref(g), hs, len(self.chains)))
+        self._h = g
+        for c in self.chains:
+            c._group = self
+
+    def __repr__(self):
+        return f"DeviceMonteCarloGroup(k={len(self.chains)})"
+
+    def trial(self, moves):
+        """One trial per chain: ``moves[c]`` is ``("move", idx, positions[n, m, 3])`` (rows: n + 1, row 0 where the molecule is now;
+        n = 0 gives the deletion energy), ``("insert", i, positions[n, m, 3])`` (n rows of a new molecule of kind ``i``; one kind
+        per call) or None (idle).  -> list of float64[rows, 4] (None for idle chains)."""
+        k = len(self.chains)
+        if len(moves) != k:
+            raise ValueError(f"{len(moves)} moves for {k} chains")
+        mol = np.full(k, -2, dtype=np.int32)
+        n = np.zeros(k, dtype=np.int32)
+        kinds, parts, nrows = None, [], []
+        for c, (chain, mv) in enumerate(zip(self.chains, moves)):
+            if mv is None:
+                nrows.append(0)
+                continue
+            what, idx, positions = mv
+            if what == "move":
+                mol[c] = chain._slot[idx[0]][idx[1]]
+                m = len(chain.mc.ffidx[idx[0]])
+            elif what == "insert":
+                mol[c] = -1
+                k_i = [ix - 1 for ix in chain.mc.ffidx[idx]]
+                if kinds is not None and k_i != kinds:
+                    raise ValueError("one inserted species per group call")
+                kinds, m = k_i, len(k_i)
+            else:
+                raise ValueError(f"unknown move {what!r}")
+            t = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, m, 3)
+            n[c] = len(t)
+            parts.append(t.reshape(-1))
+            nrows.append(len(t) + (1 if what == "move" else 0))
+        trial = np.ascontiguousarray(np.concatenate(parts) if parts else np.empty(0), dtype=np.float64)
+        out = np.empty((sum(nrows), 4), dtype=np.float64)
+        ik = np.ascontiguousarray(kinds if kinds is not None else [0], dtype=np.int32)
+        _abi.check(self._lib, self._lib.ceg_mc_group_trial(self._h, _abi.i32ptr(mol), _abi.i32ptr(n), _abi.i32ptr(ik),
+                                                           len(kinds) if kinds is not None else 0,
+                                                           _abi.dptr(trial) if len(trial) else None, _abi.dptr(out.reshape(-1))))
+        rows, o = [], 0
+        for mv, r in zip(moves, nrows):
+            rows.append(None if mv is None else out[o:o + r])
+            o += r
+        return rows
+
+    def accept(self, accepted) -> None:
+        """update_mc! on every chain whose entry is ``(idx, positions[m, 3])`` (None: nothing for that chain); asynchronous."""
+        k = len(self.chains)
+        if len(accepted) != k:
+            raise ValueError(f"{len(accepted)} entries for {k} chains")
+        mol = np.full(k, -1, dtype=np.int32)
+        parts = []
+        for c, (chain, a) in enumerate(zip(self.chains, accepted)):
+            if a is None:
+                continue
+            idx, positions = a
+            mol[c] = chain._slot[idx[0]][idx[1]]
+            parts.append(np.ascontiguousarray(positions, dtype=np.float64).reshape(-1))
+        p = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(1), dtype=np.float64)
+        _abi.check(self._lib, self._lib.ceg_mc_group_accept(self._h, _abi.i32ptr(mol), _abi.dptr(p)))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            rc = self._lib.ceg_mc_group_destroy(self._h)
+            self._h = None
+            for c in self.chains:
+                c._group = None
+            _abi.check(self._lib, rc)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
     def __del__(self):
         try:

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -222,11 +223,25 @@ __device__ __forceinline__ double2 molecule_sf(const McView& v, const double2* t
 
 // INSERT: the molecule is described by `nm` and is not in the system -- no current-position row, nothing excluded from the
 // pair sum, rest = framework + sums[:, 1]
-template <bool FAST, bool INSERT, bool CELLS>
-__global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mc_trial(McView v, int32_t molecule, McLocal L, const double* __restrict__ trial, int64_t n,
-                                                          double* __restrict__ out, int stride, unsigned* done, unsigned long long* flag,
-                                                          unsigned long long seq)
+// The row of one workgroup.  `at` says which: at.b() = 0 the molecule where it is now, b >= 1 trial placement b - 1 (at
+// trial[(b - 1) m 3]); the row goes to at.row(out)[0..3]; at.nblocks() workgroups share `done` (the last one to finish raises `flag`).
+// k_mc_trial passes its kernarg view and McAtBlock, k_mcg_trial a chain's view from device memory and McAtChainRow.  (The row index,
+// the output pointer and the workgroup count are worked out where they are used: computed in front of the body, they stayed live
+// through it and cost the batch-1 kernel a spill.)
+struct McAtBlock {
+    template <bool INSERT> __device__ __forceinline__ int64_t b() const { return INSERT ? (int64_t)blockIdx.x + 1 : (int64_t)blockIdx.x; }
+    __device__ __forceinline__ double* row(double* out) const { return out + 4 * (size_t)blockIdx.x; }
+    __device__ __forceinline__ unsigned nblocks() const { return gridDim.x * gridDim.y; }
+    __device__ __forceinline__ bool table_in_lds(const McView& v) const { return v.table_in_lds; }
+};
+
+template <bool FAST, bool INSERT, bool CELLS, class At>
+__device__ __forceinline__ void mc_trial_row(const McView& v, int32_t molecule, const McLocal& L, const double* __restrict__ trial,
+                                             double* __restrict__ out, int stride, unsigned* done, unsigned long long* flag,
+                                             unsigned long long seq, const At& at)
 {
+    const int64_t b = at.template b<INSERT>();        // 0: where the molecule is now; b >= 1: trial b - 1
+    const bool table_in_lds = at.table_in_lds(v);
     // dynamic LDS: [m][stride] double2 tables, then (table_in_lds) the pair table
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     __shared__ double s_pos[MC_MAX_ATOMS * 3];
@@ -239,12 +254,11 @@ __global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mc_trial(McView 
     // the latency of a small batch is the longest term, not their sum; gridDim.y == 1: one workgroup does all three
     const int term = gridDim.y == 1 ? -1 : (int)blockIdx.y;
     const bool do_frame = term < 0 || term == 0, do_ewald = term < 0 || term == 1, do_pairs = term < 0 || term == 2;
-    const int64_t b = INSERT ? (int64_t)blockIdx.x + 1 : (int64_t)blockIdx.x;     // 0: where the molecule is now; b >= 1: trial b - 1
     const int first = L.first, m = L.m;
     double2* tab = reinterpret_cast<double2*>(s_raw);
     const DevRule* rules = v.rules;
     const int32_t* offset = v.rule_offset;
-    if (v.table_in_lds && do_pairs) {
+    if (table_in_lds && do_pairs) {
         DevRule* lr = reinterpret_cast<DevRule*>(s_raw + sizeof(double2) * (size_t)m * stride);
         int32_t* lo = reinterpret_cast<int32_t*>(lr + (v.nrules > 0 ? v.nrules : 1));
         for (int t = tid; t < v.nrules; t += MC_THREADS) lr[t] = v.rules[t];
@@ -339,7 +353,7 @@ __global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mc_trial(McView 
         }
     }
     // ---- single_contribution_vdw (energy.jl:407-427)
-    if (v.table_in_lds) __syncthreads();
+    if (table_in_lds) __syncthreads();
     if (do_pairs) {
         const double* M = v.mat;
         const double* I = v.invmat;
@@ -437,7 +451,7 @@ __global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mc_trial(McView 
         double tot[5] = {0, 0, 0, 0, 0};
         for (int w = 0; w < MC_THREADS / 64; ++w)
             for (int c = 0; c < 5; ++c) tot[c] += s_red[w][c];
-        double* o = out + 4 * (size_t)blockIdx.x;
+        double* o = at.row(out);
         if (do_frame) { o[0] = tot[0]; o[1] = tot[1]; }
         if (do_pairs) o[2] = tot[2];
         if (do_ewald) o[3] = 2.0 * tot[3] + tot[4];
@@ -445,13 +459,68 @@ __global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mc_trial(McView 
         // hipStreamSynchronize (whose wake-up costs about as much as this kernel); the last workgroup to finish raises it
         if (flag) {
             __threadfence_system();
-            if (atomicAdd(done, 1u) == gridDim.x * gridDim.y - 1) {
+            if (atomicAdd(done, 1u) == at.nblocks() - 1) {
                 *done = 0u;
                 __threadfence_system();
                 __atomic_store_n(flag, seq, __ATOMIC_RELEASE);
             }
         }
     }
+}
+
+template <bool FAST, bool INSERT, bool CELLS>
+__global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mc_trial(McView v, int32_t molecule, McLocal L, const double* __restrict__ trial, int64_t n,
+                                                          double* __restrict__ out, int stride, unsigned* done, unsigned long long* flag,
+                                                          unsigned long long seq)
+{
+    mc_trial_row<FAST, INSERT, CELLS>(v, molecule, L, trial, out, stride, done, flag, seq, McAtBlock{});
+}
+
+// ---- a chain group (ceg_mc_group_*): one step of K chains in one launch per (FAST, INSERT, CELLS) class.  What a chain of the
+// launch needs travels in mapped host memory like a small batch of k_mc_trial; the views stay in device memory.
+struct McGroupRow {
+    int32_t view, molecule, stride, _pad;    // view: index of the chain in the group (views[view]); molecule -1 for an insertion
+    int64_t trial, out;                      // offsets of the chain's placements (doubles) and of its first row (rows)
+    McLocal L;
+};
+
+// the chains' views through the constant address space: the pointers in them are then known to address global memory (read through a
+// generic pointer they became flat accesses, +16 VGPRs in k_mcg_accept); the array does not change while a kernel runs
+#if defined(__HIP_DEVICE_COMPILE__)
+template <class T> __device__ __forceinline__ const __attribute__((address_space(4))) T* as_constant(const T* p) { return (const __attribute__((address_space(4))) T*)p; }
+#else
+template <class T> __device__ __forceinline__ const T* as_constant(const T* p) { return p; }
+#endif
+
+struct McAtChainRow {
+    int64_t out;             // row of `out` (fetched in front of the body: at its end it would be a round trip to host memory)
+    int r;                   // row of the chain
+    unsigned n;              // workgroups of all the launches of the call
+    int table_ok;            // the call's LDS leaves room for the pair tables
+    template <bool INSERT> __device__ __forceinline__ int64_t b() const { return INSERT ? (int64_t)r + 1 : (int64_t)r; }
+    __device__ __forceinline__ double* row(double* o) const { return o + 4 * (size_t)out; }
+    __device__ __forceinline__ unsigned nblocks() const { return n; }
+    __device__ __forceinline__ bool table_in_lds(const McView& v) const { return table_ok && v.table_in_lds; }
+};
+
+// workgroup x of the launch: row x - ends[c - 1] of the chain c with ends[c - 1] <= x < ends[c] (ends: row prefix of the launch)
+template <bool FAST, bool INSERT, bool CELLS>
+__global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mcg_trial(const McView* __restrict__ views, const McGroupRow* __restrict__ chains,
+                                                           const int32_t* __restrict__ ends, int nchains, int table_ok,
+                                                           const double* __restrict__ trial, double* __restrict__ out, unsigned* done,
+                                                           unsigned long long* flag, unsigned long long seq, unsigned nblocks)
+{
+    __shared__ int s_chain, s_row0;
+    const int x = (int)blockIdx.x;
+    for (int t = threadIdx.x; t < nchains; t += MC_THREADS) {          // one round trip for the whole table
+        const int lo = t > 0 ? ends[t - 1] : 0;
+        if (lo <= x && x < ends[t]) { s_chain = t; s_row0 = lo; }
+    }
+    __syncthreads();
+    const McGroupRow& C = as_constant(chains)[__builtin_amdgcn_readfirstlane(s_chain)];
+    const int r = x - __builtin_amdgcn_readfirstlane(s_row0);
+    const McAtChainRow at{C.out + r, r, nblocks, table_ok};
+    mc_trial_row<FAST, INSERT, CELLS>(as_constant(views)[C.view], C.molecule, C.L, trial + C.trial, out, C.stride, done, flag, seq, at);
 }
 
 // ---- the same rows for LARGE batches: one WAVE per placement, one kernel per term (round 4).
@@ -912,7 +981,7 @@ __global__ __launch_bounds__(64 * MCW_WAVES, CEG_PAIRFRAC_WAVES) void k_mcw_pair
 }
 
 // update_mc! for a displacement (montecarlo.jl:615-628): positions; sums[:,1] += new - sums[:,ij+1]; sums[:,ij+1] = new
-__global__ __launch_bounds__(MC_THREADS) void k_mc_accept(McView v, int32_t molecule, McPositions np, McCellOps ops, int stride)
+__device__ __forceinline__ void mc_accept_body(const McView& v, int32_t molecule, const McPositions& np, const McCellOps& ops, int stride)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     __shared__ double s_pos[MC_MAX_ATOMS * 3];
@@ -943,6 +1012,24 @@ __global__ __launch_bounds__(MC_THREADS) void k_mc_accept(McView v, int32_t mole
         v.sf_tot[q] = t;
         mine[q] = make_double2(sr, si);
     });
+}
+
+__global__ __launch_bounds__(MC_THREADS) void k_mc_accept(McView v, int32_t molecule, McPositions np, McCellOps ops, int stride)
+{
+    mc_accept_body(v, molecule, np, ops, stride);
+}
+
+// one workgroup per accepted chain of a group (what the chain's update needs in pinned, device-mapped host memory)
+struct McGroupAccept {
+    int32_t view, molecule, stride, _pad;
+    McPositions np;
+    McCellOps ops;
+};
+
+__global__ __launch_bounds__(MC_THREADS) void k_mcg_accept(const McView* __restrict__ views, const McGroupAccept* __restrict__ items)
+{
+    const McGroupAccept& A = items[blockIdx.x];
+    mc_accept_body(as_constant(views)[A.view], A.molecule, A.np, A.ops, A.stride);
 }
 
 // sums[:, ij+1] of every molecule from its current positions (one workgroup per molecule)
@@ -1179,6 +1266,8 @@ struct CellMirror {
 
 }  // namespace
 
+struct ceg_mc_group;
+
 struct ceg_mc {
     int device = 0;
     McView v{};
@@ -1222,6 +1311,9 @@ struct ceg_mc {
     // set when a state-changing call failed after it had started to change the host mirror (counts, slot lists, cell lists) or the
     // device state: host and device may then disagree, so every later call fails until ceg_mc_set_guests rebuilds both
     bool poisoned = false;
+    uint64_t v_version = 1;                      // bumped wherever `v` is written (a group re-uploads its copy of `v` when this moved)
+    ceg_mc_group* group = nullptr;               // the chain group this handle belongs to (its work then runs on the group's stream)
+    hipStream_t own_stream = nullptr;            // the handle's own stream while it is in a group
 };
 
 namespace {
@@ -1379,6 +1471,7 @@ extern "C" int ceg_mc_create(ceg_mc_t** handle, int32_t device, ceg_interp_t* co
 extern "C" int ceg_mc_destroy(ceg_mc_t* h)
 {
     if (!h) return CEG_OK;
+    if (h->group) return merr(CEG_ERR_INVALID, "the handle is a member of a chain group: ceg_mc_group_destroy first");
     Guard guard(h->device);
     if (guard.ok) {
         if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
@@ -1440,6 +1533,7 @@ int ensure_capacity(ceg_mc* h, int64_t natoms, int64_t nmol)
         h->mol_cap = cap;
     }
     h->v.atoms = h->d_atoms; h->v.fatoms = h->d_atoms + h->atoms_cap; h->v.mol = h->d_molidx; h->v.sf_mol = h->d_mol;
+    ++h->v_version;
     if (regrown && h->v.natoms > 0) {
         hipLaunchKernelGGL(k_mc_frac_fill, dim3((unsigned)((h->v.natoms + 255) / 256)), dim3(256), 0, h->stream, h->v, (int64_t)h->v.natoms);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return merr(CEG_ERR_HIP, "could not convert the guest atoms");
@@ -1475,6 +1569,7 @@ int rebuild_cells(ceg_mc* h)
     bool ok = hipMemcpy(d_map, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(h->d_cell_count, count.data(), sizeof(int32_t) * count.size(), hipMemcpyHostToDevice) == hipSuccess;
     h->v.cells = h->d_cells; h->v.fcells = h->d_cells + (size_t)ncells * cm.cap; h->v.cell_count = h->d_cell_count; h->v.cell_cap = cm.cap;
+    ++h->v_version;
     if (ok) {
         const int64_t n = (int64_t)map.size();
         hipLaunchKernelGGL(k_mc_cells_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->v, d_map, n);
@@ -1720,6 +1815,23 @@ int run_trial(ceg_mc* h, bool insert, int32_t molecule, const McMolecule& nm, in
     return CEG_OK;
 }
 
+// update_mc! of `molecule` on the host mirror of the cell lists: the operations the accept kernel applies; true: a cell outgrew its
+// capacity (or the operations do not fit), the caller rebuilds the device cells after the launch
+bool accept_cell_ops(ceg_mc* h, int32_t molecule, const double* positions, McCellOps& ops)
+{
+    if (!h->cm.on) return false;
+    CellMirror& cm = h->cm;
+    const int first = h->h_mol[molecule].x, m = h->h_mol[molecule].y;
+    cm.begin();
+    for (int a = 0; a < m; ++a) {
+        const int c = cm.bin_of(positions + 3 * a);
+        if (c == cm.cell_of[first + a]) { cm.refresh(first + a); continue; }     // same cell: new coordinates in place
+        cm.take_out(first + a);
+        cm.put_in(first + a, c);
+    }
+    return !cm.finish(ops);
+}
+
 int check_molecule(const ceg_mc* h, const int32_t* kinds, int32_t m, McMolecule* nm)
 {
     if (!kinds || m < 1) return merr(CEG_ERR_INVALID, "bad argument");
@@ -1764,6 +1876,7 @@ extern "C" int ceg_mc_set_guests(ceg_mc_t* h, const double* positions, const int
     if (hipStreamSynchronize(h->stream) != hipSuccess) return poison(h, merr(CEG_ERR_HIP, "stream synchronisation failed"));
     h->poisoned = true;                                    // until this call has rebuilt host and device state completely
     h->v.natoms = 0; h->v.nmol = 0;                        // nothing worth copying when the arrays grow
+    ++h->v_version;
     h->h_mol.clear();
     if (int rc = ensure_capacity(h, std::max<int64_t>(natoms, 1), std::max<int64_t>(nmol, 1))) return rc;
     bool ok = !injected_failure("set_guests");
@@ -1775,6 +1888,7 @@ extern "C" int ceg_mc_set_guests(ceg_mc_t* h, const double* positions, const int
     h->free_runs.assign(MC_MAX_ATOMS + 1, {});
     McView& v = h->v;
     v.natoms = (int32_t)natoms; v.nmol = nmol;
+    ++h->v_version;
     if (natoms > 0) {
         hipLaunchKernelGGL(k_mc_frac_fill, dim3((unsigned)((natoms + 255) / 256)), dim3(256), 0, h->stream, v, (int64_t)natoms);
         if (hipGetLastError() != hipSuccess) return merr(CEG_ERR_HIP, "could not convert the guest atoms");
@@ -1876,19 +1990,7 @@ extern "C" int ceg_mc_accept(ceg_mc_t* h, int32_t molecule, const double* positi
     Guard guard(h->device);
     if (!guard.ok) return merr(CEG_ERR_HIP, "hipSetDevice failed");
     McCellOps ops{};
-    bool rebuild = false;
-    if (h->cm.on) {
-        CellMirror& cm = h->cm;
-        const int first = h->h_mol[molecule].x;
-        cm.begin();
-        for (int a = 0; a < m; ++a) {
-            const int c = cm.bin_of(positions + 3 * a);
-            if (c == cm.cell_of[first + a]) { cm.refresh(first + a); continue; }     // same cell: new coordinates in place
-            cm.take_out(first + a);
-            cm.put_in(first + a, c);
-        }
-        rebuild = !cm.finish(ops);
-    }
+    const bool rebuild = accept_cell_ops(h, molecule, positions, ops);
     // (from here on the cell mirror already describes the accepted state: any failure leaves host and device out of step)
     if (!injected_failure("accept"))
         hipLaunchKernelGGL(k_mc_accept, dim3(1), dim3(MC_THREADS), tables_bytes(h, m), h->stream, h->v, molecule, np, ops, h->stride);
@@ -1917,11 +2019,13 @@ extern "C" int ceg_mc_insert(ceg_mc_t* h, const int32_t* kinds, int32_t m, const
     } else {
         first = h->v.natoms;
         h->v.natoms += m;
+        ++h->v_version;
     }
     const int32_t molecule = h->v.nmol;
     McPositions np{};
     for (int t = 0; t < 3 * m; ++t) np.xyz[t] = positions[t];
     h->v.nmol += 1;
+    ++h->v_version;
     h->h_mol.push_back(make_int2(first, m));
     if ((int64_t)h->h_kind.size() < (int64_t)first + m) h->h_kind.resize((size_t)first + m, 0);
     for (int a = 0; a < m; ++a) h->h_kind[(size_t)first + a] = nm.kinds[a];
@@ -1968,6 +2072,7 @@ extern "C" int ceg_mc_remove(ceg_mc_t* h, int32_t molecule, int32_t* moved_out)
     if (last != molecule) h->h_mol[molecule] = h->h_mol[last];
     h->h_mol.pop_back();
     h->v.nmol = last;
+    ++h->v_version;
     if (moved_out) *moved_out = last;     // like remove_one_system! (ewald.jl:404-413): the molecule that was `last` is now `molecule`
     return CEG_OK;
 }
@@ -2006,4 +2111,321 @@ extern "C" int ceg_mc_get_state(ceg_mc_t* h, double* positions, double* sf_total
         }
     }
     return CEG_OK;
+}
+
+// ---- chain groups: one step of K Markov chains (handles on one device) per trial launch and per accept launch.  The members' own
+// asynchronous work runs on the group's stream while they are grouped, so per-handle calls and group calls stay in order.
+struct ceg_mc_group {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::vector<ceg_mc*> chains;
+    std::vector<uint64_t> uploaded;              // v_version of each member's view in d_views (0: never uploaded)
+    McView* d_views = nullptr;                   // [K] device memory, read by k_mcg_trial / k_mcg_accept
+    McView* h_views = nullptr;                   // [K] pinned staging of the view uploads
+    bool uploads_pending = false;                // an upload out of h_views may not have run yet
+    // per-call staging, pinned and device-mapped: trial entries + row prefixes + placements in, rows out; accept entries
+    unsigned char *h_in = nullptr, *dm_in = nullptr;
+    double *h_out = nullptr, *dm_out = nullptr;
+    McGroupAccept *h_acc = nullptr, *dm_acc = nullptr;
+    bool accept_pending = false;                 // the last accept launch may still read h_acc
+    unsigned long long *h_flag = nullptr, *dm_flag = nullptr;
+    unsigned* d_done = nullptr;
+    unsigned long long seq = 0;
+};
+
+namespace {
+
+constexpr size_t MCG_IN_BYTES = 1 << 20;         // entries, row prefixes and placements of one group trial call
+constexpr size_t MCG_OUT_BYTES = 1 << 20;        // rows of one group trial call (32 768)
+
+void group_free(ceg_mc_group* g)
+{
+    if (g->stream) { (void)hipStreamSynchronize(g->stream); (void)hipStreamDestroy(g->stream); }
+    if (g->d_views) (void)hipFree(g->d_views);
+    if (g->d_done) (void)hipFree(g->d_done);
+    for (void* p : {(void*)g->h_views, (void*)g->h_in, (void*)g->h_out, (void*)g->h_acc, (void*)g->h_flag})
+        if (p) (void)hipHostFree(p);
+    delete g;
+}
+
+int group_refuse_poisoned(int c)
+{
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "chain %d of the group is inconsistent after an earlier failure of accept / insert / remove: call ceg_mc_set_guests on it", c);
+    return merr(CEG_ERR_HIP, msg);
+}
+
+int group_bad(int c, const char* what)
+{
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "chain %d: %s", c, what);
+    return merr(CEG_ERR_INVALID, msg);
+}
+
+// the views of chains `used` (used[c] != 0) into d_views where they changed since their last upload, in stream order
+bool group_upload_views(ceg_mc_group* g, const std::vector<char>& used)
+{
+    bool any = false;
+    for (size_t c = 0; c < g->chains.size(); ++c)
+        any = any || (used[c] && g->uploaded[c] != g->chains[c]->v_version);
+    if (!any) return true;
+    if (g->uploads_pending && hipStreamSynchronize(g->stream) != hipSuccess) return false;     // h_views is about to be rewritten
+    for (size_t c = 0; c < g->chains.size(); ++c) {
+        if (!used[c] || g->uploaded[c] == g->chains[c]->v_version) continue;
+        g->h_views[c] = g->chains[c]->v;
+        if (hipMemcpyAsync(g->d_views + c, g->h_views + c, sizeof(McView), hipMemcpyHostToDevice, g->stream) != hipSuccess) return false;
+        g->uploaded[c] = g->chains[c]->v_version;
+    }
+    g->uploads_pending = true;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int ceg_mc_group_create(ceg_mc_group_t** group, ceg_mc_t* const* chains, int32_t k)
+{
+    if (!group || !chains || k < 1 || k > CEG_MC_GROUP_MAX) return merr(CEG_ERR_INVALID, "bad argument (1 <= k <= CEG_MC_GROUP_MAX chains)");
+    *group = nullptr;
+    for (int32_t c = 0; c < k; ++c) {
+        ceg_mc* h = chains[c];
+        if (!h) return group_bad(c, "no handle");
+        if (h->device != chains[0]->device) return group_bad(c, "the handles of a group must live on one device");
+        for (int32_t d = 0; d < c; ++d)
+            if (chains[d] == h) return group_bad(c, "the handle appears twice");
+        if (h->group) return group_bad(c, "the handle is already in a group");
+        if (!h->d_atoms || !h->d_molidx) return group_bad(c, "ceg_mc_set_guests has never been called on the handle");
+    }
+    Guard guard(chains[0]->device);
+    if (!guard.ok) return merr(CEG_ERR_HIP, "hipSetDevice failed");
+    ceg_mc_group* g = new ceg_mc_group();
+    g->device = chains[0]->device;
+    g->chains.assign(chains, chains + k);
+    g->uploaded.assign((size_t)k, 0);
+    bool ok = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) == hipSuccess &&
+              hipMalloc((void**)&g->d_views, sizeof(McView) * (size_t)k) == hipSuccess &&
+              hipHostMalloc((void**)&g->h_views, sizeof(McView) * (size_t)k, hipHostMallocDefault) == hipSuccess &&
+              hipHostMalloc((void**)&g->h_in, MCG_IN_BYTES, hipHostMallocMapped) == hipSuccess &&
+              hipHostGetDevicePointer((void**)&g->dm_in, g->h_in, 0) == hipSuccess &&
+              hipHostMalloc((void**)&g->h_out, MCG_OUT_BYTES, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
+              hipHostGetDevicePointer((void**)&g->dm_out, g->h_out, 0) == hipSuccess &&
+              hipHostMalloc((void**)&g->h_acc, sizeof(McGroupAccept) * (size_t)k, hipHostMallocMapped) == hipSuccess &&
+              hipHostGetDevicePointer((void**)&g->dm_acc, g->h_acc, 0) == hipSuccess &&
+              hipHostMalloc((void**)&g->h_flag, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
+              hipHostGetDevicePointer((void**)&g->dm_flag, g->h_flag, 0) == hipSuccess &&
+              hipMalloc((void**)&g->d_done, sizeof(unsigned)) == hipSuccess && hipMemset(g->d_done, 0, sizeof(unsigned)) == hipSuccess;
+    if (ok) *g->h_flag = 0ull;
+    for (int32_t c = 0; ok && c < k; ++c) ok = hipStreamSynchronize(chains[c]->stream) == hipSuccess;
+    if (!ok) {
+        group_free(g);
+        return merr(CEG_ERR_HIP, "could not set up the chain group");
+    }
+    for (ceg_mc* h : g->chains) {                // from here on every member's asynchronous work goes to the group's stream
+        h->group = g;
+        h->own_stream = h->stream;
+        h->stream = g->stream;
+    }
+    *group = g;
+    return CEG_OK;
+}
+
+extern "C" int ceg_mc_group_destroy(ceg_mc_group_t* g)
+{
+    if (!g) return CEG_OK;
+    Guard guard(g->device);
+    const bool ok = guard.ok && hipStreamSynchronize(g->stream) == hipSuccess;
+    for (ceg_mc* h : g->chains) {
+        h->stream = h->own_stream;
+        h->own_stream = nullptr;
+        h->group = nullptr;
+    }
+    group_free(g);
+    return ok ? CEG_OK : merr(CEG_ERR_HIP, "stream synchronisation failed");
+}
+
+extern "C" int ceg_mc_group_trial(ceg_mc_group_t* g, const int32_t* molecule, const int32_t* n, const int32_t* insert_kinds, int32_t insert_m,
+                                  const double* trial, double* out)
+{
+    if (!g || !molecule || !n) return merr(CEG_ERR_INVALID, "bad argument");
+    const int k = (int)g->chains.size();
+    // chain c: its class (fast, insert, cells), rows, atoms per placement, offsets of its placements and rows
+    std::vector<int> cls((size_t)k, -1), mm((size_t)k, 0);
+    std::vector<int64_t> rows((size_t)k, 0), toff((size_t)k, 0), roff((size_t)k, 0);
+    std::vector<char> used((size_t)k, 0);
+    McMolecule nm{};
+    int64_t total_rows = 0, total_in = 0;
+    size_t lds = 0, pair_table = 0;
+    for (int c = 0; c < k; ++c) {
+        ceg_mc* h = g->chains[c];
+        const int32_t mol = molecule[c];
+        if (mol == -2) continue;
+        if (h->poisoned) return group_refuse_poisoned(c);
+        if (n[c] < 0) return group_bad(c, "negative number of placements");
+        int m;
+        if (mol == -1) {
+            if (int rc = check_molecule(h, insert_kinds, insert_m, &nm)) return rc;
+            m = insert_m;
+            rows[c] = n[c];
+        } else {
+            if (mol < 0 || mol >= h->v.nmol) return group_bad(c, "no such molecule");
+            m = h->h_mol[mol].y;
+            rows[c] = (int64_t)n[c] + 1;
+        }
+        if (tables_bytes(h, m) > 64 * 1024) return merr(CEG_ERR_UNSUPPORTED, "k-space tables of the molecule do not fit in LDS");
+        if (n[c] > 0 && !trial) return merr(CEG_ERR_INVALID, "bad argument");
+        used[c] = 1;
+        mm[c] = m;
+        cls[c] = (h->v.fast ? 4 : 0) | (mol == -1 ? 2 : 0) | (h->v.use_cells ? 1 : 0);
+        toff[c] = total_in;
+        roff[c] = total_rows;
+        total_in += (int64_t)n[c] * m * 3;
+        total_rows += rows[c];
+        lds = std::max(lds, tables_bytes(h, m));
+        if (h->v.table_in_lds)
+            pair_table = std::max(pair_table, sizeof(DevRule) * (size_t)(h->v.nrules > 0 ? h->v.nrules : 1) + sizeof(int32_t) * ((size_t)h->v.nkinds * h->v.nkinds + 1));
+    }
+    if (total_rows > 0 && !out) return merr(CEG_ERR_INVALID, "bad argument");
+    // the mapped input area: [K] entries, [K] row prefixes, the placements (8-byte aligned)
+    const size_t entries_bytes = sizeof(McGroupRow) * (size_t)k, ends_bytes = (sizeof(int32_t) * (size_t)k + 15) & ~(size_t)15;
+    if ((size_t)total_rows * 4 * sizeof(double) > MCG_OUT_BYTES || entries_bytes + ends_bytes + (size_t)total_in * sizeof(double) > MCG_IN_BYTES)
+        return merr(CEG_ERR_UNSUPPORTED, "the call's placements or rows exceed the group's mapped staging (1 MiB each): ceg_mc_trial_device takes large batches");
+    if (total_rows == 0) return CEG_OK;
+    // the pair table in LDS only if the largest tables of the call leave room for it (run_trial's rule)
+    const int table_ok = lds + pair_table <= 64 * 1024 ? 1 : 0;
+    if (table_ok) lds += pair_table;
+    Guard guard(g->device);
+    if (!guard.ok) return merr(CEG_ERR_HIP, "hipSetDevice failed");
+    if (!group_upload_views(g, used)) return merr(CEG_ERR_HIP, "view upload failed");
+    McGroupRow* entries = reinterpret_cast<McGroupRow*>(g->h_in);
+    int32_t* ends = reinterpret_cast<int32_t*>(g->h_in + entries_bytes);
+    double* tin = reinterpret_cast<double*>(g->h_in + entries_bytes + ends_bytes);
+    if (total_in > 0) memcpy(tin, trial, sizeof(double) * (size_t)total_in);
+    // entries grouped by class, in chain order within a class; one launch per class present
+    struct Launch { int cls, first, count; int32_t rows; };
+    std::vector<Launch> launches;
+    int e = 0;
+    for (int cl = 0; cl < 8; ++cl) {
+        Launch L{cl, e, 0, 0};
+        for (int c = 0; c < k; ++c) {
+            if (cls[c] != cl) continue;
+            ceg_mc* h = g->chains[c];
+            McGroupRow& R = entries[e];
+            R = McGroupRow{};
+            R.view = c;
+            R.molecule = molecule[c];
+            R.stride = h->stride;
+            R.trial = toff[c];
+            R.out = roff[c];
+            const bool ins = molecule[c] == -1;
+            R.L.first = ins ? 0 : h->h_mol[molecule[c]].x;
+            R.L.m = mm[c];
+            for (int a = 0; a < mm[c]; ++a) {
+                R.L.kinds[a] = ins ? nm.kinds[a] : h->h_kind[(size_t)R.L.first + a];
+                R.L.q[a] = h->h_charge[(size_t)R.L.kinds[a]];
+            }
+            L.rows += (int32_t)rows[c];
+            ends[e] = L.rows;
+            ++e;
+            ++L.count;
+        }
+        if (L.count > 0 && L.rows > 0) launches.push_back(L);
+    }
+    const unsigned nblocks = (unsigned)(3 * total_rows);
+    ++g->seq;
+    const McView* views = g->d_views;
+    const double* d_in = reinterpret_cast<const double*>(g->dm_in + entries_bytes + ends_bytes);
+    for (const Launch& L : launches) {
+        const McGroupRow* d_entries = reinterpret_cast<const McGroupRow*>(g->dm_in) + L.first;
+        const int32_t* d_ends = reinterpret_cast<const int32_t*>(g->dm_in + entries_bytes) + L.first;
+        const dim3 grid((unsigned)L.rows, 3u), block(MC_THREADS);
+#define CEG_MCG_LAUNCH(F, I, CL) hipLaunchKernelGGL((k_mcg_trial<F, I, CL>), grid, block, lds, g->stream, views, d_entries, d_ends, L.count, table_ok, d_in, \
+                                                    g->dm_out, g->d_done, g->dm_flag, g->seq, nblocks)
+        switch (L.cls) {
+            case 0: CEG_MCG_LAUNCH(false, false, false); break;
+            case 1: CEG_MCG_LAUNCH(false, false, true); break;
+            case 2: CEG_MCG_LAUNCH(false, true, false); break;
+            case 3: CEG_MCG_LAUNCH(false, true, true); break;
+            case 4: CEG_MCG_LAUNCH(true, false, false); break;
+            case 5: CEG_MCG_LAUNCH(true, false, true); break;
+            case 6: CEG_MCG_LAUNCH(true, true, false); break;
+            default: CEG_MCG_LAUNCH(true, true, true); break;
+        }
+#undef CEG_MCG_LAUNCH
+        // (a launch that failed never raises the flag: nothing of this call is polled then, the stream is synchronised)
+        if (hipGetLastError() != hipSuccess) {
+            (void)hipStreamSynchronize(g->stream);
+            return merr(CEG_ERR_HIP, "group trial kernel launch failed");
+        }
+    }
+    // poll the completion flag as run_trial does; after ~20 ms without it fall back to the stream
+    bool seen = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spin = 0;; ++spin) {
+        if (__atomic_load_n(g->h_flag, __ATOMIC_ACQUIRE) == g->seq) { seen = true; break; }
+        if ((spin & 1023u) == 1023u && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > 20.0) break;
+        __builtin_ia32_pause();
+    }
+    if (!seen && hipStreamSynchronize(g->stream) != hipSuccess) return merr(CEG_ERR_HIP, "group trial kernel failed");
+    g->accept_pending = false;                   // everything enqueued before this call has run
+    g->uploads_pending = false;
+    memcpy(out, g->h_out, sizeof(double) * 4 * (size_t)total_rows);
+    return CEG_OK;
+}
+
+extern "C" int ceg_mc_group_accept(ceg_mc_group_t* g, const int32_t* molecule, const double* positions)
+{
+    if (!g || !molecule) return merr(CEG_ERR_INVALID, "bad argument");
+    const int k = (int)g->chains.size();
+    std::vector<char> used((size_t)k, 0);
+    std::vector<const double*> at((size_t)k, nullptr);
+    size_t off = 0, lds = 0;
+    int count = 0;
+    for (int c = 0; c < k; ++c) {
+        if (molecule[c] < 0) continue;
+        ceg_mc* h = g->chains[c];
+        if (h->poisoned) return group_refuse_poisoned(c);
+        if (molecule[c] >= h->v.nmol) return group_bad(c, "no such molecule");
+        if (!positions) return merr(CEG_ERR_INVALID, "bad argument");
+        const int m = h->h_mol[molecule[c]].y;
+        used[c] = 1;
+        at[c] = positions + off;
+        off += 3 * (size_t)m;
+        lds = std::max(lds, tables_bytes(h, m));
+        ++count;
+    }
+    if (count == 0) return CEG_OK;
+    Guard guard(g->device);
+    if (!guard.ok) return merr(CEG_ERR_HIP, "hipSetDevice failed");
+    if (g->accept_pending && hipStreamSynchronize(g->stream) != hipSuccess) return merr(CEG_ERR_HIP, "stream synchronisation failed");
+    g->accept_pending = false;
+    if (!group_upload_views(g, used)) return merr(CEG_ERR_HIP, "view upload failed");
+    // the cell operations of every chain on its host mirror (from here on a failure leaves the touched chains out of step)
+    std::vector<char> rebuild((size_t)k, 0);
+    int e = 0;
+    for (int c = 0; c < k; ++c) {
+        if (!used[c]) continue;
+        ceg_mc* h = g->chains[c];
+        McGroupAccept& A = g->h_acc[e++];
+        A.view = c;
+        A.molecule = molecule[c];
+        A.stride = h->stride;
+        A._pad = 0;
+        const int m = h->h_mol[molecule[c]].y;
+        for (int t = 0; t < 3 * m; ++t) A.np.xyz[t] = at[c][t];
+        A.ops = McCellOps{};
+        rebuild[c] = accept_cell_ops(h, molecule[c], at[c], A.ops) ? 1 : 0;
+    }
+    auto poison_all = [&](int rc) {
+        for (int c = 0; c < k; ++c)
+            if (used[c]) g->chains[c]->poisoned = true;
+        return rc;
+    };
+    hipLaunchKernelGGL(k_mcg_accept, dim3((unsigned)count), dim3(MC_THREADS), lds, g->stream, g->d_views, g->dm_acc);
+    if (hipGetLastError() != hipSuccess) return poison_all(merr(CEG_ERR_HIP, "group accept kernel launch failed"));
+    g->accept_pending = true;
+    for (int c = 0; c < k; ++c)          // a cell that outgrew its capacity: the whole structure again, on the group's stream
+        if (rebuild[c]) {
+            if (int rc = rebuild_cells(g->chains[c])) return poison_all(rc);
+            g->accept_pending = false;   // (rebuild_cells leaves the stream idle)
+        }
+    return CEG_OK;                       // asynchronous: later calls on the group and on its members are ordered behind it
 }

@@ -542,6 +542,60 @@ function mc_remove(h::Ptr{Cvoid}, ij::Int)
     Int(moved[]) + 1
 end
 
+# ---- chain groups (ceg_mc_group_*): the chains of make_isotherm (src/parameterinputs.jl:316-329), one per pressure, stepped in
+# lockstep -- one launch for every chain's trial, one for every accepted move.  Like the rest of this file these four are not
+# executed here (no Julia in the build image); tests/test_gpu_mc_chains.py runs the same calls through ceg_hip.energy.
+
+"`ceg_mc_group_create` over the handles of K chains (`mc_handle`, one per `run_gcmc`); drive the group and its chains from one task"
+function mc_group(handles::Vector{Ptr{Cvoid}})
+    g = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve handles _check(ccall((:ceg_mc_group_create, LIB[]), Cint, (Ref{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Int32),
+                                      g, handles, length(handles)))
+    g[]
+end
+
+"""
+One trial per chain: `moves[c]` is `(ij, placements)` (displacement of species `ij`, Ewald index, 1-based; 4 x (n + 1) energies,
+column 1 where it is; `placements` empty for the deletion energy), `(:insert, placements)` (a new species with ff indices
+`insert_idx`, 4 x n) or `nothing` (idle).  Each placement is a vector of positions.  Returns the energies per chain.
+"""
+function mc_group_trial!(g::Ptr{Cvoid}, moves::Vector, insert_idx::Vector{Int}=Int[])
+    k = length(moves)
+    mol = fill(Int32(-2), k); n = zeros(Int32, k); nrows = zeros(Int, k); pts = Float64[]
+    for (c, mv) in enumerate(moves)
+        mv === nothing && continue
+        what, placements = mv
+        for p in placements
+            append!(pts, _pts(p))
+        end
+        n[c] = length(placements)
+        mol[c] = what === :insert ? Int32(-1) : Int32(what - 1)
+        nrows[c] = length(placements) + (what === :insert ? 0 : 1)
+    end
+    kinds = Int32.(insert_idx .- 1); out = Matrix{Float64}(undef, 4, sum(nrows))
+    GC.@preserve mol n kinds pts out _check(ccall((:ceg_mc_group_trial, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Float64}, Ptr{Float64}), g, mol, n, kinds, length(kinds), pts, out))
+    first = cumsum([0; nrows])
+    [moves[c] === nothing ? nothing : out[:, first[c]+1:first[c+1]] for c in 1:k]
+end
+
+"update_mc! on every chain whose entry of `accepted` is `(ij, newpos)` (`nothing`: no change); asynchronous"
+function mc_group_accept!(g::Ptr{Cvoid}, accepted::Vector)
+    mol = Int32[a === nothing ? -1 : a[1] - 1 for a in accepted]
+    pts = Float64[]
+    for a in accepted
+        a === nothing || append!(pts, _pts(a[2]))
+    end
+    GC.@preserve mol pts _check(ccall((:ceg_mc_group_accept, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}), g, mol, pts))
+    nothing
+end
+
+"`ceg_mc_group_destroy`: the chains get their own streams back and stay valid"
+function mc_group_close(g::Ptr{Cvoid})
+    _check(ccall((:ceg_mc_group_destroy, LIB[]), Cint, (Ptr{Cvoid},), g))
+    nothing
+end
+
 "(bins per axis, capacity) of the guest neighbour cells (the CellListMap branch of src/energy.jl:399-404), or `nothing` when the MC cell is small enough for the exhaustive loop"
 function mc_neighbour_cells(h::Ptr{Cvoid})
     nb = zeros(Int32, 3)

@@ -472,7 +472,8 @@ CEG_API int ceg_pairs_neighbour_cells(ceg_pairs_t* handle, int32_t nb[3]);
  *  kvec_ijk, kfactors, sf_re, sf_im, nk, ks, ewald_invmat as ceg_recip_create (nk = 0: no Ewald summation)
  *
  * Threading: a handle is NOT thread-safe -- one Markov chain, one caller at a time (the reference's update_mc! is not either);
- * different handles may be driven from different threads.
+ * different handles may be driven from different threads.  A chain group (ceg_mc_group_*, below) and all its members are driven
+ * from ONE thread: while a handle is grouped its calls share the group's stream and staging.
  * Errors: accept / insert / remove keep a host mirror (molecule table, free atom slots, neighbour-cell lists) in step with the
  * device state.  If one of them fails after it has started to change either side (kernel launch failure, allocation failure
  * while growing the arrays or rebuilding the cells) the handle is marked inconsistent: every later call except
@@ -524,6 +525,38 @@ CEG_API int ceg_mc_get_state(ceg_mc_t* handle, double* positions, double* sf_tot
  * Returns 1 with the bin counts and the per-cell capacity when the cells are in use, 0 (and zeros) for the exhaustive loop;
  * the energies are the same sums either way.  Environment: CEG_HIP_MC_CELLS=1|0 forces the choice, CEG_HIP_MC_BIN = bin width, A. */
 CEG_API int ceg_mc_neighbour_cells(ceg_mc_t* handle, int32_t nb[3], int32_t* capacity);
+/* ---- chain groups: one Markov step of K chains per launch (make_isotherm's chains, src/parameterinputs.jl:316-329) ----
+ * K handles on ONE device stepped in lockstep: one launch evaluates the trials of every chain, one launch applies every accepted
+ * move; the acceptance rule stays with the caller.  A batch-1 ceg_mc_trial is mostly launch and completion latency; a group pays
+ * it once per step for all K chains.
+ *
+ * create: 1 <= k <= CEG_MC_GROUP_MAX handles, all on one device, each at most once, none already in a group, each after
+ *   ceg_mc_set_guests (CEG_ERR_INVALID otherwise).  Synchronises every member's stream; until destroy, every member's own
+ *   asynchronous work (accept, insert, remove, the _device trials) runs on the group's stream, so per-handle calls stay legal
+ *   and are ordered with the group calls.  ceg_mc_destroy of a grouped handle returns CEG_ERR_INVALID.
+ * destroy: synchronises the group and gives every member its own stream back (the handles stay valid).
+ * trial (host memory, synchronous): for chain c
+ *   molecule[c] >= 0  displacement of that molecule: n[c] + 1 rows as ceg_mc_trial lays them out (n[c] = 0: row 0 alone, the
+ *                     deletion energy);
+ *   molecule[c] == -1 insertion of a molecule of kinds insert_kinds[0..insert_m) (one species per call): n[c] rows as ceg_mc_trial_insert;
+ *   molecule[c] == -2 the chain is idle in this step.
+ *   trial holds the placements [n[c]][m_c][3] packed in chain order, out the rows [.][4] packed in chain order.  A chain's rows come
+ *   from the kernel body of ceg_mc_trial / ceg_mc_trial_insert with its three-workgroup split (the single-handle path up to 256
+ *   rows): columns 0, 2, 3 bit-identical, column 1 (framework direct) to ~1e-12 relative, where the compiler fuses a few
+ *   multiply-adds of the interpolation differently.  More placements or rows than the group's mapped staging holds (1 MiB
+ *   each way: 32 768 rows) -> CEG_ERR_UNSUPPORTED: large batches belong on ceg_mc_trial_device.
+ * accept (asynchronous): update_mc! for every chain with molecule[c] >= 0 (negative: nothing for that chain), positions [m_c][3]
+ *   of the accepted chains only, packed in chain order.  If the call fails after it has changed a chain's host mirror, every chain
+ *   it touched is marked inconsistent (see Errors above).
+ * A call that would use a chain marked inconsistent returns CEG_ERR_HIP, with the chain's index in ceg_last_error(). */
+#define CEG_MC_GROUP_MAX 256
+typedef struct ceg_mc_group ceg_mc_group_t;
+
+CEG_API int ceg_mc_group_create(ceg_mc_group_t** group, ceg_mc_t* const* chains, int32_t k);
+CEG_API int ceg_mc_group_destroy(ceg_mc_group_t* group);
+CEG_API int ceg_mc_group_trial(ceg_mc_group_t* group, const int32_t* molecule, const int32_t* n,
+                               const int32_t* insert_kinds, int32_t insert_m, const double* trial, double* out);
+CEG_API int ceg_mc_group_accept(ceg_mc_group_t* group, const int32_t* molecule, const double* positions);
 
 /* ---- blocking masks on the grid lattice ----------------------------- */
 /*
