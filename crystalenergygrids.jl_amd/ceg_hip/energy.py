@@ -247,9 +247,10 @@ class DeviceMonteCarlo:
 
     ``grids_from``: another instance on the same device and framework whose grid interpolators this one uses instead of uploading
     its own (the chains of an isotherm share one framework); the interpolators are released when the last instance using them
-    is closed."""
+    is closed.  ``upload_guests=False`` (a setup without molecules only): the handle as ``ceg_mc_create`` leaves it, an empty box,
+    without a call of ``ceg_mc_set_guests``."""
 
-    def __init__(self, mc, device: int = 0, grids_from: Optional["DeviceMonteCarlo"] = None):
+    def __init__(self, mc, device: int = 0, grids_from: Optional["DeviceMonteCarlo"] = None, upload_guests: bool = True):
         from .hostmirror.constants import COULOMBIC_CONVERSION_FACTOR
         self._lib = _abi.load_library()
         self.mc = mc
@@ -289,7 +290,12 @@ class DeviceMonteCarlo:
                                      _abi.i32ptr(offsets), COULOMBIC_CONVERSION_FACTOR, *kargs)
         _abi.check(self._lib, rc)
         self._h = h
-        self.refresh()
+        if upload_guests:
+            self.refresh()
+        elif any(len(kind) for kind in mc.positions):
+            raise ValueError("upload_guests=False needs a setup without molecules")
+        else:
+            self._slot = [[] for _ in mc.positions]
 
     def neighbour_cells(self):
         """-> (bins per axis, capacity per cell) of the guest neighbour cells, or None when the guest-guest sum runs the exhaustive

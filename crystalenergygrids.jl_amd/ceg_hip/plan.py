@@ -19,7 +19,42 @@ from .grids import _grid_args, _matT, coulomb_scaling, vdw_scaling
 from .hostmirror.probes import ProbeSystem
 
 
-class GridPlan:
+class _PlainBuilds:
+    """The ordinary ``ceg_plan_build_vdw / _coulomb / _fused`` and ``ceg_plan_eval_points`` calls on ``self._h``.  On a
+    multi-probe plan they use probe 0 (include/ceg_hip.h)."""
+
+    # ------------------------------------------------------------------ builds (device pointers)
+    def build_vdw(self, d_out: int, channel_stride: int, i_begin: int, i_end: int, i_origin: int = 0,
+                  algo: int = _abi.ALGO_AUTO, stream: int = 0) -> None:
+        lam, thr = vdw_scaling()
+        _abi.check(self._lib, self._lib.ceg_plan_build_vdw(self._h, lam, thr, i_begin, i_end, d_out, channel_stride,
+                                                           i_origin, algo, stream))
+
+    def build_coulomb(self, d_out: int, channel_stride: int, i_begin: int, i_end: int, i_origin: int = 0,
+                      algo: int = _abi.ALGO_AUTO, stream: int = 0) -> None:
+        lam, thr = coulomb_scaling()
+        _abi.check(self._lib, self._lib.ceg_plan_build_coulomb(self._h, lam, thr, i_begin, i_end, d_out,
+                                                               channel_stride, i_origin, algo, stream))
+
+    def build_fused(self, d_vdw: int, d_coulomb: int, channel_stride: int, i_begin: int, i_end: int,
+                    i_origin: int = 0, algo: int = _abi.ALGO_AUTO, stream: int = 0) -> None:
+        lv, tv = vdw_scaling()
+        lc, tc = coulomb_scaling()
+        _abi.check(self._lib, self._lib.ceg_plan_build_fused(self._h, lv, tv, lc, tc, i_begin, i_end, d_vdw,
+                                                             d_coulomb, channel_stride, i_origin, algo, stream))
+
+    # ------------------------------------------------------------------ raw FP64 sums at points
+    def eval_points(self, which: str, points, algo: int = _abi.ALGO_AUTO) -> np.ndarray:
+        """compute_derivatives_vdw / _ewald (probes.jl:71-117) at cartesian points ->
+        float64[n, 8] (value, d1[3], d2[3], d3)."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        out = np.empty((len(pts), 8), dtype=np.float64)
+        w = {"vdw": 0, "coulomb": 1}[which]
+        _abi.check(self._lib, self._lib.ceg_plan_eval_points(self._h, w, algo, _abi.dptr(pts), len(pts), _abi.dptr(out)))
+        return out
+
+
+class GridPlan(_PlainBuilds):
     def __init__(self, cset: GridCoordinatesSetup, vdw: Optional[ProbeSystem] = None,
                  coulomb: Optional[ProbeSystem] = None, alpha: float = 0.0, device: int = 0):
         if vdw is None and coulomb is None:
@@ -82,38 +117,8 @@ class GridPlan:
         except Exception:
             pass
 
-    # ------------------------------------------------------------------ builds (device pointers)
-    def build_vdw(self, d_out: int, channel_stride: int, i_begin: int, i_end: int, i_origin: int = 0,
-                  algo: int = _abi.ALGO_AUTO, stream: int = 0) -> None:
-        lam, thr = vdw_scaling()
-        _abi.check(self._lib, self._lib.ceg_plan_build_vdw(self._h, lam, thr, i_begin, i_end, d_out, channel_stride,
-                                                           i_origin, algo, stream))
 
-    def build_coulomb(self, d_out: int, channel_stride: int, i_begin: int, i_end: int, i_origin: int = 0,
-                      algo: int = _abi.ALGO_AUTO, stream: int = 0) -> None:
-        lam, thr = coulomb_scaling()
-        _abi.check(self._lib, self._lib.ceg_plan_build_coulomb(self._h, lam, thr, i_begin, i_end, d_out,
-                                                               channel_stride, i_origin, algo, stream))
-
-    def build_fused(self, d_vdw: int, d_coulomb: int, channel_stride: int, i_begin: int, i_end: int,
-                    i_origin: int = 0, algo: int = _abi.ALGO_AUTO, stream: int = 0) -> None:
-        lv, tv = vdw_scaling()
-        lc, tc = coulomb_scaling()
-        _abi.check(self._lib, self._lib.ceg_plan_build_fused(self._h, lv, tv, lc, tc, i_begin, i_end, d_vdw,
-                                                             d_coulomb, channel_stride, i_origin, algo, stream))
-
-    # ------------------------------------------------------------------ raw FP64 sums at points
-    def eval_points(self, which: str, points, algo: int = _abi.ALGO_AUTO) -> np.ndarray:
-        """compute_derivatives_vdw / _ewald (probes.jl:71-117) at cartesian points ->
-        float64[n, 8] (value, d1[3], d2[3], d3)."""
-        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
-        out = np.empty((len(pts), 8), dtype=np.float64)
-        w = {"vdw": 0, "coulomb": 1}[which]
-        _abi.check(self._lib, self._lib.ceg_plan_eval_points(self._h, w, algo, _abi.dptr(pts), len(pts), _abi.dptr(out)))
-        return out
-
-
-class MultiGridPlan:
+class MultiGridPlan(_PlainBuilds):
     """The K VdW probes (one grid each) + optionally the charges of ONE framework made resident on one GPU
     (``ceg_plan_create_multi``): what ``setup_RASPA`` needs for a molecule -- one ``create_grid_vdw`` per distinct
     guest atom and one ``create_grid_coulomb`` (raspa.jl:497-520) -- from one lattice-image list in one pass.

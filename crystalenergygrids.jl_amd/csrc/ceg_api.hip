@@ -1306,10 +1306,15 @@ int run(ceg_plan* p, int mode, const Output& out, const Points& pts, bool culled
 {
     if (mode != MODE_COULOMB && !p->has_rules) return fail(CEG_ERR_INVALID, "plan was created without rules");
     if (mode != MODE_VDW && !p->has_charge) return fail(CEG_ERR_INVALID, "plan was created without charges");
-    RuleTable rt{p->d_rules, p->d_offset, p->nkinds};
+    RuleTable rt{p->d_rules, p->d_offset, p->nkinds};          // (a multi-probe plan keeps probe 0's rules here: brute force uses probe 0 too)
     hipError_t e;
     if (culled) {
-        e = launch_culled(mode, p->d_pc, p->g, p->vdwk, p->ew2 ? 2 : (p->fast_ewald ? 1 : 0), out, pts, stream);
+        // a multi-probe plan: the ordinary calls use probe 0, i.e. ITS constant block (rule classes, the tabulated Buckingham
+        // class, the per-image flags of that probe) and ITS hot-loop variant -- the plan-level block carries the union image flags
+        // and no Buckingham table.  The Coulomb grid alone needs no probe: the plan-level block, as in ceg_plan_build_multi.
+        const bool probe0 = p->nprobes > 0 && mode != MODE_COULOMB;
+        e = launch_culled(mode, probe0 ? p->probes[0].d_pc : p->d_pc, p->g, probe0 ? p->probes[0].vdwk : p->vdwk,
+                          p->ew2 ? 2 : (p->fast_ewald ? 1 : 0), out, pts, stream);
     } else {
         AtomTable at{p->d_atoms, p->has_rules ? p->d_kind : nullptr, p->natoms};
         e = launch_bruteforce(mode, p->g, at, rt, out, pts, stream);

@@ -297,6 +297,8 @@ __device__ __forceinline__ void mc_trial_row(const McView& v, int32_t molecule, 
     KChunk cur;
     if (v.nk > 0 && do_ewald) load_chunk(tid, cur);
     double4 A_first = make_double4(0.0, 0.0, 0.0, 0.0);             // likewise the first guest atom of this thread
+    // (with no guest this reads slot 0 of the minimum array ceg_mc_create allocates and zeroes: in bounds, and used by no pair.  A test
+    //  of natoms here moves the register allocation of the batch-1 kernels, which tests/test_mc_chains_static.py pins.)
     if (do_pairs && !CELLS) A_first = v.atoms[tid < v.natoms ? tid : 0];
     __syncthreads();
 
@@ -1311,6 +1313,7 @@ struct ceg_mc {
     // set when a state-changing call failed after it had started to change the host mirror (counts, slot lists, cell lists) or the
     // device state: host and device may then disagree, so every later call fails until ceg_mc_set_guests rebuilds both
     bool poisoned = false;
+    bool guests_set = false;                     // ceg_mc_set_guests has succeeded at least once (what a chain group asks of its members)
     uint64_t v_version = 1;                      // bumped wherever `v` is written (a group re-uploads its copy of `v` when this moved)
     ceg_mc_group* group = nullptr;               // the chain group this handle belongs to (its work then runs on the group's stream)
     hipStream_t own_stream = nullptr;            // the handle's own stream while it is in a group
@@ -1318,6 +1321,7 @@ struct ceg_mc {
 
 namespace {
 int rebuild_cells(ceg_mc* h);
+int ensure_capacity(ceg_mc* h, int64_t natoms, int64_t nmol);
 
 int poison(ceg_mc* h, int rc)
 {
@@ -1451,6 +1455,11 @@ extern "C" int ceg_mc_create(ceg_mc_t** handle, int32_t device, ceg_interp_t* co
     v.vdw = h->d_vdw; v.kind_charge = h->d_charge; v.rules = h->d_rules; v.rule_offset = h->d_offset;
     v.ijk = h->d_ijk; v.kf = h->d_kf; v.sf_fw = h->d_fw; v.sf_tot = h->d_tot;
     v.desc = h->d_desc; v.qof = h->d_qof; v.geom = h->d_geom;
+    // the handle is an empty box from here on (what ceg_mc_set_guests with nmol = 0 leaves): the minimum atom / molecule arrays,
+    // so that no kernel of a trial insertion or of the first ceg_mc_insert is handed a null array
+    h->free_runs.assign(MC_MAX_ATOMS + 1, {});
+    if (int rc = ensure_capacity(h, 1, 1)) { ceg_mc_destroy(h); return rc; }
+    if (hipMemset(h->d_atoms, 0, 2 * sizeof(double4) * (size_t)h->atoms_cap) != hipSuccess) { ceg_mc_destroy(h); return merr(CEG_ERR_HIP, "hipMemset failed"); }
     {
         CellMirror& cm = h->cm;
         cm.bins = ceg_consumers::choose_cell_bins(invmat, cutoff);
@@ -1911,6 +1920,7 @@ extern "C" int ceg_mc_set_guests(ceg_mc_t* h, const double* positions, const int
             return merr(CEG_ERR_HIP, "structure-factor kernels failed");
     }
     h->poisoned = false;
+    h->guests_set = true;
     return CEG_OK;
 }
 
@@ -2193,7 +2203,7 @@ extern "C" int ceg_mc_group_create(ceg_mc_group_t** group, ceg_mc_t* const* chai
         for (int32_t d = 0; d < c; ++d)
             if (chains[d] == h) return group_bad(c, "the handle appears twice");
         if (h->group) return group_bad(c, "the handle is already in a group");
-        if (!h->d_atoms || !h->d_molidx) return group_bad(c, "ceg_mc_set_guests has never been called on the handle");
+        if (!h->guests_set) return group_bad(c, "ceg_mc_set_guests has never been called on the handle");
     }
     Guard guard(chains[0]->device);
     if (!guard.ok) return merr(CEG_ERR_HIP, "hipSetDevice failed");

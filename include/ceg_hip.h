@@ -481,6 +481,8 @@ CEG_API int ceg_pairs_neighbour_cells(ceg_pairs_t* handle, int32_t nb[3]);
  */
 typedef struct ceg_mc ceg_mc_t;
 
+/* A new handle is an EMPTY BOX and usable as it is: ceg_mc_trial_insert / _insert_device, ceg_mc_insert and ceg_mc_get_state need no
+ * ceg_mc_set_guests first (a GCMC isotherm starts there); ceg_mc_set_guests with nmol = 0 gives the same state. */
 CEG_API int ceg_mc_create(ceg_mc_t** handle, int32_t device, ceg_interp_t* const* vdw_grids, ceg_interp_t* coulomb_grid,
                           const double* kind_charge, int32_t nkinds, const double mat[9], const double invmat[9],
                           double cutoff2, const ceg_rule_t* rules, const int32_t* rule_offset, double coulombic,

@@ -223,4 +223,5 @@ class OracleMonteCarlo:
         return self.sums_re[:, 0] + 1j * self.sums_im[:, 0]
 
     def flat_positions(self) -> np.ndarray:
-        return np.concatenate([p for _i, _j, p in self.molecules()])
+        mols = [p for _i, _j, p in self.molecules()]
+        return np.concatenate(mols) if mols else np.empty((0, 3))
