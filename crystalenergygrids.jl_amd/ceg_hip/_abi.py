@@ -158,6 +158,10 @@ PROTOTYPES = {
     "ceg_mc_group_destroy": (C.c_int, [C.c_void_p]),
     "ceg_mc_group_trial": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p, C.c_int32, c_double_p, c_double_p]),
     "ceg_mc_group_accept": (C.c_int, [C.c_void_p, c_int32_p, c_double_p]),
+    "ceg_energy_grid": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, c_double_p, c_double_p, C.c_int32,
+                                  c_double_p, C.c_int32, c_double_p, c_int32_p,
+                                  C.c_void_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                  C.c_double, C.c_double, C.c_void_p, C.c_int32, C.c_void_p]),
     "ceg_recip_energy_device": (C.c_int, [C.c_void_p, C.c_void_p, c_double_p, C.c_int32, C.c_int64, C.c_double, C.c_double,
                                           C.c_void_p, C.c_void_p]),
 }

@@ -111,6 +111,52 @@ class GpuEnergySetup:
         e = self.energy_points(pos)
         return (e[:, 0] + e[:, 1]).reshape(numA, numB, numC)
 
+    def energy_grid_rotations(self, step: float, rotations, out_device_ptr: Optional[int] = None, stream: int = 0) -> np.ndarray:
+        """``energy_grid(setup, step, num_rotate)`` for a polyatomic guest (grids.jl:346-424) in ONE device pass
+        (``ceg_energy_grid``): float64[nrot, numA, numB, numC] of ``sum(energy_point)`` with the molecule turned by
+        ``rotations[k]`` (3x3, applied as ``r @ p``, grids.jl:389; e.g. from :func:`ceg_hip.hostmirror.lebedev.rotation_matrices`)
+        on the lattice of :meth:`energy_grid`.  The array is a view of the buffer in Julia's memory order of ``allvals``
+        (rotation fastest).  With ``out_device_ptr`` (device memory for nrot*numA*numB*numC doubles) the result stays on the
+        device, the call is asynchronous on ``stream`` and the lattice shape is returned instead."""
+        s = self.setup
+        lib = _abi.load_library()
+        a, b, c = s.framework.mat[:, 0], s.framework.mat[:, 1], s.framework.mat[:, 2]
+        numA = int(math.floor(np.linalg.norm(a) / step)) + 1
+        numB = int(math.floor(np.linalg.norm(b) / step)) + 1
+        numC = int(math.floor(np.linalg.norm(c) / step)) + 1
+        steps = np.ascontiguousarray(np.stack([a / numA, b / numB, c / numC]).reshape(-1))      # columns stepA, stepB, stepC
+        num = np.array([numA, numB, numC], dtype=np.int32)
+        rot = np.asarray(rotations, dtype=np.float64).reshape(-1, 3, 3)
+        nrot = len(rot)
+        rot_cm = np.ascontiguousarray(rot.transpose(0, 2, 1).reshape(-1))                       # column-major
+        base = np.ascontiguousarray(np.asarray(s.molecule.position, dtype=np.float64).reshape(-1, 3))
+        natoms = len(base)
+        q = np.ascontiguousarray(s.charges, dtype=np.float64)
+        handles = (C.c_void_p * natoms)(*[self.vdw[i]._h if self.vdw[i] is not None else None for i in s.atomsidx])
+        enc = static = 0.0
+        if self.has_coulomb:
+            enc, static = ewald_context_constants(s.ewald, ((s.molecule,),))
+        if s.block.empty:
+            bargs = (None, None, None, None, None, None)
+            keep = ()
+        else:
+            cs = s.block.csetup
+            mask = np.ascontiguousarray(s.block.block, dtype=np.uint8)
+            keep = (mask, np.ascontiguousarray(cs.dims, dtype=np.int32), np.ascontiguousarray(cs.size, dtype=np.float64),
+                    np.ascontiguousarray(cs.shift, dtype=np.float64), _matT(cs.cell.mat), _matT(cs.cell.invmat))
+            bargs = (keep[0].ctypes.data, _abi.i32ptr(keep[1]), _abi.dptr(keep[2]), _abi.dptr(keep[3]), _abi.dptr(keep[4]), _abi.dptr(keep[5]))
+        on_device = out_device_ptr is not None
+        buf = None if on_device else np.empty(nrot * numA * numB * numC, dtype=np.float64)
+        _abi.check(lib, lib.ceg_energy_grid(handles, self.coulomb._h if self.has_coulomb else None, self.recip._h if self.has_coulomb else None,
+                                            _abi.dptr(base.reshape(-1)), _abi.dptr(q), natoms, _abi.dptr(rot_cm), nrot, _abi.dptr(steps),
+                                            _abi.i32ptr(num), *bargs, enc, static,
+                                            C.c_void_p(int(out_device_ptr)) if on_device else buf.ctypes.data, 1 if on_device else 0,
+                                            C.c_void_p(stream) if stream else None))
+        del keep
+        if on_device:
+            return (nrot, numA, numB, numC)
+        return buf.reshape(numC, numB, numA, nrot).transpose(3, 2, 1, 0)
+
     def close(self) -> None:
         for it in self.vdw:
             if it is not None:

@@ -53,9 +53,15 @@ class GridCoordinatesSetup:
 
 
 def wrap_atom(point, cell: CellMatrix) -> np.ndarray:
-    """coordinates.jl:58-61"""
-    abc = cell.invmat @ np.asarray(point, dtype=np.float64)
-    return cell.mat @ (abc - np.floor(abc))
+    """coordinates.jl:58-61.  The two products are the reference's SMatrix * SVector: each component is summed left to right from
+    separately rounded products (no fused multiply-add), as ``ceg_consumers::interp_point`` and the oracle do.  A BLAS ``@`` sums
+    in its own order, and for a point ON a cell face that decides whether the fractional coordinate is 0.0 or -6e-18, i.e. on
+    which face of the cell the point is looked up."""
+    p = np.asarray(point, dtype=np.float64)
+    I, M = cell.invmat, cell.mat
+    abc = (I[:, 0] * p[0] + I[:, 1] * p[1]) + I[:, 2] * p[2]
+    abc = abc - np.floor(abc)
+    return (M[:, 0] * abc[0] + M[:, 1] * abc[1]) + M[:, 2] * abc[2]
 
 
 def offsetpoint(point, csetup: GridCoordinatesSetup) -> np.ndarray:

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <vector>
 
 #include "../../include/ceg_hip.h"
 #include "ceg_internal.h"
@@ -450,3 +451,20 @@ struct ceg_interp {
     ceg_consumers::HostIo io;          // ceg_interp_points
 };
 
+
+// the reciprocal-Ewald handle (ceg_recip.hip owns its life cycle; ceg_egrid.hip reads the k-vectors and their constants)
+struct ceg_recip {
+    int device = 0;
+    int64_t nk = 0;
+    int32_t ks[3] = {0, 0, 0};
+    double invmat[9];
+    // the k-vectors regrouped into rows (j, k) x (i0 .. i0 + len - 1), cut into segments and dealt to the lanes (see k_recip)
+    int nrounds = 0, ns = 0;
+    std::vector<int64_t> slot_of;       // plane index (slot * 64 + lane) of k-vector q
+    std::vector<double> h_kf;
+    std::vector<int32_t> h_ijk;         // [3 nk] in the caller's order
+    std::vector<double> h_sf_re, h_sf_im;      // the structure factor currently summed against, caller's order
+    int32_t* d_desc = nullptr;
+    double* d_c = nullptr;              // planes A, B, kf: [3][ns * 64]
+    ceg_consumers::HostIo io;           // ceg_recip_energy
+};

@@ -139,19 +139,7 @@ int rerr(int code, const char* msg)
 
 }  // namespace
 
-struct ceg_recip {
-    int device = 0;
-    int64_t nk = 0;
-    int32_t ks[3] = {0, 0, 0};
-    double invmat[9];
-    // the k-vectors regrouped into rows (j, k) x (i0 .. i0 + len - 1), cut into segments and dealt to the lanes (see the kernel)
-    int nrounds = 0, ns = 0;
-    std::vector<int64_t> slot_of;       // plane index (slot * 64 + lane) of k-vector q
-    std::vector<double> h_kf;
-    int32_t* d_desc = nullptr;
-    double* d_c = nullptr;              // planes A, B, kf: [3][ns * 64]
-    ceg_consumers::HostIo io;           // ceg_recip_energy
-};
+// struct ceg_recip: ceg_consumers.h (ceg_egrid.hip reads the k-space tables of a handle)
 
 namespace {
 
@@ -166,6 +154,8 @@ int upload_constants(ceg_recip* h, const double* sf_re, const double* sf_im)
         c[plane + at] = t * sf_im[q];
         c[2 * plane + at] = t;
     }
+    h->h_sf_re.assign(sf_re, sf_re + h->nk);       // natural-order copy for ceg_energy_grid
+    h->h_sf_im.assign(sf_im, sf_im + h->nk);
     return hipMemcpy(h->d_c, c.data(), 3 * plane * sizeof(double), hipMemcpyHostToDevice) == hipSuccess ? 0 : 1;
 }
 
@@ -217,6 +207,7 @@ extern "C" int ceg_recip_create(ceg_recip_t** handle, int32_t device, const int3
     h->ns = best.ns;
     h->slot_of = std::move(best.slot_of);
     h->h_kf.assign(kfactors, kfactors + nk);
+    h->h_ijk.assign(kvec_ijk, kvec_ijk + 3 * nk);
     const size_t plane = std::max<size_t>((size_t)h->ns * 64, 1), nd = std::max<size_t>((size_t)h->nrounds * 64, 1);
     bool ok = hipMalloc((void**)&h->d_desc, nd * sizeof(int32_t)) == hipSuccess &&
               hipMalloc((void**)&h->d_c, 3 * plane * sizeof(double)) == hipSuccess;

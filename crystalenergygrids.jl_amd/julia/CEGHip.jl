@@ -26,7 +26,8 @@ using CrystalEnergyGrids: ProbeSystem, ForceField, InteractionRule, InteractionR
                           EwaldFramework, GridCoordinatesSetup, GRID_TO_KELVIN,
                           COULOMBIC_CONVERSION_FACTOR, TÅ
 using Unitful, UnitfulAtomic
-using AtomsBase: AbstractSystem
+using AtomsBase: AbstractSystem, position
+using LinearAlgebra: norm
 using StaticArrays
 
 const LIB = Ref(get(ENV, "CEG_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libceg_hip.so")))
@@ -633,6 +634,78 @@ function block_spheres(csetup::GridCoordinatesSetup, centers::Vector{SVector{3,F
         (Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{UInt8}),
         device, dims, Δ, shift, m, im, ortho, safemin^2, cs, radius2, length(radius2), mask))
     CEG.BlockFile(csetup, _to_bitarray(mask, a, b, c))
+end
+
+# ------------------------------------------------------------------ energy_grid for polyatomic guests (ceg_energy_grid)
+"""
+    energy_grid_rotations(setup, vdw, coulomb, recip, rots, numABC, stepABC) -> Array{Float64,4}
+
+`allvals[k, iA, iB, iC]` of energy_grid (src/grids.jl:391-419) from ONE device pass: `vdw` = interpolation handle of each grid of
+`setup.grids` (C_NULL for a zero grid), `coulomb` / `recip` = handles of the Coulomb grid and of `setup.ewald` (both C_NULL when the
+framework carries no charges), `rots` the rotation matrices (any source: `get_rotation_matrices`), `stepABC` the three step vectors (Å).
+The array is the buffer the library filled: its element order is Julia's.
+"""
+function energy_grid_rotations(setup::CEG.CrystalEnergySetup, vdw::Vector{Ptr{Cvoid}}, coulomb::Ptr{Cvoid}, recip::Ptr{Cvoid},
+                               rots, numABC::NTuple{3,Int}, stepABC)
+    molecule = setup.molecule
+    base = Float64[NoUnits(x/u"Å") for p in position(molecule) for x in p]                   # grids.jl:356
+    natoms = length(setup.atomsidx)
+    handles = Ptr{Cvoid}[vdw[setup.atomsidx[i]] for i in 1:natoms]                             # grids.jl:316
+    rotv = Float64[x for r in rots for x in r]                                               # SMatrix iterates column-major
+    steps = Float64[x for s in stepABC for x in s]
+    num = Int32[numABC...]
+    enc = 0.0; static = 0.0
+    if coulomb != C_NULL
+        ctx = CEG.EwaldContext(setup.ewald, ((molecule,),))                                  # grids.jl:365
+        enc = NoUnits(ctx.energy_net_charges/u"K"); static = NoUnits(ctx.static_contribution[]/u"K")
+    end
+    blk = setup.block
+    cs = blk.csetup
+    mask = blk.empty ? UInt8[] : vec(UInt8.(permutedims(blk.block, (3, 2, 1))))              # [x][y][z], z fastest
+    bdims, bsize, bshift, _ = _geometry(cs)
+    bmat = Vector{Float64}(vec(NoUnits.(cs.cell.mat ./ u"Å"))); binv = Vector{Float64}(vec(NoUnits.(cs.cell.invmat .* u"Å")))
+    out = Array{Float64,4}(undef, length(rots), numABC[1], numABC[2], numABC[3])             # grids.jl:391
+    GC.@preserve handles base rotv steps num mask bdims bsize bshift bmat binv out _check(ccall((:ceg_energy_grid, LIB[]), Cint,
+        (Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Int32},
+         Ptr{UInt8}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Int32, Ptr{Cvoid}),
+        handles, coulomb, recip, base, setup.charges, natoms, rotv, length(rots), steps, num,
+        (blk.empty ? Ptr{UInt8}(C_NULL) : pointer(mask)), bdims, bsize, bshift, bmat, binv, enc, static, out, 0, C_NULL))
+    out
+end
+
+"""
+    energy_grid(setup::CrystalEnergySetup, step, num_rotate=40)
+
+The reference's energy_grid (src/grids.jl:346-424) with the loop nest :394-419 on the GPU; lattice (:378-384) and rotations (:385-390,
+`get_rotation_matrices`) are the reference's own.  Not covered: `num_rotate < 0` (random offsets, :404-406), the scratchspace cache
+(:349-354) and a `MonteCarloSetup` -- for those call `CrystalEnergyGrids.energy_grid`.
+"""
+function energy_grid(setup::CEG.CrystalEnergySetup, step, num_rotate=40)
+    num_rotate < 0 && return CEG.energy_grid(setup, step, num_rotate)
+    molecule = setup.molecule
+    axeA, axeB, axeC = CEG.bounding_box(setup.framework)
+    numA = floor(Int, norm(axeA) / step) + 1
+    numB = floor(Int, norm(axeB) / step) + 1
+    numC = floor(Int, norm(axeC) / step) + 1
+    stepABC = (NoUnits.(axeA ./ numA ./ u"Å"), NoUnits.(axeB ./ numB ./ u"Å"), NoUnits.(axeC ./ numC ./ u"Å"))
+    rots = if num_rotate == 0 || length(molecule) == 1
+        [one(SMatrix{3,3,Float64,9})]
+    else
+        first(CEG.get_rotation_matrices(molecule, num_rotate))
+    end
+    vdw = Ptr{Cvoid}[g.ewald_precision == Inf ? interp_handle(g) : C_NULL for g in setup.grids]
+    withcoulomb = setup.coulomb.ewald_precision != -Inf
+    coulomb = withcoulomb ? interp_handle(setup.coulomb) : C_NULL
+    recip = withcoulomb ? recip_handle(setup.ewald) : C_NULL
+    try
+        return energy_grid_rotations(setup, vdw, coulomb, recip, rots, (numA, numB, numC), stepABC)
+    finally
+        for h in vdw
+            h == C_NULL || ccall((:ceg_interp_destroy, LIB[]), Cint, (Ptr{Cvoid},), h)
+        end
+        withcoulomb && ccall((:ceg_interp_destroy, LIB[]), Cint, (Ptr{Cvoid},), coulomb)
+        withcoulomb && ccall((:ceg_recip_destroy, LIB[]), Cint, (Ptr{Cvoid},), recip)
+    end
 end
 
 # ------------------------------------------------------------------ build + file in one call (row f4)

@@ -414,6 +414,44 @@ CEG_API int ceg_recip_energy_device(ceg_recip_t* handle, const double* d_positio
  * of the moved molecule for every trial placement. */
 CEG_API int ceg_recip_set_structure_factor(ceg_recip_t* handle, const double* sf_re, const double* sf_im);
 
+/* ---- energy_grid for a rigid molecule in many orientations (SURVEY 8f, rows f1 + f2 on a lattice) ---- */
+/*
+ * energy_grid (src/grids.jl:346-424) of a CrystalEnergySetup: for every point (iA, iB, iC) of the lattice
+ * iA*stepA + iB*stepB + iC*stepC (:382-384, :396) and every orientation k of the molecule, sum(energy_point(...)) (:311-327) with the
+ * atoms at offset + rotations[k] * base[a] (:389, :409): 1e100 when an atom sits on a blocked node of the BlockFile, else
+ *   sum_a interpolate_grid(vdw grid of atom a) + sum_a q_a interpolate_grid(coulomb grid) + compute_ewald of the molecule there.
+ * The atom positions are generated on the device and never stored; the reciprocal term uses the lattice: the structure factor of
+ * the molecule is (phase of the offset) x (structure factor of the rotated molecule), so all placements share one real matrix
+ * product over the k-vectors (csrc/ceg_egrid.hip) instead of one table build and one k-space walk per placement.
+ *
+ *  vdw_grids     [natoms] handle of the VdW grid of each atom (setup.grids[atomsidx[i]]); NULL = zero grid -> 0 K
+ *  coulomb_grid  NULL: setup.coulomb.ewald_precision == -Inf, the Coulomb terms are 0 (grids.jl:317)
+ *  recip         NULL iff coulomb_grid is NULL; the structure factor it currently holds is the one summed against
+ *  base          [natoms][3] A: position(molecule);  charges [natoms] e: setup.charges;  natoms 1 .. 16
+ *  rotations     [nrot][9] column-major, applied as r * p (grids.jl:389); ANY 3x3 matrix, not checked for orthogonality;  nrot >= 1
+ *  steps         stepA, stepB, stepC as columns (grids.jl:382-384);  num = numA, numB, numC
+ *  block         NULL = no blocking; else the BlockFile mask [block_dims[0]+1][block_dims[1]+1][block_dims[2]+1] (z fastest, 1 =
+ *                blocked) as ceg_block_* writes it, host memory, with the csetup of the BlockFile (coordinates.jl:58-70, 83-101):
+ *                block_dims / block_size / block_shift as for the grids, block_mat / block_invmat the unit cell
+ *  energy_net_charges, static_contribution   the two EwaldContext constants, as ceg_recip_energy
+ *  out           nrot*numA*numB*numC doubles in Julia's memory order of `allvals`: element (k, iA, iB, iC), 0-based, at
+ *                k + nrot*(iA + numA*(iB + numB*iC)).  out_on_device = 1: device memory on the handles' device, asynchronous on
+ *                `stream`.  out_on_device = 0: host memory, synchronous; the lattice travels in slabs of iC of at most
+ *                CEG_HIP_EGRID_SLAB_BYTES (default 256 MiB; at least one iC plane), so the device holds one slab besides the
+ *                tables.  The result does not depend on the slab size, nor on where `out` lives, bit for bit.
+ * All handles must live on one device (CEG_ERR_INVALID otherwise); natoms > 16 -> CEG_ERR_UNSUPPORTED.
+ * Not covered: the MonteCarloSetup variant (energy_point_mc!, guests retained), the num_rotate < 0 random-offset mode
+ * (grids.jl:404-406), the scratchspace cache (:349-354, host business) and the Lebedev tables (an artifact the reference
+ * downloads): the rotation matrices are an input.
+ */
+CEG_API int ceg_energy_grid(ceg_interp_t* const* vdw_grids, ceg_interp_t* coulomb_grid, ceg_recip_t* recip,
+                            const double* base, const double* charges, int32_t natoms,
+                            const double* rotations, int32_t nrot, const double steps[9], const int32_t num[3],
+                            const uint8_t* block, const int32_t block_dims[3], const double block_size[3], const double block_shift[3],
+                            const double block_mat[9], const double block_invmat[9],
+                            double energy_net_charges, double static_contribution,
+                            double* out, int32_t out_on_device, void* stream);
+
 /* ---- guest-guest pair energies for trial placements ---------------- */
 /*
  * single_contribution_vdw (src/energy.jl:397-427, the exhaustive variant :407-427) of a rigid
