@@ -21,11 +21,7 @@
 #include <initializer_list>
 
 #include "ceg_internal.h"
-
-namespace ceg_host {
-hipError_t pool_malloc(void** out, size_t bytes);      // the plan-table block cache of ceg_api.hip
-void pool_free(void* ptr);
-}
+#include "ceg_host.h"      // pool_malloc / pool_free: the plan-table block cache of ceg_api.hip
 
 namespace ceg {
 

@@ -3,12 +3,14 @@
 # Writes gpurun_out/pmc_<tag>/summary.json; merge it into profiles/pmc_summary.json under <pmc key> with scripts/pmc_merge.py.
 # Only the TIMED launches of bench.py count (its 3 set-up launches and the warm-up launch are dropped, like scripts/kernel_stats.sh
 # does for the durations), and the summary records which library it was taken on (sha256 of the kernel sources, git commit, host).
+# A pass that fails ends the script with status 1: nothing more is launched on the card and no summary is written.
 tag=$1; shift
 key=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/pmc_$tag
 steps=3; warm=1
 i=0
+timeout() { command timeout "$@" || { local rc=$?; pass_failed=1; return $rc; }; }     # remembers a failed pass for the check below
 for ctrs in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM" \
             "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY" \
             "SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_THREAD_CYCLES_VALU SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE" \
@@ -17,6 +19,7 @@ for ctrs in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_
             "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $ctrs --output-format csv -d gpurun_out/pmc_$tag/p$i -- python bench.py --steps $steps --warmup $warm --cpu-rows 0 --no-check --no-oneshot "$@" > gpurun_out/pmc_$tag/p$i.log 2>&1 || { echo "pass $i ($ctrs) failed"; tail -5 gpurun_out/pmc_$tag/p$i.log; }
+  [ -z "$pass_failed" ] || { echo "stopping: no further pass is started"; exit 1; }
 done
 python - "$tag" "$key" "$steps" "$warm" "$*" <<'PY'
 import csv, glob, collections, hashlib, json, os, socket, subprocess, sys
