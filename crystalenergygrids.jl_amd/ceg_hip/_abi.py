@@ -162,11 +162,17 @@ PROTOTYPES = {
                                   c_double_p, C.c_int32, c_double_p, c_int32_p,
                                   C.c_void_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                   C.c_double, C.c_double, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ceg_energy_grid_reduced": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, c_double_p, c_double_p, C.c_int32,
+                                          c_double_p, C.c_int32, c_double_p, c_int32_p,
+                                          C.c_void_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                          C.c_double, C.c_double, c_double_p, C.c_int32, c_double_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "ceg_recip_energy_device": (C.c_int, [C.c_void_p, C.c_void_p, c_double_p, C.c_int32, C.c_int64, C.c_double, C.c_double,
                                           C.c_void_p, C.c_void_p]),
 }
 
 ALGO_AUTO, ALGO_BRUTEFORCE, ALGO_CULLED = 0, 1, 2
+EGRID_MAX_TEMPS = 8          # CEG_EGRID_MAX_TEMPS
 
 
 class CegError(RuntimeError):

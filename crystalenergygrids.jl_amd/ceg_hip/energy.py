@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -58,6 +58,13 @@ class ReciprocalEwald:
             self.close()
         except Exception:
             pass
+
+
+class ReducedEnergyGrid(NamedTuple):
+    """What :meth:`GpuEnergySetup.energy_grid_reduced` returns; an output that was not asked for is None."""
+    mean: Optional[np.ndarray]
+    min: Optional[np.ndarray]
+    argmin: Optional[np.ndarray]
 
 
 class GpuEnergySetup:
@@ -111,15 +118,10 @@ class GpuEnergySetup:
         e = self.energy_points(pos)
         return (e[:, 0] + e[:, 1]).reshape(numA, numB, numC)
 
-    def energy_grid_rotations(self, step: float, rotations, out_device_ptr: Optional[int] = None, stream: int = 0) -> np.ndarray:
-        """``energy_grid(setup, step, num_rotate)`` for a polyatomic guest (grids.jl:346-424) in ONE device pass
-        (``ceg_energy_grid``): float64[nrot, numA, numB, numC] of ``sum(energy_point)`` with the molecule turned by
-        ``rotations[k]`` (3x3, applied as ``r @ p``, grids.jl:389; e.g. from :func:`ceg_hip.hostmirror.lebedev.rotation_matrices`)
-        on the lattice of :meth:`energy_grid`.  The array is a view of the buffer in Julia's memory order of ``allvals``
-        (rotation fastest).  With ``out_device_ptr`` (device memory for nrot*numA*numB*numC doubles) the result stays on the
-        device, the call is asynchronous on ``stream`` and the lattice shape is returned instead."""
+    def _egrid_arguments(self, step: float, rotations):
+        """Lattice (grids.jl:378-384) and every argument ``ceg_energy_grid`` and ``ceg_energy_grid_reduced`` share, up to and
+        including ``static_contribution`` -> (args, objects the pointers in args refer to, nrot, (numA, numB, numC))."""
         s = self.setup
-        lib = _abi.load_library()
         a, b, c = s.framework.mat[:, 0], s.framework.mat[:, 1], s.framework.mat[:, 2]
         numA = int(math.floor(np.linalg.norm(a) / step)) + 1
         numB = int(math.floor(np.linalg.norm(b) / step)) + 1
@@ -145,17 +147,71 @@ class GpuEnergySetup:
             keep = (mask, np.ascontiguousarray(cs.dims, dtype=np.int32), np.ascontiguousarray(cs.size, dtype=np.float64),
                     np.ascontiguousarray(cs.shift, dtype=np.float64), _matT(cs.cell.mat), _matT(cs.cell.invmat))
             bargs = (keep[0].ctypes.data, _abi.i32ptr(keep[1]), _abi.dptr(keep[2]), _abi.dptr(keep[3]), _abi.dptr(keep[4]), _abi.dptr(keep[5]))
+        args = (handles, self.coulomb._h if self.has_coulomb else None, self.recip._h if self.has_coulomb else None,
+                _abi.dptr(base.reshape(-1)), _abi.dptr(q), natoms, _abi.dptr(rot_cm), nrot, _abi.dptr(steps),
+                _abi.i32ptr(num), *bargs, enc, static)
+        return args, (handles, base, q, rot_cm, steps, num, keep), nrot, (numA, numB, numC)
+
+    def energy_grid_rotations(self, step: float, rotations, out_device_ptr: Optional[int] = None, stream: int = 0) -> np.ndarray:
+        """``energy_grid(setup, step, num_rotate)`` for a polyatomic guest (grids.jl:346-424) in ONE device pass
+        (``ceg_energy_grid``): float64[nrot, numA, numB, numC] of ``sum(energy_point)`` with the molecule turned by
+        ``rotations[k]`` (3x3, applied as ``r @ p``, grids.jl:389; e.g. from :func:`ceg_hip.hostmirror.lebedev.rotation_matrices`)
+        on the lattice of :meth:`energy_grid`.  The array is a view of the buffer in Julia's memory order of ``allvals``
+        (rotation fastest).  With ``out_device_ptr`` (device memory for nrot*numA*numB*numC doubles) the result stays on the
+        device, the call is asynchronous on ``stream`` and the lattice shape is returned instead."""
+        lib = _abi.load_library()
+        args, keep, nrot, (numA, numB, numC) = self._egrid_arguments(step, rotations)
         on_device = out_device_ptr is not None
         buf = None if on_device else np.empty(nrot * numA * numB * numC, dtype=np.float64)
-        _abi.check(lib, lib.ceg_energy_grid(handles, self.coulomb._h if self.has_coulomb else None, self.recip._h if self.has_coulomb else None,
-                                            _abi.dptr(base.reshape(-1)), _abi.dptr(q), natoms, _abi.dptr(rot_cm), nrot, _abi.dptr(steps),
-                                            _abi.i32ptr(num), *bargs, enc, static,
-                                            C.c_void_p(int(out_device_ptr)) if on_device else buf.ctypes.data, 1 if on_device else 0,
+        _abi.check(lib, lib.ceg_energy_grid(*args, C.c_void_p(int(out_device_ptr)) if on_device else buf.ctypes.data, 1 if on_device else 0,
                                             C.c_void_p(stream) if stream else None))
         del keep
         if on_device:
             return (nrot, numA, numB, numC)
         return buf.reshape(numC, numB, numA, nrot).transpose(3, 2, 1, 0)
+
+    def energy_grid_reduced(self, step: float, rotations, temperatures=(), weights=None, want_min: bool = True,
+                            want_argmin: bool = False, out_device_ptrs=None, stream: int = 0):
+        """The rotation axis of :meth:`energy_grid_rotations` collapsed on the device (``ceg_energy_grid_reduced``): per lattice
+        point the reference's ``meanBoltzmann`` (utils.jl:415-443) at each of ``temperatures`` (K, at most 8) with the optional
+        ``weights[nrot]`` (its third argument, e.g. the Lebedev weights), the minimum over the orientations and the 0-based index
+        of the first orientation that attains it.  The nrot*numA*numB*numC elements never leave the device.
+
+        -> :class:`ReducedEnergyGrid` ``(mean, min, argmin)``: float64[ntemps, numA, numB, numC] (None without temperatures),
+        float64[numA, numB, numC] (None unless ``want_min``), int32[numA, numB, numC] (None unless ``want_argmin``).  With
+        ``out_device_ptrs = (mean, min, argmin)`` (device addresses in the layout of the C ABI, None where an output is not
+        wanted; ``want_min`` / ``want_argmin`` are then not looked at) the results stay on the device, the call is asynchronous
+        on ``stream`` and the lattice shape is returned instead."""
+        lib = _abi.load_library()
+        args, keep, nrot, (numA, numB, numC) = self._egrid_arguments(step, rotations)
+        temps = np.ascontiguousarray(np.atleast_1d(np.asarray(temperatures, dtype=np.float64)).reshape(-1))
+        ntemps = len(temps)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            if len(w) != nrot:
+                raise ValueError(f"{len(w)} weights for {nrot} rotations")
+        points = numA * numB * numC
+        on_device = out_device_ptrs is not None
+        if on_device:
+            outs = [C.c_void_p(int(p)) if p else None for p in out_device_ptrs]
+            p_mean = C.cast(outs[0], _abi.c_double_p) if outs[0] is not None else None
+        else:
+            mean = np.empty(ntemps * points, dtype=np.float64) if ntemps else None
+            mn = np.empty(points, dtype=np.float64) if want_min else None
+            amin = np.empty(points, dtype=np.int32) if want_argmin else None
+            p_mean = _abi.dptr(mean) if mean is not None else None
+            outs = [None, mn.ctypes.data if mn is not None else None, amin.ctypes.data if amin is not None else None]
+        _abi.check(lib, lib.ceg_energy_grid_reduced(*args, _abi.dptr(temps) if ntemps else None, ntemps,
+                                                    _abi.dptr(w) if w is not None else None, p_mean, outs[1], outs[2],
+                                                    1 if on_device else 0, C.c_void_p(stream) if stream else None))
+        del keep
+        if on_device:
+            return (numA, numB, numC)
+
+        def lattice(x, lead=()):
+            return None if x is None else x.reshape(lead + (numC, numB, numA)).transpose(*range(len(lead)), *(len(lead) + i for i in (2, 1, 0)))
+        return ReducedEnergyGrid(lattice(mean, (ntemps,)), lattice(mn), lattice(amin))
 
     def close(self) -> None:
         for it in self.vdw:

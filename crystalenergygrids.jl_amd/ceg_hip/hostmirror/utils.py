@@ -75,6 +75,36 @@ def prepare_periodic_distance_computations(mat: np.ndarray) -> Tuple[bool, float
     return ortho, safemin
 
 
+def mean_boltzmann(A, T: float, weights=None):
+    """utils.jl:415-443 -- Boltzmann mean over the FIRST axis of ``A`` (the rotation axis of ``allvals``) at temperature ``T`` (K),
+    optionally with one weight per entry of that axis.  1-D ``A``: a float (:417-428).  N-D ``A``: an array of shape
+    ``A.shape[1:]`` (:429-442); the loop over ``j`` runs in the reference's order for every column, the columns themselves
+    (independent of each other, threaded in the reference) are carried along as arrays."""
+    A = np.asarray(A, dtype=np.float64)
+    n = A.shape[0]
+    w = None if weights is None else np.asarray(weights, dtype=np.float64)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        if A.ndim == 1:
+            facts = np.float64(0.0)
+            tot = np.float64(0.0)
+            M = A.min() - 30.0 * T
+            for j in range(n):
+                y = A[j]
+                fact = np.exp((M - y) / T) * (True if w is None else w[j])
+                facts = facts + fact
+                tot = tot + fact * y
+            return float(tot / facts)
+        factors = np.zeros(A.shape[1:])
+        total = np.zeros(A.shape[1:])
+        m = A.min(axis=0) - 30.0 * T                              # exp(30.0) ~ 1e13
+        for j in range(n):
+            x = A[j]
+            factor = np.exp((m - x) / T) * (True if w is None else w[j])
+            factors = factors + factor
+            total = total + factor * x
+        return total / factors
+
+
 def get_atom_name(atom) -> str:
     """utils.jl:521-538 -- strip a trailing ``_<digits>`` (or trailing digits)."""
     name = str(atom)

@@ -19,9 +19,11 @@
 //                    entry per 2 x (number of rotation tiles) matrix instructions and keeps 4 accumulators per tile, where a
 //                    v_fma_f64 tile of the same shape would need every W entry in every lane or an LDS read per two FMAs.
 //   k_egrid_terms    per element: blocking mask, grid interpolations (ceg_consumers::interp_point, unchanged), the sum
+//   k_egrid_reduce   ceg_energy_grid_reduced only: the rotation axis of a finished slab collapsed per lattice point -- minimum, first
+//                    orientation that attains it, meanBoltzmann (src/utils.jl:415-443) at up to 8 temperatures
 //
-// Every element's arithmetic is independent of how the lattice is cut into launches, so slabbed host output, single-slab output and
-// device output are bit-identical.
+// Every element's arithmetic is independent of how the lattice is cut into launches, and so is the order in which k_egrid_reduce
+// combines the elements of a point, so slabbed host output, single-slab output and device output are bit-identical.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -280,6 +282,87 @@ __global__ __launch_bounds__(256) void k_egrid_terms(const EgridParams* __restri
     out[e] = val;
 }
 
+constexpr int RED_LANES = 16;       // lanes per lattice point of k_egrid_reduce (4 points per wave)
+
+struct ReduceTemps {
+    double T[CEG_EGRID_MAX_TEMPS];
+};
+
+// (value, index) of the smaller of two candidates with Julia's findmin order: a NaN beats every number, ties go to the lower index
+__device__ __forceinline__ void min_step(double& v, int& i, double ov, int oi)
+{
+    const bool vn = v != v, on = ov != ov;
+    const bool take = vn == on ? ((vn || ov == v) ? oi < i : ov < v) : on;
+    if (take) { v = ov; i = oi; }
+}
+
+// The rotation axis of a slab [point][rotation] collapsed: RED_LANES consecutive lanes own one point and read its nrot consecutive
+// doubles coalesced, lane l the rotations l, l + 16, ...  Pass 1: minimum and its first index.  Pass 2 (the point's elements come
+// from cache): per temperature t  m = min - 30 T_t,  f_k = exp((m - x_k)/T_t) w_k  as meanBoltzmann forms them (utils.jl:433-436),
+// and its mean sum(f_k x_k) / sum(f_k) taken about the minimum,  min + sum(f_k (x_k - min)) / sum(f_k):  the same number, but every
+// term of the numerator is >= 0 (no cancellation between energies of either sign), one orientation or equal elements give the
+// element itself, bit for bit, and the error scales with the spread of the energies, not their size.  Both sums are taken per
+// lane in rising k and then across the 16 lanes by a butterfly whose every step adds the same two numbers in all lanes: the order
+// depends on nrot alone.
+// mean [NT][mean_stride], mn, amin: outputs of the launch's first point (mn / amin may be nullptr).
+template <int NT>
+__global__ __launch_bounds__(256) void k_egrid_reduce(const double* __restrict__ slab, int nrot, int64_t npoints, ReduceTemps temps,
+                                                       const double* __restrict__ weights, double* __restrict__ mean, int64_t mean_stride,
+                                                       double* __restrict__ mn, int32_t* __restrict__ amin)
+{
+#pragma clang fp contract(off)
+    const int64_t p = ((int64_t)blockIdx.x * 256 + threadIdx.x) / RED_LANES;
+    if (p >= npoints) return;                                     // all 16 lanes of a point leave together
+    const int l = threadIdx.x % RED_LANES;
+    const double* x = slab + (size_t)p * nrot;
+    double vmin = 0.0;
+    int imin = 0x7fffffff;                                        // a lane without elements (nrot < 16): loses every comparison
+    bool have = false;
+    for (int k = l; k < nrot; k += RED_LANES) {
+        const double v = x[k];
+        if (!have) { vmin = v; imin = k; have = true; }
+        else min_step(vmin, imin, v, k);
+    }
+    if (!have) vmin = __builtin_huge_val();
+#pragma unroll
+    for (int o = RED_LANES / 2; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(vmin, o, RED_LANES);
+        const int oi = __shfl_xor(imin, o, RED_LANES);
+        min_step(vmin, imin, ov, oi);
+    }
+    if (l == 0) {
+        if (mn) mn[p] = vmin;
+        if (amin) amin[p] = imin;
+    }
+    if (NT == 0) return;
+    double m[NT > 0 ? NT : 1], factors[NT > 0 ? NT : 1], total[NT > 0 ? NT : 1];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        m[t] = vmin - 30.0 * temps.T[t];
+        factors[t] = 0.0;
+        total[t] = 0.0;
+    }
+    for (int k = l; k < nrot; k += RED_LANES) {
+        const double v = x[k];
+        const double w = weights ? weights[k] : 1.0;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const double factor = exp((m[t] - v) / temps.T[t]) * w;
+            factors[t] += factor;
+            total[t] += factor * (v - vmin);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+        for (int o = RED_LANES / 2; o > 0; o >>= 1) {
+            factors[t] += __shfl_xor(factors[t], o, RED_LANES);
+            total[t] += __shfl_xor(total[t], o, RED_LANES);
+        }
+        if (l == 0) mean[(size_t)t * mean_stride + p] = vmin + total[t] / factors[t];
+    }
+}
+
 int eerr(int code, const char* msg)
 {
     ceg_set_last_error_(msg);
@@ -300,15 +383,24 @@ struct Workspace {
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-}  // namespace
+// what ceg_energy_grid_reduced asks for on top of the elements (checked by the entry point)
+struct Reduction {
+    const double* temperatures;
+    int32_t ntemps;
+    const double* weights;
+    double* out_mean;
+    double* out_min;
+    int32_t* out_argmin;
+};
 
-extern "C" int ceg_energy_grid(ceg_interp_t* const* vdw_grids, ceg_interp_t* coulomb_grid, ceg_recip_t* recip, const double* base,
-                               const double* charges, int32_t natoms, const double* rotations, int32_t nrot, const double steps[9],
-                               const int32_t num[3], const uint8_t* block, const int32_t block_dims[3], const double block_size[3],
-                               const double block_shift[3], const double block_mat[9], const double block_invmat[9],
-                               double energy_net_charges, double static_contribution, double* out, int32_t out_on_device, void* stream)
+// Both entry points: the elements slab by slab into `out` (red == nullptr), or into a slab of the workspace that k_egrid_reduce
+// collapses into the outputs of `red`.
+int egrid_run(ceg_interp_t* const* vdw_grids, ceg_interp_t* coulomb_grid, ceg_recip_t* recip, const double* base, const double* charges,
+              int32_t natoms, const double* rotations, int32_t nrot, const double steps[9], const int32_t num[3], const uint8_t* block,
+              const int32_t block_dims[3], const double block_size[3], const double block_shift[3], const double block_mat[9],
+              const double block_invmat[9], double energy_net_charges, double static_contribution, double* out, const Reduction* red,
+              int32_t out_on_device, void* stream)
 {
-    if (!out) return eerr(CEG_ERR_INVALID, "out is NULL");
     if (!vdw_grids || !base || !charges || !rotations || !steps || !num) return eerr(CEG_ERR_INVALID, "NULL argument");
     if (natoms < 1) return eerr(CEG_ERR_INVALID, "natoms < 1");
     if (natoms > MAX_ATOMS) return eerr(CEG_ERR_UNSUPPORTED, "molecule has more atoms than the kernels hold (16)");
@@ -360,7 +452,8 @@ extern "C" int ceg_energy_grid(ceg_interp_t* const* vdw_grids, ceg_interp_t* cou
     const size_t o_re = align256(o_kf + sizeof(double) * (size_t)nk);
     const size_t o_im = align256(o_re + sizeof(double) * (size_t)nk);
     const size_t o_g = align256(o_im + sizeof(double) * (size_t)nk);
-    const size_t o_mask = align256(o_g + sizeof(double) * 9);
+    const size_t o_w = align256(o_g + sizeof(double) * 9);
+    const size_t o_mask = align256(o_w + (red && red->weights ? sizeof(double) * (size_t)nrot : 0));
     const size_t mask_bytes = block ? (size_t)(block_dims[0] + 1) * (block_dims[1] + 1) * (block_dims[2] + 1) : 0;
     const size_t host_bytes = align256(o_mask + mask_bytes);
     // device-only part, cleared to zero (the padding of the tables must be zero)
@@ -408,11 +501,12 @@ extern "C" int ceg_energy_grid(ceg_interp_t* const* vdw_grids, ceg_interp_t* cou
         for (int ax = 0; ax < 3; ++ax)
             for (int c = 0; c < 3; ++c) g[3 * ax + c] = I[c] * steps[3 * ax] + I[c + 3] * steps[3 * ax + 1] + I[c + 6] * steps[3 * ax + 2];
     }
+    if (red && red->weights) std::memcpy(hbuf.data() + o_w, red->weights, sizeof(double) * (size_t)nrot);
 
-    // ---- slabs of iC for host output
+    // ---- slabs of iC: host output travels in them, and a reduction never holds more elements than one of them
     const size_t per_c = sizeof(double) * (size_t)nrot * numA * numB;
     int slab_c = numC;
-    if (!out_on_device) {
+    if (!out_on_device || red) {
         size_t cap = (size_t)256 << 20;
         if (const char* e = getenv("CEG_HIP_EGRID_SLAB_BYTES")) { const long long v = atoll(e); if (v > 0) cap = (size_t)v; }
         slab_c = (int)std::max<size_t>(1, std::min<size_t>((size_t)numC, cap / per_c));
@@ -422,7 +516,14 @@ extern "C" int ceg_energy_grid(ceg_interp_t* const* vdw_grids, ceg_interp_t* cou
     Workspace ws;
     ws.stream = st;
     ws.async = out_on_device != 0;
-    const size_t out_bytes = out_on_device ? 0 : align256(per_c * (size_t)slab_c);
+    // behind the tables: the slab of elements (unless they go straight to a device `out`), then the slab's reduced outputs for the host
+    const int ntemps = red ? red->ntemps : 0;
+    const size_t slab_points = (size_t)numA * numB * slab_c;
+    const size_t o_slab = total_bytes;
+    const size_t o_rmean = o_slab + (out_on_device && !red ? 0 : align256(per_c * (size_t)slab_c));
+    const size_t o_rmin = o_rmean + (red && !out_on_device ? align256(sizeof(double) * slab_points * ntemps) : 0);
+    const size_t o_ramin = o_rmin + (red && !out_on_device && red->out_min ? align256(sizeof(double) * slab_points) : 0);
+    const size_t out_bytes = o_ramin + (red && !out_on_device && red->out_argmin ? align256(sizeof(int32_t) * slab_points) : 0) - total_bytes;
     if ((ws.async ? hipMallocAsync((void**)&ws.d, total_bytes + out_bytes, st) : hipMalloc((void**)&ws.d, total_bytes + out_bytes)) != hipSuccess) {
         ws.d = nullptr;
         return eerr(CEG_ERR_HIP, "could not allocate the device workspace");
@@ -444,7 +545,10 @@ extern "C" int ceg_energy_grid(ceg_interp_t* const* vdw_grids, ceg_interp_t* cou
     double* d_self = reinterpret_cast<double*>(d + o_self);
     double2* d_T = reinterpret_cast<double2*>(d + o_T);
     double2* d_tab = reinterpret_cast<double2*>(d + o_tab);
-    double* d_slab = out_on_device ? out : reinterpret_cast<double*>(d + total_bytes);
+    const double* d_w = red && red->weights ? reinterpret_cast<const double*>(d + o_w) : nullptr;
+    double* d_slab = out_on_device && !red ? out : reinterpret_cast<double*>(d + o_slab);
+    ReduceTemps temps{};
+    for (int t = 0; t < ntemps; ++t) temps.T[t] = red->temperatures[t];
 
     if (nk > 0) {
         const int64_t nt = (int64_t)ntab * nk;
@@ -473,9 +577,75 @@ extern "C" int ceg_energy_grid(ceg_interp_t* const* vdw_grids, ceg_interp_t* cou
         }
         hipLaunchKernelGGL(k_egrid_terms, dim3((unsigned)((nelem + 255) / 256)), dim3(256), 0, st, dP, d_rot, d_self, d_mask, c0, nelem, d_slab);
         if (hipGetLastError() != hipSuccess) return eerr(CEG_ERR_HIP, "energy-grid kernel launch failed");
-        if (!out_on_device &&
-            hipMemcpy(out + (size_t)nrot * numA * numB * c0, d_slab, sizeof(double) * (size_t)nelem, hipMemcpyDeviceToHost) != hipSuccess)
-            return eerr(CEG_ERR_HIP, "kernel execution or D2H failed");
+        if (!red) {
+            if (!out_on_device &&
+                hipMemcpy(out + (size_t)nrot * numA * numB * c0, d_slab, sizeof(double) * (size_t)nelem, hipMemcpyDeviceToHost) != hipSuccess)
+                return eerr(CEG_ERR_HIP, "kernel execution or D2H failed");
+            continue;
+        }
+        // the slab's points p0 .. p0 + np of the lattice: straight into device outputs, or into the workspace and from there to the host
+        const int64_t p0 = (int64_t)numA * numB * c0, np = (int64_t)numA * numB * nc, points = (int64_t)numA * numB * numC;
+        double* r_mean = !ntemps ? nullptr : (out_on_device ? red->out_mean + p0 : reinterpret_cast<double*>(d + o_rmean));
+        double* r_min = !red->out_min ? nullptr : (out_on_device ? red->out_min + p0 : reinterpret_cast<double*>(d + o_rmin));
+        int32_t* r_amin = !red->out_argmin ? nullptr : (out_on_device ? red->out_argmin + p0 : reinterpret_cast<int32_t*>(d + o_ramin));
+        const int64_t mean_stride = out_on_device ? points : (int64_t)slab_points;
+        auto reduce = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)((np * RED_LANES + 255) / 256)), dim3(256), 0, st, d_slab, (int)nrot, np, temps, d_w, r_mean,
+                               mean_stride, r_min, r_amin);
+        };
+        switch (ntemps) {
+        case 0: reduce(k_egrid_reduce<0>); break;
+        case 1: reduce(k_egrid_reduce<1>); break;
+        case 2: reduce(k_egrid_reduce<2>); break;
+        case 3: reduce(k_egrid_reduce<3>); break;
+        case 4: reduce(k_egrid_reduce<4>); break;
+        case 5: reduce(k_egrid_reduce<5>); break;
+        case 6: reduce(k_egrid_reduce<6>); break;
+        case 7: reduce(k_egrid_reduce<7>); break;
+        default: reduce(k_egrid_reduce<8>); break;
+        }
+        if (hipGetLastError() != hipSuccess) return eerr(CEG_ERR_HIP, "reduction kernel launch failed");
+        if (out_on_device) continue;
+        bool ok = true;
+        for (int t = 0; t < ntemps; ++t)
+            ok = ok && hipMemcpy(red->out_mean + (size_t)t * points + p0, r_mean + (size_t)t * mean_stride, sizeof(double) * (size_t)np,
+                                 hipMemcpyDeviceToHost) == hipSuccess;
+        if (r_min) ok = ok && hipMemcpy(red->out_min + p0, r_min, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost) == hipSuccess;
+        if (r_amin) ok = ok && hipMemcpy(red->out_argmin + p0, r_amin, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost) == hipSuccess;
+        if (!ok) return eerr(CEG_ERR_HIP, "kernel execution or D2H failed");
     }
     return CEG_OK;
+}
+
+}  // namespace
+
+extern "C" int ceg_energy_grid(ceg_interp_t* const* vdw_grids, ceg_interp_t* coulomb_grid, ceg_recip_t* recip, const double* base,
+                               const double* charges, int32_t natoms, const double* rotations, int32_t nrot, const double steps[9],
+                               const int32_t num[3], const uint8_t* block, const int32_t block_dims[3], const double block_size[3],
+                               const double block_shift[3], const double block_mat[9], const double block_invmat[9],
+                               double energy_net_charges, double static_contribution, double* out, int32_t out_on_device, void* stream)
+{
+    if (!out) return eerr(CEG_ERR_INVALID, "out is NULL");
+    return egrid_run(vdw_grids, coulomb_grid, recip, base, charges, natoms, rotations, nrot, steps, num, block, block_dims, block_size,
+                     block_shift, block_mat, block_invmat, energy_net_charges, static_contribution, out, nullptr, out_on_device, stream);
+}
+
+extern "C" int ceg_energy_grid_reduced(ceg_interp_t* const* vdw_grids, ceg_interp_t* coulomb_grid, ceg_recip_t* recip, const double* base,
+                                       const double* charges, int32_t natoms, const double* rotations, int32_t nrot, const double steps[9],
+                                       const int32_t num[3], const uint8_t* block, const int32_t block_dims[3], const double block_size[3],
+                                       const double block_shift[3], const double block_mat[9], const double block_invmat[9],
+                                       double energy_net_charges, double static_contribution, const double* temperatures, int32_t ntemps,
+                                       const double* weights, double* out_mean, double* out_min, int32_t* out_argmin, int32_t out_on_device,
+                                       void* stream)
+{
+    if (ntemps < 0 || ntemps > CEG_EGRID_MAX_TEMPS) return eerr(CEG_ERR_INVALID, "ntemps out of range (0 .. CEG_EGRID_MAX_TEMPS)");
+    if (ntemps > 0 && !temperatures) return eerr(CEG_ERR_INVALID, "temperatures is NULL");
+    for (int t = 0; t < ntemps; ++t)
+        if (!(temperatures[t] > 0.0) || !(temperatures[t] < __builtin_huge_val()))
+            return eerr(CEG_ERR_INVALID, "a temperature is not finite and positive");
+    if ((ntemps > 0) != (out_mean != nullptr)) return eerr(CEG_ERR_INVALID, "out_mean must be given if and only if ntemps > 0");
+    if (!out_mean && !out_min && !out_argmin) return eerr(CEG_ERR_INVALID, "no output requested");
+    const Reduction red{temperatures, ntemps, weights, out_mean, out_min, out_argmin};
+    return egrid_run(vdw_grids, coulomb_grid, recip, base, charges, natoms, rotations, nrot, steps, num, block, block_dims, block_size,
+                     block_shift, block_mat, block_invmat, energy_net_charges, static_contribution, nullptr, &red, out_on_device, stream);
 }

@@ -636,7 +636,7 @@ function block_spheres(csetup::GridCoordinatesSetup, centers::Vector{SVector{3,F
     CEG.BlockFile(csetup, _to_bitarray(mask, a, b, c))
 end
 
-# ------------------------------------------------------------------ energy_grid for polyatomic guests (ceg_energy_grid)
+# ------------------------------------------------------------------ energy_grid for polyatomic guests (ceg_energy_grid, ceg_energy_grid_reduced)
 """
     energy_grid_rotations(setup, vdw, coulomb, recip, rots, numABC, stepABC) -> Array{Float64,4}
 
@@ -647,6 +647,18 @@ The array is the buffer the library filled: its element order is Julia's.
 """
 function energy_grid_rotations(setup::CEG.CrystalEnergySetup, vdw::Vector{Ptr{Cvoid}}, coulomb::Ptr{Cvoid}, recip::Ptr{Cvoid},
                                rots, numABC::NTuple{3,Int}, stepABC)
+    a = _egrid_inputs(setup, vdw, coulomb, rots, numABC, stepABC)
+    out = Array{Float64,4}(undef, length(rots), numABC[1], numABC[2], numABC[3])             # grids.jl:391
+    GC.@preserve a out _check(ccall((:ceg_energy_grid, LIB[]), Cint,
+        (Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Int32},
+         Ptr{UInt8}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Int32, Ptr{Cvoid}),
+        a.handles, coulomb, recip, a.base, a.charges, a.natoms, a.rotv, length(rots), a.steps, a.num,
+        a.pmask, a.bdims, a.bsize, a.bshift, a.bmat, a.binv, a.enc, a.static, out, 0, C_NULL))
+    out
+end
+
+# what ceg_energy_grid and ceg_energy_grid_reduced share: every argument up to static_contribution, as flat arrays
+function _egrid_inputs(setup::CEG.CrystalEnergySetup, vdw::Vector{Ptr{Cvoid}}, coulomb::Ptr{Cvoid}, rots, numABC::NTuple{3,Int}, stepABC)
     molecule = setup.molecule
     base = Float64[NoUnits(x/u"Å") for p in position(molecule) for x in p]                   # grids.jl:356
     natoms = length(setup.atomsidx)
@@ -664,13 +676,64 @@ function energy_grid_rotations(setup::CEG.CrystalEnergySetup, vdw::Vector{Ptr{Cv
     mask = blk.empty ? UInt8[] : vec(UInt8.(permutedims(blk.block, (3, 2, 1))))              # [x][y][z], z fastest
     bdims, bsize, bshift, _ = _geometry(cs)
     bmat = Vector{Float64}(vec(NoUnits.(cs.cell.mat ./ u"Å"))); binv = Vector{Float64}(vec(NoUnits.(cs.cell.invmat .* u"Å")))
-    out = Array{Float64,4}(undef, length(rots), numABC[1], numABC[2], numABC[3])             # grids.jl:391
-    GC.@preserve handles base rotv steps num mask bdims bsize bshift bmat binv out _check(ccall((:ceg_energy_grid, LIB[]), Cint,
+    pmask = blk.empty ? Ptr{UInt8}(C_NULL) : pointer(mask)                                   # `mask` stays referenced by the tuple
+    (; handles, base, charges=setup.charges, natoms, rotv, steps, num, mask, pmask, bdims, bsize, bshift, bmat, binv, enc, static)
+end
+
+"""
+    energy_grid_reduced(setup, vdw, coulomb, recip, rots, numABC, stepABC, temperatures; weights=nothing, want_argmin=false)
+
+The rotation axis of `energy_grid_rotations` collapsed on the device (`ceg_energy_grid_reduced`): `(mean, min, argmin)` with
+`mean[iA, iB, iC, t]` = `meanBoltzmann(allvals, temperatures[t], weights)[iA, iB, iC]` (src/utils.jl:415-443), `min` the minimum over
+the orientations and `argmin` (1-based, `nothing` unless asked for) the first orientation that attains it.
+"""
+function energy_grid_reduced(setup::CEG.CrystalEnergySetup, vdw::Vector{Ptr{Cvoid}}, coulomb::Ptr{Cvoid}, recip::Ptr{Cvoid},
+                             rots, numABC::NTuple{3,Int}, stepABC, temperatures; weights=nothing, want_argmin::Bool=false)
+    a = _egrid_inputs(setup, vdw, coulomb, rots, numABC, stepABC)
+    temps = Float64[T isa Unitful.Quantity ? ustrip(u"K", T) : T for T in temperatures]        # meanBoltzmann takes plain kelvins
+    w = weights isa Nothing ? Float64[] : Vector{Float64}(weights)
+    weights isa Nothing || length(w) == length(rots) || error("one weight per rotation")
+    mean = Array{Float64,4}(undef, numABC[1], numABC[2], numABC[3], length(temps))
+    mn = Array{Float64,3}(undef, numABC...)
+    amin = Array{Int32,3}(undef, (want_argmin ? numABC : (0, 0, 0))...)
+    GC.@preserve a temps w mean mn amin _check(ccall((:ceg_energy_grid_reduced, LIB[]), Cint,
         (Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Int32},
-         Ptr{UInt8}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Int32, Ptr{Cvoid}),
-        handles, coulomb, recip, base, setup.charges, natoms, rotv, length(rots), steps, num,
-        (blk.empty ? Ptr{UInt8}(C_NULL) : pointer(mask)), bdims, bsize, bshift, bmat, binv, enc, static, out, 0, C_NULL))
-    out
+         Ptr{UInt8}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64,
+         Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Int32, Ptr{Cvoid}),
+        a.handles, coulomb, recip, a.base, a.charges, a.natoms, a.rotv, length(rots), a.steps, a.num,
+        a.pmask, a.bdims, a.bsize, a.bshift, a.bmat, a.binv, a.enc, a.static,
+        (isempty(temps) ? Ptr{Float64}(C_NULL) : pointer(temps)), length(temps), (weights isa Nothing ? Ptr{Float64}(C_NULL) : pointer(w)),
+        (isempty(temps) ? Ptr{Float64}(C_NULL) : pointer(mean)), mn, (want_argmin ? pointer(amin) : Ptr{Int32}(C_NULL)), 0, C_NULL))
+    (mean, mn, want_argmin ? amin .+ Int32(1) : nothing)
+end
+
+# lattice (grids.jl:378-384), rotations with their Lebedev weights (:385-390) and device handles of a setup; f(vdw, coulomb, recip, rots,
+# weights, numABC, stepABC) runs with the handles alive
+function _with_egrid_setup(f, setup::CEG.CrystalEnergySetup, step, num_rotate)
+    molecule = setup.molecule
+    axeA, axeB, axeC = CEG.bounding_box(setup.framework)
+    numA = floor(Int, norm(axeA) / step) + 1
+    numB = floor(Int, norm(axeB) / step) + 1
+    numC = floor(Int, norm(axeC) / step) + 1
+    stepABC = (NoUnits.(axeA ./ numA ./ u"Å"), NoUnits.(axeB ./ numB ./ u"Å"), NoUnits.(axeC ./ numC ./ u"Å"))
+    rots, weights = if num_rotate == 0 || length(molecule) == 1
+        [one(SMatrix{3,3,Float64,9})], [1.0]
+    else
+        CEG.get_rotation_matrices(molecule, num_rotate)
+    end
+    vdw = Ptr{Cvoid}[g.ewald_precision == Inf ? interp_handle(g) : C_NULL for g in setup.grids]
+    withcoulomb = setup.coulomb.ewald_precision != -Inf
+    coulomb = withcoulomb ? interp_handle(setup.coulomb) : C_NULL
+    recip = withcoulomb ? recip_handle(setup.ewald) : C_NULL
+    try
+        return f(vdw, coulomb, recip, rots, weights, (numA, numB, numC), stepABC)
+    finally
+        for h in vdw
+            h == C_NULL || ccall((:ceg_interp_destroy, LIB[]), Cint, (Ptr{Cvoid},), h)
+        end
+        withcoulomb && ccall((:ceg_interp_destroy, LIB[]), Cint, (Ptr{Cvoid},), coulomb)
+        withcoulomb && ccall((:ceg_recip_destroy, LIB[]), Cint, (Ptr{Cvoid},), recip)
+    end
 end
 
 """
@@ -682,30 +745,35 @@ The reference's energy_grid (src/grids.jl:346-424) with the loop nest :394-419 o
 """
 function energy_grid(setup::CEG.CrystalEnergySetup, step, num_rotate=40)
     num_rotate < 0 && return CEG.energy_grid(setup, step, num_rotate)
-    molecule = setup.molecule
-    axeA, axeB, axeC = CEG.bounding_box(setup.framework)
-    numA = floor(Int, norm(axeA) / step) + 1
-    numB = floor(Int, norm(axeB) / step) + 1
-    numC = floor(Int, norm(axeC) / step) + 1
-    stepABC = (NoUnits.(axeA ./ numA ./ u"Å"), NoUnits.(axeB ./ numB ./ u"Å"), NoUnits.(axeC ./ numC ./ u"Å"))
-    rots = if num_rotate == 0 || length(molecule) == 1
-        [one(SMatrix{3,3,Float64,9})]
-    else
-        first(CEG.get_rotation_matrices(molecule, num_rotate))
+    _with_egrid_setup(setup, step, num_rotate) do vdw, coulomb, recip, rots, _weights, numABC, stepABC
+        energy_grid_rotations(setup, vdw, coulomb, recip, rots, numABC, stepABC)
     end
-    vdw = Ptr{Cvoid}[g.ewald_precision == Inf ? interp_handle(g) : C_NULL for g in setup.grids]
-    withcoulomb = setup.coulomb.ewald_precision != -Inf
-    coulomb = withcoulomb ? interp_handle(setup.coulomb) : C_NULL
-    recip = withcoulomb ? recip_handle(setup.ewald) : C_NULL
-    try
-        return energy_grid_rotations(setup, vdw, coulomb, recip, rots, (numA, numB, numC), stepABC)
-    finally
-        for h in vdw
-            h == C_NULL || ccall((:ceg_interp_destroy, LIB[]), Cint, (Ptr{Cvoid},), h)
-        end
-        withcoulomb && ccall((:ceg_interp_destroy, LIB[]), Cint, (Ptr{Cvoid},), coulomb)
-        withcoulomb && ccall((:ceg_recip_destroy, LIB[]), Cint, (Ptr{Cvoid},), recip)
+end
+
+"""
+    energy_grid_reduced(setup::CrystalEnergySetup, step, temperatures; num_rotate=40, weights=nothing, want_argmin=false)
+
+`(mean, min, argmin)` of `energy_grid(setup, step, num_rotate)` over its rotation axis without the 4-D array ever reaching the host:
+`mean[:, :, :, t] == meanBoltzmann(energy_grid(setup, step, num_rotate), temperatures[t], weights)` to rounding.  `weights`: `nothing`
+(what `output_cube` and `compute_levels` use), `:lebedev` (the weights `get_rotation_matrices` returns next to the matrices) or one
+number per rotation.  Lattice and rotations are the reference's own, as for `energy_grid`; `num_rotate < 0` is not covered.
+"""
+function energy_grid_reduced(setup::CEG.CrystalEnergySetup, step, temperatures; num_rotate=40, weights=nothing, want_argmin::Bool=false)
+    num_rotate < 0 && error("num_rotate < 0 (random offsets) is not covered: reduce CrystalEnergyGrids.energy_grid with meanBoltzmann")
+    _with_egrid_setup(setup, step, num_rotate) do vdw, coulomb, recip, rots, lebedev, numABC, stepABC
+        w = weights === :lebedev ? lebedev : weights
+        energy_grid_reduced(setup, vdw, coulomb, recip, rots, numABC, stepABC, temperatures; weights=w, want_argmin=want_argmin)
     end
+end
+
+"""
+    mean_boltzmann_grid(setup, step, T; num_rotate=40) -> Array{Float64,3}
+
+What `meanBoltzmann(energy_grid(setup, step, num_rotate), T)` returns (the grid `output_cube` writes), reduced on the device.
+"""
+function mean_boltzmann_grid(setup::CEG.CrystalEnergySetup, step, T; num_rotate=40)
+    mean, _, _ = energy_grid_reduced(setup, step, (T,); num_rotate=num_rotate)
+    mean[:, :, :, 1]
 end
 
 # ------------------------------------------------------------------ build + file in one call (row f4)

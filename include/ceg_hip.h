@@ -442,7 +442,8 @@ CEG_API int ceg_recip_set_structure_factor(ceg_recip_t* handle, const double* sf
  * All handles must live on one device (CEG_ERR_INVALID otherwise); natoms > 16 -> CEG_ERR_UNSUPPORTED.
  * Not covered: the MonteCarloSetup variant (energy_point_mc!, guests retained), the num_rotate < 0 random-offset mode
  * (grids.jl:404-406), the scratchspace cache (:349-354, host business) and the Lebedev tables (an artifact the reference
- * downloads): the rotation matrices are an input.
+ * downloads): the rotation matrices are an input.  What the reference does with `allvals` next -- meanBoltzmann over the
+ * rotation axis, the minimum over the orientations -- is ceg_energy_grid_reduced below, which never moves the elements.
  */
 CEG_API int ceg_energy_grid(ceg_interp_t* const* vdw_grids, ceg_interp_t* coulomb_grid, ceg_recip_t* recip,
                             const double* base, const double* charges, int32_t natoms,
@@ -451,6 +452,44 @@ CEG_API int ceg_energy_grid(ceg_interp_t* const* vdw_grids, ceg_interp_t* coulom
                             const double block_mat[9], const double block_invmat[9],
                             double energy_net_charges, double static_contribution,
                             double* out, int32_t out_on_device, void* stream);
+
+/*
+ * The same elements collapsed over the rotation axis on the device, per lattice point (iA, iB, iC):
+ *   min     the smallest of the nrot elements;  argmin  the 0-based index of the first orientation that attains it (findmin)
+ *   mean_t  meanBoltzmann(allvals, T_t, weights) (src/utils.jl:415-443), what output_cube (src/output.jl:207-209) and compute_levels
+ *           (src/basins.jl:842-869) make of the array:  m = min - 30 T_t,  f_k = exp((m - x_k)/T_t) w_k  (w_k = 1 without weights),
+ *           mean = sum_k(f_k x_k) / sum_k(f_k), evaluated as min + sum_k(f_k (x_k - min)) / sum_k(f_k): a single orientation, or
+ *           equal elements, give the element itself bit for bit
+ * A blocked element (1e100) has f = 0 and drops out of the mean; where every orientation is blocked min is 1e100 exactly and the
+ * mean is what the formula gives, about 1e100.  A NaN element makes min and every mean of its point NaN, argmin the first NaN.
+ *
+ *  every argument up to static_contribution: as ceg_energy_grid
+ *  temperatures  [ntemps] K, each finite and > 0;  ntemps 0 .. CEG_EGRID_MAX_TEMPS (all of them share one pass over the elements)
+ *  weights       NULL or [nrot]: meanBoltzmann's third argument (the Lebedev weights get_rotation_matrices returns), host memory
+ *  out_mean      [ntemps][numA*numB*numC], NULL iff ntemps == 0;  out_min, out_argmin  [numA*numB*numC] each, either may be NULL.
+ *                Element (iA, iB, iC) at iA + numA*(iB + numB*iC): every output is an Array{Float64,3} (Int32 for argmin) in
+ *                Julia's memory order, temperature t at offset t*numA*numB*numC.
+ *                out_on_device = 0: host memory, synchronous; the lattice is worked through in slabs of iC of at most
+ *                CEG_HIP_EGRID_SLAB_BYTES of elements, the device holds one slab and its reduced outputs, and only those are copied
+ *                back.  out_on_device = 1: device memory, asynchronous on `stream`; the slab of elements (same cap) comes from the
+ *                stream-ordered allocator, the caller provides no room for the elements.
+ * The order in which the elements of a point are combined is fixed by the kernel and depends on nrot alone: the result does not
+ * depend on the slab size, on where the outputs live, nor on which other temperatures are asked for, bit for bit; min and argmin
+ * are exactly those of ceg_energy_grid's elements.
+ * CEG_ERR_INVALID: ntemps out of range, a temperature that is not finite and > 0, out_mean missing with ntemps > 0 (or given with
+ * ntemps == 0), no output requested at all; every refusal of ceg_energy_grid holds as it stands.  Nothing is launched on a bad
+ * argument.
+ */
+#define CEG_EGRID_MAX_TEMPS 8
+CEG_API int ceg_energy_grid_reduced(ceg_interp_t* const* vdw_grids, ceg_interp_t* coulomb_grid, ceg_recip_t* recip,
+                                    const double* base, const double* charges, int32_t natoms,
+                                    const double* rotations, int32_t nrot, const double steps[9], const int32_t num[3],
+                                    const uint8_t* block, const int32_t block_dims[3], const double block_size[3], const double block_shift[3],
+                                    const double block_mat[9], const double block_invmat[9],
+                                    double energy_net_charges, double static_contribution,
+                                    const double* temperatures, int32_t ntemps, const double* weights,
+                                    double* out_mean, double* out_min, int32_t* out_argmin,
+                                    int32_t out_on_device, void* stream);
 
 /* ---- guest-guest pair energies for trial placements ---------------- */
 /*
