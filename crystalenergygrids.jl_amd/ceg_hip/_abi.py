@@ -28,6 +28,19 @@ class GridHeader(C.Structure):
                 ("num_unitcell", C.c_int32 * 3), ("_pad", C.c_int32), ("ewald_precision", C.c_double), ("mat", C.c_double * 9)]
 
 
+class SweepParams(C.Structure):
+    """``ceg_mc_sweep_params_t``"""
+    _fields_ = [("seed", C.c_uint64), ("first_step", C.c_uint64), ("stream_id", C.c_void_p), ("temperature", C.c_void_p),
+                ("dmax", C.c_void_p), ("thetamax", C.c_void_p), ("p_rotation", C.c_void_p), ("bead", C.c_void_p)]
+
+
+# ``ceg_mc_sweep_stats_t`` and ``ceg_mc_sweep_record_t`` as structured arrays
+SWEEP_STATS_DTYPE = np.dtype([('translation_trials', '<i8'), ('translation_accepted', '<i8'), ('rotation_trials', '<i8'),
+                              ('rotation_accepted', '<i8'), ('blocked', '<i8'), ('delta', '<f8')], align=True)
+SWEEP_RECORD_DTYPE = np.dtype([('molecule', '<i4'), ('kind', '<i4'), ('accepted', '<i4'), ('_pad', '<i4'), ('u', '<f8'),
+                               ('rows', '<f8', (2, 4)), ('positions', '<f8', (16, 3))], align=True)
+assert SWEEP_STATS_DTYPE.itemsize == 48 and SWEEP_RECORD_DTYPE.itemsize == 472
+
 c_double_p = C.POINTER(C.c_double)
 c_float_p = C.POINTER(C.c_float)
 c_int32_p = C.POINTER(C.c_int32)
@@ -158,6 +171,7 @@ PROTOTYPES = {
     "ceg_mc_group_destroy": (C.c_int, [C.c_void_p]),
     "ceg_mc_group_trial": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p, C.c_int32, c_double_p, c_double_p]),
     "ceg_mc_group_accept": (C.c_int, [C.c_void_p, c_int32_p, c_double_p]),
+    "ceg_mc_group_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ceg_energy_grid": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, c_double_p, c_double_p, C.c_int32,
                                   c_double_p, C.c_int32, c_double_p, c_int32_p,
                                   C.c_void_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p,

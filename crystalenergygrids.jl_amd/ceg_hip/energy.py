@@ -549,7 +549,8 @@ class DeviceMonteCarlo:
 class DeviceMonteCarloGroup:
     """K :class:`DeviceMonteCarlo` chains on one device stepped in lockstep (``ceg_mc_group_*``): one launch evaluates the trials
     of every chain, one launch applies every accepted move -- the way ``make_isotherm`` (parameterinputs.jl:316-329) runs one
-    ``run_gcmc`` per pressure, with the launch cost shared by the chains.  The acceptance rule stays with the caller.  While
+    ``run_gcmc`` per pressure, with the launch cost shared by the chains.  With ``trial`` / ``accept`` the acceptance rule stays
+    with the caller; ``sweep`` runs whole sweeps of translations and rotations on the device.  While
     grouped the chains' own methods remain usable (insert, remove, single trials ...) and are ordered with the group calls; the
     group and its chains are driven from one thread.  Usable as a context manager; ``close()`` gives the chains back."""
 
@@ -627,6 +628,54 @@ class DeviceMonteCarloGroup:
             parts.append(np.ascontiguousarray(positions, dtype=np.float64).reshape(-1))
         p = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(1), dtype=np.float64)
         _abi.check(self._lib, self._lib.ceg_mc_group_accept(self._h, _abi.i32ptr(mol), _abi.dptr(p)))
+
+    def sweep(self, nsteps: int, seed: int, first_step: int = 0, *, temperature, dmax, thetamax, p_rotation=0.5, stream_id=None,
+              bead=None, degrees: bool = False, log: bool = False):
+        """``ceg_mc_group_sweep``: ``nsteps`` Markov steps of every chain on the device -- molecule and move drawn from the
+        counter-based stream of :mod:`ceg_hip.mcrng`, ``movement_energy`` before and after, the Metropolis rule of
+        ``compute_accept_move`` (montecarlo.jl:702-712), ``update_mc!`` -- with one synchronisation at the end.
+
+        ``temperature`` (K), ``dmax`` (A), ``thetamax`` (radians, or degrees with ``degrees=True``) and ``p_rotation``: one value for
+        all chains or one per chain.  ``stream_id``: one distinct id per chain (default: the chain's position).  ``bead``: per
+        chain, the 0-based atom each kind rotates about (default :func:`ceg_hip.mcrng.default_beads`, i.e. ``mc.bead``).
+        Step ``s`` of the call is the absolute step ``first_step + s`` of the stream: continue a run with ``first_step`` advanced.
+
+        -> stats (structured array [K]: trials / acceptances per move kind, blocked trials, ``delta`` = sum of after - before over
+        the accepted moves), and with ``log=True`` also the log [nsteps, K] (molecule in the DEVICE's molecule order, move kind,
+        accepted flag, ``u``, the two rows, the proposed positions).  The host-side ``mc.positions`` are NOT touched: read
+        :meth:`DeviceMonteCarlo.state`.  The adaptation of ``dmax`` / ``thetamax`` (simulation.jl:820-825) stays with the caller,
+        between sweeps."""
+        from . import mcrng
+        k = len(self.chains)
+
+        def per_chain(x, what):
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (k,)) if np.ndim(x) == 0 else x, dtype=np.float64)
+            if a.shape != (k,):
+                raise ValueError(f"{what}: one value or one per chain ({k})")
+            return a
+
+        T, dm, pr = per_chain(temperature, "temperature"), per_chain(dmax, "dmax"), per_chain(p_rotation, "p_rotation")
+        th = per_chain(thetamax, "thetamax")
+        if degrees:
+            th = np.ascontiguousarray(np.deg2rad(th))
+        sid = np.ascontiguousarray(np.arange(k) if stream_id is None else stream_id, dtype=np.uint32)
+        if sid.shape != (k,):
+            raise ValueError(f"stream_id: one per chain ({k})")
+        beads = []
+        for c, chain in enumerate(self.chains):
+            if any(len(b) for b in (getattr(chain.mc, "speciesblocks", None) or [])):
+                raise NotImplementedError("sweeps do not test block pockets (inblockpocket of choose_step!): this setup has some")
+            per_kind = mcrng.default_beads(chain.mc) if bead is None else list(bead[c])
+            by_device = {d: per_kind[i] for i, kind in enumerate(chain._slot) for d in kind}
+            beads += [by_device[d] for d in sorted(by_device)]
+        beads = np.ascontiguousarray(beads if beads else [0], dtype=np.int32)
+        params = _abi.SweepParams(int(seed), int(first_step), sid.ctypes.data, T.ctypes.data, dm.ctypes.data, th.ctypes.data,
+                                  pr.ctypes.data, beads.ctypes.data)
+        stats = np.zeros(k, dtype=_abi.SWEEP_STATS_DTYPE)
+        records = np.zeros((max(int(nsteps), 0), k), dtype=_abi.SWEEP_RECORD_DTYPE) if log else None
+        _abi.check(self._lib, self._lib.ceg_mc_group_sweep(self._h, C.addressof(params), int(nsteps), stats.ctypes.data,
+                                                           records.ctypes.data if log and records.size else None))
+        return (stats, records) if log else stats
 
     def close(self) -> None:
         if getattr(self, "_h", None):

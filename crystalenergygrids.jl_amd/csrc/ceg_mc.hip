@@ -15,7 +15,8 @@
 // all threads stride over the guest atoms for the pair sum; block 0 evaluates the molecule where it currently is
 // (with its stored structure factor, like the reference's `positions === nothing` branch).  Small batches travel
 // through a pinned, device-mapped host buffer: a batch-1 trial is ONE kernel launch and one stream synchronisation.
-// The MC driver (move proposal, acceptance rule, GCMC swaps) stays on the host, as in SURVEY 8f.
+// The MC driver stays on the host, as in SURVEY 8f, except for sweeps of translations and rotations (ceg_mc_group_sweep: proposal,
+// Metropolis rule and update of S steps of K chains on the device; GCMC swaps remain with the caller).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,6 +33,7 @@
 #include "ceg_consumers.h"
 #include "ceg_rows.h"
 #include "ceg_pairfrac.h"
+#include "ceg_philox.h"
 
 using ceg::DevRule;
 using ceg_consumers::InterpGeom;
@@ -1032,6 +1034,135 @@ __global__ __launch_bounds__(MC_THREADS) void k_mcg_accept(const McView* __restr
 {
     const McGroupAccept& A = items[blockIdx.x];
     mc_accept_body(as_constant(views)[A.view], A.molecule, A.np, A.ops, A.stride);
+}
+
+// ---- sweeps (ceg_mc_group_sweep): the proposal and the decision of every step on the device.  Per step k_mcg_sweep_trial (rows
+// before / after of every chain, the body of k_mcg_trial) and k_mcg_sweep_accept (Metropolis rule, statistics, log, the body of
+// k_mcg_accept), back to back on the group's stream.  Every workgroup of a chain's step regenerates the chain's random numbers from
+// (seed, step, stream id, purpose) (ceg_philox.h); what a step hands from the first kernel to the second -- the proposed positions
+// and the two rows -- stays in device memory.
+struct McSweepChain {            // per chain, device memory
+    uint32_t stream_id;
+    int32_t bead_off;            // the chain's first entry of the bead array
+    int32_t stride, _pad;
+    double temperature, dmax, thetamax, p_rotation;
+};
+
+struct McMove { int32_t molecule, kind; };       // kind 0 translation, 1 rotation; molecule -1: the chain is idle
+
+__device__ McCellOps d_mc_no_cell_ops;           // (sweeps refuse chains with neighbour cells: the accept body never reads it)
+
+__device__ __forceinline__ McMove sweep_select(const McView& v, const McSweepChain& P, uint64_t seed, uint64_t step)
+{
+    const int nmol = v.nmol;
+    if (nmol <= 0) return McMove{-1, -1};
+    const ceg_philox::Block w = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::SELECT);
+    int j = (int)floor(ceg_philox::uniform(w.w[0], w.w[1]) * (double)nmol);
+    j = j < nmol - 1 ? j : nmol - 1;
+    const bool rotate = v.mol[j].y > 1 && ceg_philox::uniform(w.w[2], w.w[3]) < P.p_rotation;
+    return McMove{j, rotate ? 1 : 0};
+}
+
+// coordinate `comp` of atom `a` of the proposed placement of molecule mv.molecule (atoms [mj.x, mj.x + mj.y)): random_translation /
+// random_rotation of src/mcmoves.jl:139-164 on the resident positions
+__device__ __forceinline__ double sweep_coordinate(const McView& v, const McSweepChain& P, const int32_t* __restrict__ bead, const McMove mv, const int2 mj,
+                                                   uint64_t seed, uint64_t step, int a, int comp)
+{
+#pragma clang fp contract(off)
+    const double4 A = v.atoms[mj.x + a];
+    const ceg_philox::Block g = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::GEOMETRY_A);
+    if (mv.kind == 0) {
+        uint32_t wa = g.w[0], wb = g.w[1];
+        if (comp == 1) { wa = g.w[2]; wb = g.w[3]; }
+        if (comp == 2) {
+            const ceg_philox::Block h = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::GEOMETRY_B);
+            wa = h.w[0]; wb = h.w[1];
+        }
+        const double r = (2.0 * ceg_philox::uniform(wa, wb) - 1.0) * P.dmax;
+        return (comp == 0 ? A.x : (comp == 1 ? A.y : A.z)) + r;
+    }
+    const double theta = P.thetamax * (2.0 * ceg_philox::uniform(g.w[0], g.w[1]) - 1.0);
+    int axis = (int)floor(3.0 * ceg_philox::uniform(g.w[2], g.w[3]));
+    axis = axis < 2 ? axis : 2;
+    double s, c;
+    sincos(theta, &s, &c);
+    const double4 R = v.atoms[mj.x + bead[P.bead_off + mv.molecule]];
+    const double dx = A.x - R.x, dy = A.y - R.y, dz = A.z - R.z;
+    double ox, oy, oz;                                               // the matrices of :155-161 (SMatrix fills column by column)
+    if (axis == 0) { ox = dx; oy = c * dy - s * dz; oz = s * dy + c * dz; }
+    else if (axis == 1) { ox = c * dx + s * dz; oy = dy; oz = c * dz - s * dx; }
+    else { ox = c * dx - s * dy; oy = s * dx + c * dy; oz = dz; }
+    return comp == 0 ? R.x + ox : (comp == 1 ? R.y + oy : R.z + oz);
+}
+
+// workgroup (x, y): chain list[x / 2], row x % 2 (0 where the molecule is, 1 the proposal), term y of the row.  prop[3 chain + y]: the
+// proposal as this workgroup's trial placement (written and read by the same threads); y = 0 is the copy k_mcg_sweep_accept reads.
+template <bool FAST>
+__global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mcg_sweep_trial(const McView* __restrict__ views, const McSweepChain* __restrict__ params,
+                                                                 const int32_t* __restrict__ bead, const int32_t* __restrict__ list, int table_ok,
+                                                                 uint64_t seed, uint64_t step, McPositions* prop, double* __restrict__ rows)
+{
+    __shared__ McLocal s_L;
+    const int c = list[blockIdx.x >> 1], r = (int)(blockIdx.x & 1u);
+    const McView& v = as_constant(views)[c];
+    const McSweepChain& P = as_constant(params)[c];
+    const McMove mv = sweep_select(v, P, seed, step);
+    if (mv.molecule < 0) return;
+    const int2 mj = v.mol[mv.molecule];
+    const int tid = threadIdx.x;
+    if (tid < mj.y) {
+        int kind, mol;
+        unpack(v.atoms[mj.x + tid].w, kind, mol);
+        s_L.kinds[tid] = kind;
+        s_L.q[tid] = v.kind_charge[kind];
+    }
+    if (tid == 0) { s_L.first = mj.x; s_L.m = mj.y; }
+    McPositions* mine = prop + 3 * (size_t)c + blockIdx.y;
+    if (r == 1 && tid < 3 * mj.y) mine->xyz[tid] = sweep_coordinate(v, P, bead, mv, mj, seed, step, tid / 3, tid % 3);
+    __syncthreads();
+    const McAtChainRow at{2 * (int64_t)c + r, r, 0u, table_ok};
+    mc_trial_row<FAST, false, false>(v, mv.molecule, s_L, mine->xyz, rows, P.stride, nullptr, nullptr, 0ull, at);
+}
+
+// one workgroup per chain: compute_accept_move (src/montecarlo.jl:702-712) on the two rows, statistics, the log record, update_mc!
+__global__ __launch_bounds__(MC_THREADS) void k_mcg_sweep_accept(const McView* __restrict__ views, const McSweepChain* __restrict__ params, uint64_t seed,
+                                                                 uint64_t step, const McPositions* __restrict__ prop, const double* __restrict__ rows,
+                                                                 ceg_mc_sweep_stats_t* __restrict__ stats, ceg_mc_sweep_record_t* __restrict__ log)
+{
+    const int c = (int)blockIdx.x, tid = threadIdx.x;
+    const McView& v = as_constant(views)[c];
+    const McSweepChain& P = as_constant(params)[c];
+    const McMove mv = sweep_select(v, P, seed, step);
+    const ceg_philox::Block w = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::ACCEPT);
+    const double u = ceg_philox::uniform(w.w[0], w.w[1]);
+    ceg_mc_sweep_record_t* rec = log ? log + c : nullptr;          // (the record's other entries were zeroed before the first step)
+    if (mv.molecule < 0) {
+        if (rec && tid == 0) { rec->molecule = -1; rec->kind = -1; rec->u = u; }
+        return;
+    }
+    const double* r = rows + 8 * (size_t)c;
+    double b, a;
+    {
+#pragma clang fp contract(off)
+        b = ((r[0] + r[1]) + r[2]) + r[3];
+        a = ((r[4] + r[5]) + r[6]) + r[7];
+    }
+    const bool blocked = r[4] >= 1e90;
+    const int accepted = __builtin_amdgcn_readfirstlane((!blocked && (a < b || u < exp((b - a) / P.temperature))) ? 1 : 0);
+    const McPositions& np = prop[3 * (size_t)c];
+    if (tid == 0) {
+        ceg_mc_sweep_stats_t& S = stats[c];
+        if (mv.kind == 0) { S.translation_trials += 1; S.translation_accepted += accepted; }
+        else { S.rotation_trials += 1; S.rotation_accepted += accepted; }
+        if (blocked) S.blocked += 1;
+        if (accepted) S.delta += a - b;
+        if (rec) {
+            rec->molecule = mv.molecule; rec->kind = mv.kind; rec->accepted = accepted; rec->u = u;
+            for (int t = 0; t < 8; ++t) rec->rows[t >> 2][t & 3] = r[t];
+        }
+    }
+    if (rec && tid < 3 * v.mol[mv.molecule].y) rec->positions[tid / 3][tid % 3] = np.xyz[tid];
+    if (accepted) mc_accept_body(v, mv.molecule, np, d_mc_no_cell_ops, P.stride);
 }
 
 // sums[:, ij+1] of every molecule from its current positions (one workgroup per molecule)
@@ -2141,6 +2272,10 @@ struct ceg_mc_group {
     unsigned long long *h_flag = nullptr, *dm_flag = nullptr;
     unsigned* d_done = nullptr;
     unsigned long long seq = 0;
+    // ceg_mc_group_sweep: per-chain parameters, launch lists, proposals, rows and statistics of a sweep (one allocation), the beads
+    unsigned char* d_sweep = nullptr;
+    int32_t* d_bead = nullptr;
+    size_t bead_cap = 0;
 };
 
 namespace {
@@ -2153,6 +2288,8 @@ void group_free(ceg_mc_group* g)
     if (g->stream) { (void)hipStreamSynchronize(g->stream); (void)hipStreamDestroy(g->stream); }
     if (g->d_views) (void)hipFree(g->d_views);
     if (g->d_done) (void)hipFree(g->d_done);
+    if (g->d_sweep) (void)hipFree(g->d_sweep);
+    if (g->d_bead) (void)hipFree(g->d_bead);
     for (void* p : {(void*)g->h_views, (void*)g->h_in, (void*)g->h_out, (void*)g->h_acc, (void*)g->h_flag})
         if (p) (void)hipHostFree(p);
     delete g;
@@ -2438,4 +2575,129 @@ extern "C" int ceg_mc_group_accept(ceg_mc_group_t* g, const int32_t* molecule, c
             g->accept_pending = false;   // (rebuild_cells leaves the stream idle)
         }
     return CEG_OK;                       // asynchronous: later calls on the group and on its members are ordered behind it
+}
+
+extern "C" int ceg_mc_group_sweep(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nsteps, ceg_mc_sweep_stats_t* stats_out,
+                                  ceg_mc_sweep_record_t* log_out)
+{
+    static_assert(sizeof(ceg_mc_sweep_record_t) == 472 && sizeof(ceg_mc_sweep_stats_t) == 48, "layouts the bindings restate");
+    static_assert(sizeof(((ceg_mc_sweep_record_t*)nullptr)->positions) == sizeof(McPositions), "a record holds one placement");
+    if (!g || !p || !stats_out || !p->stream_id || !p->temperature || !p->dmax || !p->thetamax || !p->p_rotation)
+        return merr(CEG_ERR_INVALID, "bad argument");
+    if (nsteps < 0) return merr(CEG_ERR_INVALID, "negative number of steps");
+    const int k = (int)g->chains.size();
+    // ---- every refusal before anything is launched or changed
+    std::vector<McSweepChain> pc((size_t)k);
+    std::vector<int32_t> beads;
+    size_t lds_trial[2] = {0, 0}, pair_table[2] = {0, 0}, lds_accept = 0;
+    std::vector<int32_t> list[2];
+    for (int c = 0; c < k; ++c) {
+        ceg_mc* h = g->chains[c];
+        if (h->poisoned) return group_refuse_poisoned(c);
+        if (h->v.use_cells || h->cm.on) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "chain %d keeps its guests in neighbour cells: sweeps take chains with the exhaustive pair loop only", c);
+            return merr(CEG_ERR_UNSUPPORTED, msg);
+        }
+        const double T = p->temperature[c], dmax = p->dmax[c], th = p->thetamax[c], pr = p->p_rotation[c];
+        if (!std::isfinite(T) || !(T > 0.0)) return group_bad(c, "the temperature must be finite and > 0");
+        if (!std::isfinite(dmax) || dmax < 0.0) return group_bad(c, "dmax must be finite and >= 0");
+        if (!std::isfinite(th) || th < 0.0) return group_bad(c, "thetamax must be finite and >= 0");
+        if (!(pr >= 0.0 && pr <= 1.0)) return group_bad(c, "p_rotation must lie in [0, 1]");
+        for (int d = 0; d < c; ++d)
+            if (p->stream_id[d] == p->stream_id[c]) return group_bad(c, "its stream id is already used by an earlier chain");
+        McSweepChain& P = pc[(size_t)c];
+        P = McSweepChain{};
+        P.stream_id = p->stream_id[c];
+        P.bead_off = (int32_t)beads.size();
+        P.stride = h->stride;
+        P.temperature = T; P.dmax = dmax; P.thetamax = th; P.p_rotation = pr;
+        if (h->v.nmol > 0 && !p->bead) return merr(CEG_ERR_INVALID, "bad argument");
+        int mmax = 0;
+        for (int j = 0; j < h->v.nmol; ++j) {
+            const int32_t b = p->bead[beads.size()];
+            if (b < 0 || b >= h->h_mol[(size_t)j].y) return group_bad(c, "a bead lies outside its molecule");
+            beads.push_back(b);
+            mmax = std::max(mmax, h->h_mol[(size_t)j].y);
+        }
+        if (h->v.nmol == 0) continue;
+        if (tables_bytes(h, mmax) > 64 * 1024) return merr(CEG_ERR_UNSUPPORTED, "k-space tables of the molecule do not fit in LDS");
+        const int cl = h->v.fast ? 1 : 0;
+        list[cl].push_back(c);
+        lds_trial[cl] = std::max(lds_trial[cl], tables_bytes(h, mmax));
+        lds_accept = std::max(lds_accept, tables_bytes(h, mmax));
+        if (h->v.table_in_lds)
+            pair_table[cl] = std::max(pair_table[cl], sizeof(DevRule) * (size_t)(h->v.nrules > 0 ? h->v.nrules : 1) + sizeof(int32_t) * ((size_t)h->v.nkinds * h->v.nkinds + 1));
+    }
+    for (int c = 0; c < k; ++c) stats_out[c] = ceg_mc_sweep_stats_t{};
+    if (nsteps == 0) return CEG_OK;
+    int table_ok[2];
+    for (int cl = 0; cl < 2; ++cl) {                     // the pair table in LDS only where the largest tables leave room (run_trial's rule)
+        table_ok[cl] = lds_trial[cl] + pair_table[cl] <= 64 * 1024 ? 1 : 0;
+        if (table_ok[cl]) lds_trial[cl] += pair_table[cl];
+    }
+    Guard guard(g->device);
+    if (!guard.ok) return merr(CEG_ERR_HIP, "hipSetDevice failed");
+    // ---- the sweep's device memory: [K] parameters | [K] launch lists | [3K] proposals | [8K] rows | [K] statistics
+    auto up16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
+    const size_t o_par = 0, o_list = up16(o_par + sizeof(McSweepChain) * (size_t)k), o_prop = up16(o_list + sizeof(int32_t) * (size_t)k),
+                 o_rows = up16(o_prop + sizeof(McPositions) * 3 * (size_t)k), o_stats = up16(o_rows + sizeof(double) * 8 * (size_t)k),
+                 total = up16(o_stats + sizeof(ceg_mc_sweep_stats_t) * (size_t)k);
+    if (!g->d_sweep && hipMalloc((void**)&g->d_sweep, total) != hipSuccess) { g->d_sweep = nullptr; return merr(CEG_ERR_HIP, "hipMalloc failed"); }
+    if (beads.size() > g->bead_cap) {
+        if (g->d_bead) (void)hipFree(g->d_bead);
+        g->d_bead = nullptr; g->bead_cap = 0;
+        if (hipMalloc((void**)&g->d_bead, sizeof(int32_t) * beads.size()) != hipSuccess) return merr(CEG_ERR_HIP, "hipMalloc failed");
+        g->bead_cap = beads.size();
+    }
+    ceg_mc_sweep_record_t* d_log = nullptr;
+    const size_t log_bytes = log_out ? sizeof(ceg_mc_sweep_record_t) * (size_t)k * (size_t)nsteps : 0;
+    if (log_out && hipMalloc((void**)&d_log, log_bytes) != hipSuccess) return merr(CEG_ERR_HIP, "hipMalloc of the log failed");
+    auto fail = [&](const char* what) {
+        if (d_log) (void)hipFree(d_log);
+        return merr(CEG_ERR_HIP, what);
+    };
+    {
+        std::vector<unsigned char> stage(total, 0);
+        memcpy(stage.data() + o_par, pc.data(), sizeof(McSweepChain) * (size_t)k);
+        int32_t* l = reinterpret_cast<int32_t*>(stage.data() + o_list);
+        for (int cl = 0, e = 0; cl < 2; ++cl)
+            for (int32_t c : list[cl]) l[e++] = c;
+        // (nothing of an earlier sweep is in flight: every sweep ends with a synchronisation)
+        if (hipMemcpy(g->d_sweep, stage.data(), total, hipMemcpyHostToDevice) != hipSuccess) return fail("H2D failed");
+        if (!beads.empty() && hipMemcpy(g->d_bead, beads.data(), sizeof(int32_t) * beads.size(), hipMemcpyHostToDevice) != hipSuccess) return fail("H2D failed");
+    }
+    if (!group_upload_views(g, std::vector<char>((size_t)k, 1))) return fail("view upload failed");
+    if (d_log && hipMemsetAsync(d_log, 0, log_bytes, g->stream) != hipSuccess) return fail("hipMemsetAsync failed");
+    const McSweepChain* d_par = reinterpret_cast<const McSweepChain*>(g->d_sweep + o_par);
+    const int32_t* d_list = reinterpret_cast<const int32_t*>(g->d_sweep + o_list);
+    McPositions* d_prop = reinterpret_cast<McPositions*>(g->d_sweep + o_prop);
+    double* d_rows = reinterpret_cast<double*>(g->d_sweep + o_rows);
+    ceg_mc_sweep_stats_t* d_stats = reinterpret_cast<ceg_mc_sweep_stats_t*>(g->d_sweep + o_stats);
+    // ---- the steps: nothing between them but the stream's own order
+    bool launched = true;
+    const bool any = !list[0].empty() || !list[1].empty();
+    for (int64_t s = 0; s < nsteps && launched && (any || d_log); ++s) {
+        const uint64_t step = p->first_step + (uint64_t)s;
+        if (!list[0].empty())
+            hipLaunchKernelGGL((k_mcg_sweep_trial<false>), dim3(2u * (unsigned)list[0].size(), 3u), dim3(MC_THREADS), lds_trial[0], g->stream, g->d_views, d_par,
+                               g->d_bead, d_list, table_ok[0], p->seed, step, d_prop, d_rows);
+        if (!list[1].empty())
+            hipLaunchKernelGGL((k_mcg_sweep_trial<true>), dim3(2u * (unsigned)list[1].size(), 3u), dim3(MC_THREADS), lds_trial[1], g->stream, g->d_views, d_par,
+                               g->d_bead, d_list + list[0].size(), table_ok[1], p->seed, step, d_prop, d_rows);
+        hipLaunchKernelGGL(k_mcg_sweep_accept, dim3((unsigned)k), dim3(MC_THREADS), lds_accept, g->stream, g->d_views, d_par, p->seed, step, d_prop, d_rows,
+                           d_stats, d_log ? d_log + (size_t)s * (size_t)k : nullptr);
+        launched = hipGetLastError() == hipSuccess;
+    }
+    const bool ok = hipStreamSynchronize(g->stream) == hipSuccess && launched &&
+                    hipMemcpy(stats_out, d_stats, sizeof(ceg_mc_sweep_stats_t) * (size_t)k, hipMemcpyDeviceToHost) == hipSuccess &&
+                    (!d_log || hipMemcpy(log_out, d_log, log_bytes, hipMemcpyDeviceToHost) == hipSuccess);
+    g->accept_pending = false;
+    g->uploads_pending = false;
+    if (d_log) (void)hipFree(d_log);
+    if (!ok) {                                           // some steps may have run: the chains' states are unknown
+        for (ceg_mc* h : g->chains) h->poisoned = true;
+        return merr(CEG_ERR_HIP, "a sweep kernel failed: every chain of the group is marked inconsistent");
+    }
+    return CEG_OK;
 }

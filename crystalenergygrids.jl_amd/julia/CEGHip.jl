@@ -591,6 +591,62 @@ function mc_group_accept!(g::Ptr{Cvoid}, accepted::Vector)
     nothing
 end
 
+# `ceg_mc_sweep_params_t`, `ceg_mc_sweep_stats_t`, `ceg_mc_sweep_record_t` of include/ceg_hip.h
+struct McSweepParams
+    seed::UInt64
+    first_step::UInt64
+    stream_id::Ptr{UInt32}
+    temperature::Ptr{Float64}
+    dmax::Ptr{Float64}
+    thetamax::Ptr{Float64}
+    p_rotation::Ptr{Float64}
+    bead::Ptr{Int32}
+end
+struct McSweepStats
+    translation_trials::Int64
+    translation_accepted::Int64
+    rotation_trials::Int64
+    rotation_accepted::Int64
+    blocked::Int64
+    delta::Float64
+end
+struct McSweepRecord
+    molecule::Int32        # 0-based Ewald index, -1 for an idle chain
+    kind::Int32            # 0 translation, 1 rotation, -1 idle
+    accepted::Int32
+    _pad::Int32
+    u::Float64
+    rows::NTuple{8,Float64}          # before (4), after (4)
+    positions::NTuple{48,Float64}    # x, y, z of up to 16 atoms
+end
+
+"""
+`ceg_mc_group_sweep`: `nsteps` steps of the inner loop of `run_montecarlo!` (src/simulation.jl:727-781; translations and rotations)
+for every chain of the group, proposals and Metropolis rule on the device, one synchronisation at the end.  `temperature` (K),
+`dmax` (Å), `thetamax` (unitful angle or radians) and `p_rotation` per chain; `bead[c]` the 1-based reference atom of every species
+of chain `c` in Ewald order (`mc.bead[i]` of its kind); step `s` of the call is step `first_step + s` of the counter-based stream.
+Returns the statistics per chain and, with `log=true`, the `nsteps x K` records (stored chain-fastest).  The adaptation of
+`statistics.dmax` / `θmax` (src/simulation.jl:820-825) stays with the caller, between sweeps.
+"""
+function mc_group_sweep!(g::Ptr{Cvoid}, nsteps::Integer, seed::Integer, first_step::Integer, temperature::Vector, dmax::Vector,
+                         thetamax::Vector, p_rotation::Vector{Float64}, bead::Vector{Vector{Int}};
+                         stream_id::Vector{UInt32}=UInt32.(0:length(temperature)-1), log::Bool=false)
+    k = length(temperature)
+    T = Float64[ustrip(u"K", t) for t in temperature]
+    dm = Float64[d isa Real ? d : ustrip(u"Å", d) for d in dmax]
+    th = Float64[t isa Real ? t : ustrip(u"rad", t) for t in thetamax]
+    beads = Int32[b - 1 for chain in bead for b in chain]
+    stats = Vector{McSweepStats}(undef, k)
+    records = Matrix{McSweepRecord}(undef, k, log ? nsteps : 0)
+    GC.@preserve stream_id T dm th p_rotation beads stats records begin
+        params = Ref(McSweepParams(UInt64(seed), UInt64(first_step), pointer(stream_id), pointer(T), pointer(dm), pointer(th),
+                                   pointer(p_rotation), pointer(beads)))
+        _check(ccall((:ceg_mc_group_sweep, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                     g, params, nsteps, stats, log && nsteps > 0 ? pointer(records) : C_NULL))
+    end
+    log ? (stats, records) : stats
+end
+
 "`ceg_mc_group_destroy`: the chains get their own streams back and stay valid"
 function mc_group_close(g::Ptr{Cvoid})
     _check(ccall((:ceg_mc_group_destroy, LIB[]), Cint, (Ptr{Cvoid},), g))

@@ -606,7 +606,8 @@ CEG_API int ceg_mc_get_state(ceg_mc_t* handle, double* positions, double* sf_tot
 CEG_API int ceg_mc_neighbour_cells(ceg_mc_t* handle, int32_t nb[3], int32_t* capacity);
 /* ---- chain groups: one Markov step of K chains per launch (make_isotherm's chains, src/parameterinputs.jl:316-329) ----
  * K handles on ONE device stepped in lockstep: one launch evaluates the trials of every chain, one launch applies every accepted
- * move; the acceptance rule stays with the caller.  A batch-1 ceg_mc_trial is mostly launch and completion latency; a group pays
+ * move; with trial / accept the acceptance rule stays with the caller (ceg_mc_group_sweep, below, runs whole sweeps of
+ * translations and rotations on the device).  A batch-1 ceg_mc_trial is mostly launch and completion latency; a group pays
  * it once per step for all K chains.
  *
  * create: 1 <= k <= CEG_MC_GROUP_MAX handles, all on one device, each at most once, none already in a group, each after
@@ -636,6 +637,64 @@ CEG_API int ceg_mc_group_destroy(ceg_mc_group_t* group);
 CEG_API int ceg_mc_group_trial(ceg_mc_group_t* group, const int32_t* molecule, const int32_t* n,
                                const int32_t* insert_kinds, int32_t insert_m, const double* trial, double* out);
 CEG_API int ceg_mc_group_accept(ceg_mc_group_t* group, const int32_t* molecule, const double* positions);
+
+/* ---- sweeps: S Markov steps of all K chains of a group with no host round trip between steps ----
+ * The inner loop of run_montecarlo! (src/simulation.jl:727-781) for rigid translations and rotations: choose a molecule and a move,
+ * build the trial placement from the resident positions, movement_energy before and after, compute_accept_move
+ * (src/montecarlo.jl:702-712), update_mc!.  Proposal, decision and update run on the device; the rows are those of
+ * ceg_mc_group_trial (the same kernel body, three workgroups per row), the update is that of ceg_mc_group_accept.  Per step two
+ * launches are enqueued back to back on the group's stream (one more where fast and exact-pair chains are mixed); a chain's
+ * per-step inputs and rows stay in device memory and the host synchronises once, at the end.
+ *
+ * Random stream: Philox4x32-10, multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85.
+ *   key = (seed low word, seed high word); counter = (step low, step high, stream id of the chain, purpose), step = first_step + s
+ *   the absolute 64-bit step number.  Known answers (counter; key) -> output:
+ *     0 0 0 0; 0 0                                            -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *     ffffffff x4; ffffffff x2                                -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *     243f6a88 85a308d3 13198a2e 03707344; a4093822 299f31d0  -> d16cfe09 94fdcceb 5001e420 24126ea1
+ *   U(a, b) = (((uint64)a << 21) | (b >> 11)) * 2^-53 in [0, 1).  One block (w0..w3) per (step, stream, purpose); every workgroup
+ *   that takes part in a chain's step regenerates it, nothing random is stored.  For stream c at step s:
+ *     purpose 0, selection: molecule j = min(floor(U(w0,w1) nmol), nmol - 1); a rotation iff molecule j has more than one atom
+ *       and U(w2,w3) < p_rotation[c], else a translation;
+ *     purposes 1 and 2, geometry: translation (random_translation, src/mcmoves.jl:139-146, scalar branch)
+ *       r = ((2U(w0,w1)-1) dmax, (2U(w2,w3)-1) dmax, (2U(w0',w1')-1) dmax), primed words from purpose 2, added to every atom;
+ *       rotation (random_rotation, :147-164) theta = thetamax (2U(w0,w1)-1) rad, axis = min(floor(3 U(w2,w3)), 2), the matrices of
+ *       :155-161, about atom `bead` of the molecule: ref + R (p - ref);
+ *     purpose 3, acceptance: u = U(w0,w1).
+ * Rule: b, a = the four columns of the row before / after summed left to right; a trial whose framework VdW column is >= 1e90 is
+ *   blocked and rejected; otherwise accepted if a < b or u < exp((b - a) / T).  A chain without molecules is idle.
+ *
+ * params: seed, first_step; per chain stream_id (pairwise distinct), temperature K (finite, > 0), dmax A and thetamax rad (finite,
+ *   >= 0), p_rotation in [0, 1]; bead: one 0-based atom index per molecule of every chain, packed in chain order (molecule order of
+ *   ceg_mc_set_guests / ceg_mc_insert).  A violation, nsteps < 0 or a missing pointer -> CEG_ERR_INVALID; a member that keeps its
+ *   guests in neighbour cells -> CEG_ERR_UNSUPPORTED (its update needs cell operations worked out on the host); a member marked
+ *   inconsistent -> CEG_ERR_HIP.  A refused call launches nothing and leaves every chain as it was.  nsteps == 0: zeros.
+ * stats_out [K]: trials and acceptances per move kind (a blocked trial counts as a trial of its kind and in `blocked`), delta =
+ *   FP64 sum of a - b over the accepted moves.
+ * log_out [nsteps][K] or NULL (production): per (step, chain) the molecule and move kind (0 translation, 1 rotation; both -1 for
+ *   an idle chain), the accepted flag, u, the rows before / after and the proposed positions (unused entries zero).
+ * Synchronous.  Afterwards every per-handle and group entry point works on the moved state; the molecule table does not change.
+ * Not covered: swap / reinsertion / random_* moves, the inblockpocket test of choose_step!, and the adaptation of dmax / thetamax
+ * (src/simulation.jl:820-825), which stays with the caller between sweeps -- the stats hold the ratios it needs. */
+typedef struct ceg_mc_sweep_params {
+    uint64_t seed, first_step;
+    const uint32_t* stream_id;                 /* [K] */
+    const double *temperature, *dmax, *thetamax, *p_rotation;      /* [K] each */
+    const int32_t* bead;                       /* [sum of the chains' molecule counts] */
+} ceg_mc_sweep_params_t;
+typedef struct ceg_mc_sweep_stats {
+    int64_t translation_trials, translation_accepted, rotation_trials, rotation_accepted, blocked;
+    double delta;
+} ceg_mc_sweep_stats_t;
+typedef struct ceg_mc_sweep_record {
+    int32_t molecule, kind, accepted, _pad;
+    double u;
+    double rows[2][4];
+    double positions[16][3];
+} ceg_mc_sweep_record_t;
+
+CEG_API int ceg_mc_group_sweep(ceg_mc_group_t* group, const ceg_mc_sweep_params_t* params, int64_t nsteps,
+                               ceg_mc_sweep_stats_t* stats_out, ceg_mc_sweep_record_t* log_out);
 
 /* ---- blocking masks on the grid lattice ----------------------------- */
 /*
