@@ -41,6 +41,27 @@ SWEEP_RECORD_DTYPE = np.dtype([('molecule', '<i4'), ('kind', '<i4'), ('accepted'
                                ('rows', '<f8', (2, 4)), ('positions', '<f8', (16, 3))], align=True)
 assert SWEEP_STATS_DTYPE.itemsize == 48 and SWEEP_RECORD_DTYPE.itemsize == 472
 
+GCMC_MAX_SPECIES = 8         # CEG_MC_GCMC_MAX_SPECIES
+
+
+class GcmcParams(C.Structure):
+    """``ceg_mc_gcmc_params_t``"""
+    _fields_ = [("seed", C.c_uint64), ("first_step", C.c_uint64), ("stream_id", C.c_void_p), ("temperature", C.c_void_p),
+                ("dmax", C.c_void_p), ("thetamax", C.c_void_p), ("nspecies", C.c_int32), ("_pad", C.c_int32), ("species", C.c_void_p),
+                ("molecule_species", C.c_void_p), ("max_molecules", C.c_void_p), ("molecule_species_out", C.c_void_p)]
+
+
+# ``ceg_mc_gcmc_species_t``, ``ceg_mc_gcmc_stats_t`` and ``ceg_mc_gcmc_record_t`` as structured arrays
+GCMC_SPECIES_DTYPE = np.dtype([('m', '<i4'), ('bead', '<i4'), ('kinds', '<i4', (16,)), ('model', '<f8', (16, 3)), ('cumulative', '<f8', (5,)),
+                               ('phiPV_div_k', '<f8'), ('self_reciprocal', '<f8'), ('tail_framework', '<f8'),
+                               ('tail_cross', '<f8', (GCMC_MAX_SPECIES,))], align=True)
+GCMC_STATS_DTYPE = np.dtype([('trials', '<i8', (7,)), ('accepted', '<i8', (7,)), ('blocked', '<i8'), ('capacity', '<i8'), ('spent', '<i8'),
+                             ('delta_moves', '<f8'), ('delta_swaps', '<f8'), ('count', '<i4', (GCMC_MAX_SPECIES,)), ('nmol', '<i4'),
+                             ('_pad', '<i4')], align=True)
+GCMC_RECORD_DTYPE = np.dtype([('species', '<i4'), ('molecule', '<i4'), ('kind', '<i4'), ('accepted', '<i4'), ('n_species', '<i4'),
+                              ('flags', '<i4'), ('u', '<f8'), ('tc', '<f8'), ('rows', '<f8', (2, 4)), ('positions', '<f8', (16, 3))], align=True)
+assert (C.sizeof(GcmcParams), GCMC_SPECIES_DTYPE.itemsize, GCMC_STATS_DTYPE.itemsize, GCMC_RECORD_DTYPE.itemsize) == (88, 584, 192, 488)
+
 c_double_p = C.POINTER(C.c_double)
 c_float_p = C.POINTER(C.c_float)
 c_int32_p = C.POINTER(C.c_int32)
@@ -172,6 +193,7 @@ PROTOTYPES = {
     "ceg_mc_group_trial": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p, C.c_int32, c_double_p, c_double_p]),
     "ceg_mc_group_accept": (C.c_int, [C.c_void_p, c_int32_p, c_double_p]),
     "ceg_mc_group_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ceg_mc_group_sweep_gcmc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ceg_energy_grid": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, c_double_p, c_double_p, C.c_int32,
                                   c_double_p, C.c_int32, c_double_p, c_int32_p,
                                   C.c_void_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p,

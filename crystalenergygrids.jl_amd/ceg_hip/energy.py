@@ -525,6 +525,13 @@ class DeviceMonteCarlo:
         host = [pos[start[d]:start[d] + sizes[d]] for kind in self._slot for d in kind]
         return (np.concatenate(host) if host else pos), (re[:nk] + 1j * im[:nk])
 
+    def pull_positions(self) -> None:
+        """``mc.positions`` from the device (after ``sweep_gcmc(..., positions=False)``): kind by kind in device molecule order."""
+        pos, _sf = self.state()
+        sizes = [len(self.mc.ffidx[i]) for i, kind in enumerate(self._slot) for _d in kind]
+        split = iter(np.split(pos, np.cumsum(sizes)[:-1]) if sizes else [])
+        self.mc.positions = [[next(split).copy() for _d in kind] for kind in self._slot]
+
     def close(self) -> None:
         if getattr(self, "_group", None) is not None:
             raise RuntimeError(f"this chain is a member of {self._group!r}: close the group first")
@@ -550,7 +557,8 @@ class DeviceMonteCarloGroup:
     """K :class:`DeviceMonteCarlo` chains on one device stepped in lockstep (``ceg_mc_group_*``): one launch evaluates the trials
     of every chain, one launch applies every accepted move -- the way ``make_isotherm`` (parameterinputs.jl:316-329) runs one
     ``run_gcmc`` per pressure, with the launch cost shared by the chains.  With ``trial`` / ``accept`` the acceptance rule stays
-    with the caller; ``sweep`` runs whole sweeps of translations and rotations on the device.  While
+    with the caller; ``sweep`` runs whole sweeps of translations and rotations on the device, ``sweep_gcmc`` whole sweeps of all six
+    move kinds of ``MCMoves``, insertions and deletions included.  While
     grouped the chains' own methods remain usable (insert, remove, single trials ...) and are ordered with the group calls; the
     group and its chains are driven from one thread.  Usable as a context manager; ``close()`` gives the chains back."""
 
@@ -675,6 +683,98 @@ class DeviceMonteCarloGroup:
         records = np.zeros((max(int(nsteps), 0), k), dtype=_abi.SWEEP_RECORD_DTYPE) if log else None
         _abi.check(self._lib, self._lib.ceg_mc_group_sweep(self._h, C.addressof(params), int(nsteps), stats.ctypes.data,
                                                            records.ctypes.data if log and records.size else None))
+        return (stats, records) if log else stats
+
+    def gcmc_species(self, moves, phiPV_div_k, self_reciprocal=None, bead=None) -> np.ndarray:
+        """The species table of ``ceg_mc_group_sweep_gcmc`` (``_abi.GCMC_SPECIES_DTYPE``) from the first chain's setup: one species
+        per kind of ``mc`` -- atom kinds, ``mc.models``, ``mc.bead``, the tail-correction rows -- with ``moves[i]`` a
+        :class:`ceg_hip.mcrng.MoveTable` and ``phiPV_div_k[i]`` in K.  ``self_reciprocal[i]`` defaults to ``ctx.energies[i]``
+        (ewald.jl:497-544): ``COULOMBIC_CONVERSION_FACTOR alpha / sqrt(pi) * sum(q^2)``."""
+        from . import mcrng
+        from .hostmirror.constants import COULOMBIC_CONVERSION_FACTOR
+        mc = self.chains[0].mc
+        ns = len(mc.ffidx)
+        if ns > _abi.GCMC_MAX_SPECIES:
+            raise ValueError(f"at most {_abi.GCMC_MAX_SPECIES} species")
+        if len(moves) != ns or len(phiPV_div_k) != ns:
+            raise ValueError(f"moves and phiPV_div_k: one entry per species ({ns})")
+        beads = mcrng.default_beads(mc) if bead is None else list(bead)
+        table = np.zeros(ns, dtype=_abi.GCMC_SPECIES_DTYPE)
+        for i, ids in enumerate(mc.ffidx):
+            m = len(ids)
+            model = np.asarray(mc.models[i] if len(mc.models) > i else np.zeros((m, 3)), dtype=np.float64).reshape(-1, 3)
+            if len(model) != m or m > 16:
+                raise ValueError(f"species {i}: the model needs {m} <= 16 atoms")
+            t = table[i]
+            t["m"], t["bead"] = m, beads[i]
+            t["kinds"][:m] = [ix - 1 for ix in ids]
+            t["model"][:m] = model
+            t["cumulative"] = moves[i].cumulatives
+            t["phiPV_div_k"] = phiPV_div_k[i]
+            if self_reciprocal is not None:
+                t["self_reciprocal"] = self_reciprocal[i]
+            elif mc.ewald.alpha != 0.0:
+                q = np.array([0.0 if np.isnan(mc.charges[ix]) else mc.charges[ix] for ix in ids])
+                t["self_reciprocal"] = float((q ** 2).sum()) * (COULOMBIC_CONVERSION_FACTOR / math.sqrt(math.pi) * mc.ewald.alpha)
+            if mc.tail_cross is not None:
+                t["tail_framework"] = mc.tail_framework[i]
+                t["tail_cross"][:ns] = np.asarray(mc.tail_cross)[i, :ns]
+        return table
+
+    def sweep_gcmc(self, nsteps: int, seed: int, first_step: int = 0, *, temperature, dmax, thetamax, moves=None, phiPV_div_k=None,
+                   max_molecules, species=None, self_reciprocal=None, stream_id=None, bead=None, degrees: bool = False, log: bool = False,
+                   positions: bool = True):
+        """``ceg_mc_group_sweep_gcmc``: ``nsteps`` steps of every chain with all six move kinds of ``MCMoves`` (translation,
+        rotation, random_translation, random_rotation, random_reinsertion, swap) proposed, decided and applied on the device; the
+        molecule table changes on the device and is read back once, at the end.
+
+        ``moves[i]`` / ``phiPV_div_k[i]`` per species (kind of ``mc``), or a ready ``species`` table (:meth:`gcmc_species`);
+        ``max_molecules``: one value or one per chain; the other arguments as :meth:`sweep`.
+
+        -> stats (``_abi.GCMC_STATS_DTYPE`` [K]) and with ``log=True`` the log [nsteps, K] (``_abi.GCMC_RECORD_DTYPE``).  Afterwards
+        every chain's ``mc.positions`` holds the final state, species by species in device molecule order, and its (kind, index)
+        addressing follows it; ``mc.tailcorrection`` and ``mc.sums`` are NOT updated.  ``positions=False`` skips the read-back of
+        the coordinates (one synchronisation and copy per chain): ``mc.positions`` then holds one ``None`` per molecule, which is
+        all the device entry points need, until :meth:`DeviceMonteCarlo.pull_positions` fills them in -- for runs of many sweeps
+        that look at the coordinates only now and then."""
+        k = len(self.chains)
+
+        def per_chain(x, what, dtype=np.float64):
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=dtype), (k,)) if np.ndim(x) == 0 else x, dtype=dtype)
+            if a.shape != (k,):
+                raise ValueError(f"{what}: one value or one per chain ({k})")
+            return a
+
+        T, dm, th = per_chain(temperature, "temperature"), per_chain(dmax, "dmax"), per_chain(thetamax, "thetamax")
+        if degrees:
+            th = np.ascontiguousarray(np.deg2rad(th))
+        cap = per_chain(max_molecules, "max_molecules", np.int32)
+        sid = np.ascontiguousarray(np.arange(k) if stream_id is None else stream_id, dtype=np.uint32)
+        if sid.shape != (k,):
+            raise ValueError(f"stream_id: one per chain ({k})")
+        table = np.ascontiguousarray(species if species is not None else self.gcmc_species(moves, phiPV_div_k, self_reciprocal, bead))
+        given = []
+        for chain in self.chains:
+            if any(len(b) for b in (getattr(chain.mc, "speciesblocks", None) or [])):
+                raise NotImplementedError("sweeps do not test block pockets (inblockpocket of choose_step!): this setup has some")
+            by_device = {d: i for i, kind in enumerate(chain._slot) for d in kind}
+            given += [by_device[d] for d in sorted(by_device)]
+        given = np.ascontiguousarray(given if given else [0], dtype=np.int32)
+        out = np.full(max(int(np.clip(cap, 0, None).sum()), 1), -1, dtype=np.int32)
+        params = _abi.GcmcParams(int(seed), int(first_step), sid.ctypes.data, T.ctypes.data, dm.ctypes.data, th.ctypes.data, len(table), 0,
+                                 table.ctypes.data, given.ctypes.data, cap.ctypes.data, out.ctypes.data)
+        stats = np.zeros(k, dtype=_abi.GCMC_STATS_DTYPE)
+        records = np.zeros((max(int(nsteps), 0), k), dtype=_abi.GCMC_RECORD_DTYPE) if log else None
+        _abi.check(self._lib, self._lib.ceg_mc_group_sweep_gcmc(self._h, C.addressof(params), int(nsteps), stats.ctypes.data,
+                                                                records.ctypes.data if log and records.size else None))
+        # the chains' host side from the reported table: _slot[i] = the device indices of species i in device order
+        offsets = np.concatenate([[0], np.cumsum(np.clip(cap, 0, None))])
+        for c, chain in enumerate(self.chains):
+            spec = out[offsets[c]:offsets[c] + int(stats[c]["nmol"])]
+            chain._slot = [[int(d) for d in np.nonzero(spec == i)[0]] for i in range(len(chain.mc.positions))]
+            chain.mc.positions = [[None] * len(kind) for kind in chain._slot]
+            if positions:
+                chain.pull_positions()
         return (stats, records) if log else stats
 
     def close(self) -> None:

@@ -11,6 +11,14 @@ Purposes for stream ``c`` at the absolute step ``s`` (key = seed low / high word
                  of purpose 1 and (w0, w1) of purpose 2; rotation (``random_rotation``, :147-164): ``theta = thetamax (2 U(w0, w1) - 1)``,
                  axis ``min(floor(3 U(w2, w3)), 2)`` of purpose 1, about atom ``bead``
   3  acceptance  ``u = U(w0, w1)``
+
+``ceg_mc_group_sweep_gcmc`` (all six move kinds of mcmoves.jl:1-8, :func:`propose_gcmc`) keeps purposes 1-3 and adds:
+  4  selection   species ``min(floor(U(w0, w1) nspecies), nspecies - 1)``; move kind: the first cumulative of the species'
+                 :class:`MoveTable` above ``U(w2, w3)``, else a swap
+  5  molecule    ``j = min(floor(U(w0, w1) N_i), N_i - 1)``, the j-th molecule of the species in device molecule order; a swap is a
+                 deletion iff ``U(w2, w3) < 0.5``
+  6, 7, 8 random_* geometry  ``r = mat (U3 - 0.5)`` with ``U3`` from (w0, w1), (w2, w3) of purpose 6 and (w0, w1) of purpose 7
+                 (mcmoves.jl:143); ``theta = pi (2 U(w2, w3) - 1)`` of purpose 7, axis ``min(floor(3 U(w0, w1)), 2)`` of purpose 8
 """
 from __future__ import annotations
 
@@ -25,6 +33,10 @@ _MASK = 0xFFFFFFFF
 
 SELECT, GEOMETRY_A, GEOMETRY_B, ACCEPT = 0, 1, 2, 3
 TRANSLATION, ROTATION = 0, 1
+GCMC_SELECT, GCMC_MOLECULE, GCMC_RANDOM_A, GCMC_RANDOM_B, GCMC_RANDOM_C = 4, 5, 6, 7, 8
+RANDOM_TRANSLATION, RANDOM_ROTATION, RANDOM_REINSERTION, SWAP_INSERTION, SWAP_DELETION = 2, 3, 4, 5, 6
+MOVE_NAMES = ("translation", "rotation", "random_translation", "random_rotation", "random_reinsertion", "swap")      # mcmovenames
+KIND_NAMES = MOVE_NAMES[:5] + ("swap_insertion", "swap_deletion")
 
 
 def philox4x32_10(counter: Sequence[int], key: Sequence[int]):
@@ -130,3 +142,159 @@ def default_beads(mc):
         d2 = ((model - model.mean(axis=0)) ** 2).sum(axis=1)
         out.append(int(np.argmin(d2)))
     return out
+
+
+# ------------------------------------------------------------------ ceg_mc_group_sweep_gcmc
+class MoveTable:
+    """``MCMoves`` (mcmoves.jl:58-118): the five cumulative probabilities of translation, rotation, random_translation,
+    random_rotation and random_reinsertion; the rest up to 1 is the swap probability.  ``MoveTable(True)`` / ``MoveTable(False)``
+    are ``MCMoves(monoatomic)`` (:62-68); ``MoveTable(translation=2, random_rotation=0.5, ...)`` normalises keyword weights like
+    ``MCMoves(; ...)`` (:84-95); ``MoveTable(cumulatives=(...))`` takes the tuple as it is."""
+
+    def __init__(self, monoatomic=None, *, cumulatives=None, **weights):
+        if cumulatives is not None:
+            c = tuple(float(x) for x in cumulatives)
+        elif monoatomic is not None:
+            c = (0.5, 0.5, 1.0, 1.0, 1.0) if monoatomic else (0.33, 0.66, 0.66, 0.66, 1.0)
+        else:
+            wrong = [n for n in weights if n not in MOVE_NAMES]
+            if wrong:
+                raise ValueError(f"invalid move name(s) {wrong}: choose among {MOVE_NAMES}")
+            tot = float(sum(weights.values()))
+            acc, c = 0.0, []
+            for name in MOVE_NAMES[:5]:
+                acc += float(weights.get(name, 0.0) / tot)
+                c.append(acc)
+            c = tuple(c)
+        if len(c) != 5 or any(b < a for a, b in zip((0.0,) + c, c)) or c[-1] > 1.0:
+            raise ValueError(f"cumulative probabilities must be five non-decreasing values in [0, 1]: {c}")
+        self.cumulatives = c
+
+    @property
+    def swap(self) -> float:
+        return 1.0 - self.cumulatives[-1]
+
+    def __call__(self, r: float) -> int:
+        """the move of the draw ``r`` in [0, 1): index into MOVE_NAMES (5: swap)"""
+        for k, c in enumerate(self.cumulatives):
+            if r < c:
+                return k
+        return 5
+
+    def __getitem__(self, name: str) -> float:
+        k = MOVE_NAMES.index(name)
+        return self.swap if k == 5 else self.cumulatives[k] - (self.cumulatives[k - 1] if k else 0.0)
+
+    def __eq__(self, other):
+        return isinstance(other, MoveTable) and self.cumulatives == other.cumulatives
+
+    def __repr__(self):
+        return "MoveTable(; " + ", ".join(f"{n}={self[n]:.9g}" for n in MOVE_NAMES if self[n] > 1e-15) + ")"
+
+
+class GcmcSpecies(NamedTuple):
+    model: np.ndarray         # float64[m, 3], mc.models[i]
+    bead: int                 # 0-based atom the species rotates about
+    moves: MoveTable
+
+
+class GcmcProposal(NamedTuple):
+    species: int
+    kind: int                 # TRANSLATION ... RANDOM_REINSERTION, SWAP_INSERTION, SWAP_DELETION
+    molecule: int             # index into ``positions_of_molecules``; an insertion: the index it takes; -1: the step is spent
+    n_species: int            # molecules of the species before the move
+    positions: np.ndarray     # float64[m, 3] proposed placement (empty for a deletion and a spent step)
+    u: float
+    spent: bool               # no molecule of the species and not an insertion (simulation.jl:282)
+    capacity: bool            # an insertion at max_molecules: counted, not evaluated, rejected
+
+
+def random_translation_vector(seed: int, step: int, stream_id: int, mat) -> np.ndarray:
+    """``mat * (rand(SVector{3}) .- 0.5)`` (mcmoves.jl:143), ``mat`` with the cell vectors as columns"""
+    g, h = draw(seed, step, stream_id, GCMC_RANDOM_A), draw(seed, step, stream_id, GCMC_RANDOM_B)
+    a, b, c = uniform(g[0], g[1]) - 0.5, uniform(g[2], g[3]) - 0.5, uniform(h[0], h[1]) - 0.5
+    M = np.asarray(mat, dtype=np.float64)
+    return np.array([(float(M[d, 0]) * a + float(M[d, 1]) * b) + float(M[d, 2]) * c for d in range(3)])
+
+
+def propose_gcmc(seed: int, step: int, stream_id: int, species_of_molecules, positions_of_molecules, species, mat, dmax: float,
+                 thetamax: float, max_molecules: int = None) -> GcmcProposal:
+    """What stream ``stream_id`` proposes at the absolute step ``step`` of ``ceg_mc_group_sweep_gcmc`` for a chain whose molecule
+    ``d`` (device molecule order) is of species ``species_of_molecules[d]`` and sits at ``positions_of_molecules[d]``.
+    ``species``: one :class:`GcmcSpecies` per species; ``mat``: the MC cell (columns); ``thetamax`` in radians."""
+    u = acceptance_draw(seed, step, stream_id)
+    ns = len(species)
+    w = draw(seed, step, stream_id, GCMC_SELECT)
+    i = min(int(math.floor(uniform(w[0], w[1]) * ns)), ns - 1)
+    sp = species[i]
+    kind = sp.moves(uniform(w[2], w[3]))
+    wm = draw(seed, step, stream_id, GCMC_MOLECULE)
+    if kind == 5 and uniform(wm[2], wm[3]) < 0.5:
+        kind = SWAP_DELETION
+    members = [d for d, s in enumerate(species_of_molecules) if s == i]
+    n_i, nmol = len(members), len(species_of_molecules)
+    none = np.empty((0, 3))
+    if kind == SWAP_INSERTION:
+        if max_molecules is not None and nmol >= max_molecules:
+            return GcmcProposal(i, kind, nmol, n_i, none, u, False, True)
+        mol, pos = nmol, np.asarray(sp.model, dtype=np.float64).reshape(-1, 3)
+    else:
+        if n_i == 0:
+            return GcmcProposal(i, kind, -1, 0, none, u, True, False)
+        mol = members[min(int(math.floor(uniform(wm[0], wm[1]) * n_i)), n_i - 1)]
+        pos = np.asarray(positions_of_molecules[mol], dtype=np.float64).reshape(-1, 3)
+        if kind == SWAP_DELETION:
+            return GcmcProposal(i, kind, mol, n_i, none, u, False, False)
+    if kind in (TRANSLATION, ROTATION):
+        if kind == ROTATION and len(pos) == 1:
+            return GcmcProposal(i, kind, mol, n_i, pos.copy(), u, False, False)
+        g = draw(seed, step, stream_id, GEOMETRY_A)
+        if kind == TRANSLATION:
+            h = draw(seed, step, stream_id, GEOMETRY_B)
+            r = np.array([(2.0 * uniform(g[0], g[1]) - 1.0) * dmax, (2.0 * uniform(g[2], g[3]) - 1.0) * dmax,
+                          (2.0 * uniform(h[0], h[1]) - 1.0) * dmax])
+            return GcmcProposal(i, kind, mol, n_i, pos + r, u, False, False)
+        theta = thetamax * (2.0 * uniform(g[0], g[1]) - 1.0)
+        axis = min(int(math.floor(3.0 * uniform(g[2], g[3]))), 2)
+        ref = pos[int(sp.bead)]
+        return GcmcProposal(i, kind, mol, n_i, ref + (pos - ref) @ rotation_matrix(theta, axis).T, u, False, False)
+    new = pos.copy()
+    if kind != RANDOM_ROTATION:
+        new = new + random_translation_vector(seed, step, stream_id, mat)
+    if kind != RANDOM_TRANSLATION and len(new) > 1:
+        h, k = draw(seed, step, stream_id, GCMC_RANDOM_B), draw(seed, step, stream_id, GCMC_RANDOM_C)
+        theta = math.pi * (2.0 * uniform(h[2], h[3]) - 1.0)
+        axis = min(int(math.floor(3.0 * uniform(k[0], k[1]))), 2)
+        ref = new[int(sp.bead)]
+        new = ref + (new - ref) @ rotation_matrix(theta, axis).T
+    return GcmcProposal(i, kind, mol, n_i, new, u, False, False)
+
+
+def tail_change(tail_framework: float, tail_cross_row, counts, i: int, num: int) -> float:
+    """``modify_species_dryrun(tc, i, num)`` (tailcorrection.jl:86-96) in the order the device evaluates it"""
+    d = float(tail_framework)
+    for j, nj in enumerate(counts):
+        d += (float(num) + 2.0 * float(nj) if j == i else 2.0 * float(nj)) * float(tail_cross_row[j])
+    return d * float(num)
+
+
+def swap_threshold(row, temperature: float, n_species: int, phiPV_div_k: float, self_reciprocal: float, tc: float, insertion: bool):
+    """(diff, threshold) of ``compute_accept_move`` / ``compute_accept_move_swap`` (montecarlo.jl:705-707, gcmc.jl:77-88) for a swap:
+    ``row`` = the insertion row, or ``movement_energy`` of the molecule to delete; the move is accepted iff ``u < threshold``."""
+    E = ((float(row[0]) + float(row[1])) + float(row[2])) + float(row[3])
+    with np.errstate(over="ignore", under="ignore"):
+        if insertion:
+            diff = (E - self_reciprocal) + tc
+            thr = ((phiPV_div_k / temperature) / float(n_species + 1)) * float(np.exp(np.float64(-diff / temperature)))
+        else:
+            diff = -(E - self_reciprocal) + tc
+            thr = ((float(n_species) * temperature) / phiPV_div_k) * float(np.exp(np.float64(-diff / temperature)))
+    return diff, thr
+
+
+def swap_rule(row, u: float, temperature: float, n_species: int, phiPV_div_k: float, self_reciprocal: float, tc: float,
+              insertion: bool) -> bool:
+    """The swap decision of ``ceg_mc_group_sweep_gcmc``; a blocked insertion (framework vdw >= 1e90) is rejected."""
+    if insertion and row[0] >= 1e90:
+        return False
+    return bool(u < swap_threshold(row, temperature, n_species, phiPV_div_k, self_reciprocal, tc, insertion)[1])

@@ -16,7 +16,8 @@
 // (with its stored structure factor, like the reference's `positions === nothing` branch).  Small batches travel
 // through a pinned, device-mapped host buffer: a batch-1 trial is ONE kernel launch and one stream synchronisation.
 // The MC driver stays on the host, as in SURVEY 8f, except for sweeps of translations and rotations (ceg_mc_group_sweep: proposal,
-// Metropolis rule and update of S steps of K chains on the device; GCMC swaps remain with the caller).
+// Metropolis rule and update of S steps of K chains on the device; ceg_mc_group_sweep_gcmc: the same with all six move kinds, swaps
+// included, and the molecule table owned by the device).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -235,6 +236,7 @@ struct McAtBlock {
     __device__ __forceinline__ double* row(double* out) const { return out + 4 * (size_t)blockIdx.x; }
     __device__ __forceinline__ unsigned nblocks() const { return gridDim.x * gridDim.y; }
     __device__ __forceinline__ bool table_in_lds(const McView& v) const { return v.table_in_lds; }
+    __device__ __forceinline__ int natoms(const McView& v) const { return v.natoms; }
 };
 
 template <bool FAST, bool INSERT, bool CELLS, class At>
@@ -301,7 +303,7 @@ __device__ __forceinline__ void mc_trial_row(const McView& v, int32_t molecule, 
     double4 A_first = make_double4(0.0, 0.0, 0.0, 0.0);             // likewise the first guest atom of this thread
     // (with no guest this reads slot 0 of the minimum array ceg_mc_create allocates and zeroes: in bounds, and used by no pair.  A test
     //  of natoms here moves the register allocation of the batch-1 kernels, which tests/test_mc_chains_static.py pins.)
-    if (do_pairs && !CELLS) A_first = v.atoms[tid < v.natoms ? tid : 0];
+    if (do_pairs && !CELLS) A_first = v.atoms[tid < at.natoms(v) ? tid : 0];
     __syncthreads();
 
     double fv = 0.0, fd = 0.0, inter = 0.0, rs = 0.0, ss = 0.0;
@@ -393,7 +395,7 @@ __device__ __forceinline__ void mc_trial_row(const McView& v, int32_t molecule, 
             }
         };
         if (!CELLS) {
-            for (int l = tid; l < v.natoms; l += MC_THREADS) pairs_with(l == tid ? A_first : v.atoms[l]);
+            for (int l = tid; l < at.natoms(v); l += MC_THREADS) pairs_with(l == tid ? A_first : v.atoms[l]);
         } else {
             // only the cells the cutoff spheres of the molecule's atoms can reach (ceg_consumers.h)
             if (tid < 3) ceg_consumers::cell_range(I, s_pos, m, tid, v.nb[tid], v.hfrac[tid], s_bin0[tid], s_nbin[tid]);
@@ -505,6 +507,7 @@ struct McAtChainRow {
     __device__ __forceinline__ double* row(double* o) const { return o + 4 * (size_t)out; }
     __device__ __forceinline__ unsigned nblocks() const { return n; }
     __device__ __forceinline__ bool table_in_lds(const McView& v) const { return table_ok && v.table_in_lds; }
+    __device__ __forceinline__ int natoms(const McView& v) const { return v.natoms; }
 };
 
 // workgroup x of the launch: row x - ends[c - 1] of the chain c with ends[c - 1] <= x < ends[c] (ends: row prefix of the launch)
@@ -1065,10 +1068,14 @@ __device__ __forceinline__ McMove sweep_select(const McView& v, const McSweepCha
 
 // coordinate `comp` of atom `a` of the proposed placement of molecule mv.molecule (atoms [mj.x, mj.x + mj.y)): random_translation /
 // random_rotation of src/mcmoves.jl:139-164 on the resident positions
-__device__ __forceinline__ double sweep_coordinate(const McView& v, const McSweepChain& P, const int32_t* __restrict__ bead, const McMove mv, const int2 mj,
-                                                   uint64_t seed, uint64_t step, int a, int comp)
+// (stream id, step sizes and the atom the molecule rotates about as plain arguments: ceg_mc_group_sweep takes them from its per-chain
+// parameters and bead array, ceg_mc_group_sweep_gcmc from its own parameters and species table)
+__device__ __forceinline__ double sweep_coordinate_of(const McView& v, uint32_t stream_id, double dmax, double thetamax, int bead_atom, int kind, const int2 mj,
+                                                      uint64_t seed, uint64_t step, int a, int comp)
 {
 #pragma clang fp contract(off)
+    struct { uint32_t stream_id; double dmax, thetamax; } P{stream_id, dmax, thetamax};
+    struct { int kind; } mv{kind};
     const double4 A = v.atoms[mj.x + a];
     const ceg_philox::Block g = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::GEOMETRY_A);
     if (mv.kind == 0) {
@@ -1086,13 +1093,19 @@ __device__ __forceinline__ double sweep_coordinate(const McView& v, const McSwee
     axis = axis < 2 ? axis : 2;
     double s, c;
     sincos(theta, &s, &c);
-    const double4 R = v.atoms[mj.x + bead[P.bead_off + mv.molecule]];
+    const double4 R = v.atoms[mj.x + bead_atom];
     const double dx = A.x - R.x, dy = A.y - R.y, dz = A.z - R.z;
     double ox, oy, oz;                                               // the matrices of :155-161 (SMatrix fills column by column)
     if (axis == 0) { ox = dx; oy = c * dy - s * dz; oz = s * dy + c * dz; }
     else if (axis == 1) { ox = c * dx + s * dz; oy = dy; oz = c * dz - s * dx; }
     else { ox = c * dx - s * dy; oy = s * dx + c * dy; oz = dz; }
     return comp == 0 ? R.x + ox : (comp == 1 ? R.y + oy : R.z + oz);
+}
+
+__device__ __forceinline__ double sweep_coordinate(const McView& v, const McSweepChain& P, const int32_t* __restrict__ bead, const McMove mv, const int2 mj,
+                                                   uint64_t seed, uint64_t step, int a, int comp)
+{
+    return sweep_coordinate_of(v, P.stream_id, P.dmax, P.thetamax, mv.kind == 0 ? 0 : bead[P.bead_off + mv.molecule], mv.kind, mj, seed, step, a, comp);
 }
 
 // workgroup (x, y): chain list[x / 2], row x % 2 (0 where the molecule is, 1 the proposal), term y of the row.  prop[3 chain + y]: the
@@ -1204,7 +1217,7 @@ __global__ void k_mc_sf_total(McView v)
 }
 
 // add_one_system! (ewald.jl:775-792, montecarlo.jl:615-621): new molecule `molecule` (= old nmol) in atom slots [first, first + m)
-__global__ __launch_bounds__(MC_THREADS) void k_mc_insert(McView v, int32_t molecule, int32_t first, McMolecule nm, McPositions np, McCellOps ops, int stride)
+__device__ __forceinline__ void mc_insert_body(const McView& v, int32_t molecule, int32_t first, const McMolecule& nm, const McPositions& np, const McCellOps& ops, int stride)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     __shared__ double s_pos[MC_MAX_ATOMS * 3];
@@ -1233,9 +1246,14 @@ __global__ __launch_bounds__(MC_THREADS) void k_mc_insert(McView v, int32_t mole
     });
 }
 
+__global__ __launch_bounds__(MC_THREADS) void k_mc_insert(McView v, int32_t molecule, int32_t first, McMolecule nm, McPositions np, McCellOps ops, int stride)
+{
+    mc_insert_body(v, molecule, first, nm, np, ops, stride);
+}
+
 // remove_one_system! (ewald.jl:794-810, :404-413): sums[:,1] -= sums[:,ij+1]; the LAST molecule takes index `molecule`
 // (its structure factor column and the molecule id of its atoms); the atom slots of the removed molecule become free
-__global__ __launch_bounds__(MC_THREADS) void k_mc_remove(McView v, int32_t molecule, int32_t last, McCellOps ops)
+__device__ __forceinline__ void mc_remove_body(const McView& v, int32_t molecule, int32_t last, const McCellOps& ops)
 {
     const int tid = threadIdx.x;
     const int2 gone = v.mol[molecule], moved = v.mol[last];
@@ -1269,6 +1287,308 @@ __global__ __launch_bounds__(MC_THREADS) void k_mc_remove(McView v, int32_t mole
     if (v.use_cells) apply_cell_ops(v, ops, tid);
     if (tid == 0 && last != molecule) v.mol[molecule] = moved;
 }
+
+__global__ __launch_bounds__(MC_THREADS) void k_mc_remove(McView v, int32_t molecule, int32_t last, McCellOps ops)
+{
+    mc_remove_body(v, molecule, last, ops);
+}
+
+// ---- GCMC sweeps (ceg_mc_group_sweep_gcmc): the six move kinds of src/mcmoves.jl:1-8 with the molecule table owned by the device.
+// Per step k_mcg_gcmc_trial (the rows of mc_trial_row: before / after of a displacement, the current row of a deletion, the insertion
+// row) and k_mcg_gcmc_accept (compute_accept_move / compute_accept_move_swap, statistics, log, and the bodies of k_mcg_accept /
+// k_mc_insert / k_mc_remove).  What changes between steps -- molecule and atom counts, the species of every molecule, the counts per
+// species, the stacks of freed atom slots -- sits in ordinary device memory (McGcmcTable and the arrays behind it), is written with
+// ordinary stores by the accept kernel and read with ordinary loads by the next launch; the nmol / natoms entries of the chains' views
+// (read through the constant address space) are not used here.
+constexpr int MC_GCMC_SPECIES = CEG_MC_GCMC_MAX_SPECIES;
+
+struct McGcmcChain {             // per chain, fixed during a sweep
+    uint32_t stream_id;
+    int32_t stride;
+    int32_t max_molecules, atoms_cap;
+    int32_t spec_off;            // the chain's first entry of the species-of-molecule array
+    int32_t free_off, free_cap;  // stack of species i: freeslots[free_off + i * free_cap ...]
+    int32_t _pad;
+    double temperature, dmax, thetamax;
+};
+
+struct McGcmcTable {             // per chain, written by k_mcg_gcmc_accept
+    int32_t nmol, natoms;        // natoms: high-water mark of the atom slots
+    int32_t count[MC_GCMC_SPECIES], nfree[MC_GCMC_SPECIES];
+};
+
+struct McGcmcMove {
+    int32_t species, kind;       // kind 0..6 (include/ceg_hip.h)
+    int32_t molecule;            // device index; an insertion: the index it takes; -1 spent
+    int32_t n_i, nmol, natoms;
+    int32_t flags;               // 1 spent, 4 capacity
+};
+
+__device__ __forceinline__ int32_t gcmc_ld(const int32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+
+// the move of chain `P` at `step`, by the whole workgroup (the j-th molecule of the species is found by a scan of the table)
+__device__ __forceinline__ McGcmcMove gcmc_select(const McGcmcChain& P, const ceg_mc_gcmc_species_t* __restrict__ spec, int nspecies,
+                                                  const McGcmcTable* T, const int32_t* molspec, uint64_t seed, uint64_t step)
+{
+    __shared__ int s_wcnt[MC_THREADS / 64], s_found;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    McGcmcMove mv;
+    mv.nmol = gcmc_ld(&T->nmol);
+    mv.natoms = gcmc_ld(&T->natoms);
+    const ceg_philox::Block w = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::GCMC_SELECT);
+    int i = (int)floor(ceg_philox::uniform(w.w[0], w.w[1]) * (double)nspecies);
+    i = i < nspecies - 1 ? i : nspecies - 1;
+    const double uk = ceg_philox::uniform(w.w[2], w.w[3]);
+    int kind = 5;
+    for (int k = 4; k >= 0; --k)
+        if (uk < spec[i].cumulative[k]) kind = k;
+    const ceg_philox::Block wm = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::GCMC_MOLECULE);
+    if (kind == 5 && ceg_philox::uniform(wm.w[2], wm.w[3]) < 0.5) kind = 6;
+    mv.species = i;
+    mv.kind = kind;
+    mv.n_i = gcmc_ld(&T->count[i]);
+    mv.flags = 0;
+    mv.molecule = -1;
+    if (kind == 5) {
+        mv.molecule = mv.nmol;
+        if (mv.nmol >= P.max_molecules) mv.flags = 4;
+        return mv;
+    }
+    if (mv.n_i <= 0) { mv.flags = 1; return mv; }
+    int j = (int)floor(ceg_philox::uniform(wm.w[0], wm.w[1]) * (double)mv.n_i);
+    j = j < mv.n_i - 1 ? j : mv.n_i - 1;
+    const int32_t* ms = molspec + P.spec_off;
+    const int chunk = (mv.nmol + MC_THREADS - 1) / MC_THREADS;
+    const int lo = tid * chunk, hi = lo + chunk < mv.nmol ? lo + chunk : mv.nmol;
+    int cnt = 0;
+    for (int t = lo; t < hi; ++t) cnt += gcmc_ld(ms + t) == i ? 1 : 0;
+    int incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(incl, o);
+        if (lane >= o) incl += up;
+    }
+    if (tid == 0) s_found = -1;
+    if (lane == 63) s_wcnt[wave] = incl;
+    __syncthreads();
+    int before = incl - cnt;
+    for (int q = 0; q < wave; ++q) before += s_wcnt[q];
+    if (cnt > 0 && before <= j && j < before + cnt) {
+        int seen = before;
+        for (int t = lo; t < hi; ++t)
+            if (gcmc_ld(ms + t) == i && seen++ == j) s_found = t;
+    }
+    __syncthreads();
+    mv.molecule = __builtin_amdgcn_readfirstlane(s_found);
+    if (mv.molecule < 0) mv.flags = 1;          // (the counts and the table disagree: cannot happen; the step is spent)
+    return mv;
+}
+
+// coordinate `comp` of atom `a` of the proposal: kinds 0 / 1 from sweep_coordinate, the random_* kinds and the insertion from
+// src/mcmoves.jl:139-164 with the MC cell / 180 degrees (simulation.jl:294-305)
+__device__ __forceinline__ double gcmc_coordinate(const McView& v, const McGcmcChain& P, const ceg_mc_gcmc_species_t& S, const McGcmcMove& mv, const int2 mj,
+                                                  uint64_t seed, uint64_t step, int a, int comp)
+{
+#pragma clang fp contract(off)
+    if (mv.kind <= 1) {
+        if (mv.kind == 1 && mj.y == 1) return comp == 0 ? v.atoms[mj.x].x : (comp == 1 ? v.atoms[mj.x].y : v.atoms[mj.x].z);
+        return sweep_coordinate_of(v, P.stream_id, P.dmax, P.thetamax, S.bead, mv.kind, mj, seed, step, a, comp);
+    }
+    const bool model = mv.kind == 5;
+    double px, py, pz, bx, by, bz;
+    if (model) {
+        px = S.model[a][0]; py = S.model[a][1]; pz = S.model[a][2];
+        bx = S.model[S.bead][0]; by = S.model[S.bead][1]; bz = S.model[S.bead][2];
+    } else {
+        const double4 A = v.atoms[mj.x + a], B = v.atoms[mj.x + S.bead];
+        px = A.x; py = A.y; pz = A.z;
+        bx = B.x; by = B.y; bz = B.z;
+    }
+    const ceg_philox::Block h = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::GCMC_RANDOM_B);
+    if (mv.kind != 3) {                          // random_translation: r = mat (U3 - 0.5)
+        const ceg_philox::Block g = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::GCMC_RANDOM_A);
+        const double ua = ceg_philox::uniform(g.w[0], g.w[1]) - 0.5, ub = ceg_philox::uniform(g.w[2], g.w[3]) - 0.5,
+                     uc = ceg_philox::uniform(h.w[0], h.w[1]) - 0.5;
+        const double* M = v.mat;
+        const double rx = (M[0] * ua + M[3] * ub) + M[6] * uc, ry = (M[1] * ua + M[4] * ub) + M[7] * uc, rz = (M[2] * ua + M[5] * ub) + M[8] * uc;
+        px += rx; py += ry; pz += rz;
+        bx += rx; by += ry; bz += rz;
+    }
+    if (mv.kind == 2 || mj.y == 1) return comp == 0 ? px : (comp == 1 ? py : pz);
+    const double theta = 3.141592653589793 * (2.0 * ceg_philox::uniform(h.w[2], h.w[3]) - 1.0);
+    const ceg_philox::Block k = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::GCMC_RANDOM_C);
+    int axis = (int)floor(3.0 * ceg_philox::uniform(k.w[0], k.w[1]));
+    axis = axis < 2 ? axis : 2;
+    double s, c;
+    sincos(theta, &s, &c);
+    const double dx = px - bx, dy = py - by, dz = pz - bz;
+    double ox, oy, oz;
+    if (axis == 0) { ox = dx; oy = c * dy - s * dz; oz = s * dy + c * dz; }
+    else if (axis == 1) { ox = c * dx + s * dz; oy = dy; oz = c * dz - s * dx; }
+    else { ox = c * dx - s * dy; oy = s * dx + c * dy; oz = dz; }
+    return comp == 0 ? bx + ox : (comp == 1 ? by + oy : bz + oz);
+}
+
+struct McAtGcmcRow {
+    int64_t out;
+    int r;                   // 0: where the molecule is; 1: the proposal (an insertion passes 0: its only row is the proposal)
+    int table_ok, n;         // n: high-water mark of the atom slots, from the device's table
+    template <bool INSERT> __device__ __forceinline__ int64_t b() const { return INSERT ? (int64_t)r + 1 : (int64_t)r; }
+    __device__ __forceinline__ double* row(double* o) const { return o + 4 * (size_t)out; }
+    __device__ __forceinline__ unsigned nblocks() const { return 0u; }
+    __device__ __forceinline__ bool table_in_lds(const McView& v) const { return table_ok && v.table_in_lds; }
+    __device__ __forceinline__ int natoms(const McView&) const { return n; }
+};
+
+// workgroup (x, y): chain list[x / 2], row x % 2, term y of the row, as k_mcg_sweep_trial; a deletion has no row 1, an insertion no row 0
+template <bool FAST>
+__global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mcg_gcmc_trial(const McView* __restrict__ views, const McGcmcChain* __restrict__ params,
+                                                                const ceg_mc_gcmc_species_t* __restrict__ spec, int nspecies, const McGcmcTable* tables,
+                                                                const int32_t* molspec, const int32_t* __restrict__ list, int table_ok, uint64_t seed,
+                                                                uint64_t step, McPositions* prop, double* __restrict__ rows)
+{
+    __shared__ McLocal s_L;
+    const int c = list[blockIdx.x >> 1], r = (int)(blockIdx.x & 1u);
+    const McView& v = as_constant(views)[c];
+    const McGcmcChain& P = as_constant(params)[c];
+    const McGcmcMove mv = gcmc_select(P, spec, nspecies, tables + c, molspec, seed, step);
+    if (mv.flags) return;
+    if ((mv.kind == 6 && r == 1) || (mv.kind == 5 && r == 0)) return;
+    const ceg_mc_gcmc_species_t& S = spec[mv.species];
+    const int2 mj = mv.kind == 5 ? make_int2(0, S.m) : v.mol[mv.molecule];
+    const int tid = threadIdx.x;
+    if (tid < mj.y) {
+        const int kind = S.kinds[tid];
+        s_L.kinds[tid] = kind;
+        s_L.q[tid] = v.kind_charge[kind];
+    }
+    if (tid == 0) { s_L.first = mj.x; s_L.m = mj.y; }
+    McPositions* mine = prop + 3 * (size_t)c + blockIdx.y;
+    if (r == 1 && tid < 3 * mj.y) mine->xyz[tid] = gcmc_coordinate(v, P, S, mv, mj, seed, step, tid / 3, tid % 3);
+    __syncthreads();
+    const McAtGcmcRow at{2 * (int64_t)c + r, mv.kind == 5 ? 0 : r, table_ok, mv.natoms};
+    if (mv.kind == 5) mc_trial_row<FAST, true, false>(v, -1, s_L, mine->xyz, rows, P.stride, nullptr, nullptr, 0ull, at);
+    else mc_trial_row<FAST, false, false>(v, mv.molecule, s_L, mine->xyz, rows, P.stride, nullptr, nullptr, 0ull, at);
+}
+
+// one workgroup per chain: the decision, statistics, the log record, the update of the state and of the chain's table
+__global__ __launch_bounds__(MC_THREADS) void k_mcg_gcmc_accept(const McView* __restrict__ views, const McGcmcChain* __restrict__ params,
+                                                                const ceg_mc_gcmc_species_t* __restrict__ spec, int nspecies, McGcmcTable* tables,
+                                                                int32_t* molspec, int32_t* freeslots, uint64_t seed, uint64_t step,
+                                                                const McPositions* __restrict__ prop, const double* __restrict__ rows,
+                                                                ceg_mc_gcmc_stats_t* __restrict__ stats, ceg_mc_gcmc_record_t* __restrict__ log)
+{
+    __shared__ McMolecule s_nm;
+    const int c = (int)blockIdx.x, tid = threadIdx.x;
+    const McView& v = as_constant(views)[c];
+    const McGcmcChain& P = as_constant(params)[c];
+    McGcmcTable* T = tables + c;
+    const McGcmcMove mv = gcmc_select(P, spec, nspecies, T, molspec, seed, step);
+    const ceg_philox::Block w = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::ACCEPT);
+    const double u = ceg_philox::uniform(w.w[0], w.w[1]);
+    ceg_mc_gcmc_record_t* rec = log ? log + c : nullptr;          // (zeroed before the first step)
+    ceg_mc_gcmc_stats_t& S = stats[c];
+    const ceg_mc_gcmc_species_t& sp = spec[mv.species];
+    const int i = mv.species, m = sp.m;
+    int32_t* fstack = freeslots + P.free_off + (size_t)i * P.free_cap;
+    const int nf = mv.kind == 5 ? gcmc_ld(&T->nfree[i]) : 0;
+    // an insertion without a freed run takes fresh slots at the high-water mark: they must lie inside the reserved arrays
+    const bool fits = mv.kind != 5 || nf > 0 || mv.natoms + m <= P.atoms_cap;
+    const int flags = mv.flags | (fits ? 0 : 4);
+    if (flags) {
+        if (tid == 0) {
+            if (flags & 1) S.spent += 1;
+            else { S.trials[5] += 1; S.capacity += 1; }
+            if (rec) {
+                rec->species = i; rec->molecule = (flags & 1) ? -1 : mv.molecule; rec->kind = mv.kind; rec->accepted = 0;
+                rec->n_species = mv.n_i; rec->flags = flags; rec->u = u;
+            }
+        }
+        return;
+    }
+    const double* r = rows + 8 * (size_t)c;
+    double row[8];
+    for (int t = 0; t < 8; ++t) row[t] = ((mv.kind == 6 && t >= 4) || (mv.kind == 5 && t < 4)) ? 0.0 : r[t];
+    bool blocked = false;
+    int acc;
+    double tc = 0.0, delta;
+    {
+#pragma clang fp contract(off)
+        if (mv.kind <= 4) {
+            const double b = ((row[0] + row[1]) + row[2]) + row[3], a = ((row[4] + row[5]) + row[6]) + row[7];
+            blocked = row[4] >= 1e90;
+            acc = (!blocked && (a < b || u < exp((b - a) / P.temperature))) ? 1 : 0;
+            delta = a - b;
+        } else {
+            const double n = mv.kind == 5 ? 1.0 : -1.0;
+            double d = sp.tail_framework;                         // modify_species_dryrun, tailcorrection.jl:86-96
+            for (int j = 0; j < nspecies; ++j) {
+                const int nj = gcmc_ld(&T->count[j]);
+                d += (j == i ? n + 2.0 * (double)nj : 2.0 * (double)nj) * sp.tail_cross[j];
+            }
+            tc = d * n;
+            const double temp = P.temperature;
+            if (mv.kind == 5) {
+                const double E = ((row[4] + row[5]) + row[6]) + row[7];
+                blocked = row[4] >= 1e90;
+                delta = (E - sp.self_reciprocal) + tc;
+                acc = (!blocked && u < ((sp.phiPV_div_k / temp) / (double)(mv.n_i + 1)) * exp(-delta / temp)) ? 1 : 0;
+            } else {
+                const double E = ((row[0] + row[1]) + row[2]) + row[3];
+                delta = -(E - sp.self_reciprocal) + tc;
+                acc = (u < (((double)mv.n_i * temp) / sp.phiPV_div_k) * exp(-delta / temp)) ? 1 : 0;
+            }
+        }
+    }
+    const int accepted = __builtin_amdgcn_readfirstlane(acc);
+    const McPositions& np = prop[3 * (size_t)c];
+    if (tid == 0) {
+        S.trials[mv.kind] += 1;
+        S.accepted[mv.kind] += accepted;
+        if (blocked) S.blocked += 1;
+        if (accepted) {
+            if (mv.kind <= 4) S.delta_moves += delta;
+            else S.delta_swaps += delta;
+        }
+        if (rec) {
+            rec->species = i; rec->molecule = mv.molecule; rec->kind = mv.kind; rec->accepted = accepted;
+            rec->n_species = mv.n_i; rec->flags = blocked ? 2 : 0; rec->u = u; rec->tc = tc;
+            for (int t = 0; t < 8; ++t) rec->rows[t >> 2][t & 3] = row[t];
+        }
+    }
+    if (rec && mv.kind != 6 && tid < 3 * m) rec->positions[tid / 3][tid % 3] = np.xyz[tid];
+    if (!accepted) return;
+    if (mv.kind <= 4) {
+        mc_accept_body(v, mv.molecule, np, d_mc_no_cell_ops, P.stride);
+    } else if (mv.kind == 5) {
+        const int first = nf > 0 ? gcmc_ld(fstack + nf - 1) : mv.natoms;
+        if (tid < m) s_nm.kinds[tid] = sp.kinds[tid];
+        if (tid == 0) s_nm.m = m;
+        __syncthreads();
+        mc_insert_body(v, mv.nmol, first, s_nm, np, d_mc_no_cell_ops, P.stride);
+        if (tid == 0) {
+            molspec[P.spec_off + mv.nmol] = i;
+            T->nmol = mv.nmol + 1;
+            T->count[i] = mv.n_i + 1;
+            if (nf > 0) T->nfree[i] = nf - 1;
+            else T->natoms = mv.natoms + m;
+        }
+    } else {
+        const int last = mv.nmol - 1;
+        const int first_gone = v.mol[mv.molecule].x;
+        const int spec_last = gcmc_ld(molspec + P.spec_off + last);
+        const int nfd = gcmc_ld(&T->nfree[i]);
+        __syncthreads();                             // (every thread has read the table before thread 0 of the body rewrites it)
+        mc_remove_body(v, mv.molecule, last, d_mc_no_cell_ops);
+        if (tid == 0) {
+            if (last != mv.molecule) molspec[P.spec_off + mv.molecule] = spec_last;
+            if (nfd < P.free_cap) { fstack[nfd] = first_gone; T->nfree[i] = nfd + 1; }      // (a full stack cannot happen: the run would be lost, not reused)
+            T->nmol = last;
+            T->count[i] = mv.n_i - 1;
+        }
+    }
+}
+
 
 // cells[i] = atoms[map[i]] for every occupied entry (map[i] >= 0): the whole structure from the host's cell lists
 __global__ void k_mc_cells_fill(McView v, const int32_t* __restrict__ map, int64_t n)
@@ -2276,6 +2596,9 @@ struct ceg_mc_group {
     unsigned char* d_sweep = nullptr;
     int32_t* d_bead = nullptr;
     size_t bead_cap = 0;
+    // ceg_mc_group_sweep_gcmc: parameters, species table, proposals, rows, statistics and the chains' device-owned tables (one allocation)
+    unsigned char* d_gcmc = nullptr;
+    size_t gcmc_cap = 0;
 };
 
 namespace {
@@ -2290,6 +2613,7 @@ void group_free(ceg_mc_group* g)
     if (g->d_done) (void)hipFree(g->d_done);
     if (g->d_sweep) (void)hipFree(g->d_sweep);
     if (g->d_bead) (void)hipFree(g->d_bead);
+    if (g->d_gcmc) (void)hipFree(g->d_gcmc);
     for (void* p : {(void*)g->h_views, (void*)g->h_in, (void*)g->h_out, (void*)g->h_acc, (void*)g->h_flag})
         if (p) (void)hipHostFree(p);
     delete g;
@@ -2698,6 +3022,266 @@ extern "C" int ceg_mc_group_sweep(ceg_mc_group_t* g, const ceg_mc_sweep_params_t
     if (!ok) {                                           // some steps may have run: the chains' states are unknown
         for (ceg_mc* h : g->chains) h->poisoned = true;
         return merr(CEG_ERR_HIP, "a sweep kernel failed: every chain of the group is marked inconsistent");
+    }
+    return CEG_OK;
+}
+
+extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps, ceg_mc_gcmc_stats_t* stats_out,
+                                       ceg_mc_gcmc_record_t* log_out)
+{
+    static_assert(sizeof(ceg_mc_gcmc_species_t) == 584 && sizeof(ceg_mc_gcmc_params_t) == 88 && sizeof(ceg_mc_gcmc_stats_t) == 192 &&
+                      sizeof(ceg_mc_gcmc_record_t) == 488,
+                  "layouts the bindings restate");
+    static_assert(sizeof(((ceg_mc_gcmc_record_t*)nullptr)->positions) == sizeof(McPositions), "a record holds one placement");
+    static_assert(CEG_MC_GCMC_MAX_SPECIES >= 4, "the documented minimum");
+    if (!g || !p || !stats_out || !p->stream_id || !p->temperature || !p->dmax || !p->thetamax || !p->species || !p->max_molecules)
+        return merr(CEG_ERR_INVALID, "bad argument");
+    if (nsteps < 0) return merr(CEG_ERR_INVALID, "negative number of steps");
+    const int k = (int)g->chains.size();
+    const int ns = p->nspecies;
+    // ---- every refusal before anything is launched or changed
+    for (int c = 0; c < k; ++c) {
+        ceg_mc* h = g->chains[c];
+        if (h->poisoned) return group_refuse_poisoned(c);
+        if (h->v.use_cells || h->cm.on) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "chain %d keeps its guests in neighbour cells: sweeps take chains with the exhaustive pair loop only", c);
+            return merr(CEG_ERR_UNSUPPORTED, msg);
+        }
+    }
+    if (ns < 1 || ns > CEG_MC_GCMC_MAX_SPECIES) return merr(CEG_ERR_INVALID, "1 <= nspecies <= CEG_MC_GCMC_MAX_SPECIES");
+    int mmax = 1;
+    int64_t swap_atoms = 0;                              // atoms of one molecule of every species that can be inserted
+    for (int i = 0; i < ns; ++i) {
+        const ceg_mc_gcmc_species_t& S = p->species[i];
+        char msg[160];
+        auto bad = [&](const char* what) {
+            std::snprintf(msg, sizeof msg, "species %d: %s", i, what);
+            return merr(CEG_ERR_INVALID, msg);
+        };
+        if (S.m < 1 || S.m > MC_MAX_ATOMS) return bad("1 <= m <= 16 atoms");
+        if (S.bead < 0 || S.bead >= S.m) return bad("the bead lies outside the molecule");
+        for (int a = 0; a < S.m; ++a) {
+            if (S.kinds[a] < 0 || S.kinds[a] >= g->chains[0]->v.nkinds) return bad("atom kind outside the pair table");
+            for (int d = 0; d < 3; ++d)
+                if (!std::isfinite(S.model[a][d])) return bad("the model positions must be finite");
+        }
+        double prev = 0.0;
+        for (int q = 0; q < 5; ++q) {
+            if (!(S.cumulative[q] >= prev && S.cumulative[q] <= 1.0)) return bad("the cumulative probabilities must be non-decreasing in [0, 1]");
+            prev = S.cumulative[q];
+        }
+        const bool swaps = S.cumulative[4] < 1.0;
+        if (swaps && !(std::isfinite(S.phiPV_div_k) && S.phiPV_div_k > 0.0)) return bad("phiPV_div_k must be finite and > 0 where the swap probability is > 0");
+        if (!std::isfinite(S.self_reciprocal) || !std::isfinite(S.tail_framework)) return bad("self_reciprocal and the tail correction must be finite");
+        for (int j = 0; j < ns; ++j)
+            if (!std::isfinite(S.tail_cross[j])) return bad("self_reciprocal and the tail correction must be finite");
+        mmax = std::max(mmax, (int)S.m);
+        if (swaps) swap_atoms += S.m;
+    }
+    std::vector<McGcmcChain> pc((size_t)k);
+    std::vector<McGcmcTable> tab((size_t)k);
+    std::vector<int32_t> list[2];
+    size_t lds_trial[2] = {0, 0}, pair_table[2] = {0, 0}, lds_accept = 0;
+    size_t nspec_total = 0, nfree_total = 0, given = 0, nout_total = 0;
+    std::vector<size_t> out_off((size_t)k, 0);           // chain c of molecule_species_out: the sum of max_molecules[0..c), as documented
+    for (int c = 0; c < k; ++c) {
+        ceg_mc* h = g->chains[c];
+        const double T = p->temperature[c], dmax = p->dmax[c], th = p->thetamax[c];
+        if (!std::isfinite(T) || !(T > 0.0)) return group_bad(c, "the temperature must be finite and > 0");
+        if (!std::isfinite(dmax) || dmax < 0.0) return group_bad(c, "dmax must be finite and >= 0");
+        if (!std::isfinite(th) || th < 0.0) return group_bad(c, "thetamax must be finite and >= 0");
+        for (int d = 0; d < c; ++d)
+            if (p->stream_id[d] == p->stream_id[c]) return group_bad(c, "its stream id is already used by an earlier chain");
+        for (int i = 0; i < ns; ++i)
+            for (int a = 0; a < p->species[i].m; ++a)
+                if (p->species[i].kinds[a] >= h->v.nkinds) return group_bad(c, "a species' atom kind lies outside the chain's pair table");
+        const int nmol = h->v.nmol;
+        const int maxmol = p->max_molecules[c];
+        if (maxmol < nmol || maxmol < 0) return group_bad(c, "max_molecules is below the chain's molecule count");
+        if (nmol > 0 && !p->molecule_species) return merr(CEG_ERR_INVALID, "bad argument");
+        McGcmcTable& D = tab[(size_t)c];
+        D = McGcmcTable{};
+        D.nmol = nmol;
+        D.natoms = h->v.natoms;
+        for (int j = 0; j < nmol; ++j) {
+            const int32_t s = p->molecule_species[given + (size_t)j];
+            if (s < 0 || s >= ns) return group_bad(c, "a molecule's species lies outside the species table");
+            const ceg_mc_gcmc_species_t& S = p->species[s];
+            const int2 mj = h->h_mol[(size_t)j];
+            if (mj.y != S.m) return group_bad(c, "a molecule's species has another atom count than the molecule");
+            for (int a = 0; a < S.m; ++a)
+                if (h->h_kind[(size_t)mj.x + a] != S.kinds[a]) return group_bad(c, "a molecule's species has other atom kinds than the molecule");
+            D.count[s] += 1;
+        }
+        given += (size_t)nmol;
+        if (tables_bytes(h, mmax) > 64 * 1024) return merr(CEG_ERR_UNSUPPORTED, "k-space tables of the molecule do not fit in LDS");
+        McGcmcChain& P = pc[(size_t)c];
+        P = McGcmcChain{};
+        P.stream_id = p->stream_id[c];
+        P.stride = h->stride;
+        P.max_molecules = maxmol;
+        P.temperature = T; P.dmax = dmax; P.thetamax = th;
+        // freed runs of the host mirror: the runs of m atoms go to the first species with m atoms
+        int most = 0;
+        for (int i = 0; i < ns; ++i) {
+            bool firstof = true;
+            for (int j = 0; j < i; ++j) firstof = firstof && p->species[j].m != p->species[i].m;
+            D.nfree[i] = firstof && !h->free_runs.empty() ? (int32_t)h->free_runs[(size_t)p->species[i].m].size() : 0;
+            most = std::max(most, (int)D.nfree[i]);
+        }
+        P.free_cap = most + std::max(maxmol, 1);
+        P.spec_off = (int32_t)nspec_total;
+        P.free_off = (int32_t)nfree_total;
+        nspec_total += (size_t)std::max(maxmol, 1);       // (device storage: at least one entry per chain)
+        out_off[(size_t)c] = nout_total;
+        nout_total += (size_t)maxmol;
+        nfree_total += (size_t)ns * (size_t)P.free_cap;
+        // atom slots: an insertion takes a freed run of its species or fresh slots; the worst case is every insertable species filled
+        // to max_molecules from fresh slots, one after the other
+        const int64_t need = (int64_t)h->v.natoms + (int64_t)maxmol * swap_atoms;
+        if (need > 0x3fffffff) return group_bad(c, "max_molecules is too large");
+        P.atoms_cap = (int32_t)std::max<int64_t>(need, 1);
+        const int cl = h->v.fast ? 1 : 0;
+        list[cl].push_back(c);
+        lds_trial[cl] = std::max(lds_trial[cl], tables_bytes(h, mmax));
+        lds_accept = std::max(lds_accept, tables_bytes(h, mmax));
+        if (h->v.table_in_lds)
+            pair_table[cl] = std::max(pair_table[cl], sizeof(DevRule) * (size_t)(h->v.nrules > 0 ? h->v.nrules : 1) + sizeof(int32_t) * ((size_t)h->v.nkinds * h->v.nkinds + 1));
+    }
+    auto fill_counts = [&](int c, const McGcmcTable& D, const int32_t* ms) {
+        for (int i = 0; i < CEG_MC_GCMC_MAX_SPECIES; ++i) stats_out[c].count[i] = i < ns ? D.count[i] : 0;
+        stats_out[c].nmol = D.nmol;
+        if (p->molecule_species_out && D.nmol > 0) memcpy(p->molecule_species_out + out_off[(size_t)c], ms, sizeof(int32_t) * (size_t)D.nmol);
+    };
+    for (int c = 0; c < k; ++c) stats_out[c] = ceg_mc_gcmc_stats_t{};
+    if (nsteps == 0) {
+        size_t o = 0;
+        for (int c = 0; c < k; ++c) {
+            fill_counts(c, tab[(size_t)c], p->molecule_species ? p->molecule_species + o : nullptr);
+            o += (size_t)tab[(size_t)c].nmol;
+        }
+        return CEG_OK;
+    }
+    int table_ok[2];
+    for (int cl = 0; cl < 2; ++cl) {
+        table_ok[cl] = lds_trial[cl] + pair_table[cl] <= 64 * 1024 ? 1 : 0;
+        if (table_ok[cl]) lds_trial[cl] += pair_table[cl];
+    }
+    Guard guard(g->device);
+    if (!guard.ok) return merr(CEG_ERR_HIP, "hipSetDevice failed");
+    // ---- reserve atoms, mol and sf_mol of every chain for max_molecules (contents kept; a failure here has changed no state)
+    for (int c = 0; c < k; ++c)
+        if (int rc = ensure_capacity(g->chains[c], pc[(size_t)c].atoms_cap, std::max(pc[(size_t)c].max_molecules, 1))) return rc;
+    for (int c = 0; c < k; ++c) pc[(size_t)c].atoms_cap = (int32_t)std::min<int64_t>(g->chains[c]->atoms_cap, 0x3fffffff);
+    // ---- device memory: [K] parameters | [K] launch lists | [3K] proposals | [8K] rows | [ns] species | [K] statistics | [K] tables |
+    //      species of the molecules | stacks of freed slots        (from the statistics on: read back after the sweep)
+    auto up16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
+    const size_t o_par = 0, o_list = up16(o_par + sizeof(McGcmcChain) * (size_t)k), o_prop = up16(o_list + sizeof(int32_t) * (size_t)k),
+                 o_rows = up16(o_prop + sizeof(McPositions) * 3 * (size_t)k), o_spec = up16(o_rows + sizeof(double) * 8 * (size_t)k),
+                 o_stats = up16(o_spec + sizeof(ceg_mc_gcmc_species_t) * (size_t)ns), o_tab = up16(o_stats + sizeof(ceg_mc_gcmc_stats_t) * (size_t)k),
+                 o_ms = up16(o_tab + sizeof(McGcmcTable) * (size_t)k), o_free = up16(o_ms + sizeof(int32_t) * nspec_total),
+                 total = up16(o_free + sizeof(int32_t) * nfree_total);
+    if (total > g->gcmc_cap) {
+        if (g->d_gcmc) (void)hipFree(g->d_gcmc);
+        g->d_gcmc = nullptr; g->gcmc_cap = 0;
+        if (hipMalloc((void**)&g->d_gcmc, total) != hipSuccess) return merr(CEG_ERR_HIP, "hipMalloc failed");
+        g->gcmc_cap = total;
+    }
+    ceg_mc_gcmc_record_t* d_log = nullptr;
+    const size_t log_bytes = log_out ? sizeof(ceg_mc_gcmc_record_t) * (size_t)k * (size_t)nsteps : 0;
+    if (log_out && hipMalloc((void**)&d_log, log_bytes) != hipSuccess) return merr(CEG_ERR_HIP, "hipMalloc of the log failed");
+    auto fail = [&](const char* what) {
+        if (d_log) (void)hipFree(d_log);
+        return merr(CEG_ERR_HIP, what);
+    };
+    std::vector<unsigned char> stage(total, 0);
+    {
+        memcpy(stage.data() + o_par, pc.data(), sizeof(McGcmcChain) * (size_t)k);
+        int32_t* l = reinterpret_cast<int32_t*>(stage.data() + o_list);
+        for (int cl = 0, e = 0; cl < 2; ++cl)
+            for (int32_t c : list[cl]) l[e++] = c;
+        memcpy(stage.data() + o_spec, p->species, sizeof(ceg_mc_gcmc_species_t) * (size_t)ns);
+        memcpy(stage.data() + o_tab, tab.data(), sizeof(McGcmcTable) * (size_t)k);
+        int32_t* ms = reinterpret_cast<int32_t*>(stage.data() + o_ms);
+        int32_t* fr = reinterpret_cast<int32_t*>(stage.data() + o_free);
+        size_t o = 0;
+        for (int c = 0; c < k; ++c) {
+            const McGcmcChain& P = pc[(size_t)c];
+            for (int j = 0; j < tab[(size_t)c].nmol; ++j) ms[P.spec_off + j] = p->molecule_species[o + (size_t)j];
+            o += (size_t)tab[(size_t)c].nmol;
+            for (int i = 0; i < ns; ++i)
+                for (int q = 0; q < tab[(size_t)c].nfree[i]; ++q)
+                    fr[(size_t)P.free_off + (size_t)i * P.free_cap + q] = g->chains[c]->free_runs[(size_t)p->species[i].m][(size_t)q];
+        }
+        // (nothing of an earlier sweep is in flight: every sweep ends with a synchronisation)
+        if (hipMemcpy(g->d_gcmc, stage.data(), total, hipMemcpyHostToDevice) != hipSuccess) return fail("H2D failed");
+    }
+    if (!group_upload_views(g, std::vector<char>((size_t)k, 1))) return fail("view upload failed");
+    if (d_log && hipMemsetAsync(d_log, 0, log_bytes, g->stream) != hipSuccess) return fail("hipMemsetAsync failed");
+    const McGcmcChain* d_par = reinterpret_cast<const McGcmcChain*>(g->d_gcmc + o_par);
+    const int32_t* d_list = reinterpret_cast<const int32_t*>(g->d_gcmc + o_list);
+    McPositions* d_prop = reinterpret_cast<McPositions*>(g->d_gcmc + o_prop);
+    double* d_rows = reinterpret_cast<double*>(g->d_gcmc + o_rows);
+    const ceg_mc_gcmc_species_t* d_spec = reinterpret_cast<const ceg_mc_gcmc_species_t*>(g->d_gcmc + o_spec);
+    ceg_mc_gcmc_stats_t* d_stats = reinterpret_cast<ceg_mc_gcmc_stats_t*>(g->d_gcmc + o_stats);
+    McGcmcTable* d_tab = reinterpret_cast<McGcmcTable*>(g->d_gcmc + o_tab);
+    int32_t* d_ms = reinterpret_cast<int32_t*>(g->d_gcmc + o_ms);
+    int32_t* d_free = reinterpret_cast<int32_t*>(g->d_gcmc + o_free);
+    // ---- the steps: nothing between them but the stream's own order
+    bool launched = true;
+    for (int64_t s = 0; s < nsteps && launched; ++s) {
+        const uint64_t step = p->first_step + (uint64_t)s;
+        if (!list[0].empty())
+            hipLaunchKernelGGL((k_mcg_gcmc_trial<false>), dim3(2u * (unsigned)list[0].size(), 3u), dim3(MC_THREADS), lds_trial[0], g->stream, g->d_views, d_par,
+                               d_spec, ns, d_tab, d_ms, d_list, table_ok[0], p->seed, step, d_prop, d_rows);
+        if (!list[1].empty())
+            hipLaunchKernelGGL((k_mcg_gcmc_trial<true>), dim3(2u * (unsigned)list[1].size(), 3u), dim3(MC_THREADS), lds_trial[1], g->stream, g->d_views, d_par,
+                               d_spec, ns, d_tab, d_ms, d_list + list[0].size(), table_ok[1], p->seed, step, d_prop, d_rows);
+        hipLaunchKernelGGL(k_mcg_gcmc_accept, dim3((unsigned)k), dim3(MC_THREADS), lds_accept, g->stream, g->d_views, d_par, d_spec, ns, d_tab, d_ms, d_free,
+                           p->seed, step, d_prop, d_rows, d_stats, d_log ? d_log + (size_t)s * (size_t)k : nullptr);
+        launched = hipGetLastError() == hipSuccess;
+    }
+    bool ok = hipStreamSynchronize(g->stream) == hipSuccess && launched &&
+              hipMemcpy(stage.data() + o_stats, g->d_gcmc + o_stats, total - o_stats, hipMemcpyDeviceToHost) == hipSuccess &&
+              (!d_log || hipMemcpy(log_out, d_log, log_bytes, hipMemcpyDeviceToHost) == hipSuccess);
+    g->accept_pending = false;
+    g->uploads_pending = false;
+    if (d_log) (void)hipFree(d_log);
+    // ---- the host mirrors from the device: molecule table, kinds, freed runs, counts and high-water mark of every chain that swapped
+    const ceg_mc_gcmc_stats_t* st = reinterpret_cast<const ceg_mc_gcmc_stats_t*>(stage.data() + o_stats);
+    const McGcmcTable* nt = reinterpret_cast<const McGcmcTable*>(stage.data() + o_tab);
+    const int32_t* ms = reinterpret_cast<const int32_t*>(stage.data() + o_ms);
+    const int32_t* fr = reinterpret_cast<const int32_t*>(stage.data() + o_free);
+    for (int c = 0; ok && c < k; ++c) {
+        ceg_mc* h = g->chains[c];
+        const McGcmcChain& P = pc[(size_t)c];
+        const McGcmcTable& D = nt[c];
+        if (st[c].accepted[5] + st[c].accepted[6] == 0) continue;
+        if (D.nmol < 0 || D.nmol > P.max_molecules || D.natoms < 0 || D.natoms > h->atoms_cap) { ok = false; break; }
+        std::vector<int2> mol((size_t)D.nmol);
+        if (D.nmol > 0 && hipMemcpy(mol.data(), h->d_molidx, sizeof(int2) * (size_t)D.nmol, hipMemcpyDeviceToHost) != hipSuccess) { ok = false; break; }
+        h->h_mol = mol;
+        h->h_kind.resize((size_t)D.natoms, 0);
+        for (int j = 0; j < D.nmol; ++j) {
+            const ceg_mc_gcmc_species_t& S = p->species[ms[P.spec_off + j]];
+            for (int a = 0; a < S.m; ++a) h->h_kind[(size_t)mol[(size_t)j].x + a] = S.kinds[a];
+        }
+        if (h->free_runs.empty()) h->free_runs.assign(MC_MAX_ATOMS + 1, {});
+        for (int i = 0; i < ns; ++i) h->free_runs[(size_t)p->species[i].m].clear();
+        for (int i = 0; i < ns; ++i)
+            for (int q = 0; q < D.nfree[i]; ++q) h->free_runs[(size_t)p->species[i].m].push_back(fr[(size_t)P.free_off + (size_t)i * P.free_cap + q]);
+        h->v.nmol = D.nmol;
+        h->v.natoms = D.natoms;
+        ++h->v_version;
+    }
+    if (!ok) {                                           // some steps may have run: the chains' states are unknown
+        for (ceg_mc* h : g->chains) h->poisoned = true;
+        return merr(CEG_ERR_HIP, "a sweep kernel failed: every chain of the group is marked inconsistent");
+    }
+    for (int c = 0; c < k; ++c) {
+        stats_out[c] = st[c];
+        fill_counts(c, nt[c], ms + pc[(size_t)c].spec_off);
     }
     return CEG_OK;
 }

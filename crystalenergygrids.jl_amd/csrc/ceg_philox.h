@@ -45,6 +45,9 @@ CEG_PHILOX_HD Block draw(uint64_t seed, uint64_t step, uint32_t stream, uint32_t
 }
 
 enum : uint32_t { SELECT = 0, GEOMETRY_A = 1, GEOMETRY_B = 2, ACCEPT = 3 };
+// ceg_mc_group_sweep_gcmc: species and move kind; molecule and swap direction; random_translation (x, y), (z, theta of random_rotation),
+// axis of random_rotation
+enum : uint32_t { GCMC_SELECT = 4, GCMC_MOLECULE = 5, GCMC_RANDOM_A = 6, GCMC_RANDOM_B = 7, GCMC_RANDOM_C = 8 };
 
 }  // namespace ceg_philox
 

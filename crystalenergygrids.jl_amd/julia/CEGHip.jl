@@ -647,6 +647,88 @@ function mc_group_sweep!(g::Ptr{Cvoid}, nsteps::Integer, seed::Integer, first_st
     log ? (stats, records) : stats
 end
 
+# `ceg_mc_gcmc_species_t`, `ceg_mc_gcmc_params_t`, `ceg_mc_gcmc_stats_t`, `ceg_mc_gcmc_record_t` of include/ceg_hip.h
+# (584, 88, 192 and 488 bytes; CEG_MC_GCMC_MAX_SPECIES = 8)
+struct McGcmcSpecies
+    m::Int32
+    bead::Int32                      # 0-based
+    kinds::NTuple{16,Int32}          # 0-based force-field indices
+    model::NTuple{48,Float64}        # x, y, z of up to 16 atoms (mc.models[i])
+    cumulative::NTuple{5,Float64}    # MCMoves.cumulatives
+    phiPV_div_k::Float64
+    self_reciprocal::Float64         # ctx.energies[i]
+    tail_framework::Float64
+    tail_cross::NTuple{8,Float64}
+end
+struct McGcmcParams
+    seed::UInt64
+    first_step::UInt64
+    stream_id::Ptr{UInt32}
+    temperature::Ptr{Float64}
+    dmax::Ptr{Float64}
+    thetamax::Ptr{Float64}
+    nspecies::Int32
+    _pad::Int32
+    species::Ptr{McGcmcSpecies}
+    molecule_species::Ptr{Int32}
+    max_molecules::Ptr{Int32}
+    molecule_species_out::Ptr{Int32}
+end
+struct McGcmcStats
+    trials::NTuple{7,Int64}          # translation, rotation, random_translation, random_rotation, random_reinsertion, swap_insertion, swap_deletion
+    accepted::NTuple{7,Int64}
+    blocked::Int64
+    capacity::Int64
+    spent::Int64
+    delta_moves::Float64
+    delta_swaps::Float64
+    count::NTuple{8,Int32}
+    nmol::Int32
+    _pad::Int32
+end
+struct McGcmcRecord
+    species::Int32
+    molecule::Int32
+    kind::Int32
+    accepted::Int32
+    n_species::Int32
+    flags::Int32                     # 1 spent, 2 blocked, 4 capacity
+    u::Float64
+    tc::Float64
+    rows::NTuple{8,Float64}
+    positions::NTuple{48,Float64}
+end
+
+"""
+`ceg_mc_group_sweep_gcmc`: `nsteps` steps of the inner loop of `run_montecarlo!` (src/simulation.jl:730-781) with all six move kinds of
+`MCMoves`, swaps included, on the device; the molecule table changes there and `molecule_species` (0-based species of every molecule
+of every chain, in Ewald order) is the table the sweep starts from; it is left as it is, and the final table is returned.  `species` is built by the caller from `mc.mcmoves[i].cumulatives`,
+`mc.models[i]`, `mc.bead[i] - 1`, `φPV_div_k[i]`, `mc.ewald.ctx.energies[i]` and the rows of `mc.tailcorrection`.  Returns the statistics
+per chain (and the records with `log=true`) and the final species of every chain's molecules.  Never executed here (no Julia in the image).
+"""
+function mc_group_sweep_gcmc!(g::Ptr{Cvoid}, nsteps::Integer, seed::Integer, first_step::Integer, temperature::Vector, dmax::Vector,
+                              thetamax::Vector, species::Vector{McGcmcSpecies}, molecule_species::Vector{Vector{Int32}},
+                              max_molecules::Vector{Int32}; stream_id::Vector{UInt32}=UInt32.(0:length(temperature)-1), log::Bool=false)
+    k = length(temperature)
+    T = Float64[ustrip(u"K", t) for t in temperature]
+    dm = Float64[d isa Real ? d : ustrip(u"Å", d) for d in dmax]
+    th = Float64[t isa Real ? t : ustrip(u"rad", t) for t in thetamax]
+    given = Int32[s for chain in molecule_species for s in chain]
+    push!(given, Int32(0))
+    out = fill(Int32(-1), max(sum(max_molecules), 1))
+    stats = Vector{McGcmcStats}(undef, k)
+    records = Matrix{McGcmcRecord}(undef, k, log ? nsteps : 0)
+    GC.@preserve stream_id T dm th species given max_molecules out stats records begin
+        params = Ref(McGcmcParams(UInt64(seed), UInt64(first_step), pointer(stream_id), pointer(T), pointer(dm), pointer(th),
+                                  Int32(length(species)), Int32(0), pointer(species), pointer(given), pointer(max_molecules), pointer(out)))
+        _check(ccall((:ceg_mc_group_sweep_gcmc, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                     g, params, nsteps, stats, log && nsteps > 0 ? pointer(records) : C_NULL))
+    end
+    offsets = cumsum(vcat(0, max_molecules))
+    final = [out[offsets[c]+1:offsets[c]+stats[c].nmol] for c in 1:k]
+    log ? (stats, final, records) : (stats, final)
+end
+
 "`ceg_mc_group_destroy`: the chains get their own streams back and stay valid"
 function mc_group_close(g::Ptr{Cvoid})
     _check(ccall((:ceg_mc_group_destroy, LIB[]), Cint, (Ptr{Cvoid},), g))

@@ -674,7 +674,7 @@ CEG_API int ceg_mc_group_accept(ceg_mc_group_t* group, const int32_t* molecule, 
  * log_out [nsteps][K] or NULL (production): per (step, chain) the molecule and move kind (0 translation, 1 rotation; both -1 for
  *   an idle chain), the accepted flag, u, the rows before / after and the proposed positions (unused entries zero).
  * Synchronous.  Afterwards every per-handle and group entry point works on the moved state; the molecule table does not change.
- * Not covered: swap / reinsertion / random_* moves, the inblockpocket test of choose_step!, and the adaptation of dmax / thetamax
+ * Not covered: swap / reinsertion / random_* moves (ceg_mc_group_sweep_gcmc, below), the inblockpocket test of choose_step!, and the adaptation of dmax / thetamax
  * (src/simulation.jl:820-825), which stays with the caller between sweeps -- the stats hold the ratios it needs. */
 typedef struct ceg_mc_sweep_params {
     uint64_t seed, first_step;
@@ -695,6 +695,101 @@ typedef struct ceg_mc_sweep_record {
 
 CEG_API int ceg_mc_group_sweep(ceg_mc_group_t* group, const ceg_mc_sweep_params_t* params, int64_t nsteps,
                                ceg_mc_sweep_stats_t* stats_out, ceg_mc_sweep_record_t* log_out);
+
+/* ---- GCMC sweeps: all six move kinds of src/mcmoves.jl:1-8, the molecule table owned by the device ----
+ * The inner loop of run_montecarlo! (src/simulation.jl:730-781) with choose_step! (:271-326): species, move kind and molecule drawn
+ * per step, the proposal built on the device, movement_energy rows from the kernel body of ceg_mc_group_trial (displacement and
+ * insertion rows alike), compute_accept_move / compute_accept_move_swap (src/montecarlo.jl:702-712, src/gcmc.jl:77-88), then
+ * update_mc! / add_one_system! / remove_one_system! with the semantics of ceg_mc_accept / ceg_mc_insert / ceg_mc_remove -- all on the
+ * device, two launches per step (three where fast and exact-pair chains are mixed), one synchronisation per sweep.
+ * ceg_mc_group_sweep, its stream and its results are unchanged; this entry point shares purposes 1-3 of its stream and adds 4-8.
+ *
+ * Move kinds (record.kind, index of stats.trials / stats.accepted): 0 translation, 1 rotation, 2 random_translation, 3 random_rotation,
+ *   4 random_reinsertion, 5 swap_insertion, 6 swap_deletion.
+ * Random stream (Philox4x32-10, key, counter and U(a, b) as for ceg_mc_group_sweep), stream c at the absolute step s:
+ *   purpose 4, selection: species i = min(floor(U(w0,w1) nspecies), nspecies - 1); move kind = the first k in 0..4 with
+ *     U(w2,w3) < cumulative[k] of species i, else swap;
+ *   purpose 5, molecule: with N_i the molecules of species i, j = min(floor(U(w0,w1) N_i), N_i - 1): the j-th molecule of species i
+ *     counted in device molecule order; a swap is a deletion iff U(w2,w3) < 0.5, else an insertion;
+ *   purposes 1 and 2: translation and rotation exactly as ceg_mc_group_sweep draws them (dmax, thetamax of the chain, atom `bead` of
+ *     the species);
+ *   purposes 6, 7, 8: random_translation (mcmoves.jl:143) r = mat (U3 - 0.5) with U3 = (U(w0,w1), U(w2,w3)) of purpose 6 and U(w0,w1)
+ *     of purpose 7, r_x = (mat[0] a + mat[3] b) + mat[6] c etc. (mat column-major, the MC cell); random_rotation theta =
+ *     pi (2 U(w2,w3) - 1) from purpose 7, axis = min(floor(3 U(w0,w1)), 2) from purpose 8, the matrices of mcmoves.jl:155-161 about
+ *     atom `bead`; random_reinsertion: t = p + r for every atom, then t_bead + R (t - t_bead); swap_insertion: the same pair applied
+ *     to the species' model positions (simulation.jl:300-305).  A rotation of a one-atom molecule is the identity;
+ *   purpose 3, acceptance: u = U(w0,w1).
+ * A step whose species has N_i == 0 and whose move is not an insertion is SPENT (simulation.jl:282): nothing is evaluated, nothing
+ *   is counted but stats.spent.
+ * Rows: displacement kinds rows[0] / rows[1] = movement_energy before / after; deletion rows[0] = movement_energy where the molecule
+ *   is, rows[1] = zeros; insertion rows[0] = zeros, rows[1] = the row of ceg_mc_trial_insert at the proposed placement.
+ * Rule: displacements as ceg_mc_group_sweep (framework VdW of the trial row >= 1e90: blocked, rejected).  Swaps, all in FP64 and in
+ *   this order: E = ((row[0] + row[1]) + row[2]) + row[3]; tc = modify_species_dryrun(i, +-1) (src/tailcorrection.jl:86-96) on the
+ *   chain's current counts: d = tail_framework[i]; for j = 0..nspecies-1 in order: d += (j == i) ? (double)(n + 2 N_j) tail_cross[i][j]
+ *   : (double)(2 N_j) tail_cross[i][j]; tc = d (double)n with n = +1 / -1;
+ *   insertion: diff = (E - self_reciprocal) + tc, accepted iff u < ((phiPV_div_k / T) / (N_i + 1)) exp(-diff / T); an insertion whose
+ *     framework VdW column is >= 1e90 is blocked and rejected;
+ *   deletion:  diff = -(E - self_reciprocal) + tc, accepted iff u < ((N_i T) / phiPV_div_k) exp(-diff / T).
+ * Update: an accepted insertion becomes molecule nmol (the last); after an accepted deletion of molecule d the LAST molecule takes
+ *   index d.  Atom slots: the slots of a deleted molecule go on a per-species stack the next insertion of that species pops; with an
+ *   empty stack the insertion takes fresh slots at the high-water mark.
+ * Capacity: an insertion proposed while the chain holds max_molecules molecules is counted as a swap_insertion trial and in
+ *   stats.capacity, is not evaluated (rows zero) and is rejected: a caller that sees capacity > 0 knows the sweep was truncated.
+ *
+ * params: seed, first_step, stream_id, temperature, dmax, thetamax as ceg_mc_sweep_params_t.  species [nspecies], 1 <= nspecies <=
+ *   CEG_MC_GCMC_MAX_SPECIES, shared by the chains: m atoms (1..16) of kinds[m], model positions (mc.models[i]), bead (0-based),
+ *   cumulative[5] (the MCMoves tuple: non-decreasing, in [0, 1]; swap probability = 1 - cumulative[4]), phiPV_div_k K (finite, > 0
+ *   where the swap probability is > 0), self_reciprocal K (ctx.energies[i], simulation.jl:768,770), tail_framework and
+ *   tail_cross[0..nspecies) (zeros: no tail correction).  molecule_species: the species of every current molecule, packed in chain
+ *   order and device molecule order (atom count and kinds must match the handle's molecule).  max_molecules [K] >= the chain's count.
+ *   molecule_species_out (may be NULL): the final table, chain c at offset sum of max_molecules[0..c), stats[c].nmol entries.
+ *   Violations -> CEG_ERR_INVALID; a member with neighbour cells -> CEG_ERR_UNSUPPORTED; a member marked inconsistent -> CEG_ERR_HIP;
+ *   each decided before anything is launched or changed.
+ * stats_out [K]; log_out [nsteps][K] or NULL.  record.molecule: device index (an insertion: the index it takes if accepted; -1 for a
+ *   spent step); record.flags: 1 spent, 2 blocked, 4 capacity; record.n_species = N_i before the move; record.tc = the tail-correction
+ *   change of a swap (0 otherwise).  stats.delta_moves = sum of a - b over accepted displacements, stats.delta_swaps = sum of diff over
+ *   accepted swaps.
+ * Synchronous.  Afterwards the handles' host mirrors (molecule table, free atom slots, high-water mark) are rebuilt from the device and
+ *   every per-handle and group entry point works on the new state.
+ * Not covered: the inblockpocket retry loop of choose_step! (chains with block pockets stay with the caller), the adaptation of dmax /
+ *   thetamax, the fugacity coefficient (phiPV_div_k comes from the caller, as the reference takes it from Clapeyron), and chains
+ *   that keep their guests in neighbour cells. */
+#define CEG_MC_GCMC_MAX_SPECIES 8
+typedef struct ceg_mc_gcmc_species {
+    int32_t m, bead;
+    int32_t kinds[16];
+    double model[16][3];
+    double cumulative[5];
+    double phiPV_div_k, self_reciprocal, tail_framework;
+    double tail_cross[CEG_MC_GCMC_MAX_SPECIES];
+} ceg_mc_gcmc_species_t;
+typedef struct ceg_mc_gcmc_params {
+    uint64_t seed, first_step;
+    const uint32_t* stream_id;                 /* [K] */
+    const double *temperature, *dmax, *thetamax;      /* [K] each */
+    int32_t nspecies, _pad;
+    const ceg_mc_gcmc_species_t* species;      /* [nspecies] */
+    const int32_t* molecule_species;           /* [sum of the chains' molecule counts] */
+    const int32_t* max_molecules;              /* [K] */
+    int32_t* molecule_species_out;             /* [sum of max_molecules] or NULL */
+} ceg_mc_gcmc_params_t;
+typedef struct ceg_mc_gcmc_stats {
+    int64_t trials[7], accepted[7];
+    int64_t blocked, capacity, spent;
+    double delta_moves, delta_swaps;
+    int32_t count[CEG_MC_GCMC_MAX_SPECIES];
+    int32_t nmol, _pad;
+} ceg_mc_gcmc_stats_t;
+typedef struct ceg_mc_gcmc_record {
+    int32_t species, molecule, kind, accepted;
+    int32_t n_species, flags;
+    double u, tc;
+    double rows[2][4];
+    double positions[16][3];
+} ceg_mc_gcmc_record_t;
+
+CEG_API int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* group, const ceg_mc_gcmc_params_t* params, int64_t nsteps,
+                                    ceg_mc_gcmc_stats_t* stats_out, ceg_mc_gcmc_record_t* log_out);
 
 /* ---- blocking masks on the grid lattice ----------------------------- */
 /*
