@@ -485,6 +485,41 @@ def test_gcmc_shapes_one_and_sixteen_atoms_fast_and_exact_chains(setup):
     _close(devs)
 
 
+def test_plain_sweep_after_a_gcmc_sweep_on_the_same_group(setup):
+    """The group keeps one device block for both kinds of sweep, and it only grows.  On one group of 2 chains (Na + 3 CO2 each), 8 steps
+    each with logs: a plain sweep, a GCMC sweep that needs a larger block (species table, the chains' tables, the species of the
+    molecules, the stacks of freed slots for max_molecules = 10), the plain sweep again.  The third call's log and statistics are those
+    of the same plain sweep run alone on a fresh group over chains in the same state, byte for byte: nothing stale is read after the
+    block grew."""
+    from ceg_hip.energy import DeviceMonteCarloGroup
+    mc, _owner = setup
+    K, S = 2, 8
+    start = [mc.positions[0], mc.positions[1][:3]]
+    common = dict(temperature=[300.0, 700.0], dmax=0.4, thetamax=0.8, stream_id=[4, 9], log=True)
+    a, _ = _chains(setup, K, positions=start)
+    b, _ = _chains(setup, K, positions=start)
+    with DeviceMonteCarloGroup(a) as ga:
+        table = _tail(ga.gcmc_species([NA_MOVES, CO2_MOVES], [5000.0, 5000.0]))
+        _sa1, la1 = ga.sweep(S, SEED + 70, 0, p_rotation=0.5, **common)
+        _sa2, la2 = ga.sweep_gcmc(S, SEED + 70, S, species=table, max_molecules=[10, 10], **common)
+        sa3, la3 = ga.sweep(S, SEED + 70, 2 * S, p_rotation=0.5, **common)
+    with DeviceMonteCarloGroup(b) as gb:                             # the same two sweeps bring the twins into the same state
+        _sb1, lb1 = gb.sweep(S, SEED + 70, 0, p_rotation=0.5, **common)
+        _sb2, lb2 = gb.sweep_gcmc(S, SEED + 70, S, species=table, max_molecules=[10, 10], **common)
+    assert la1.tobytes() == lb1.tobytes() and la2.tobytes() == lb2.tobytes()
+    with DeviceMonteCarloGroup(b) as fresh:                          # a new group: its block is allocated for this sweep alone
+        sb3, lb3 = fresh.sweep(S, SEED + 70, 2 * S, p_rotation=0.5, **common)
+    assert la3.tobytes() == lb3.tobytes()
+    assert sa3.tobytes() == sb3.tobytes()
+    assert (la3["molecule"] >= 0).all() and (sa3["translation_trials"] + sa3["rotation_trials"] == S).all()
+    for x, y in zip(a, b):
+        px, sx = x.state()
+        py, sy = y.state()
+        assert np.array_equal(px, py) and np.array_equal(sx, sy)
+    _close(b)
+    _close(a)
+
+
 def test_gcmc_chain_without_capacity_in_front(setup):
     """max_molecules = 0 for an empty first chain: its insertions are counted in `capacity`, and the table of the chain behind it is
     reported at the documented offset (the sum of max_molecules in front of it)."""

@@ -1,5 +1,5 @@
 """Register budgets of the Monte-Carlo trial / accept kernels once their bodies are shared with the chain-group kernels
-(k_mcg_trial / k_mcg_accept).  hipcc cross-compiles ceg_mc.hip for gfx950 with the resource-usage remark; no GPU needed.
+(k_mcg_trial / k_mcg_accept, ceg_mc_group.hip).  hipcc cross-compiles both files for gfx950 with the resource-usage remark; no GPU needed.
 
 The batch-1 path sits at the edge of three waves per SIMD (168 VGPRs), so the refactoring must leave the existing kernels'
 code as it was: the same VGPR counts and scratch, variant by variant.  The group variants may cost at most 8 VGPRs more
@@ -24,12 +24,15 @@ def usage():
     if not HIPCC.exists():
         pytest.fail("hipcc is needed to check the kernel budgets")
     flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fvisibility=hidden", "-Dceg_EXPORTS"]
-    r = subprocess.run([str(HIPCC), *flags, "--cuda-device-only", "-c", "-o", "/dev/null", "ceg_mc.hip", "-Rpass-analysis=kernel-resource-usage"],
-                       cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
     out = {}
     name = None
-    for line in r.stderr.splitlines():
+    lines = []
+    for source in ("ceg_mc.hip", "ceg_mc_group.hip"):        # k_mc_trial / k_mc_accept, then k_mcg_trial / k_mcg_accept
+        r = subprocess.run([str(HIPCC), *flags, "--cuda-device-only", "-c", "-o", "/dev/null", source, "-Rpass-analysis=kernel-resource-usage"],
+                           cwd=CSRC, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines += r.stderr.splitlines()
+    for line in lines:
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             name = m.group(1)
