@@ -71,6 +71,7 @@ class Replay:
         self.peak = len(self.tab)
         self.tc_nonzero = self.flips = 0
         self.seen_species = set()
+        self.events = []          # every decided step: (kind, device molecule index, nmol before the step, accepted, species)
 
     def step(self, seed, step, sid, rec=None, what=None):
         omc, tab = self.omc, self.tab
@@ -146,6 +147,7 @@ class Replay:
         self.blocked += bool(blocked)
         self.seen.add((kind, bool(ok)))
         self.seen_species.add((i, kind, bool(ok)))
+        self.events.append((kind, pr.molecule, len(tab), bool(ok), i))
         if not ok:
             return
         self.delta[0 if kind <= 4 else 1] += diff

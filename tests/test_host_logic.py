@@ -170,6 +170,43 @@ def test_reciprocal_row_layout_host_side():
     assert lib.ceg_recip_layout(None, 0, _abi.i32ptr(np.array([2, 2, 2], dtype=np.int32)), C.byref(nr), C.byref(ns), None, None) == 0 and nr.value == 0
 
 
+def test_kspace_boxes_beyond_the_nine_bit_fields_are_refused():
+    """The descriptors pack i0, j + ky and k + kz into nine bits each (values up to 511).  The table bound (kx + 1) + (2 ky + 1) +
+    (2 kz + 1) <= 400 of ceg_recip_create / ceg_recip_layout / ceg_mc_create keeps every field at 397 or below, so no refusal of its
+    own is needed: any axis with ks > 255 in y or z, and any kx > 397, is refused (CEG_ERR_UNSUPPORTED) before anything is launched;
+    the largest box accepted along each axis gives descriptors that decode to its k-vectors."""
+    import ctypes as C
+    lib = _abi.load_library()
+    nr, ns = C.c_int32(), C.c_int32()
+    h = C.c_void_p()
+    one = np.array([[0, 0, 0]], dtype=np.int32)
+    kf = np.ones(1); z = np.zeros(1)
+    inv = np.eye(3).reshape(-1) / 30.0
+    mat = np.eye(3).reshape(-1) * 30.0
+    rules = np.zeros(1, dtype=_abi.RULE_DTYPE)
+    off = np.zeros(2, dtype=np.int32)
+    for ks in ((0, 256, 0), (0, 0, 256), (256, 256, 256), (398, 0, 0), (0, 199, 0), (0, 0, 199), (1 << 20, 0, 0)):
+        k = np.array(ks, dtype=np.int32)
+        assert lib.ceg_recip_layout(_abi.i32ptr(one.reshape(-1)), 1, _abi.i32ptr(k), C.byref(nr), C.byref(ns), None, None) == -5, ks
+        assert lib.ceg_recip_create(C.byref(h), 0, _abi.i32ptr(one.reshape(-1)), _abi.dptr(kf), _abi.dptr(z), _abi.dptr(z), 1, _abi.i32ptr(k),
+                                    _abi.dptr(inv)) == -5 and not h.value, ks
+        assert lib.ceg_mc_create(C.byref(h), 0, None, None, _abi.dptr(z), 1, _abi.dptr(mat), _abi.dptr(inv), 144.0, rules.ctypes.data,
+                                 _abi.i32ptr(off), 1.0, _abi.i32ptr(one.reshape(-1)), _abi.dptr(kf), _abi.dptr(z), _abi.dptr(z), 1, _abi.i32ptr(k),
+                                 _abi.dptr(inv)) == -5 and not h.value, ks
+    for ks, ijk in (((397, 0, 0), [[397, 0, 0], [1, 0, 0]]), ((0, 198, 0), [[0, 198, 0], [0, -198, 0]]), ((0, 0, 198), [[0, 0, 198], [0, 0, -198]])):
+        k, ijk = np.array(ks, dtype=np.int32), np.array(ijk, dtype=np.int32)
+        assert lib.ceg_recip_layout(_abi.i32ptr(ijk.reshape(-1)), 2, _abi.i32ptr(k), C.byref(nr), C.byref(ns), None, None) == 0, ks
+        slot, desc = np.empty(2, dtype=np.int64), np.empty(nr.value * 64, dtype=np.int32)
+        assert lib.ceg_recip_layout(_abi.i32ptr(ijk.reshape(-1)), 2, _abi.i32ptr(k), C.byref(nr), C.byref(ns), slot.ctypes.data, desc.ctypes.data) == 0
+        L = (desc >> 27).reshape(nr.value, 64)[:, 0]
+        first = np.concatenate([[0], np.cumsum(L)])
+        rnd = np.searchsorted(first, slot // 64, side="right") - 1
+        d = desc.reshape(nr.value, 64)[rnd, slot % 64]
+        i0, jj, kk = d & 0x1ff, (d >> 9) & 0x1ff, (d >> 18) & 0x1ff
+        assert np.array_equal(jj - k[1], ijk[:, 1]) and np.array_equal(kk - k[2], ijk[:, 2]), ks
+        assert np.array_equal(slot // 64 - first[rnd], ijk[:, 0] - i0), ks
+
+
 def test_grid_coordinates_setup_cha():
     """coordinates.jl:32-41 on the CHA fixture (numbers of SURVEY appendix A)."""
     fw = ceg.load_framework_RASPA("CHA_1.4_3b4eeb96", FFNAME)
