@@ -43,6 +43,13 @@ class _PlainBuilds:
         _abi.check(self._lib, self._lib.ceg_plan_build_fused(self._h, lv, tv, lc, tc, i_begin, i_end, d_vdw,
                                                              d_coulomb, channel_stride, i_origin, algo, stream))
 
+    @property
+    def uniform_class(self) -> int:
+        """0: per-candidate Lennard-Jones records; 1: one Lennard-Jones record for every VdW-active atom, its constants applied once
+        per tile of grid points; 2: and one charge (``ceg_plan_uniform_class``; of probe 0 on a multi-probe plan).
+        ``CEG_HIP_UNIFORM_CLASS=0`` (or 1) in the environment at plan creation caps it."""
+        return int(self._lib.ceg_plan_uniform_class(self._h))
+
     # ------------------------------------------------------------------ raw FP64 sums at points
     def eval_points(self, which: str, points, algo: int = _abi.ALGO_AUTO) -> np.ndarray:
         """compute_derivatives_vdw / _ewald (probes.jl:71-117) at cartesian points ->

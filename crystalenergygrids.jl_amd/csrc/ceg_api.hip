@@ -59,6 +59,39 @@ extern "C" int ceg_device_count(void)
     return n;
 }
 
+namespace ceg {
+UniformClass detect_uniform_class(const FastVdw* fast, int32_t nkinds, const int32_t* kind, const double* charge, int64_t natoms)
+{
+    UniformClass u;
+    std::vector<char> present((size_t)std::max(nkinds, 1), 0);
+    for (int64_t a = 0; a < natoms; ++a)
+        if (kind[a] >= 0 && kind[a] < nkinds) present[kind[a]] = 1;
+    const FastVdw* first = nullptr;
+    for (int32_t k = 0; k < nkinds; ++k) {
+        const FastVdw& f = fast[k];
+        if (!present[k] || f.cls == 0) continue;          // absent, or no rule with this probe: not a VdW-active kind
+        if (f.cls != 1) return u;
+        if (!first) first = &f;
+        else if (memcmp(&first->p0, &f.p0, 4 * sizeof(double)) != 0) return u;      // bit-identical {4 eps, sigma^2, sigma^6, shift}
+    }
+    if (!first) return u;
+    const double e4 = first->p0, s6 = first->p2, sh = first->shift;
+    if (!(std::fabs(e4) >= 1e-9 && std::fabs(e4) <= 1e9) || !(s6 >= 1e-9 && s6 <= 1e9) || !std::isfinite(sh)) return u;
+    u.cls = 1; u.eps4 = e4; u.s6 = s6; u.shift = sh;
+    if (!charge) return u;
+    bool have = false;
+    double q = 0.0;
+    for (int64_t a = 0; a < natoms; ++a) {
+        const int32_t k = kind[a];
+        if (k < 0 || k >= nkinds || fast[k].cls == 0) continue;
+        if (!have) { q = charge[a]; have = true; }
+        else if (memcmp(&q, &charge[a], sizeof(double)) != 0) return u;
+    }
+    if (have && std::fabs(q) >= 1e-6 && std::fabs(q) <= 1e6) { u.cls = 2; u.q = q; }
+    return u;
+}
+}  // namespace ceg
+
 // ------------------------------------------------------------------ plan
 struct ceg_plan {
     int device = 0;
@@ -93,6 +126,7 @@ struct ceg_plan {
     bool single_buck = false;    // every present kind with a VdW rule is the same Buckingham (+ hard sphere) -> candidate for vdwk 3
     double bk[4] = {0, 0, 0, 0}; // its A, B, C, shift
     double* d_bk2 = nullptr;
+    UniformClass uni;            // one Lennard-Jones record (+ one charge) for every VdW-active atom: k_culled VDWK 4 / 5 (0: none)
     double r_exact2 = CEG_R_EXACT2;
     std::vector<FastVdw> h_fast;
     FastVdw* d_fast = nullptr;
@@ -115,6 +149,7 @@ struct ceg_plan {
         bool single_buck = false;
         double bk[4] = {0, 0, 0, 0};
         double* d_bk2 = nullptr;
+        UniformClass uni;               // the probe's own uniform class: the plain builds on the plan run probe 0 with it
         int32_t* d_imgkind = nullptr;   // per image: kind | "the kind has a rule with THIS probe" (the shared list carries the union)
     };
     int nprobes = 0;             // 0: ordinary plan
@@ -237,6 +272,35 @@ int convert_rules(ceg_plan* p, const ceg_rule_t* rules, const int32_t* rule_offs
     p->r_exact2 = std::max(CEG_R_EXACT2, hs_max2 * (1.0 + 1e-9) + 1e-9);
     if (p->r_exact2 >= p->g.cutoff2) p->vdwk = 0, p->r_exact2 = CEG_R_EXACT2;
     return CEG_OK;
+}
+
+// The uniform class of a Lennard-Jones-only plan (vdwk == 1) for the hot loops of k_culled:
+//   1 (uni_lj): every kind that is present and has a rule with the probe carries a bit-identical fast record {4 eps, sigma^2, sigma^6,
+//               shift} -- the hot loop then sums the channels in units of 4 eps sigma^6 and applies that and count * shift once per tile;
+//   2 (uni_q):  1, and every atom of such a kind carries a bit-identical charge (per ATOM: charges are not a property of the kind) --
+//               the Coulomb channels of the VdW-active group are summed in units of q.
+// The sums are divided by 4 eps sigma^6 (q) on the exact path and multiplied back at the end of a tile, so these must be ordinary
+// numbers of moderate size: |4 eps| and sigma^6 in [1e-9, 1e9], |q| in [1e-6, 1e6] (force fields hold 1e-2 .. 1e3 K, 1 .. 5 A and
+// 1e-2 .. 4 e); all finite.
+void set_uniform_class(ceg_plan* p)
+{
+    p->uni = UniformClass{};
+    if (p->vdwk != 1 || p->natoms <= 0) return;
+    p->uni = detect_uniform_class(p->h_fast.data(), p->nkinds, p->h_kind.data(), p->h_charge.empty() ? nullptr : p->h_charge.data(), p->natoms);
+}
+
+// what PlanConst carries of it
+void fill_uniform_class(PlanConst& c, const UniformClass& u)
+{
+    c.uni_class = u.cls;
+    if (u.cls == 0) return;
+    const double unit = u.eps4 * u.s6;
+    c.uni_unit = unit; c.uni_s6 = u.s6; c.uni_shift = u.shift;
+    c.uni_k1 = 2.0 * u.s6; c.uni_k2 = 3.5 * u.s6; c.uni_k3 = 5.6 * u.s6;
+    c.uni_sv = 1.0 / unit; c.uni_s1 = -1.0 / (6.0 * unit); c.uni_s2 = 1.0 / (48.0 * unit); c.uni_s3 = -1.0 / (480.0 * unit);
+    if (u.cls == 2) {
+        c.uni_q = u.q; c.uni_inv_q = 1.0 / u.q; c.uni_qs2 = 1.0 / (3.0 * u.q); c.uni_qs3 = 1.0 / (15.0 * u.q);
+    }
 }
 
 // ---- small-block cache for the plan tables.  A plan is a dozen small device arrays; hipMalloc +
@@ -1012,6 +1076,8 @@ static int create_impl(ceg_plan_t** plan, int32_t device,
                 ceg_plan::ProbeTab& t = p->probes[q];
                 t.rules = p->h_rules; t.offset = p->h_offset; t.fast = p->h_fast;
                 t.vdwk = p->vdwk; t.single_buck = p->single_buck;
+                set_uniform_class(p);
+                t.uni = p->uni;
                 for (int c = 0; c < 4; ++c) t.bk[c] = p->bk[c];
                 r_exact2 = std::max(r_exact2, p->r_exact2);          // ONE exact-path radius for the plan: the largest any probe asks for
                 for (int32_t k = 0; k < nkinds; ++k) any[k] |= (t.offset[k + 1] > t.offset[k]) ? 1 : 0;
@@ -1027,6 +1093,17 @@ static int create_impl(ceg_plan_t** plan, int32_t device,
             p->h_offset_union.assign(nkinds + 1, 0);
             for (int32_t k = 0; k < nkinds; ++k) p->h_offset_union[k + 1] = p->h_offset_union[k] + any[k];
             p->h_offset = p->probes[0].offset;
+            p->uni = UniformClass{};      // the plan-level block serves the multi-probe launches and the Coulomb grid: per-candidate records
+        } else {
+            set_uniform_class(p);
+        }
+        // CEG_HIP_UNIFORM_CLASS=0 keeps the per-candidate records (one library runs both paths: tests, A/B); =1 defers the
+        // Lennard-Jones constants only
+        if (const char* e = std::getenv("CEG_HIP_UNIFORM_CLASS")) {
+            const int cap = std::max(0, atoi(e));
+            auto limit = [cap](UniformClass& u) { if (u.cls > cap) u.cls = cap; if (u.cls == 0) u = UniformClass{}; };
+            limit(p->uni);
+            for (auto& t : p->probes) limit(t.uni);
         }
     }
     // culling needs: finite cutoff, every perpendicular width >= 2*cutoff (two images of one atom
@@ -1081,6 +1158,7 @@ static int create_impl(ceg_plan_t** plan, int32_t device,
         if (p->h_fast.empty()) p->h_fast.assign(1, FastVdw{});
         rc = upload(&p->d_fast, p->h_fast.data(), p->h_fast.size());
         hc.fastvdw = p->d_fast;
+        fill_uniform_class(hc, p->uni);
         p->fast_ewald = false;
         bool any_vdwk2 = p->vdwk == 2;
         for (const auto& t : p->probes) any_vdwk2 = any_vdwk2 || t.vdwk == 2;
@@ -1151,6 +1229,7 @@ static int create_impl(ceg_plan_t** plan, int32_t device,
                 PlanConst hq = hc;
                 hq.rt = hc.rtm[q];
                 hq.fastvdw = hc.fastm[q];
+                fill_uniform_class(hq, t.uni);
                 setup_bk2(t.vdwk, t.single_buck, t.bk, &t.d_bk2, hq);
                 // per image: does ITS kind have a rule with this probe?  The shared list carries the union of the probes (what the
                 // launches of several Lennard-Jones probes stage by); a single-probe launch drops / declasses the images that are
@@ -1245,6 +1324,32 @@ extern "C" int ceg_image_cache_stats(int64_t* hits, int64_t* misses, int64_t* en
 
 extern "C" int ceg_plan_can_cull(const ceg_plan_t* p) { return (p && p->can_cull) ? 1 : 0; }
 
+extern "C" int ceg_plan_uniform_class(const ceg_plan_t* p)
+{
+    if (!p) return 0;
+    return p->nprobes > 0 ? p->probes[0].uni.cls : p->uni.cls;
+}
+
+// host only: the classification of convert_rules + detect_uniform_class on a caller's tables
+extern "C" int ceg_uniform_class(const int64_t* atomkind, const double* charge, int64_t natoms, const ceg_rule_t* rules,
+                                 const int32_t* rule_offset, int32_t nkinds, double cutoff2, double constants[4])
+{
+    if (!atomkind || natoms <= 0 || !rules || !rule_offset || nkinds <= 0) return fail(CEG_ERR_INVALID, "atom / rule tables missing");
+    ceg_plan tmp;
+    tmp.natoms = natoms;
+    tmp.g.cutoff2 = cutoff2;
+    tmp.h_kind.resize((size_t)natoms);
+    for (int64_t a = 0; a < natoms; ++a) {
+        if (atomkind[a] < 1 || atomkind[a] > nkinds) return fail(CEG_ERR_INVALID, "atomkind[%lld] outside 1..%d", (long long)a, nkinds);
+        tmp.h_kind[a] = (int32_t)(atomkind[a] - 1);
+    }
+    if (charge) tmp.h_charge.assign(charge, charge + natoms);
+    if (int rc = convert_rules(&tmp, rules, rule_offset, nkinds)) return rc;
+    set_uniform_class(&tmp);
+    if (constants) { constants[0] = tmp.uni.eps4; constants[1] = tmp.uni.s6; constants[2] = tmp.uni.shift; constants[3] = tmp.uni.q; }
+    return tmp.uni.cls;
+}
+
 extern "C" int64_t ceg_plan_num_images(const ceg_plan_t* p) { return (p && p->images_built) ? p->ib.nimages : 0; }
 
 // the lattice-image list of a plan copied to the host (tests: the device build against the host build): xyzq [4 n], kind / atom [n],
@@ -1293,8 +1398,10 @@ int run(ceg_plan* p, int mode, const Output& out, const Points& pts, bool culled
         // class, the per-image flags of that probe) and ITS hot-loop variant -- the plan-level block carries the union image flags
         // and no Buckingham table.  The Coulomb grid alone needs no probe: the plan-level block, as in ceg_plan_build_multi.
         const bool probe0 = p->nprobes > 0 && mode != MODE_COULOMB;
+        // (the uniform class of the plan or of probe 0: these calls only; ceg_plan_build_multi keeps the per-candidate records, so that
+        //  a grid does not depend on how that call cuts a request into launches)
         e = launch_culled(mode, probe0 ? p->probes[0].d_pc : p->d_pc, p->g, probe0 ? p->probes[0].vdwk : p->vdwk,
-                          p->ew2 ? 2 : (p->fast_ewald ? 1 : 0), out, pts, stream);
+                          p->ew2 ? 2 : (p->fast_ewald ? 1 : 0), out, pts, stream, probe0 ? p->probes[0].uni.cls : p->uni.cls);
     } else {
         AtomTable at{p->d_atoms, p->has_rules ? p->d_kind : nullptr, p->natoms};
         e = launch_bruteforce(mode, p->g, at, rt, out, pts, stream);

@@ -131,6 +131,15 @@ struct PlanConst {
     double bk_B, bk_C, bk_invC;                       // single tabulated Buckingham class: B, C, 1/C and the constants of the
     double bk_nshift, bk_c1, bk_c2, bk_c3, bk_c4;      // scaled hot loop: -shift/C, -B/6, -B/48, B^2/3, -B/160
     double bk_s1, bk_s2, bk_s3;                        // exact path: 1/(6C), -1/(48C), 1/(480C)
+    // One Lennard-Jones record (and, uni_class 2, one charge) for every VdW-active image of the plan (k_culled VDWK = 4 / 5): the
+    // hot loop accumulates the VdW channels in units of U = 4 eps sigma^6 (and the Coulomb channels in units of q), the constants are
+    // applied once per tile.  uni_class: 0 none, 1 Lennard-Jones record, 2 record + charge.
+    int32_t uni_class, _pad_uni;
+    double uni_unit, uni_s6, uni_shift, uni_q;         // U = 4 eps sigma^6, sigma^6, shift, charge
+    double uni_k1, uni_k2, uni_k3;                     // hot loop: 2 sigma^6, 3.5 sigma^6, 5.6 sigma^6
+    double uni_inv_q;                                  // 1/q: the Coulomb-only candidates are staged with q_i/q
+    double uni_sv, uni_s1, uni_s2, uni_s3;             // exact path, VdW: 1/U, -1/(6 U), 1/(48 U), -1/(480 U)
+    double uni_qs2, uni_qs3;                           // exact path, Coulomb: 1/(3 q), 1/(15 q)
     int32_t all_simple;        // grid mode: every image a tile can keep is provably the fractionally wrapped one (no per-candidate test)
     int32_t nprobes;           // multi-probe plans: number of probes (0 = ordinary plan)
     // multi-probe plans (all probes Lennard-Jones-only): per probe the rule table (exact path) and the per-kind fast records
@@ -179,8 +188,18 @@ hipError_t launch_bruteforce(int mode, const Geom& g, const AtomTable& atoms, co
                              const Output& out, const Points& pts, hipStream_t stream);
 // ewk: real-space Ewald arithmetic of the hot loop -- 0 libm-grade erfc / exp, 1 erfcx table + exp (alpha*cutoff <= 5),
 // 2 r^2-indexed tables
+// uni: the plan's uniform class (PlanConst::uni_class of d_pc; 0 keeps the per-candidate records).  It selects VDWK = 4 / 5 for
+// single-probe Lennard-Jones launches (vdwk == 1), see launch_cull_flags.
 hipError_t launch_culled(int mode, const PlanConst* d_pc, const Geom& g, int vdwk, int ewk,
-                         const Output& out, const Points& pts, hipStream_t stream);
+                         const Output& out, const Points& pts, hipStream_t stream, int uni = 0);
+
+// Plan-time detection of the uniform class (host code, ceg_api.hip): present[k] != 0 for kinds that occur in the atom list,
+// fast[k] the per-kind records, kind[a] (0-based) / charge[a] (may be null) per atom.  Returns 0 / 1 / 2 and the constants.
+struct UniformClass {
+    int cls = 0;
+    double eps4 = 0, s6 = 0, shift = 0, q = 0;
+};
+UniformClass detect_uniform_class(const FastVdw* fast, int32_t nkinds, const int32_t* kind, const double* charge, int64_t natoms);
 // multi-probe grid build: np (2..CEG_MAX_PROBES; with mode == MODE_FUSED at most CEG_MAX_PROBES_FUSED) Lennard-Jones probes of a
 // multi-probe plan in one pass, out.vdwm / out.probe_idx say which; mode MODE_VDW or MODE_FUSED (+ the Coulomb grid, EWK = 2)
 constexpr int CEG_MAX_PROBES_FUSED = 2;

@@ -378,8 +378,10 @@ __global__ __launch_bounds__(256) void k_bruteforce(Geom g, AtomTable atoms, Rul
 #ifndef CEG_NW_MULTI_FUSED
 #define CEG_NW_MULTI_FUSED 8         // 8 waves x 64 x 96 B + 19.7 KB of tables + 8 KB = 77 KB: two workgroups per CU
 #endif
-constexpr int culled_waves(int mode, int vdwk, int ewk, int np = 1)
+constexpr bool vdwk_uniform(int vdwk) { return vdwk == 4 || vdwk == 5; }      // one Lennard-Jones record for the whole plan
+constexpr int culled_waves(int mode, int vdwk_, int ewk, int np = 1)
 {
+    const int vdwk = vdwk_uniform(vdwk_) ? 1 : vdwk_;      // the uniform variants are Lennard-Jones variants with fewer live values
     return np > 1 ? (mode == 2 ? CEG_WAVES_MULTI_FUSED : (np == 2 ? CEG_WAVES_MULTI_VDW : 3))
            : (mode == 2 && vdwk >= 2 && ewk) ? CEG_WAVES_FUSED_BUCK
            : (mode == 2 && vdwk == 1 && ewk) ? CEG_WAVES_FUSED_LJ
@@ -424,7 +426,10 @@ struct __attribute__((aligned(16))) CandRec {
 // position, invmat*d, wrap, mat*f, neighbour search (periodic_distance2_literal) -- and evaluated
 // with the literal radial formulas.  Runs after the hot loop so that its registers do not
 // overlap the hot loop's.
-template <int MODE, bool FASTEW, bool LJSLOW, bool EWSCALED, bool BKSCALED, int NP, bool DOV = true, bool DOC = true, typename Rec>
+// UNI: 0, or the uniform class of the launch (1: the VdW accumulators are in units of U = 4 eps sigma^6; 2: the Coulomb accumulators in units of
+// q as well).  A pair of this path adds its literal term -- shift included -- divided by the unit and is NOT counted among the
+// pairs whose shift the hot loop applies as count * shift at the end of the tile.
+template <int MODE, bool FASTEW, bool LJSLOW, bool EWSCALED, bool BKSCALED, int NP, int UNI = 0, bool DOV = true, bool DOC = true, typename Rec>
 __device__ __forceinline__ void slow_pairs(const PlanConst* __restrict__ pc, unsigned long long cands, int lane,
                                            double px, double py, double pz,
                                            const Rec* s_rec,
@@ -460,7 +465,9 @@ __device__ __forceinline__ void slow_pairs(const PlanConst* __restrict__ pc, uns
             const int kd = mt & META_KINDMASK;
             double v, p1, p2, p3;
             vdw_terms<LJSLOW, true>(pc->rt.rules, pc->rt.offset[kd], pc->rt.offset[kd + 1], r2, v, p1, p2, p3);
-            if (LJSLOW) {        // the LJ-only hot loop accumulates p1/-6, p2/48, p3/-480 (scaled once per tile at the end)
+            if (UNI) {           // the uniform hot loop accumulates v/U, p1/(-6 U), p2/(48 U), p3/(-480 U)
+                v *= pc->uni_sv; p1 *= pc->uni_s1; p2 *= pc->uni_s2; p3 *= pc->uni_s3;     // (from memory, like bk_s1 below)
+            } else if (LJSLOW) { // the LJ-only hot loop accumulates p1/-6, p2/48, p3/-480 (scaled once per tile at the end)
                 p1 *= -1.0 / 6.0; p2 *= 1.0 / 48.0; p3 *= -1.0 / 480.0;
             }
             if (BKSCALED) {      // the single-Buckingham hot loop accumulates v/C, p1/(6C), p2/(-48C), p3/(480C)
@@ -479,7 +486,9 @@ __device__ __forceinline__ void slow_pairs(const PlanConst* __restrict__ pc, uns
                 ewald_terms_poly(g.alpha, O.w, r2, v, p1, p2, p3);
             else
                 ewald_terms(g.alpha, O.w, r2, v, p1, p2, p3);
-            if (EWSCALED) {      // the r^2-table hot loop accumulates p2/3 and p3/15 (scaled once per tile at the end)
+            if (UNI == 2) {      // uniform charge: v/q, p1/q, p2/(3 q), p3/(15 q)
+                v *= pc->uni_inv_q; p1 *= pc->uni_inv_q; p2 *= pc->uni_qs2; p3 *= pc->uni_qs3;
+            } else if (EWSCALED) {      // the r^2-table hot loop accumulates p2/3 and p3/15 (scaled once per tile at the end)
                 p2 *= 1.0 / 3.0; p3 *= 1.0 / 15.0;
             }
             accum_add(ac, v, p1, p2, p3, dx, dy, dz);
@@ -561,6 +570,13 @@ __device__ __forceinline__ void set_lj_record(CandRecS&, int, Quad) {}
 //           2: every kind present is none / LJ / Buckingham (+ hard spheres that lie inside the
 //              exact-path radius): the per-kind parameters travel with the candidate through LDS
 //              and the pair term uses the shared 1/r (and the table exp for Buckingham)
+//           4: VDWK 1 where every VdW-active image carries the SAME Lennard-Jones record (one adsorbate-site kind, or kinds with
+//              bit-identical rules): sigma^6 and its multiples sit in scalar registers, the candidate record has no VdW part
+//              (48 B), the loop accumulates the channels in units of U = 4 eps sigma^6 and counts the pairs; U and count * shift
+//              are applied once per tile
+//           5: 4, and every VdW-active image carries the same charge q (fused launches on the r^2-indexed tables): the Coulomb
+//              channels of the VdW-active group are accumulated in units of q, the Coulomb-only candidates are staged with
+//              q_i / q, q is applied once per tile
 //   (EWK replaces round 1's FASTEW flag; FASTEW = EWK != 0 below: the erfcx-polynomial slow path is valid)
 //           polynomial, no division); otherwise libm-style erfc/exp
 //   EWK     real-space Ewald term: 0 libm-style erfc / exp; 1 (alpha*cutoff <= ERFCX_XMAX) one table exp + erfcx table,
@@ -579,6 +595,9 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
     constexpr bool EW2 = EWK == 2 && MODE != MODE_VDW;
     constexpr int WG = 64 * culled_nw(MODE, VDWK, EWK, NP);
     constexpr bool BK2 = VDWK == 3 && MODE != MODE_COULOMB;       // one Buckingham class, G0(r^2) tabulated
+    constexpr bool UNI = vdwk_uniform(VDWK) && MODE != MODE_COULOMB;        // one Lennard-Jones record for every VdW-active image
+    constexpr bool UNIQ = VDWK == 5 && MODE == MODE_FUSED && EWK == 2;      // and one charge
+    static_assert(!vdwk_uniform(VDWK) || (NP == 1 && MODE != MODE_COULOMB && (VDWK == 4 || UNIQ)), "uniform variants");
     // One workgroup = CEG_WG/64 waves; each wave owns one tile and its own slice of the staging
     // arrays (waves never touch each other's slice, so no workgroup barrier inside the loops --
     // LDS operations of one wave complete in order).  The function tables are shared.
@@ -729,6 +748,12 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
     const int bk2_off = BK2 ? __builtin_amdgcn_readfirstlane(-pc->bk2_base * (CEG_BK2_STRIDE * 8)) : 0;
     int bk2_stride = CEG_BK2_STRIDE * 8;
     asm volatile("" : "+v"(bk2_stride));
+    // uniform class: sigma^6 and its multiples (hot loop) and 1/q (staging) in scalar registers; U, shift and q are read at the end
+    const double uni_s6 = UNI ? uniform(pc->uni_s6) : 0.0, uni_k1 = UNI ? uniform(pc->uni_k1) : 0.0;
+    const double uni_k2 = UNI ? uniform(pc->uni_k2) : 0.0, uni_k3 = UNI ? uniform(pc->uni_k3) : 0.0;
+    const double uni_inv_q = UNIQ ? uniform(pc->uni_inv_q) : 0.0;
+    int uni_count = 0;                // per lane: regular VdW pairs of the range-tested loop (the shift is applied as count * shift)
+    int uni_count_all = 0;            // wave-uniform: candidates of the interior loop (every lane has the pair)
     const double bk_B = pc->bk_B, bk_nshift = pc->bk_nshift, bk_c1 = pc->bk_c1, bk_c2 = pc->bk_c2, bk_c3 = pc->bk_c3, bk_c4 = pc->bk_c4;
 
     for (int rbase = 0; rbase < nrows; rbase += 64) {
@@ -815,7 +840,7 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
                                 LJM[p] = make_double4(F.p0, F.p1, F.p2, F.shift);
                             }
                         }
-                    } else if (FASTVDW && VDWK != 3 && hasvdw && keep) {
+                    } else if (FASTVDW && VDWK != 3 && !UNI && hasvdw && keep) {
                         const FastVdw F = pc->fastvdw[kd];          // class + parameters of this kind
                         LJ = make_double4(F.p0, F.p1, F.p2, F.shift);
                         vclass = F.cls;
@@ -863,7 +888,8 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
                 const unsigned long long mine = !simple_c ? mask_x : (withv ? (interior ? mask_vi : mask_vb) : (interior ? mask_ni : mask_nb));
                 const int first = !simple_c ? nreg : (withv ? (interior ? 0 : nvi) : (interior ? nv : nni));
                 const int slot = first + __builtin_amdgcn_mbcnt_hi((unsigned)(mine >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mine, 0));
-                s_rec[slot].xyzq = Quad{P.x, P.y, P.z, P.w};
+                // (uniform charge: the Coulomb-only candidates carry q_i / q, so that both groups add into sums in units of q)
+                s_rec[slot].xyzq = Quad{P.x, P.y, P.z, (UNIQ && !withv) ? mul_sc(P.w, uni_inv_q) : P.w};
                 if constexpr (MULTI) {
 #pragma unroll
                     for (int p = 0; p < NP; ++p) set_lj_record(s_rec[slot], p, Quad{LJM[p].x, LJM[p].y, LJM[p].z, LJM[p].w});
@@ -909,7 +935,7 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
                 double rr = 0.0, rinv = 0.0, inv = 0.0;
                 // sqrt(r2) is needed by Buckingham's exp(-B r) and by the erfcx form of the Ewald term; Lennard-Jones and the
                 // r^2-indexed Ewald tables only use 1/r2
-                constexpr bool NEED_SQRT = (VDWK >= 2 && MODE != MODE_COULOMB) || (EWK == 1 && MODE != MODE_VDW);
+                constexpr bool NEED_SQRT = ((VDWK == 2 || VDWK == 3) && MODE != MODE_COULOMB) || (EWK == 1 && MODE != MODE_VDW);
                 if (NEED_SQRT) {
                     fast_sqrt_rsqrt(r2, rr, rinv);
                     inv = rinv * rinv;
@@ -951,7 +977,20 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
                     }
                 } else if constexpr (WITH_VDW) {
                     double v, p1, p2, p3;
-                    if constexpr (VDWK == 3) {
+                    if constexpr (UNI) {
+                        // the LJ branch below in units of U = 4 eps sigma^6, with z = r^-6, a = r^-12 and s = sigma^6 (s, 2 s, 3.5 s, 5.6 s
+                        // from scalar register pairs):
+                        //   v/U = s a - z (the shift: counted, see uni_count),  p1/(-6 U) = (2 s a - z)/r^2,
+                        //   p2/(48 U) = (3.5 s a - z)/r^4,  p3/(-480 U) = (5.6 s a - z)/r^8
+                        const double inv2 = inv * inv;
+                        const double z = inv2 * inv;
+                        const double a = z * z;
+                        v = fms_vsv(a, uni_s6, z);
+                        p1 = fms_vsv(a, uni_k1, z) * inv;
+                        p2 = fms_vsv(a, uni_k2, z) * inv2;
+                        p3 = fms_vsv(a, uni_k3, z) * (inv2 * inv2);
+                        if constexpr (!INTERIOR) ++uni_count;
+                    } else if constexpr (VDWK == 3) {
                         // derivativesGrid, Buckingham branch (src/interactions.jl:447-457) with G0 = A exp(-B r) from the table,
                         // u = G0/r, x6 = C/r^6 and D = (1/r) d/dr:  D G0 = -B u,  D u = -(B G0 + u)/r^2
                         //   v = G0 - x6 - shift,  p1 = -B u + 6 x6/r^2,  p2 = B (B G0 + u)/r^2 - 48 x6/r^4,
@@ -1057,7 +1096,8 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
                         b0 = __builtin_fma(b0, t, a01.x);
                         cc = __builtin_fma(cc, t, a6c0.y);
                         // accumulated as B2/3 and B3/15 (one FMA + one product per step); the factors are applied once per tile
-                        const double qb0 = A.w * b0, qc = A.w * cc;
+                        // (uniform charge: the VdW-active group in units of q; the record of a Coulomb-only candidate holds q_i / q)
+                        const double qb0 = (UNIQ && WITH_VDW) ? b0 : A.w * b0, qc = (UNIQ && WITH_VDW) ? cc : A.w * cc;
                         const double b1 = (qb0 + qc) * inv;
                         const double b2 = fma_vsv(qc, ew_k3, b1) * inv;        // B2/3  = (B1 + (2 alpha^2/3) C)/s
                         const double b3 = fma_vsv(qc, ew_k15, b2) * inv;       // B3/15 = (B2/3 + (4 alpha^4/15) C)/s
@@ -1100,6 +1140,7 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
 #endif
             if (MODE != MODE_COULOMB) {
                 for (int q = 0; q < nvi; ++q) pair_body(q, std::true_type{}, std::true_type{});
+                if (UNI) uni_count_all += nvi;
                 for (int q = nvi; q < nv; ++q) pair_body(q, std::true_type{}, std::false_type{});
             }
             if (MODE != MODE_VDW) {
@@ -1127,10 +1168,10 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
                 if constexpr (MULTI && MODE == MODE_FUSED) {
                     // two passes (the literal distance is redone): the registers of the Lennard-Jones and of the Ewald evaluation are
                     // not needed at the same time beside the three accumulator sets
-                    slow_pairs<MODE, FASTEW, true, EW2, false, NP, true, false>(pc, slow, lane, px, py, pz, s_rec, s_odd, avm, out.probe_idx, ac, smallest_d2);
-                    slow_pairs<MODE, FASTEW, true, EW2, false, NP, false, true>(pc, slow, lane, px, py, pz, s_rec, s_odd, avm, out.probe_idx, ac, smallest_d2);
+                    slow_pairs<MODE, FASTEW, true, EW2, false, NP, 0, true, false>(pc, slow, lane, px, py, pz, s_rec, s_odd, avm, out.probe_idx, ac, smallest_d2);
+                    slow_pairs<MODE, FASTEW, true, EW2, false, NP, 0, false, true>(pc, slow, lane, px, py, pz, s_rec, s_odd, avm, out.probe_idx, ac, smallest_d2);
                 } else
-                    slow_pairs<MODE, FASTEW, VDWK == 1, EW2, VDWK == 3 && MODE != MODE_COULOMB, NP>(pc, slow, lane, px, py, pz, s_rec, s_odd, avm, out.probe_idx, ac, smallest_d2);
+                    slow_pairs<MODE, FASTEW, VDWK == 1 || UNI, EW2, VDWK == 3 && MODE != MODE_COULOMB, NP, UNIQ ? 2 : (UNI ? 1 : 0)>(pc, slow, lane, px, py, pz, s_rec, s_odd, avm, out.probe_idx, ac, smallest_d2);
             }
         }
     }
@@ -1142,6 +1183,17 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
             a.d2xy *= 48.0; a.d2xz *= 48.0; a.d2yz *= 48.0;
             a.d3 *= -480.0;
         }
+    }
+    if (UNI) {      // uniform Lennard-Jones record: U and the derivative factors once per tile, the shift once per counted pair
+        const double e4 = pc->uni_unit;
+        av.v = __builtin_fma(av.v, e4, -((double)(uni_count + uni_count_all) * pc->uni_shift));
+        av.d1x *= -6.0 * e4; av.d1y *= -6.0 * e4; av.d1z *= -6.0 * e4;
+        av.d2xy *= 48.0 * e4; av.d2xz *= 48.0 * e4; av.d2yz *= 48.0 * e4;
+        av.d3 *= -480.0 * e4;
+    }
+    if (UNIQ) {     // uniform charge of the VdW-active images (the factors 3 and 15 of the recurrence follow below)
+        const double q = pc->uni_q;
+        ac.v *= q; ac.d1x *= q; ac.d1y *= q; ac.d1z *= q; ac.d2xy *= q; ac.d2xz *= q; ac.d2yz *= q; ac.d3 *= q;
     }
     if (VDWK == 3 && MODE != MODE_COULOMB) {      // constant factors of the single Buckingham class
         const double C = pc->bk_C;
@@ -1283,7 +1335,7 @@ hipError_t launch_bruteforce(int mode, const Geom& g, const AtomTable& atoms, co
 }
 
 template <int MODE, bool POINTS>
-static hipError_t launch_cull_flags(int vdwk, int ewk, hipStream_t stream, const PlanConst* pc, const Output& out, const Points& pts,
+static hipError_t launch_cull_flags(int vdwk, int ewk, int uni, hipStream_t stream, const PlanConst* pc, const Output& out, const Points& pts,
                                     int tj, int tk, int64_t ntiles)
 {
     // Which k_culled<MODE, POINTS, VDWK, EWK> runs for a plan's (vdwk, ewk).  The plan classifies its rules (ceg_api.hip convert_rules:
@@ -1303,20 +1355,30 @@ static hipError_t launch_cull_flags(int vdwk, int ewk, hipStream_t stream, const
     //   FUSED     (3, 1) (3, 0)         <2, 1> <2, 0>        without the r^2-indexed Ewald tables the Buckingham probe runs as class 2 (per-candidate
     //                                                        parameters, table exp): same terms, other arithmetic, within the suite's tolerance
     //   (ewk == 0 and vdwk == 3 in VDW mode cannot meet: MODE_VDW forces ewk = 1 first.)
+    //   VDW       (1, any), uni >= 1    <4, 1>               one Lennard-Jones record for the whole plan (PlanConst::uni_class): constants deferred
+    //   FUSED     (1, 2), uni 1 | 2     <4, 2> <5, 2>        the same beside the r^2-indexed tables; 5: the charge of the VdW-active images deferred too
+    //   FUSED     (1, 1) (1, 0), uni    <1, 1> <1, 0>        the uniform variants are instantiated beside EWK = 2 only
     // Multi-probe launches (launch_multi_t) are <1, 2, NP> only: Lennard-Jones probes on the r^2-indexed tables.
     if (MODE == MODE_VDW) ewk = 1;
     if (MODE == MODE_COULOMB) vdwk = 1;
     if (ewk == 2 && vdwk == 0) ewk = 1;          // the generic rule interpreter keeps the erfcx variant
     if (vdwk == 3 && MODE == MODE_FUSED && ewk != 2) vdwk = 2;     // the tabulated Buckingham class is instantiated beside EWK = 2 only
+    if (vdwk == 1 && uni > 0 && MODE == MODE_VDW) vdwk = 4;
+    if (vdwk == 1 && uni > 0 && MODE == MODE_FUSED && ewk == 2) vdwk = uni == 2 ? 5 : 4;
     const int nw = culled_nw(MODE, vdwk, ewk);
     const int64_t nblocks = (ntiles + nw - 1) / nw;
     if (nblocks > 0x7fffffffLL) return hipErrorInvalidValue;
     const dim3 grid((unsigned)nblocks), block(64 * nw);
 #define CEG_LAUNCH(V, F) hipLaunchKernelGGL((k_culled<MODE, POINTS, V, F>), grid, block, 0, stream, pc, out, pts, tj, tk, ntiles)
     if (ewk == 2 && MODE != MODE_VDW) {
-        if (vdwk == 1) CEG_LAUNCH(1, 2); else if (vdwk == 3) CEG_LAUNCH(3, 2); else CEG_LAUNCH(2, 2);
+        if (vdwk == 1) CEG_LAUNCH(1, 2); else if (vdwk == 3) CEG_LAUNCH(3, 2);
+        else if (vdwk == 4) { if constexpr (MODE == MODE_FUSED) CEG_LAUNCH(4, 2); }
+        else if (vdwk == 5) { if constexpr (MODE == MODE_FUSED) CEG_LAUNCH(5, 2); }
+        else CEG_LAUNCH(2, 2);
     } else if (ewk) {
-        if (vdwk == 1) CEG_LAUNCH(1, 1); else if (vdwk == 2) CEG_LAUNCH(2, 1); else if (vdwk == 3) CEG_LAUNCH(3, 1); else CEG_LAUNCH(0, 1);
+        if (vdwk == 1) CEG_LAUNCH(1, 1); else if (vdwk == 2) CEG_LAUNCH(2, 1); else if (vdwk == 3) CEG_LAUNCH(3, 1);
+        else if (vdwk == 4) { if constexpr (MODE == MODE_VDW) CEG_LAUNCH(4, 1); }
+        else CEG_LAUNCH(0, 1);
     } else {
         if (vdwk == 1) CEG_LAUNCH(1, 0); else if (vdwk == 2) CEG_LAUNCH(2, 0); else if (vdwk == 3) CEG_LAUNCH(2, 0); else CEG_LAUNCH(0, 0);
     }
@@ -1325,14 +1387,14 @@ static hipError_t launch_cull_flags(int vdwk, int ewk, hipStream_t stream, const
 }
 
 template <bool POINTS>
-static hipError_t launch_cull_t(int mode, const PlanConst* pc, int vdwk, int ewk, const Output& out,
+static hipError_t launch_cull_t(int mode, const PlanConst* pc, int vdwk, int ewk, int uni, const Output& out,
                                 const Points& pts, int64_t ntiles, int tj, int tk, hipStream_t stream)
 {
     if (ntiles <= 0) return hipSuccess;
     switch (mode) {
-    case MODE_VDW: return launch_cull_flags<MODE_VDW, POINTS>(vdwk, ewk, stream, pc, out, pts, tj, tk, ntiles);
-    case MODE_COULOMB: return launch_cull_flags<MODE_COULOMB, POINTS>(vdwk, ewk, stream, pc, out, pts, tj, tk, ntiles);
-    default: return launch_cull_flags<MODE_FUSED, POINTS>(vdwk, ewk, stream, pc, out, pts, tj, tk, ntiles);
+    case MODE_VDW: return launch_cull_flags<MODE_VDW, POINTS>(vdwk, ewk, uni, stream, pc, out, pts, tj, tk, ntiles);
+    case MODE_COULOMB: return launch_cull_flags<MODE_COULOMB, POINTS>(vdwk, ewk, uni, stream, pc, out, pts, tj, tk, ntiles);
+    default: return launch_cull_flags<MODE_FUSED, POINTS>(vdwk, ewk, uni, stream, pc, out, pts, tj, tk, ntiles);
     }
 }
 
@@ -1367,12 +1429,12 @@ hipError_t launch_culled_multi(int mode, int np, const PlanConst* d_pc, const Ge
 }
 
 hipError_t launch_culled(int mode, const PlanConst* d_pc, const Geom& g, int vdwk, int ewk,
-                         const Output& out, const Points& pts, hipStream_t stream)
+                         const Output& out, const Points& pts, hipStream_t stream, int uni)
 {
-    if (pts.xyz) return launch_cull_t<true>(mode, d_pc, vdwk, ewk, out, pts, (pts.n + 63) / 64, 1, 1, stream);
+    if (pts.xyz) return launch_cull_t<true>(mode, d_pc, vdwk, ewk, uni, out, pts, (pts.n + 63) / 64, 1, 1, stream);
     const int ni = out.i_end - out.i_begin;
     const int ti = (ni + 3) / 4, tj = (g.dims[1] + 1 + 3) / 4, tk = (g.dims[2] + 1 + 3) / 4;
-    return launch_cull_t<false>(mode, d_pc, vdwk, ewk, out, pts, (int64_t)ti * tj * tk, tj, tk, stream);
+    return launch_cull_t<false>(mode, d_pc, vdwk, ewk, uni, out, pts, (int64_t)ti * tj * tk, tj, tk, stream);
 }
 
 }  // namespace ceg

@@ -222,6 +222,18 @@ CEG_API int ceg_image_cache_stats(int64_t* hits, int64_t* misses, int64_t* entri
  * `mat` is >= 2*cutoff, which ProbeSystem guarantees, src/probes.jl:24), else 0. */
 CEG_API int ceg_plan_can_cull(const ceg_plan_t* plan);
 
+/* Uniform class of the plan's VdW-active atoms (of probe 0 on a multi-probe plan), what ceg_plan_build_vdw / _fused and
+ * ceg_plan_eval_points run with: 0 per-candidate Lennard-Jones records; 1 every kind that is present and has a rule with the probe
+ * carries ONE bit-identical Lennard-Jones rule (4 eps, sigma, shift are applied once per tile of grid points); 2 as 1, and every
+ * atom of those kinds carries one bit-identical charge (applied once per tile in the fused build).  CEG_HIP_UNIFORM_CLASS=0 | 1 in
+ * the environment at plan creation caps it.  Results agree with class 0 to rounding (the constants multiply a sum, not each term). */
+CEG_API int ceg_plan_uniform_class(const ceg_plan_t* plan);
+/* The same classification on a caller's tables, without a device (diagnostics, CPU tests): atomkind 1-based as in
+ * ceg_plan_create, charge may be NULL.  Returns 0 / 1 / 2 or a negative error; constants (may be NULL) receives
+ * {4 eps, sigma^6, shift, q}, zeros where not applicable. */
+CEG_API int ceg_uniform_class(const int64_t* atomkind, const double* charge, int64_t natoms, const ceg_rule_t* rules,
+                              const int32_t* rule_offset, int32_t nkinds, double cutoff2, double constants[4]);
+
 /* number of lattice images kept by the culled algorithm (0 before first use) */
 CEG_API int64_t ceg_plan_num_images(const ceg_plan_t* plan);
 /* The plan's lattice-image list copied to the host (diagnostics / tests: the list is built on the device since round 4 and must be
