@@ -7,7 +7,11 @@ through the suite's compare functions at their present tolerances, and with the 
 (6e-8 relative), which ``compare_raw``'s 1e-9 is not meant for; the FP64 sums at the grid's own points go through ``compare_raw``.
 
 The fixture's two oxygen kinds carry different charges (Oz -1.1427, Oa -0.9354): the plan as it comes is class 1.  Class 2 is
-exercised with the Oa charges set to Oz's."""
+exercised with the Oa charges set to Oz's.
+
+Other cells (wrap-boundary candidates, the stale-vector range, the ortho shortcut), other cutoffs, plans without the r^2-indexed
+Ewald tables, unshifted records and records / charges of extreme size: ``tests/test_gpu_uniform_class_cells.py`` (cases from
+``tests/uniform_cases.py``), which imports ``_switch`` / ``_build`` / ``_bits`` from here."""
 import copy
 import os
 from contextlib import contextmanager

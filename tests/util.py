@@ -10,10 +10,13 @@ from ceg_hip.hostmirror.probes import ProbeSystem
 from ceg_hip.workloads import grid_setup_with_dims
 
 
-def tiny_forcefield(cutoff: float = 12.0, hs_radius: float = 1.5, generic: bool = False) -> ForceField:
+def tiny_forcefield(cutoff: float = 12.0, hs_radius: float = 1.5, generic: bool = False, uniform=None) -> ForceField:
     """kinds: 1 LJ-shifted, 2 Buckingham+HardSphere(hs_radius), 3 none, 4 LJ (other params) -- or,
     with generic=True, a LJ+Buckingham sum that has no fast class in the kernel; probe = 5 (P).  Probes 6 (Q) and 7 (R) are
-    Lennard-Jones-only against all four kinds (Q: none against C, LJ + CoulombEwaldDirect against D; R: none against B)."""
+    Lennard-Jones-only against all four kinds (Q: none against C, LJ + CoulombEwaldDirect against D; R: none against B).
+    uniform=(eps, sigma, shifted): P's rule with kinds A AND D becomes one Lennard-Jones record (shift = V(cutoff) when `shifted`,
+    else 0.0) -- with atoms of kinds A, D, C only, a plan the kernel classes as uniform (one record on two present kinds, one
+    present kind without a rule, and the absent kind B with another rule).  None: the force field above, unchanged."""
     lj = InteractionRule(FF.LennardJones, [107.69, 3.15], 0.0, False)
     lj = InteractionRule(FF.LennardJones, [107.69, 3.15], lj(cutoff), False)
     buck = InteractionRuleSum([InteractionRule(FF.HardSphere, [hs_radius, 0.0]), InteractionRule(FF.Buckingham, [5.581e7, 3.985, 9.167e5]),
@@ -22,6 +25,12 @@ def tiny_forcefield(cutoff: float = 12.0, hs_radius: float = 1.5, generic: bool 
     lj2 = InteractionRule(FF.LennardJones, [262.0, 2.396])
     if generic:
         lj2 = InteractionRuleSum([InteractionRule(FF.LennardJones, [40.0, 2.9]), InteractionRule(FF.Buckingham, [3.0e6, 3.2, 2.0e4])])
+    if uniform is not None:
+        eps, sigma, shifted = uniform
+        uni = InteractionRule(FF.LennardJones, [float(eps), float(sigma)], 0.0)
+        if shifted:
+            uni = InteractionRule(FF.LennardJones, [float(eps), float(sigma)], uni(cutoff))
+        lj = lj2 = uni
     n = 7
     inter = [[none] * n for _ in range(n)]
     for k, r in enumerate((lj, buck, none, lj2)):
