@@ -61,6 +61,10 @@ GCMC_STATS_DTYPE = np.dtype([('trials', '<i8', (7,)), ('accepted', '<i8', (7,)),
 GCMC_RECORD_DTYPE = np.dtype([('species', '<i4'), ('molecule', '<i4'), ('kind', '<i4'), ('accepted', '<i4'), ('n_species', '<i4'),
                               ('flags', '<i4'), ('u', '<f8'), ('tc', '<f8'), ('rows', '<f8', (2, 4)), ('positions', '<f8', (16, 3))], align=True)
 assert (C.sizeof(GcmcParams), GCMC_SPECIES_DTYPE.itemsize, GCMC_STATS_DTYPE.itemsize, GCMC_RECORD_DTYPE.itemsize) == (88, 584, 192, 488)
+# ``ceg_mc_block_t`` (``mask``: the address of a uint8 array in host memory, 0 = empty; ``mat`` / ``invmat`` column-major)
+MC_BLOCK_DTYPE = np.dtype([('mask', '<u8'), ('dims', '<i4', (3,)), ('_pad', '<i4'), ('size', '<f8', (3,)), ('shift', '<f8', (3,)),
+                           ('offset', '<f8', (3,)), ('mat', '<f8', (9,)), ('invmat', '<f8', (9,))], align=True)
+assert MC_BLOCK_DTYPE.itemsize == 240
 
 c_double_p = C.POINTER(C.c_double)
 c_float_p = C.POINTER(C.c_float)
@@ -196,6 +200,8 @@ PROTOTYPES = {
     "ceg_mc_group_accept": (C.c_int, [C.c_void_p, c_int32_p, c_double_p]),
     "ceg_mc_group_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ceg_mc_group_sweep_gcmc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ceg_mc_group_set_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "ceg_mc_group_block_counts": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
     "ceg_energy_grid": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, c_double_p, c_double_p, C.c_int32,
                                   c_double_p, C.c_int32, c_double_p, c_int32_p,
                                   C.c_void_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p,

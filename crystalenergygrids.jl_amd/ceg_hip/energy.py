@@ -575,9 +575,50 @@ class DeviceMonteCarloGroup:
         self._h = g
         for c in self.chains:
             c._group = self
+        self._blocks = None           # what set_blocks installed: (species blocks, atom blocks)
 
     def __repr__(self):
         return f"DeviceMonteCarloGroup(k={len(self.chains)})"
+
+    @staticmethod
+    def _carries_blocks(mc) -> bool:
+        return any(b is not None and not b.empty for b in list(getattr(mc, "speciesblocks", None) or []) + list(getattr(mc, "atomblocks", None) or []))
+
+    def set_blocks(self, species_blocks, atom_blocks=None) -> None:
+        """``ceg_mc_group_set_blocks``: the block pockets that :meth:`sweep_gcmc` tests (``inblockpocket`` and the retry loop of
+        ``choose_step!``, simulation.jl:271-326).  ``species_blocks``: one :class:`ceg_hip.grids.BlockFile` (or None: empty) per
+        species; ``atom_blocks``: one per force-field index (``mc.atomblocks``: entry ``ix - 1`` for the atoms of ff index ``ix``), looked
+        up at ``point + delta / 2`` (montecarlo.jl:636), or None for no atom blocks.  The masks are copied to the device once and stay
+        until they are replaced or cleared with ``set_blocks(None)``."""
+        species_blocks, atom_blocks = list(species_blocks or []), list(atom_blocks or [])
+        table = np.zeros(len(species_blocks) + len(atom_blocks), dtype=_abi.MC_BLOCK_DTYPE)
+        keep = []
+        for t, b, half in zip(table, species_blocks + atom_blocks, [False] * len(species_blocks) + [True] * len(atom_blocks)):
+            if b is None:             # (no grid for this ff index: never blocked; a geometry that passes the checks)
+                t["dims"], t["size"], t["mat"], t["invmat"] = 1, 1.0, np.eye(3).reshape(-1), np.eye(3).reshape(-1)
+                continue
+            cs = b.csetup
+            t["dims"], t["size"], t["shift"] = cs.dims, cs.size, cs.shift
+            t["mat"], t["invmat"] = np.asarray(cs.cell.mat, dtype=np.float64).T.reshape(-1), np.asarray(cs.cell.invmat, dtype=np.float64).T.reshape(-1)
+            if half:
+                t["offset"] = (np.asarray(cs.size, dtype=np.float64) / np.asarray(cs.dims, dtype=np.float64)) / 2.0
+            if not b.empty:
+                mask = np.ascontiguousarray(b.block, dtype=np.uint8)
+                if mask.shape != tuple(int(d) + 1 for d in cs.dims):
+                    raise ValueError(f"a block mask of shape {mask.shape} on a lattice of {tuple(int(d) + 1 for d in cs.dims)} points")
+                keep.append(mask)
+                t["mask"] = mask.ctypes.data
+        ns = len(species_blocks)
+        _abi.check(self._lib, self._lib.ceg_mc_group_set_blocks(self._h, table[:ns].ctypes.data if ns else None, ns,
+                                                                table[ns:].ctypes.data if atom_blocks else None, len(atom_blocks)))
+        self._blocks = (species_blocks, atom_blocks) if len(table) else None
+
+    def block_counts(self):
+        """``ceg_mc_group_block_counts``: per chain, the pocket-blocked steps of the last :meth:`sweep_gcmc` and the sum of the attempt
+        indices its proposals used -> (int64[K], int64[K])."""
+        pocket, attempts = np.zeros(len(self.chains), dtype=np.int64), np.zeros(len(self.chains), dtype=np.int64)
+        _abi.check(self._lib, self._lib.ceg_mc_group_block_counts(self._h, _abi.i64ptr(pocket), _abi.i64ptr(attempts)))
+        return pocket, attempts
 
     def trial(self, moves):
         """One trial per chain: ``moves[c]`` is ``("move", idx, positions[n, m, 3])`` (rows: n + 1, row 0 where the molecule is now;
@@ -671,8 +712,9 @@ class DeviceMonteCarloGroup:
             raise ValueError(f"stream_id: one per chain ({k})")
         beads = []
         for c, chain in enumerate(self.chains):
-            if any(len(b) for b in (getattr(chain.mc, "speciesblocks", None) or [])):
-                raise NotImplementedError("sweeps do not test block pockets (inblockpocket of choose_step!): this setup has some")
+            if self._carries_blocks(chain.mc):
+                raise NotImplementedError("plain sweeps do not test block pockets (inblockpocket of choose_step!), and this setup has some: "
+                                          "sweep_gcmc does")
             per_kind = mcrng.default_beads(chain.mc) if bead is None else list(bead[c])
             by_device = {d: per_kind[i] for i, kind in enumerate(chain._slot) for d in kind}
             beads += [by_device[d] for d in sorted(by_device)]
@@ -731,6 +773,10 @@ class DeviceMonteCarloGroup:
         ``moves[i]`` / ``phiPV_div_k[i]`` per species (kind of ``mc``), or a ready ``species`` table (:meth:`gcmc_species`);
         ``max_molecules``: one value or one per chain; the other arguments as :meth:`sweep`.
 
+        Block pockets: the masks of :meth:`set_blocks`, or else ``mc.speciesblocks`` / ``mc.atomblocks`` of the first chain's setup where
+        it carries any, are tested as ``choose_step!`` tests them (``inblockpocket``, the 1000-attempt retry loop); :meth:`block_counts`
+        reports the pocket-blocked steps and the attempts.
+
         -> stats (``_abi.GCMC_STATS_DTYPE`` [K]) and with ``log=True`` the log [nsteps, K] (``_abi.GCMC_RECORD_DTYPE``).  Afterwards
         every chain's ``mc.positions`` holds the final state, species by species in device molecule order, and its (kind, index)
         addressing follows it; ``mc.tailcorrection`` and ``mc.sums`` are NOT updated.  ``positions=False`` skips the read-back of
@@ -754,9 +800,10 @@ class DeviceMonteCarloGroup:
             raise ValueError(f"stream_id: one per chain ({k})")
         table = np.ascontiguousarray(species if species is not None else self.gcmc_species(moves, phiPV_div_k, self_reciprocal, bead))
         given = []
+        mc0 = self.chains[0].mc
+        if self._blocks is None and self._carries_blocks(mc0):          # the setup's own masks, unless the caller installed some
+            self.set_blocks(mc0.speciesblocks or [None] * len(mc0.ffidx), mc0.atomblocks)
         for chain in self.chains:
-            if any(len(b) for b in (getattr(chain.mc, "speciesblocks", None) or [])):
-                raise NotImplementedError("sweeps do not test block pockets (inblockpocket of choose_step!): this setup has some")
             by_device = {d: i for i, kind in enumerate(chain._slot) for d in kind}
             given += [by_device[d] for d in sorted(by_device)]
         given = np.ascontiguousarray(given if given else [0], dtype=np.int32)

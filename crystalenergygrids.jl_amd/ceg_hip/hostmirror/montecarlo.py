@@ -125,6 +125,8 @@ class MonteCarloSetup:
     tail_cross: Optional[np.ndarray] = None
     sums: Optional[np.ndarray] = None     # complex[num_kvecs, 1 + nmolecules], set by baseline_energy
     models: List[np.ndarray] = field(default_factory=list)   # per kind: atom positions of the model molecule (mc.models)
+    speciesblocks: list = field(default_factory=list)        # per kind: grids.BlockFile of its .block file (mc.speciesblocks); empty: none
+    atomblocks: list = field(default_factory=list)           # per ff index - 1: BlockFile(grids[ix]) (mc.atomblocks); empty: none
 
     # ---- flat views
     def molecules(self):
@@ -332,11 +334,15 @@ def remove_molecule(mc: MonteCarloSetup, idx: Tuple[int, int]) -> int:
     return last
 
 
-def setup_montecarlo(framework, pff, systems: Sequence[RASPASystem], *, blockfiles=None, gridstep: float = 0.15,
+def setup_montecarlo(framework, pff, systems: Sequence[RASPASystem], *, blockfiles=None, atomblocks: bool = False, gridstep: float = 0.15,
                      supercell=None, new: bool = False, cutoff: float = 12.0, ngpus: int = 1) -> MonteCarloSetup:
     """montecarlo.jl:266-323 + :70-216 for explicit rigid molecules (one entry of ``systems`` per
     molecule; entries with the same atom symbols form one kind).  ``framework`` is a RASPA name, or a
-    3x3 matrix for an empty cell.  Blocking spheres do not enter any energy and are not parsed here."""
+    3x3 matrix for an empty cell.  Block pockets enter no energy; they steer the proposals of the GCMC sweeps
+    (``DeviceMonteCarloGroup.sweep_gcmc``): ``blockfiles[i]`` is the path of the ``.block`` file of kind ``i`` (None or False: none),
+    parsed into ``speciesblocks`` on the lattice of the grids (montecarlo.jl:107-111); ``atomblocks=True`` fills ``atomblocks`` with
+    ``BlockFile(grids[ix])`` of every VdW grid (montecarlo.jl:181-186; the scan runs on the GPU).  Both are off by default: a setup
+    without them is swept as before."""
     is_void = isinstance(framework, np.ndarray)
     ff = _ff(pff, cutoff=cutoff)
     if is_void:
@@ -394,5 +400,15 @@ def setup_montecarlo(framework, pff, systems: Sequence[RASPASystem], *, blockfil
         num_framework_atoms[ff.sdict[get_atom_name(sym)] - 1] += PI
     lam = 2 * math.pi / float(np.linalg.det(cellmat))
     value, tframework, tcross = tail_correction(ff, ffidx, num_framework_atoms, lam, [len(p) for p in positions])
-    return MonteCarloSetup(ff, cellmat, np.linalg.inv(cellmat), ffidx, charges, positions, ewald, coulomb, grids, value,
-                           tframework, tcross, models=[np.array(m.position, dtype=np.float64).reshape(-1, 3) for m in models])
+    mc = MonteCarloSetup(ff, cellmat, np.linalg.inv(cellmat), ffidx, charges, positions, ewald, coulomb, grids, value,
+                         tframework, tcross, models=[np.array(m.position, dtype=np.float64).reshape(-1, 3) for m in models])
+    if blockfiles is not None and any(blockfiles):
+        from ..grids import BlockFile, parse_blockfile
+        if len(blockfiles) != len(kinds):
+            raise ValueError(f"blockfiles: one entry per kind ({len(kinds)})")
+        cset = next((g.csetup for g in grids if g is not None), None) or GridCoordinatesSetup.from_cell(mat, gridstep)
+        mc.speciesblocks = [parse_blockfile(f, cset) if f else BlockFile(cset) for f in blockfiles]
+    if atomblocks and grids:
+        from ..grids import blockfile_from_grid_gpu
+        mc.atomblocks = [None if g is None else blockfile_from_grid_gpu(g) for g in grids]
+    return mc

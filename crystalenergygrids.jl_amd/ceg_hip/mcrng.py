@@ -19,6 +19,10 @@ Purposes for stream ``c`` at the absolute step ``s`` (key = seed low / high word
                  deletion iff ``U(w2, w3) < 0.5``
   6, 7, 8 random_* geometry  ``r = mat (U3 - 0.5)`` with ``U3`` from (w0, w1), (w2, w3) of purpose 6 and (w0, w1) of purpose 7
                  (mcmoves.jl:143); ``theta = pi (2 U(w2, w3) - 1)`` of purpose 7, axis ``min(floor(3 U(w0, w1)), 2)`` of purpose 8
+
+Block pockets (``ceg_mc_group_set_blocks``; ``propose_gcmc(..., blocks=...)``): attempt ``t = 0..999`` of a proposal that ``choose_step!``
+retries (simulation.jl:299-320) draws purposes 6-8 with counter word 3 = ``purpose | (t << 8)`` (:func:`draw_attempt`); attempt 0 is the
+plain purpose.  :func:`block_lookup` is ``BlockFile`` getindex (coordinates.jl:58-66,97-101) in the device's operation order.
 """
 from __future__ import annotations
 
@@ -59,6 +63,58 @@ def draw(seed: int, step: int, stream_id: int, purpose: int):
     """The block of (seed, absolute step, stream, purpose)."""
     seed, step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF
     return philox4x32_10((step & _MASK, step >> 32, stream_id, purpose), (seed & _MASK, seed >> 32))
+
+
+ATTEMPTS = 1000           # the retry loop of choose_step! (simulation.jl:299)
+
+
+def draw_attempt(seed: int, step: int, stream_id: int, purpose: int, attempt: int):
+    """The block of attempt ``attempt`` of a retried proposal: purposes 6-8 with counter word 3 = ``purpose | (attempt << 8)``."""
+    if not (GCMC_RANDOM_A <= purpose <= GCMC_RANDOM_C and 0 <= attempt < ATTEMPTS):
+        raise ValueError("only purposes 6-8 are retried, 1000 times at the most")
+    return draw(seed, step, stream_id, purpose | (attempt << 8))
+
+
+def block_lookup(mask, dims, size, shift, offset, mat, invmat, point) -> bool:
+    """``BlockFile`` getindex at ``point + offset`` (coordinates.jl:58-66,97-101), every operation in the order of the device:
+    ``wrap_atom`` with the products summed left to right, ``(q - shift) * dims / size + 1``, round to nearest even, the index clamped
+    to the mask for memory safety only.  ``mask``: [dims[0]+1, dims[1]+1, dims[2]+1] (None: an empty block, never blocked);
+    ``mat`` / ``invmat``: the block's cell with the vectors as columns."""
+    if mask is None:
+        return False
+    M, I = np.asarray(mat, dtype=np.float64), np.asarray(invmat, dtype=np.float64)
+    q = [float(point[c]) + float(offset[c]) for c in range(3)]
+    abc = [(float(I[r, 0]) * q[0] + float(I[r, 1]) * q[1]) + float(I[r, 2]) * q[2] for r in range(3)]
+    abc = [x - math.floor(x) for x in abc]
+    w = [(float(M[r, 0]) * abc[0] + float(M[r, 1]) * abc[1]) + float(M[r, 2]) * abc[2] for r in range(3)]
+    idx = []
+    for c in range(3):
+        sh = (w[c] - float(shift[c])) * float(int(dims[c])) / float(size[c]) + 1.0
+        idx.append(min(max(int(np.rint(sh)) - 1, 0), int(dims[c])))
+    return bool(mask[idx[0], idx[1], idx[2]])
+
+
+class Blocks:
+    """The masks of a chain group as :func:`propose_gcmc` asks for them: ``species[i]`` and ``atoms[kind]`` are objects with ``block``
+    (bool[nx, ny, nz] or None) and ``csetup`` (dims, size, shift, cell.mat, cell.invmat) such as ``grids.BlockFile``, or None; ``atoms``
+    empty: no atom blocks.  Atom blocks are looked up at ``point + (size / dims) / 2`` (montecarlo.jl:636)."""
+
+    def __init__(self, species, atoms=()):
+        self.species, self.atoms = list(species), list(atoms or ())
+
+    @staticmethod
+    def _holds(b, point, half: bool) -> bool:
+        if b is None or b.block is None or not b.block.any():
+            return False
+        cs = b.csetup
+        offset = [(float(cs.size[c]) / float(int(cs.dims[c]))) / 2.0 if half else 0.0 for c in range(3)]
+        return block_lookup(b.block, cs.dims, cs.size, cs.shift, offset, cs.cell.mat, cs.cell.invmat, point)
+
+    def species_blocked(self, i: int, point) -> bool:
+        return self._holds(self.species[i], point, False)
+
+    def atom_blocked(self, kind: int, point) -> bool:
+        return bool(self.atoms) and self._holds(self.atoms[kind], point, True)
 
 
 def rotation_matrix(theta: float, axis: int) -> np.ndarray:
@@ -196,6 +252,7 @@ class GcmcSpecies(NamedTuple):
     model: np.ndarray         # float64[m, 3], mc.models[i]
     bead: int                 # 0-based atom the species rotates about
     moves: MoveTable
+    kinds: tuple = ()         # 0-based atom kinds (ff index - 1): what the atom blocks are indexed by
 
 
 class GcmcProposal(NamedTuple):
@@ -207,21 +264,49 @@ class GcmcProposal(NamedTuple):
     u: float
     spent: bool               # no molecule of the species and not an insertion (simulation.jl:282)
     capacity: bool            # an insertion at max_molecules: counted, not evaluated, rejected
+    attempt: int = 0          # with blocks: the attempt the proposal comes from (999 when the retry loop ran out)
+    pocket: bool = False      # with blocks: the step is pocket-blocked (positions: the proposal tested, empty when the loop ran out)
 
 
-def random_translation_vector(seed: int, step: int, stream_id: int, mat) -> np.ndarray:
+def random_translation_vector(seed: int, step: int, stream_id: int, mat, attempt: int = 0) -> np.ndarray:
     """``mat * (rand(SVector{3}) .- 0.5)`` (mcmoves.jl:143), ``mat`` with the cell vectors as columns"""
-    g, h = draw(seed, step, stream_id, GCMC_RANDOM_A), draw(seed, step, stream_id, GCMC_RANDOM_B)
+    g, h = draw_attempt(seed, step, stream_id, GCMC_RANDOM_A, attempt), draw_attempt(seed, step, stream_id, GCMC_RANDOM_B, attempt)
     a, b, c = uniform(g[0], g[1]) - 0.5, uniform(g[2], g[3]) - 0.5, uniform(h[0], h[1]) - 0.5
     M = np.asarray(mat, dtype=np.float64)
     return np.array([(float(M[d, 0]) * a + float(M[d, 1]) * b) + float(M[d, 2]) * c for d in range(3)])
 
 
+def random_placement(seed: int, step: int, stream_id: int, kind: int, pos, bead: int, mat, attempt: int = 0) -> np.ndarray:
+    """Attempt ``attempt`` of the placement a random_* kind or an insertion proposes for a molecule (an insertion: the model) at ``pos``:
+    random_translation by ``mat (U3 - 0.5)`` (not for random_rotation), then, unless the kind is random_translation or the molecule
+    has one atom, the rotation by ``pi (2U - 1)`` about atom ``bead`` (simulation.jl:294-305)."""
+    new = np.array(pos, dtype=np.float64).reshape(-1, 3)
+    if kind != RANDOM_ROTATION:
+        new = new + random_translation_vector(seed, step, stream_id, mat, attempt)
+    if kind != RANDOM_TRANSLATION and len(new) > 1:
+        h, k = draw_attempt(seed, step, stream_id, GCMC_RANDOM_B, attempt), draw_attempt(seed, step, stream_id, GCMC_RANDOM_C, attempt)
+        theta = math.pi * (2.0 * uniform(h[2], h[3]) - 1.0)
+        axis = min(int(math.floor(3.0 * uniform(k[0], k[1]))), 2)
+        ref = new[int(bead)]
+        new = ref + (new - ref) @ rotation_matrix(theta, axis).T
+    return new
+
+
+def in_block_pocket(blocks, i: int, kinds, positions) -> bool:
+    """``inblockpocket`` (montecarlo.jl:631-640): some atom in the species block of ``i`` or in the atom block of its kind"""
+    return any(blocks.species_blocked(i, p) or blocks.atom_blocked(int(kinds[a]), p) for a, p in enumerate(positions))
+
+
 def propose_gcmc(seed: int, step: int, stream_id: int, species_of_molecules, positions_of_molecules, species, mat, dmax: float,
-                 thetamax: float, max_molecules: int = None) -> GcmcProposal:
+                 thetamax: float, max_molecules: int = None, blocks=None) -> GcmcProposal:
     """What stream ``stream_id`` proposes at the absolute step ``step`` of ``ceg_mc_group_sweep_gcmc`` for a chain whose molecule
     ``d`` (device molecule order) is of species ``species_of_molecules[d]`` and sits at ``positions_of_molecules[d]``.
-    ``species``: one :class:`GcmcSpecies` per species; ``mat``: the MC cell (columns); ``thetamax`` in radians."""
+    ``species``: one :class:`GcmcSpecies` per species; ``mat``: the MC cell (columns); ``thetamax`` in radians.
+
+    ``blocks`` (an object with ``species_blocked(i, point)`` and ``atom_blocked(kind, point)``, e.g. :class:`Blocks`; the species need
+    their ``kinds``): the block-pocket rules of ``choose_step!`` (simulation.jl:271-326).  Translation, rotation and random_rotation
+    are tested once; random_translation and random_reinsertion take the first of 1000 attempts outside every pocket; an insertion takes
+    the first attempt whose bead lies outside the species block and is pocket-blocked if the whole placement is not."""
     u = acceptance_draw(seed, step, stream_id)
     ns = len(species)
     w = draw(seed, step, stream_id, GCMC_SELECT)
@@ -245,29 +330,34 @@ def propose_gcmc(seed: int, step: int, stream_id: int, species_of_molecules, pos
         pos = np.asarray(positions_of_molecules[mol], dtype=np.float64).reshape(-1, 3)
         if kind == SWAP_DELETION:
             return GcmcProposal(i, kind, mol, n_i, none, u, False, False)
+
+    def tested(new):          # a kind that is not retried: the one proposal, pocket-blocked or not
+        return GcmcProposal(i, kind, mol, n_i, new, u, False, False, 0, blocks is not None and in_block_pocket(blocks, i, sp.kinds, new))
+
     if kind in (TRANSLATION, ROTATION):
         if kind == ROTATION and len(pos) == 1:
-            return GcmcProposal(i, kind, mol, n_i, pos.copy(), u, False, False)
+            return tested(pos.copy())
         g = draw(seed, step, stream_id, GEOMETRY_A)
         if kind == TRANSLATION:
             h = draw(seed, step, stream_id, GEOMETRY_B)
             r = np.array([(2.0 * uniform(g[0], g[1]) - 1.0) * dmax, (2.0 * uniform(g[2], g[3]) - 1.0) * dmax,
                           (2.0 * uniform(h[0], h[1]) - 1.0) * dmax])
-            return GcmcProposal(i, kind, mol, n_i, pos + r, u, False, False)
+            return tested(pos + r)
         theta = thetamax * (2.0 * uniform(g[0], g[1]) - 1.0)
         axis = min(int(math.floor(3.0 * uniform(g[2], g[3]))), 2)
         ref = pos[int(sp.bead)]
-        return GcmcProposal(i, kind, mol, n_i, ref + (pos - ref) @ rotation_matrix(theta, axis).T, u, False, False)
-    new = pos.copy()
-    if kind != RANDOM_ROTATION:
-        new = new + random_translation_vector(seed, step, stream_id, mat)
-    if kind != RANDOM_TRANSLATION and len(new) > 1:
-        h, k = draw(seed, step, stream_id, GCMC_RANDOM_B), draw(seed, step, stream_id, GCMC_RANDOM_C)
-        theta = math.pi * (2.0 * uniform(h[2], h[3]) - 1.0)
-        axis = min(int(math.floor(3.0 * uniform(k[0], k[1]))), 2)
-        ref = new[int(sp.bead)]
-        new = ref + (new - ref) @ rotation_matrix(theta, axis).T
-    return GcmcProposal(i, kind, mol, n_i, new, u, False, False)
+        return tested(ref + (pos - ref) @ rotation_matrix(theta, axis).T)
+
+    if blocks is None or kind == RANDOM_ROTATION:
+        return tested(random_placement(seed, step, stream_id, kind, pos, sp.bead, mat))
+    for attempt in range(ATTEMPTS):
+        new = random_placement(seed, step, stream_id, kind, pos, sp.bead, mat, attempt)
+        if kind == SWAP_INSERTION:
+            if not blocks.species_blocked(i, new[int(sp.bead)]):
+                return GcmcProposal(i, kind, mol, n_i, new, u, False, False, attempt, in_block_pocket(blocks, i, sp.kinds, new))
+        elif not in_block_pocket(blocks, i, sp.kinds, new):
+            return GcmcProposal(i, kind, mol, n_i, new, u, False, False, attempt, False)
+    return GcmcProposal(i, kind, mol, n_i, none, u, False, False, ATTEMPTS - 1, True)
 
 
 def tail_change(tail_framework: float, tail_cross_row, counts, i: int, num: int) -> float:

@@ -2,6 +2,7 @@
 //   ceg_mc_group_trial / _accept   one step of K chains in one launch per class: the bodies of k_mc_trial / k_mc_accept (ceg_mc_state.h)
 //   ceg_mc_group_sweep             S steps of translations and rotations: proposal, Metropolis rule and update on the device
 //   ceg_mc_group_sweep_gcmc        the same with all six move kinds, swaps included, and the molecule table owned by the device
+//   ceg_mc_group_set_blocks        block pockets: inblockpocket and the retry loop of choose_step!, resolved inside the GCMC trial launch
 // The two sweeps have their own kernels, per-chain parameters and read-back, and share one host driver (run_sweep).
 #include "ceg_mc_state.h"
 
@@ -303,19 +304,35 @@ __device__ __forceinline__ McGcmcMove gcmc_select(const McGcmcChain& P, const ce
     return mv;
 }
 
-// coordinate `comp` of atom `a` of the proposal: kinds 0 / 1 from sweep_coordinate, the random_* kinds and the insertion from
-// src/mcmoves.jl:139-164 with the MC cell / 180 degrees (simulation.jl:294-305)
-__device__ __forceinline__ double gcmc_coordinate(const McView& v, const McGcmcChain& P, const ceg_mc_gcmc_species_t& S, const McGcmcMove& mv, const int2 mj,
-                                                  uint64_t seed, uint64_t step, int a, int comp)
+// the placement of one atom by the random_* kinds and the insertion (src/mcmoves.jl:139-164 with the MC cell / 180 degrees,
+// simulation.jl:294-305) from the blocks g, h, k of purposes 6, 7, 8 of its attempt: (px, py, pz) the atom, (bx, by, bz) the bead atom
+__device__ __forceinline__ void gcmc_random_point(const double* M, int kind, int m, const ceg_philox::Block& g, const ceg_philox::Block& h,
+                                                  const ceg_philox::Block& k, double& px, double& py, double& pz, double bx, double by, double bz)
 {
 #pragma clang fp contract(off)
-    if (mv.kind <= 1) {
-        if (mv.kind == 1 && mj.y == 1) return comp == 0 ? v.atoms[mj.x].x : (comp == 1 ? v.atoms[mj.x].y : v.atoms[mj.x].z);
-        return sweep_coordinate_of(v, P.stream_id, P.dmax, P.thetamax, S.bead, mv.kind, mj, seed, step, a, comp);
+    if (kind != 3) {                             // random_translation: r = mat (U3 - 0.5)
+        const double ua = ceg_philox::uniform(g.w[0], g.w[1]) - 0.5, ub = ceg_philox::uniform(g.w[2], g.w[3]) - 0.5,
+                     uc = ceg_philox::uniform(h.w[0], h.w[1]) - 0.5;
+        const double rx = (M[0] * ua + M[3] * ub) + M[6] * uc, ry = (M[1] * ua + M[4] * ub) + M[7] * uc, rz = (M[2] * ua + M[5] * ub) + M[8] * uc;
+        px += rx; py += ry; pz += rz;
+        bx += rx; by += ry; bz += rz;
     }
-    const bool model = mv.kind == 5;
-    double px, py, pz, bx, by, bz;
-    if (model) {
+    if (kind == 2 || m == 1) return;
+    const double theta = 3.141592653589793 * (2.0 * ceg_philox::uniform(h.w[2], h.w[3]) - 1.0);
+    int axis = (int)floor(3.0 * ceg_philox::uniform(k.w[0], k.w[1]));
+    axis = axis < 2 ? axis : 2;
+    double s, c;
+    sincos(theta, &s, &c);
+    double dx = px - bx, dy = py - by, dz = pz - bz;
+    rotate_about(axis, s, c, dx, dy, dz);
+    px = bx + dx; py = by + dy; pz = bz + dz;
+}
+
+// atom `a` and the bead atom of what a random_* kind or the insertion displaces: the species' model for an insertion, else the molecule
+__device__ __forceinline__ void gcmc_random_source(const McView& v, const ceg_mc_gcmc_species_t& S, int kind, const int2 mj, int a, double& px, double& py,
+                                                   double& pz, double& bx, double& by, double& bz)
+{
+    if (kind == 5) {
         px = S.model[a][0]; py = S.model[a][1]; pz = S.model[a][2];
         bx = S.model[S.bead][0]; by = S.model[S.bead][1]; bz = S.model[S.bead][2];
     } else {
@@ -323,26 +340,127 @@ __device__ __forceinline__ double gcmc_coordinate(const McView& v, const McGcmcC
         px = A.x; py = A.y; pz = A.z;
         bx = B.x; by = B.y; bz = B.z;
     }
-    const ceg_philox::Block h = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::GCMC_RANDOM_B);
-    if (mv.kind != 3) {                          // random_translation: r = mat (U3 - 0.5)
-        const ceg_philox::Block g = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::GCMC_RANDOM_A);
-        const double ua = ceg_philox::uniform(g.w[0], g.w[1]) - 0.5, ub = ceg_philox::uniform(g.w[2], g.w[3]) - 0.5,
-                     uc = ceg_philox::uniform(h.w[0], h.w[1]) - 0.5;
-        const double* M = v.mat;
-        const double rx = (M[0] * ua + M[3] * ub) + M[6] * uc, ry = (M[1] * ua + M[4] * ub) + M[7] * uc, rz = (M[2] * ua + M[5] * ub) + M[8] * uc;
-        px += rx; py += ry; pz += rz;
-        bx += rx; by += ry; bz += rz;
+}
+
+// coordinate `comp` of atom `a` of the proposal: kinds 0 / 1 from sweep_coordinate, the random_* kinds and the insertion from attempt
+// `attempt` of purposes 6-8 (0 wherever choose_step! does not retry)
+__device__ __forceinline__ double gcmc_coordinate(const McView& v, const McGcmcChain& P, const ceg_mc_gcmc_species_t& S, const McGcmcMove& mv, const int2 mj,
+                                                  uint64_t seed, uint64_t step, uint32_t attempt, int a, int comp)
+{
+    if (mv.kind <= 1) {
+        if (mv.kind == 1 && mj.y == 1) return comp == 0 ? v.atoms[mj.x].x : (comp == 1 ? v.atoms[mj.x].y : v.atoms[mj.x].z);
+        return sweep_coordinate_of(v, P.stream_id, P.dmax, P.thetamax, S.bead, mv.kind, mj, seed, step, a, comp);
     }
-    if (mv.kind == 2 || mj.y == 1) return comp == 0 ? px : (comp == 1 ? py : pz);
-    const double theta = 3.141592653589793 * (2.0 * ceg_philox::uniform(h.w[2], h.w[3]) - 1.0);
-    const ceg_philox::Block k = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::GCMC_RANDOM_C);
-    int axis = (int)floor(3.0 * ceg_philox::uniform(k.w[0], k.w[1]));
-    axis = axis < 2 ? axis : 2;
-    double s, c;
-    sincos(theta, &s, &c);
-    double dx = px - bx, dy = py - by, dz = pz - bz;
-    rotate_about(axis, s, c, dx, dy, dz);
-    return comp == 0 ? bx + dx : (comp == 1 ? by + dy : bz + dz);
+    double px, py, pz, bx, by, bz;
+    gcmc_random_source(v, S, mv.kind, mj, a, px, py, pz, bx, by, bz);
+    ceg_philox::Block g{}, k{};
+    const ceg_philox::Block h = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::attempt_purpose(ceg_philox::GCMC_RANDOM_B, attempt));
+    if (mv.kind != 3) g = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::attempt_purpose(ceg_philox::GCMC_RANDOM_A, attempt));
+    if (mv.kind != 2 && mj.y != 1) k = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::attempt_purpose(ceg_philox::GCMC_RANDOM_C, attempt));
+    gcmc_random_point(v.mat, mv.kind, mj.y, g, h, k, px, py, pz, bx, by, bz);
+    return comp == 0 ? px : (comp == 1 ? py : pz);
+}
+
+// ---- block pockets (ceg_mc_group_set_blocks): inblockpocket and the retry loop of choose_step! (src/simulation.jl:271-326,
+// src/montecarlo.jl:631-640), resolved by every workgroup of a chain's step in front of its row.
+// blocks[0 .. nspecies): the species blocks; blocks[nspecies + kind]: the atom blocks (nkinds == 0: none); masks in device memory.
+using McBlock = ceg_mc_block_t;
+
+// BlockFile getindex at p + offset (src/coordinates.jl:58-66,97-101; blocked_at of ceg_egrid.hip): a NULL mask is empty
+__device__ __forceinline__ bool block_holds(const McBlock& B, double px, double py, double pz)
+{
+#pragma clang fp contract(off)
+    if (!B.mask) return false;
+    px = px + B.offset[0]; py = py + B.offset[1]; pz = pz + B.offset[2];
+    const double* I = B.invmat;
+    const double* M = B.mat;
+    double a0 = (I[0] * px + I[3] * py) + I[6] * pz;
+    double a1 = (I[1] * px + I[4] * py) + I[7] * pz;
+    double a2 = (I[2] * px + I[5] * py) + I[8] * pz;
+    a0 -= floor(a0); a1 -= floor(a1); a2 -= floor(a2);
+    const double q[3] = {(M[0] * a0 + M[3] * a1) + M[6] * a2, (M[1] * a0 + M[4] * a1) + M[7] * a2, (M[2] * a0 + M[5] * a1) + M[8] * a2};
+    int idx[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double sh = (q[c] - B.shift[c]) * (double)B.dims[c] / B.size[c] + 1.0;
+        const int i = (int)rint(sh) - 1;
+        idx[c] = i < 0 ? 0 : (i > B.dims[c] ? B.dims[c] : i);                          // memory safety only
+    }
+    const size_t ny = (size_t)B.dims[1] + 1, nz = (size_t)B.dims[2] + 1;
+    return B.mask[((size_t)idx[0] * ny + idx[1]) * nz + idx[2]] != 0;
+}
+
+// what a step's trial launch hands to its accept launch, one word per chain: attempt << 2 | exhausted << 1 | pocket-blocked
+constexpr int MC_POCKET = 1, MC_EXHAUSTED = 2;
+constexpr int MC_RESOLVE_PASSES = (ceg_philox::GCMC_ATTEMPTS + 15) / 16;
+
+// The attempt of the step's proposal and whether the step is pocket-blocked, by the whole workgroup.  16 attempts per pass, one per
+// 16 lanes, lane a of an attempt on atom a: the three Philox blocks of the attempt are drawn by its lanes 0-2 and shared, every lane
+// places its atom and looks it up; a ballot gives each attempt its verdict and the lowest passing attempt of the pass ends the loop.
+// Kinds 0, 1, 3 have the one proposal (attempt 0) and pass with its verdict.
+__device__ __forceinline__ int gcmc_resolve(const McView& v, const McGcmcChain& P, const ceg_mc_gcmc_species_t& S, const McGcmcMove& mv, const int2 mj,
+                                            const McBlock* __restrict__ blocks, int nspecies, int nkinds, uint64_t seed, uint64_t step)
+{
+    static_assert(MC_THREADS == 256 && MC_MAX_ATOMS == 16, "16 attempts of 16 lanes");
+    __shared__ unsigned s_verdict[2][MC_THREADS / 64];
+    const int tid = threadIdx.x, wave = tid >> 6, a = tid & 15;
+    const bool retried = mv.kind == 2 || mv.kind == 4 || mv.kind == 5;
+    const int npass = retried ? MC_RESOLVE_PASSES : 1;
+    const McBlock& SB = blocks[mv.species];
+    const int akind = S.kinds[a < mj.y ? a : 0];
+    for (int p = 0; p < npass; ++p) {
+        const int t = 16 * p + (tid >> 4);
+        const bool live = a < mj.y && (retried ? t < (int)ceg_philox::GCMC_ATTEMPTS : t == 0);
+        double x = 0.0, y = 0.0, z = 0.0;
+        if (mv.kind <= 1) {
+            if (live) {
+                x = gcmc_coordinate(v, P, S, mv, mj, seed, step, 0u, a, 0);
+                y = gcmc_coordinate(v, P, S, mv, mj, seed, step, 0u, a, 1);
+                z = gcmc_coordinate(v, P, S, mv, mj, seed, step, 0u, a, 2);
+            }
+        } else {
+            const ceg_philox::Block mine = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::attempt_purpose(ceg_philox::GCMC_RANDOM_A + (uint32_t)(a % 3), (uint32_t)t));
+            ceg_philox::Block g, h, k;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                g.w[w] = (uint32_t)__shfl((int)mine.w[w], 0, 16);
+                h.w[w] = (uint32_t)__shfl((int)mine.w[w], 1, 16);
+                k.w[w] = (uint32_t)__shfl((int)mine.w[w], 2, 16);
+            }
+            if (live) {
+                double bx, by, bz;
+                gcmc_random_source(v, S, mv.kind, mj, a, x, y, z, bx, by, bz);
+                gcmc_random_point(v.mat, mv.kind, mj.y, g, h, k, x, y, z, bx, by, bz);
+            }
+        }
+        bool in_species = false, in_any = false;
+        if (live) {
+            in_species = block_holds(SB, x, y, z);
+            in_any = in_species || (nkinds > 0 && block_holds(blocks[nspecies + akind], x, y, z));
+        }
+        const unsigned long long bs = __ballot(in_species), ba = __ballot(in_any);
+        unsigned verdict = 0;                    // bits 0-3: the wave's four attempts pass; bits 4-7: their placements lie in a pocket
+        for (int q = 0; q < 4; ++q) {
+            const unsigned s16 = (unsigned)(bs >> (16 * q)) & 0xffffu, a16 = (unsigned)(ba >> (16 * q)) & 0xffffu;
+            const int tq = 16 * p + 4 * wave + q;
+            const bool pass = retried ? tq < (int)ceg_philox::GCMC_ATTEMPTS && (mv.kind == 5 ? ((s16 >> S.bead) & 1u) == 0u : a16 == 0u) : tq == 0;
+            verdict |= (pass ? 1u : 0u) << q | (a16 != 0u ? 16u : 0u) << q;
+        }
+        if ((tid & 63) == 0) s_verdict[p & 1][wave] = verdict;
+        __syncthreads();                         // (one per pass: the buffer of pass p is next written in pass p + 2, behind the barrier of p + 1)
+        unsigned pass = 0, pocket = 0;
+        for (int w = 0; w < MC_THREADS / 64; ++w) {
+            const unsigned r = s_verdict[p & 1][w];
+            pass |= (r & 15u) << (4 * w);
+            pocket |= (r >> 4) << (4 * w);
+        }
+        pass = (unsigned)__builtin_amdgcn_readfirstlane((int)pass);
+        if (pass) {
+            const int q = __ffs((int)pass) - 1;
+            return (16 * p + q) << 2 | (((pocket >> q) & 1u) ? MC_POCKET : 0);
+        }
+    }
+    return ((int)ceg_philox::GCMC_ATTEMPTS - 1) << 2 | MC_EXHAUSTED | MC_POCKET;
 }
 
 struct McAtGcmcRow {
@@ -361,7 +479,8 @@ template <bool FAST>
 __global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mcg_gcmc_trial(const McView* __restrict__ views, const McGcmcChain* __restrict__ params,
                                                                 const ceg_mc_gcmc_species_t* __restrict__ spec, int nspecies, const McGcmcTable* tables,
                                                                 const int32_t* molspec, const int32_t* __restrict__ list, int table_ok, uint64_t seed,
-                                                                uint64_t step, McPositions* prop, double* __restrict__ rows)
+                                                                uint64_t step, const McBlock* __restrict__ blocks, int nblock_kinds, int32_t* resolved,
+                                                                McPositions* prop, double* __restrict__ rows)
 {
     __shared__ McLocal s_L;
     const int c = list[blockIdx.x >> 1], r = (int)(blockIdx.x & 1u);
@@ -373,6 +492,18 @@ __global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mcg_gcmc_trial(c
     const ceg_mc_gcmc_species_t& S = spec[mv.species];
     const int2 mj = mv.kind == 5 ? make_int2(0, S.m) : v.mol[mv.molecule];
     const int tid = threadIdx.x;
+    uint32_t attempt = 0;
+    if (blocks && mv.kind != 6) {                // (masks installed: the same for every workgroup of the launch)
+        const int w = gcmc_resolve(v, P, S, mv, mj, blocks, nspecies, nblock_kinds, seed, step);
+        attempt = (uint32_t)(w >> 2);
+        const bool reports = r == 1 && blockIdx.y == 0;
+        if (reports && tid == 0) resolved[c] = w;
+        if (w & MC_POCKET) {                     // no row is evaluated; the accept kernel logs the proposal that was tested
+            if (reports && !(w & MC_EXHAUSTED) && tid < 3 * mj.y)
+                prop[3 * (size_t)c].xyz[tid] = gcmc_coordinate(v, P, S, mv, mj, seed, step, attempt, tid / 3, tid % 3);
+            return;
+        }
+    }
     if (tid < mj.y) {
         const int kind = S.kinds[tid];
         s_L.kinds[tid] = kind;
@@ -380,7 +511,7 @@ __global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mcg_gcmc_trial(c
     }
     if (tid == 0) { s_L.first = mj.x; s_L.m = mj.y; }
     McPositions* mine = prop + 3 * (size_t)c + blockIdx.y;
-    if (r == 1 && tid < 3 * mj.y) mine->xyz[tid] = gcmc_coordinate(v, P, S, mv, mj, seed, step, tid / 3, tid % 3);
+    if (r == 1 && tid < 3 * mj.y) mine->xyz[tid] = gcmc_coordinate(v, P, S, mv, mj, seed, step, attempt, tid / 3, tid % 3);
     __syncthreads();
     const McAtGcmcRow at{2 * (int64_t)c + r, mv.kind == 5 ? 0 : r, table_ok, mv.natoms};
     if (mv.kind == 5) mc_trial_row<FAST, true, false>(v, -1, s_L, mine->xyz, rows, P.stride, nullptr, nullptr, 0ull, at);
@@ -391,6 +522,7 @@ __global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mcg_gcmc_trial(c
 __global__ __launch_bounds__(MC_THREADS) void k_mcg_gcmc_accept(const McView* __restrict__ views, const McGcmcChain* __restrict__ params,
                                                                 const ceg_mc_gcmc_species_t* __restrict__ spec, int nspecies, McGcmcTable* tables,
                                                                 int32_t* molspec, int32_t* freeslots, uint64_t seed, uint64_t step,
+                                                                const int32_t* resolved, int64_t* __restrict__ pockets,
                                                                 const McPositions* __restrict__ prop, const double* __restrict__ rows,
                                                                 ceg_mc_gcmc_stats_t* __restrict__ stats, ceg_mc_gcmc_record_t* __restrict__ log)
 {
@@ -420,6 +552,24 @@ __global__ __launch_bounds__(MC_THREADS) void k_mcg_gcmc_accept(const McView* __
                 rec->n_species = mv.n_i; rec->flags = flags; rec->u = u;
             }
         }
+        return;
+    }
+    const McPositions& np = prop[3 * (size_t)c];
+    // what the trial launch resolved (masks installed): pockets[2c] counts the pocket-blocked steps, pockets[2c + 1] sums the attempts
+    const int res = resolved && mv.kind != 6 ? gcmc_ld(resolved + c) : 0;
+    const int attempt = res >> 2;
+    if (res & MC_POCKET) {
+        if (tid == 0) {
+            S.trials[mv.kind] += 1;
+            S.blocked += 1;
+            pockets[2 * c] += 1;
+            pockets[2 * c + 1] += attempt;
+            if (rec) {
+                rec->species = i; rec->molecule = mv.molecule; rec->kind = mv.kind; rec->accepted = 0;
+                rec->n_species = mv.n_i; rec->flags = 8 | attempt << 16; rec->u = u;
+            }
+        }
+        if (rec && !(res & MC_EXHAUSTED) && tid < 3 * m) rec->positions[tid / 3][tid % 3] = np.xyz[tid];
         return;
     }
     const double* r = rows + 8 * (size_t)c;
@@ -454,10 +604,10 @@ __global__ __launch_bounds__(MC_THREADS) void k_mcg_gcmc_accept(const McView* __
         }
     }
     const int accepted = __builtin_amdgcn_readfirstlane(acc);
-    const McPositions& np = prop[3 * (size_t)c];
     if (tid == 0) {
         S.trials[mv.kind] += 1;
         S.accepted[mv.kind] += accepted;
+        if (attempt) pockets[2 * c + 1] += attempt;
         if (blocked) S.blocked += 1;
         if (accepted) {
             if (mv.kind <= 4) S.delta_moves += delta;
@@ -465,7 +615,7 @@ __global__ __launch_bounds__(MC_THREADS) void k_mcg_gcmc_accept(const McView* __
         }
         if (rec) {
             rec->species = i; rec->molecule = mv.molecule; rec->kind = mv.kind; rec->accepted = accepted;
-            rec->n_species = mv.n_i; rec->flags = blocked ? 2 : 0; rec->u = u; rec->tc = tc;
+            rec->n_species = mv.n_i; rec->flags = (blocked ? 2 : 0) | attempt << 16; rec->u = u; rec->tc = tc;
             for (int t = 0; t < 8; ++t) rec->rows[t >> 2][t & 3] = row[t];
         }
     }
@@ -525,6 +675,11 @@ struct ceg_mc_group {
     // the device memory of a sweep of either kind (SweepLayout): one block that only grows, written whole before the first step
     unsigned char* d_scratch = nullptr;
     size_t scratch_cap = 0;
+    // block pockets (ceg_mc_group_set_blocks): [blk_species] species blocks then [blk_kinds] atom blocks, their masks in d_masks
+    ceg_mc_block_t* d_blocks = nullptr;
+    std::vector<uint8_t*> d_masks;
+    int blk_species = 0, blk_kinds = 0;
+    std::vector<int64_t> pockets;                // [2K] of the last GCMC sweep: pocket-blocked steps, sum of the attempt indices
 };
 
 namespace {
@@ -532,9 +687,19 @@ namespace {
 constexpr size_t MCG_IN_BYTES = 1 << 20;         // entries, row prefixes and placements of one group trial call
 constexpr size_t MCG_OUT_BYTES = 1 << 20;        // rows of one group trial call (32 768)
 
+void group_free_blocks(ceg_mc_group* g)
+{
+    for (uint8_t* m : g->d_masks) (void)hipFree(m);
+    g->d_masks.clear();
+    if (g->d_blocks) (void)hipFree(g->d_blocks);
+    g->d_blocks = nullptr;
+    g->blk_species = g->blk_kinds = 0;
+}
+
 void group_free(ceg_mc_group* g)
 {
     if (g->stream) { (void)hipStreamSynchronize(g->stream); (void)hipStreamDestroy(g->stream); }
+    group_free_blocks(g);
     if (g->d_views) (void)hipFree(g->d_views);
     if (g->d_done) (void)hipFree(g->d_done);
     if (g->d_scratch) (void)hipFree(g->d_scratch);
@@ -817,6 +982,69 @@ extern "C" int ceg_mc_group_accept(ceg_mc_group_t* g, const int32_t* molecule, c
     return CEG_OK;                       // asynchronous: later calls on the group and on its members are ordered behind it
 }
 
+// ---- block pockets of a group: the masks go to the device once and stay there
+extern "C" int ceg_mc_group_set_blocks(ceg_mc_group_t* g, const ceg_mc_block_t* species_blocks, int32_t nspecies, const ceg_mc_block_t* atom_blocks,
+                                       int32_t nkinds)
+{
+    static_assert(sizeof(ceg_mc_block_t) == 240, "layout the bindings restate");
+    if (!g || nspecies < 0 || nspecies > CEG_MC_GCMC_MAX_SPECIES || nkinds < 0 || (nspecies > 0 && !species_blocks) || (nkinds > 0 && !atom_blocks))
+        return merr(CEG_ERR_INVALID, "bad argument (0 <= nspecies <= CEG_MC_GCMC_MAX_SPECIES, nkinds >= 0)");
+    if (nspecies == 0 && nkinds > 0) return merr(CEG_ERR_INVALID, "atom blocks need the species blocks (NULL masks where a species has none)");
+    std::vector<ceg_mc_block_t> all;
+    all.insert(all.end(), species_blocks, species_blocks + nspecies);
+    all.insert(all.end(), atom_blocks, atom_blocks + nkinds);
+    for (size_t b = 0; b < all.size(); ++b) {
+        const ceg_mc_block_t& B = all[b];
+        bool ok = true;
+        for (int d = 0; d < 3; ++d)
+            ok = ok && B.dims[d] > 0 && std::isfinite(B.size[d]) && B.size[d] > 0.0 && std::isfinite(B.shift[d]) && std::isfinite(B.offset[d]);
+        for (int d = 0; d < 9; ++d) ok = ok && std::isfinite(B.mat[d]) && std::isfinite(B.invmat[d]);
+        if (!ok) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "%s block %d: dims must be > 0, size > 0 and the geometry finite", b < (size_t)nspecies ? "species" : "atom",
+                          (int)(b < (size_t)nspecies ? b : b - (size_t)nspecies));
+            return merr(CEG_ERR_INVALID, msg);
+        }
+    }
+    Guard guard(g->device);
+    if (!guard.ok) return merr(CEG_ERR_HIP, "hipSetDevice failed");
+    if (hipStreamSynchronize(g->stream) != hipSuccess) return merr(CEG_ERR_HIP, "stream synchronisation failed");
+    g->accept_pending = false;
+    g->uploads_pending = false;
+    group_free_blocks(g);
+    if (all.empty()) return CEG_OK;
+    bool ok = true;
+    for (ceg_mc_block_t& B : all) {
+        if (!B.mask) continue;
+        const size_t bytes = ((size_t)B.dims[0] + 1) * ((size_t)B.dims[1] + 1) * ((size_t)B.dims[2] + 1);
+        uint8_t* d = nullptr;
+        ok = ok && hipMalloc((void**)&d, bytes) == hipSuccess;
+        if (!ok) break;
+        g->d_masks.push_back(d);
+        ok = hipMemcpy(d, B.mask, bytes, hipMemcpyHostToDevice) == hipSuccess;
+        B.mask = d;
+    }
+    ok = ok && hipMalloc((void**)&g->d_blocks, sizeof(ceg_mc_block_t) * all.size()) == hipSuccess &&
+         hipMemcpy(g->d_blocks, all.data(), sizeof(ceg_mc_block_t) * all.size(), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        group_free_blocks(g);
+        return merr(CEG_ERR_HIP, "could not copy the block masks to the device");
+    }
+    g->blk_species = nspecies;
+    g->blk_kinds = nkinds;
+    return CEG_OK;
+}
+
+extern "C" int ceg_mc_group_block_counts(ceg_mc_group_t* g, int64_t* pocket_out, int64_t* attempts_out)
+{
+    if (!g) return merr(CEG_ERR_INVALID, "bad argument");
+    for (size_t c = 0; c < g->chains.size(); ++c) {
+        if (pocket_out) pocket_out[c] = g->pockets.empty() ? 0 : g->pockets[2 * c];
+        if (attempts_out) attempts_out[c] = g->pockets.empty() ? 0 : g->pockets[2 * c + 1];
+    }
+    return CEG_OK;
+}
+
 // ---- what the two sweeps share on the host: the refusals, the launch plan, the layout of the group's device block and the driver
 namespace {
 
@@ -946,6 +1174,7 @@ extern "C" int ceg_mc_group_sweep(ceg_mc_group_t* g, const ceg_mc_sweep_params_t
     if (!g || !p || !stats_out || !p->stream_id || !p->temperature || !p->dmax || !p->thetamax || !p->p_rotation)
         return merr(CEG_ERR_INVALID, "bad argument");
     if (nsteps < 0) return merr(CEG_ERR_INVALID, "negative number of steps");
+    if (g->d_blocks) return merr(CEG_ERR_UNSUPPORTED, "the group has block masks installed: only ceg_mc_group_sweep_gcmc tests block pockets");
     const int k = (int)g->chains.size();
     // ---- every refusal before anything is launched or changed, chain by chain
     std::vector<McSweepChain> pc((size_t)k);
@@ -1039,6 +1268,12 @@ extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_para
         mmax = std::max(mmax, (int)S.m);
         if (swaps) swap_atoms += S.m;
     }
+    if (g->d_blocks) {                                   // block pockets: the masks must be those of this species table
+        if (ns != g->blk_species) return merr(CEG_ERR_INVALID, "nspecies differs from the nspecies of ceg_mc_group_set_blocks");
+        for (int i = 0; i < ns && g->blk_kinds > 0; ++i)
+            for (int a = 0; a < p->species[i].m; ++a)
+                if (p->species[i].kinds[a] >= g->blk_kinds) return merr(CEG_ERR_INVALID, "a species' atom kind has no atom block (kind >= nkinds of ceg_mc_group_set_blocks)");
+    }
     std::vector<McGcmcChain> pc((size_t)k);
     std::vector<McGcmcTable> tab((size_t)k);
     SweepPlan plan;
@@ -1102,6 +1337,7 @@ extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_para
         if (p->molecule_species_out && D.nmol > 0) memcpy(p->molecule_species_out + out_off[(size_t)c], ms, sizeof(int32_t) * (size_t)D.nmol);
     };
     for (int c = 0; c < k; ++c) stats_out[c] = ceg_mc_gcmc_stats_t{};
+    g->pockets.assign(2 * (size_t)k, 0);
     if (nsteps == 0) {
         size_t o = 0;
         for (int c = 0; c < k; ++c) {
@@ -1116,12 +1352,15 @@ extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_para
     for (int c = 0; c < k; ++c)
         if (int rc = ensure_capacity(g->chains[c], pc[(size_t)c].atoms_cap, std::max(pc[(size_t)c].max_molecules, 1))) return rc;
     for (int c = 0; c < k; ++c) pc[(size_t)c].atoms_cap = (int32_t)std::min<int64_t>(g->chains[c]->atoms_cap, 0x3fffffff);
-    // ---- added to the common segments: [ns] species | [K] statistics | [K] tables | species of the molecules | stacks of freed slots
-    //      (from the statistics on: read back after the sweep)
+    // ---- added to the common segments: [ns] species | [K] resolved attempts | [K] statistics | [K] tables | species of the molecules |
+    //      stacks of freed slots | [2K] pocket counters (from the statistics on: read back after the sweep)
     SweepLayout lay((size_t)k, sizeof(McGcmcChain));
-    const size_t o_spec = lay.segment(sizeof(ceg_mc_gcmc_species_t) * (size_t)ns), o_stats = lay.segment(sizeof(ceg_mc_gcmc_stats_t) * (size_t)k),
-                 o_tab = lay.segment(sizeof(McGcmcTable) * (size_t)k), o_ms = lay.segment(sizeof(int32_t) * nspec_total),
-                 o_free = lay.segment(sizeof(int32_t) * nfree_total);
+    const size_t o_spec = lay.segment(sizeof(ceg_mc_gcmc_species_t) * (size_t)ns), o_res = lay.segment(sizeof(int32_t) * (size_t)k),
+                 o_stats = lay.segment(sizeof(ceg_mc_gcmc_stats_t) * (size_t)k), o_tab = lay.segment(sizeof(McGcmcTable) * (size_t)k),
+                 o_ms = lay.segment(sizeof(int32_t) * nspec_total), o_free = lay.segment(sizeof(int32_t) * nfree_total),
+                 o_pock = lay.segment(sizeof(int64_t) * 2 * (size_t)k);
+    const ceg_mc_block_t* blocks = g->d_blocks;          // NULL: no masks, the kernels take the path without the resolve stage
+    const int block_kinds = g->blk_kinds;
     std::vector<unsigned char> stage(lay.total, 0);
     memcpy(stage.data() + lay.par, pc.data(), sizeof(McGcmcChain) * (size_t)k);
     memcpy(stage.data() + o_spec, p->species, sizeof(ceg_mc_gcmc_species_t) * (size_t)ns);
@@ -1138,15 +1377,17 @@ extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_para
     auto trial = [&](bool fast, dim3 grid, size_t lds, const int32_t* list, int table_ok, uint64_t step) {
         hipLaunchKernelGGL((fast ? k_mcg_gcmc_trial<true> : k_mcg_gcmc_trial<false>), grid, dim3(MC_THREADS), lds, g->stream, g->d_views, sweep_at<const McGcmcChain>(g, lay.par),
                                sweep_at<const ceg_mc_gcmc_species_t>(g, o_spec), ns, sweep_at<const McGcmcTable>(g, o_tab), sweep_at<const int32_t>(g, o_ms), list,
-                               table_ok, p->seed, step, sweep_at<McPositions>(g, lay.prop), sweep_at<double>(g, lay.rows));
+                               table_ok, p->seed, step, blocks, block_kinds, sweep_at<int32_t>(g, o_res), sweep_at<McPositions>(g, lay.prop),
+                               sweep_at<double>(g, lay.rows));
     };
     auto accept = [&](dim3 grid, size_t lds, uint64_t step, ceg_mc_gcmc_record_t* rec) {
         hipLaunchKernelGGL(k_mcg_gcmc_accept, grid, dim3(MC_THREADS), lds, g->stream, g->d_views, sweep_at<const McGcmcChain>(g, lay.par),
                            sweep_at<const ceg_mc_gcmc_species_t>(g, o_spec), ns, sweep_at<McGcmcTable>(g, o_tab), sweep_at<int32_t>(g, o_ms),
-                           sweep_at<int32_t>(g, o_free), p->seed, step, sweep_at<const McPositions>(g, lay.prop), sweep_at<const double>(g, lay.rows),
-                           sweep_at<ceg_mc_gcmc_stats_t>(g, o_stats), rec);
+                           sweep_at<int32_t>(g, o_free), p->seed, step, blocks ? sweep_at<const int32_t>(g, o_res) : nullptr, sweep_at<int64_t>(g, o_pock),
+                           sweep_at<const McPositions>(g, lay.prop), sweep_at<const double>(g, lay.rows), sweep_at<ceg_mc_gcmc_stats_t>(g, o_stats), rec);
     };
     if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept)) return rc;
+    memcpy(g->pockets.data(), stage.data() + o_pock, sizeof(int64_t) * 2 * (size_t)k);
     // ---- the host mirrors from the device: molecule table, kinds, freed runs, counts and high-water mark of every chain that swapped
     const ceg_mc_gcmc_stats_t* st = reinterpret_cast<const ceg_mc_gcmc_stats_t*>(stage.data() + o_stats);
     const McGcmcTable* nt = reinterpret_cast<const McGcmcTable*>(stage.data() + o_tab);

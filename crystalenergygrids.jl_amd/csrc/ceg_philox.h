@@ -48,6 +48,10 @@ enum : uint32_t { SELECT = 0, GEOMETRY_A = 1, GEOMETRY_B = 2, ACCEPT = 3 };
 // ceg_mc_group_sweep_gcmc: species and move kind; molecule and swap direction; random_translation (x, y), (z, theta of random_rotation),
 // axis of random_rotation
 enum : uint32_t { GCMC_SELECT = 4, GCMC_MOLECULE = 5, GCMC_RANDOM_A = 6, GCMC_RANDOM_B = 7, GCMC_RANDOM_C = 8 };
+// attempt t = 0..999 of a proposal that choose_step! retries (block pockets): purposes 6-8 with counter word 3 = purpose | (t << 8);
+// attempt 0 is the plain purpose
+constexpr uint32_t GCMC_ATTEMPTS = 1000;
+CEG_PHILOX_HD uint32_t attempt_purpose(uint32_t purpose, uint32_t attempt) { return purpose | (attempt << 8); }
 
 }  // namespace ceg_philox
 

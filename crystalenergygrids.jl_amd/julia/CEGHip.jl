@@ -729,6 +729,53 @@ function mc_group_sweep_gcmc!(g::Ptr{Cvoid}, nsteps::Integer, seed::Integer, fir
     log ? (stats, final, records) : (stats, final)
 end
 
+# `ceg_mc_block_t` of include/ceg_hip.h (240 bytes)
+struct McBlock
+    mask::Ptr{UInt8}                 # host memory, [x][y][z] with z fastest; C_NULL: an empty block
+    dims::NTuple{3,Int32}
+    _pad::Int32
+    size::NTuple{3,Float64}
+    shift::NTuple{3,Float64}
+    offset::NTuple{3,Float64}
+    mat::NTuple{9,Float64}           # column-major
+    invmat::NTuple{9,Float64}
+end
+
+_block_mask(b::CEG.BlockFile) = b.empty ? UInt8[] : vec(UInt8.(permutedims(b.block, (3, 2, 1))))
+function _mc_block(b::CEG.BlockFile, mask::Vector{UInt8}, half::Bool)
+    cs = b.csetup
+    size = Float64[NoUnits(x/u"Å") for x in cs.size]
+    offset = half ? (size ./ cs.dims) ./ 2 : zeros(3)
+    McBlock(isempty(mask) ? Ptr{UInt8}(C_NULL) : pointer(mask), Tuple(Int32.(cs.dims)), Int32(0), Tuple(size),
+            Tuple(Float64[NoUnits(x/u"Å") for x in cs.shift]), Tuple(offset), Tuple(Float64[NoUnits(x/u"Å") for x in vec(cs.cell.mat)]),
+            Tuple(Float64[NoUnits(x*u"Å") for x in vec(cs.cell.invmat)]))
+end
+
+"""
+`ceg_mc_group_set_blocks`: the block pockets `ceg_mc_group_sweep_gcmc` tests like `choose_step!` (src/simulation.jl:271-326):
+`speciesblocks` = `mc.speciesblocks`, `atomblocks` = `mc.atomblocks` (looked up at `pos + Δ/2`, src/montecarlo.jl:636; empty: none).
+The masks are copied to the device; two empty vectors clear them.  Never executed here (no Julia in the image).
+"""
+function mc_group_set_blocks!(g::Ptr{Cvoid}, speciesblocks::Vector{CEG.BlockFile}, atomblocks::Vector{CEG.BlockFile}=CEG.BlockFile[])
+    smasks = [_block_mask(b) for b in speciesblocks]
+    amasks = [_block_mask(b) for b in atomblocks]
+    GC.@preserve smasks amasks begin
+        sb = McBlock[_mc_block(b, m, false) for (b, m) in zip(speciesblocks, smasks)]
+        ab = McBlock[_mc_block(b, m, true) for (b, m) in zip(atomblocks, amasks)]
+        GC.@preserve sb ab _check(ccall((:ceg_mc_group_set_blocks, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int32),
+                                        g, isempty(sb) ? C_NULL : pointer(sb), length(sb), isempty(ab) ? C_NULL : pointer(ab), length(ab)))
+    end
+    nothing
+end
+
+"`ceg_mc_group_block_counts`: per chain, the pocket-blocked steps of the last GCMC sweep and the sum of the attempt indices it used"
+function mc_group_block_counts(g::Ptr{Cvoid}, k::Integer)
+    pocket = zeros(Int64, k)
+    attempts = zeros(Int64, k)
+    _check(ccall((:ceg_mc_group_block_counts, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), g, pocket, attempts))
+    pocket, attempts
+end
+
 "`ceg_mc_group_destroy`: the chains get their own streams back and stay valid"
 function mc_group_close(g::Ptr{Cvoid})
     _check(ccall((:ceg_mc_group_destroy, LIB[]), Cint, (Ptr{Cvoid},), g))

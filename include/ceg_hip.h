@@ -686,8 +686,9 @@ CEG_API int ceg_mc_group_accept(ceg_mc_group_t* group, const int32_t* molecule, 
  * log_out [nsteps][K] or NULL (production): per (step, chain) the molecule and move kind (0 translation, 1 rotation; both -1 for
  *   an idle chain), the accepted flag, u, the rows before / after and the proposed positions (unused entries zero).
  * Synchronous.  Afterwards every per-handle and group entry point works on the moved state; the molecule table does not change.
- * Not covered: swap / reinsertion / random_* moves (ceg_mc_group_sweep_gcmc, below), the inblockpocket test of choose_step!, and the adaptation of dmax / thetamax
- * (src/simulation.jl:820-825), which stays with the caller between sweeps -- the stats hold the ratios it needs. */
+ * Not covered: swap / reinsertion / random_* moves (ceg_mc_group_sweep_gcmc, below), the inblockpocket test of choose_step! (a group with
+ * masks installed by ceg_mc_group_set_blocks is refused with CEG_ERR_UNSUPPORTED rather than swept without them), and the adaptation of
+ * dmax / thetamax (src/simulation.jl:820-825), which stays with the caller between sweeps -- the stats hold the ratios it needs. */
 typedef struct ceg_mc_sweep_params {
     uint64_t seed, first_step;
     const uint32_t* stream_id;                 /* [K] */
@@ -763,9 +764,36 @@ CEG_API int ceg_mc_group_sweep(ceg_mc_group_t* group, const ceg_mc_sweep_params_
  *   accepted swaps.
  * Synchronous.  Afterwards the handles' host mirrors (molecule table, free atom slots, high-water mark) are rebuilt from the device and
  *   every per-handle and group entry point works on the new state.
- * Not covered: the inblockpocket retry loop of choose_step! (chains with block pockets stay with the caller), the adaptation of dmax /
- *   thetamax, the fugacity coefficient (phiPV_div_k comes from the caller, as the reference takes it from Clapeyron), and chains
- *   that keep their guests in neighbour cells. */
+ * Not covered: the adaptation of dmax / thetamax, the fugacity coefficient and the accessible-volume factor of GCMCData (phiPV_div_k
+ *   comes from the caller, as the reference takes it from Clapeyron), and chains that keep their guests in neighbour cells.
+ *
+ * Block pockets (ceg_mc_group_set_blocks): the inblockpocket test and the 1000-attempt retry loop of choose_step!
+ * (src/simulation.jl:271-326, src/montecarlo.jl:631-640), resolved inside the trial launch of the step (no launch is added).
+ *   Masks: a block is a byte mask [dims[0]+1][dims[1]+1][dims[2]+1], z fastest, 1 = blocked, as ceg_block_from_grid / ceg_block_spheres
+ *     write it, with its own dims, size, shift, mat, invmat (column-major) and offset[3].  The lookup of a point p (BlockFile getindex,
+ *     src/coordinates.jl:58-66,97-101) runs in FP64 without contraction: q = p + offset; abc = invmat q summed left to right;
+ *     abc -= floor(abc); w = mat abc; index_c = rint((w_c - shift_c) * dims_c / size_c + 1) - 1 (ties to even), clamped to [0, dims_c] for
+ *     memory safety only.  A NULL mask is BlockFile.empty: never blocked.  Species blocks: one per species, offset = 0.  Atom blocks
+ *     (atomblocks of src/montecarlo.jl:181-186): one per atom kind (0-based, the index used in species.kinds), offset_c =
+ *     (size_c / dims_c) / 2, the csetup.Delta ./ 2 of montecarlo.jl:636.
+ *   inblockpocket(i, pos) is true iff for some atom a the species block of i holds pos[a], or atom blocks are installed and the atom
+ *     block of kinds[a] holds pos[a].
+ *   Random stream: attempt t = 0..999 of a retried proposal draws purposes 6, 7, 8 with counter word 3 = purpose | (t << 8); attempt 0
+ *     is the block a group without masks draws.  Purposes 0-5 are never retried.
+ *   Per move kind, after the selection (spent and capacity steps are decided first and are unchanged):
+ *     0 translation, 1 rotation, 3 random_rotation: one proposal; if inblockpocket, the step is pocket-blocked;
+ *     2 random_translation, 4 random_reinsertion: the first attempt t with !inblockpocket is the proposal; none in 1000: pocket-blocked;
+ *     5 swap_insertion: the first attempt t whose bead atom lies outside the species block (species block and bead only,
+ *       simulation.jl:310-316) is the proposal; if inblockpocket of that whole placement, the step is pocket-blocked; none in 1000:
+ *       pocket-blocked;
+ *     6 swap_deletion: no test.
+ *   A pocket-blocked step is counted in stats.trials[kind], in stats.blocked and in the chain's pocket counter
+ *     (ceg_mc_group_block_counts); no energy row is evaluated (both rows of the record are zero); it is rejected, the state untouched.
+ *   Record: flags bit 3 (value 8) = pocket-blocked; flags >> 16 = the index of the attempt used (0 where the kind is not retried, 999
+ *     on exhaustion); positions = the proposal that was tested (zeros on exhaustion).  With no masks installed every record is
+ *     bit-identical to that of a group that never heard of masks.
+ *   With masks installed the call returns CEG_ERR_INVALID, before anything is launched, if params->nspecies differs from the nspecies
+ *     of the masks, or if atom blocks are installed and some species.kinds[a] >= nkinds. */
 #define CEG_MC_GCMC_MAX_SPECIES 8
 typedef struct ceg_mc_gcmc_species {
     int32_t m, bead;
@@ -802,6 +830,20 @@ typedef struct ceg_mc_gcmc_record {
 
 CEG_API int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* group, const ceg_mc_gcmc_params_t* params, int64_t nsteps,
                                     ceg_mc_gcmc_stats_t* stats_out, ceg_mc_gcmc_record_t* log_out);
+
+/* Block pockets of a group (semantics: above).  set_blocks copies the masks (host memory) to the group's device once; they stay until
+ * they are replaced, cleared with (NULL, 0, NULL, 0) or the group is destroyed.  Synchronises the group.  CEG_ERR_INVALID: dims <= 0,
+ * a geometry entry that is not finite, size <= 0, nspecies outside [0, CEG_MC_GCMC_MAX_SPECIES], nkinds < 0, or a missing array.
+ * block_counts: per chain, the pocket-blocked steps of the last ceg_mc_group_sweep_gcmc and the sum of the attempt indices it used
+ * (zeros before any sweep and after a sweep without masks); either pointer may be NULL. */
+typedef struct ceg_mc_block {
+    const uint8_t* mask;                       /* host memory; NULL = empty */
+    int32_t dims[3], _pad;
+    double size[3], shift[3], offset[3], mat[9], invmat[9];
+} ceg_mc_block_t;
+CEG_API int ceg_mc_group_set_blocks(ceg_mc_group_t* group, const ceg_mc_block_t* species_blocks, int32_t nspecies,
+                                    const ceg_mc_block_t* atom_blocks, int32_t nkinds);
+CEG_API int ceg_mc_group_block_counts(ceg_mc_group_t* group, int64_t* pocket_out /*[K]*/, int64_t* attempts_out /*[K]*/);
 
 /* ---- blocking masks on the grid lattice ----------------------------- */
 /*
