@@ -125,6 +125,8 @@ PROTOTYPES = {
     "ceg_plan_can_cull": (C.c_int, [C.c_void_p]),
     "ceg_plan_uniform_class": (C.c_int, [C.c_void_p]),
     "ceg_uniform_class": (C.c_int, [c_int64_p, c_double_p, C.c_int64, C.c_void_p, c_int32_p, C.c_int32, C.c_double, c_double_p]),
+    "ceg_plan_ew2_fine": (C.c_int, [C.c_void_p]),
+    "ceg_ew2_table": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int32, c_double_p, C.c_int64, c_int32_p, c_int32_p, c_int32_p, c_double_p]),
     "ceg_plan_num_images": (C.c_int64, [C.c_void_p]),
     "ceg_plan_copy_images": (C.c_int, [C.c_void_p, c_double_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
     "ceg_plan_build_vdw": (C.c_int, [

@@ -50,6 +50,12 @@ class _PlainBuilds:
         ``CEG_HIP_UNIFORM_CLASS=0`` (or 1) in the environment at plan creation caps it."""
         return int(self._lib.ceg_plan_uniform_class(self._h))
 
+    @property
+    def ew2_fine(self) -> bool:
+        """True if the plan holds the fine r^2-indexed Ewald table (``ceg_plan_ew2_fine``): the fused builds of uniform class 1 / 2 and
+        the Coulomb launches read it.  ``CEG_HIP_EW2_FINE=0`` in the environment at plan creation suppresses it."""
+        return bool(self._lib.ceg_plan_ew2_fine(self._h))
+
     # ------------------------------------------------------------------ raw FP64 sums at points
     def eval_points(self, which: str, points, algo: int = _abi.ALGO_AUTO) -> np.ndarray:
         """compute_derivatives_vdw / _ewald (probes.jl:71-117) at cartesian points ->
@@ -196,3 +202,22 @@ class MultiGridPlan(_PlainBuilds):
         lc, tc = coulomb_scaling()
         _abi.check(self._lib, self._lib.ceg_plan_build_multi(self._h, lv, tv, lc, tc, i_begin, i_end, ptrs, int(d_coulomb) if d_coulomb else None,
                                                              channel_stride, i_origin, stream))
+
+
+
+def ew2_table(alpha: float, cutoff2: float, fine: bool, r_exact2: float = 4.0):
+    """The r^2-indexed table of the real-space Ewald functions a plan builds (``ceg_ew2_table``; host only).  Returns
+    ``(table[ni, stride] or None, base, ni, worst, used)``: ``used`` says whether a plan would take the table; ``table`` is ``None``
+    when none was built (more intervals than the kernels hold -- ``ni`` is then the number needed -- or arguments out of range)."""
+    lib = _abi.load_library()
+    base, ni, stride, worst = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+    rc = lib.ceg_ew2_table(alpha, r_exact2, cutoff2, int(fine), None, 0, C.byref(base), C.byref(ni), C.byref(stride), C.byref(worst))
+    if rc < 0:
+        _abi.check(lib, rc)
+    if stride.value == 0:
+        return None, base.value, ni.value, worst.value, False
+    tab = np.empty((ni.value, stride.value), dtype=np.float64)
+    rc = lib.ceg_ew2_table(alpha, r_exact2, cutoff2, int(fine), _abi.dptr(tab), tab.size, None, None, None, None)
+    if rc < 0:
+        _abi.check(lib, rc)
+    return tab, base.value, ni.value, worst.value, bool(rc)

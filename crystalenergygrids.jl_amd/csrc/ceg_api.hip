@@ -133,6 +133,8 @@ struct ceg_plan {
     bool fast_ewald = false;     // alpha*cutoff within the erfcx polynomial's domain
     bool ew2 = false;            // r^2-indexed Ewald tables built (hot-loop variant EWK = 2)
     double* d_ew2 = nullptr;
+    bool ew2f = false;           // and the fine layout beside them (EWK = 3 where a variant can hold it)
+    double* d_ew2f = nullptr;
     // multi-probe plans (ceg_plan_create_multi): the rule tables of every probe; d_pc holds probe 0 in its single-probe slots and
     // all of them in rtm / fastm, d_pc_probe[p] is the same block with probe p in the single-probe slots (launches of one probe)
     struct ProbeTab {
@@ -838,28 +840,54 @@ bool build_ewald_tables_uncached(double alpha, double cutoff2, std::vector<doubl
 }
 
 // r^2-indexed tables of B0(s) = erfc(alpha sqrt(s))/sqrt(s) and C(s) = 2 alpha/sqrt(pi) exp(-alpha^2 s) (ceg_internal.h,
-// CEG_EW2_*): per interval a degree-5 interpolant at the Chebyshev nodes of the interval, in long double, expressed in
-// t = s - s_lo (the interval's lower end: clearing the low bits of s gives it).  Returns false if the range needs more than CEG_EW2_NI_MAX intervals or a polynomial misses `tol`
-// (relative) anywhere -- the caller then keeps the erfcx / libm variants.
-// `which` 0: the two Ewald functions (record = CEG_EW2_STRIDE doubles, tolerance relative);  1: G0(s) = A exp(-B sqrt(s)) of a
+// CEG_EW2_* / CEG_EW2F_*): per interval an interpolant of the layout's degree at the Chebyshev nodes of the interval, in long double,
+// expressed in t = s - s_lo (the interval's lower end: clearing the low bits of s gives it).  Returns false if the range needs more
+// than the layout's ni_max intervals or a polynomial misses the tolerance (relative) anywhere -- the caller then keeps the erfcx /
+// libm variants (coarse layout) or the coarse table (fine layout).
+// `which` 0: the two Ewald functions (record = 2 (degree + 1) doubles, tolerance relative);  1: G0(s) = A exp(-B sqrt(s)) of a
 // Buckingham class with alpha := B, record = CEG_BK2_STRIDE doubles, tolerance relative to G0 at the start of the table + the
 // dispersion term C/s^3 it is added to (exp(-B r) spans 17 decades up to the cutoff).
-bool build_ew2_table_uncached(double alpha, double r_exact2, double cutoff2, std::vector<double>& tab, int32_t* base_out,
+struct Ew2Layout {
+    int logm;          // 2^logm intervals per octave of s
+    int degree;        // of each polynomial
+    int ni_max;        // intervals the kernels have room for
+    int cover_logm;    // the table ends where a table with 2^cover_logm intervals per octave ends (<= logm)
+    constexpr int shift() const { return 20 - logm; }              // bits of the high word below the interval key
+    constexpr int nd() const { return degree + 1; }                // coefficients per polynomial = Chebyshev nodes per interval
+    constexpr int stride() const { return 2 * nd(); }              // doubles per record of the Ewald pair
+    bool operator==(const Ew2Layout& o) const { return logm == o.logm && degree == o.degree && ni_max == o.ni_max && cover_logm == o.cover_logm; }
+};
+constexpr Ew2Layout EW2_COARSE{CEG_EW2_LOGM, 6, CEG_EW2_NI_MAX, CEG_EW2_LOGM};
+// (the fine table covers the range of the ordinary one, two intervals for each of its: 330 for 165 at 12 A, at most 352 for 176)
+constexpr Ew2Layout EW2_FINE{CEG_EW2F_LOGM, CEG_EW2F_ND - 1, CEG_EW2F_NI_MAX, CEG_EW2_LOGM};
+constexpr Ew2Layout BK2_LAYOUT{CEG_BK2_LOGM, CEG_BK2_ND - 1, CEG_BK2_NI_MAX, CEG_BK2_LOGM};
+static_assert(EW2_COARSE.stride() == CEG_EW2_STRIDE && EW2_COARSE.shift() == CEG_EW2_SHIFT, "coarse layout");
+static_assert(EW2_FINE.stride() == CEG_EW2F_STRIDE && EW2_FINE.shift() == CEG_EW2F_SHIFT, "fine layout");
+static_assert(BK2_LAYOUT.nd() <= CEG_BK2_STRIDE && BK2_LAYOUT.shift() == CEG_BK2_SHIFT, "Buckingham layout");
+
+bool build_ew2_table_uncached(double alpha, double r_exact2, double cutoff2, const Ew2Layout& lay, std::vector<double>& tab, int32_t* base_out,
                               int32_t* ni_out, double* worst_out, int which = 0, double bkA = 0.0, double bkC = 0.0)
 {
-    const int SHIFT = which == 0 ? CEG_EW2_SHIFT : CEG_BK2_SHIFT, ni_max = which == 0 ? CEG_EW2_NI_MAX : CEG_BK2_NI_MAX;
+    const int SHIFT = lay.shift(), ni_max = lay.ni_max;
     auto key_of = [SHIFT](double s) { uint64_t b; memcpy(&b, &s, 8); return (int32_t)((uint32_t)(b >> 32) >> SHIFT); };
-    if (!(alpha > 0.0) || !(r_exact2 >= 1.0) || !(cutoff2 > r_exact2)) return false;
-    const int32_t base = key_of(r_exact2), last = key_of(cutoff2 * (1.0 + 4e-9) + 4e-9);
+    *base_out = 0; *ni_out = 0; *worst_out = 0.0;
+    if (!(alpha > 0.0) || !(r_exact2 >= 1.0) || !(cutoff2 > r_exact2) || lay.degree < 1 || lay.logm < 0 || lay.logm > 12 || lay.cover_logm < 0 ||
+        lay.cover_logm > lay.logm)
+        return false;
+    const int up = lay.logm - lay.cover_logm;              // last interval: the one that ends where the covering layout's last one ends
+    const int32_t base = key_of(r_exact2), last = (((key_of(cutoff2 * (1.0 + 4e-9) + 4e-9) >> up) + 1) << up) - 1;
     const int32_t ni = last - base + 1;
+    *base_out = base; *ni_out = ni;
     if (ni < 1 || ni > ni_max) return false;
     const long double a = alpha, ka = 2.0L * a / sqrtl(3.14159265358979323846264338327950288L);
     auto B0 = [&](long double s) { const long double r = sqrtl(s); return which == 0 ? erfcl(a * r) / r : (long double)bkA * expl(-a * r); };
     auto Cf = [&](long double s) { return ka * expl(-a * a * s); };
-    const int nf = which == 0 ? 2 : 1, stride = which == 0 ? CEG_EW2_STRIDE : CEG_BK2_STRIDE;
-    const int ND = which == 0 ? 7 : CEG_BK2_ND;            // coefficients per polynomial: degree 6 (Ewald pair, 14 doubles) / degree 7
+    const int nf = which == 0 ? 2 : 1, stride = which == 0 ? lay.stride() : CEG_BK2_STRIDE;
+    const int ND = lay.nd();                               // coefficients per polynomial: degree 6 / 5 (Ewald pair, 14 / 12 doubles) / degree 7
+    const int NC = ND + 1;                                 // columns of the augmented Vandermonde matrix
     const long double PI = 3.14159265358979323846264338327950288L;
-    long double node[8];
+    std::vector<long double> node((size_t)ND), Vm((size_t)ND * NC), cu((size_t)ND), ct((size_t)ND);
+    auto V = [&](int r, int c) -> long double& { return Vm[(size_t)r * NC + c]; };
     for (int k = 0; k < ND; ++k) node[k] = cosl(PI * (k + 0.5L) / (long double)ND);       // u in [-1, 1]
     tab.assign((size_t)ni * stride, 0.0);
     double worst = 0.0;
@@ -871,28 +899,27 @@ bool build_ew2_table_uncached(double alpha, double r_exact2, double cutoff2, std
         memcpy(&s_lo, &lo_bits, 8); memcpy(&s_mid, &mid_bits, 8); memcpy(&s_hi, &hi_bits, 8);
         const long double hh = 0.5L * ((long double)s_hi - (long double)s_lo);           // half width; s_mid is the exact centre
         for (int f = 0; f < nf; ++f) {
-            long double V[8][9];
             for (int r = 0; r < ND; ++r) {
                 long double pw = 1.0L;
-                for (int c = 0; c < ND; ++c) { V[r][c] = pw; pw *= node[r]; }
+                for (int c = 0; c < ND; ++c) { V(r, c) = pw; pw *= node[r]; }
                 const long double s = (long double)s_mid + node[r] * hh;
-                V[r][ND] = f == 0 ? B0(s) : Cf(s);
+                V(r, ND) = f == 0 ? B0(s) : Cf(s);
             }
             for (int c = 0; c < ND; ++c) {                      // Gauss-Jordan with partial pivoting
                 int piv = c;
-                for (int r = c + 1; r < ND; ++r) if (fabsl(V[r][c]) > fabsl(V[piv][c])) piv = r;
-                for (int q = 0; q <= ND; ++q) std::swap(V[c][q], V[piv][q]);
-                const long double d = V[c][c];
-                for (int q = 0; q <= ND; ++q) V[c][q] /= d;
+                for (int r = c + 1; r < ND; ++r) if (fabsl(V(r, c)) > fabsl(V(piv, c))) piv = r;
+                for (int q = 0; q <= ND; ++q) std::swap(V(c, q), V(piv, q));
+                const long double d = V(c, c);
+                for (int q = 0; q <= ND; ++q) V(c, q) /= d;
                 for (int r = 0; r < ND; ++r) if (r != c) {
-                    const long double g = V[r][c];
-                    for (int q = 0; q <= ND; ++q) V[r][q] -= g * V[c][q];
+                    const long double g = V(r, c);
+                    for (int q = 0; q <= ND; ++q) V(r, q) -= g * V(c, q);
                 }
             }
             // P(u), u = (t - hh)/hh with t = s - s_lo  ->  coefficients in t (binomial expansion in long double)
-            long double cu[8], ct[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            std::fill(ct.begin(), ct.end(), 0.0L);
             long double sc = 1.0L;
-            for (int c = 0; c < ND; ++c) { cu[c] = V[c][ND] * sc; sc /= hh; }             // in (t - hh)
+            for (int c = 0; c < ND; ++c) { cu[c] = V(c, ND) * sc; sc /= hh; }             // in (t - hh)
             for (int c = 0; c < ND; ++c) {                                                 // (t - hh)^c = sum_k C(c,k) t^k (-hh)^(c-k)
                 long double binom = 1.0L;
                 for (int k = 0; k <= c; ++k) {
@@ -913,26 +940,29 @@ bool build_ew2_table_uncached(double alpha, double r_exact2, double cutoff2, std
             }
         }
     }
-    *base_out = base; *ni_out = ni; *worst_out = worst;
+    *worst_out = worst;
     return worst < 5e-11;
 }
 
-bool build_ew2_table(double alpha, double r_exact2, double cutoff2, std::vector<double>& tab, int32_t* base_out, int32_t* ni_out)
+// memoised per layout: a plan asks for the coarse and for the fine table of the same (alpha, r_exact2, cutoff2)
+bool build_ew2_table(double alpha, double r_exact2, double cutoff2, const Ew2Layout& lay, std::vector<double>& tab, int32_t* base_out,
+                     int32_t* ni_out, double* worst_out = nullptr)
 {
-    struct Memo { bool valid = false, ok = false; double alpha = 0, r_exact2 = 0, cutoff2 = 0; int32_t base = 0, ni = 0; std::vector<double> tab; };
+    struct Memo { bool valid = false, ok = false; Ew2Layout lay{0, 0, 0, 0}; double alpha = 0, r_exact2 = 0, cutoff2 = 0, worst = 0; int32_t base = 0, ni = 0; std::vector<double> tab; };
     static std::mutex m;
-    static Memo memo;
+    static Memo memos[2];
     std::lock_guard<std::mutex> lock(m);
-    if (!(memo.valid && memo.alpha == alpha && memo.r_exact2 == r_exact2 && memo.cutoff2 == cutoff2)) {
+    Memo& memo = memos[lay == EW2_COARSE ? 0 : 1];
+    if (!(memo.valid && memo.lay == lay && memo.alpha == alpha && memo.r_exact2 == r_exact2 && memo.cutoff2 == cutoff2)) {
         memo.tab.clear();
-        double worst = 0.0;
-        memo.ok = build_ew2_table_uncached(alpha, r_exact2, cutoff2, memo.tab, &memo.base, &memo.ni, &worst);
-        memo.alpha = alpha; memo.r_exact2 = r_exact2; memo.cutoff2 = cutoff2; memo.valid = true;
+        memo.ok = build_ew2_table_uncached(alpha, r_exact2, cutoff2, lay, memo.tab, &memo.base, &memo.ni, &memo.worst);
+        memo.lay = lay; memo.alpha = alpha; memo.r_exact2 = r_exact2; memo.cutoff2 = cutoff2; memo.valid = true;
         if (std::getenv("CEG_HIP_TRACE"))
-            fprintf(stderr, "[ceg_hip] r^2-indexed Ewald table: %d intervals, worst relative error %.2e -> %s\n", memo.ni, worst,
-                    memo.ok ? "used" : "not used");
+            fprintf(stderr, "[ceg_hip] r^2-indexed Ewald table (%d per octave, degree %d): %d intervals, worst relative error %.2e -> %s\n",
+                    1 << lay.logm, lay.degree, memo.ni, memo.worst, memo.ok ? "used" : "not used");
     }
     tab = memo.tab; *base_out = memo.base; *ni_out = memo.ni;
+    if (worst_out) *worst_out = memo.worst;
     return memo.ok;
 }
 
@@ -945,7 +975,7 @@ bool build_bk2_table(double A, double B, double C, double r_exact2, double cutof
     if (!(memo.valid && memo.A == A && memo.B == B && memo.C == C && memo.r_exact2 == r_exact2 && memo.cutoff2 == cutoff2)) {
         memo.tab.clear();
         double worst = 0.0;
-        memo.ok = build_ew2_table_uncached(B, r_exact2, cutoff2, memo.tab, &memo.base, &memo.ni, &worst, 1, A, C) && worst < CEG_BK2_TOL;
+        memo.ok = build_ew2_table_uncached(B, r_exact2, cutoff2, BK2_LAYOUT, memo.tab, &memo.base, &memo.ni, &worst, 1, A, C) && worst < CEG_BK2_TOL;
         memo.A = A; memo.B = B; memo.C = C; memo.r_exact2 = r_exact2; memo.cutoff2 = cutoff2; memo.valid = true;
         if (std::getenv("CEG_HIP_TRACE"))
             fprintf(stderr, "[ceg_hip] r^2-indexed Buckingham table: %d intervals, worst error %.2e of the pair energy -> %s\n", memo.ni, worst,
@@ -1185,12 +1215,22 @@ static int create_impl(ceg_plan_t** plan, int32_t device,
             if (ok && want_ewald && !rc && !std::getenv("CEG_HIP_NO_EW2")) {
                 std::vector<double> t2;
                 int32_t base = 0, ni = 0;
-                if (build_ew2_table(alpha, p->r_exact2, cutoff2, t2, &base, &ni)) {
+                if (build_ew2_table(alpha, p->r_exact2, cutoff2, EW2_COARSE, t2, &base, &ni)) {
                     rc = upload(&p->d_ew2, t2.data(), t2.size());
                     hc.ew2_tab = p->d_ew2;
                     hc.ew2_ni = ni;
                     hc.ew2_base = base;
                     p->ew2 = !rc;
+                }
+                // the fine layout beside it (a cutoff that needs more intervals than the kernels hold has none: nothing else changes).
+                // CEG_HIP_EW2_FINE=0 keeps the coarse table alone: one library runs both paths (tests, A/B)
+                const char* fine_env = std::getenv("CEG_HIP_EW2_FINE");
+                if (p->ew2 && !(fine_env && atoi(fine_env) == 0) && build_ew2_table(alpha, p->r_exact2, cutoff2, EW2_FINE, t2, &base, &ni)) {
+                    rc = upload(&p->d_ew2f, t2.data(), t2.size());
+                    hc.ew2f_tab = p->d_ew2f;
+                    hc.ew2f_ni = ni;
+                    hc.ew2f_base = base;
+                    p->ew2f = !rc;
                 }
             }
         }
@@ -1305,7 +1345,7 @@ extern "C" int ceg_plan_destroy(ceg_plan_t* p)
     (void)hipDeviceSynchronize();          // what hipFree would do: no kernel of this plan is still running
     p->images.reset();                     // the image arrays belong to the (possibly cached, possibly shared) ImageSet
     for (void* ptr : {(void*)p->d_atoms, (void*)p->d_kind, (void*)p->d_rules, (void*)p->d_offset, (void*)p->d_pc, (void*)p->d_erfcx,
-                      (void*)p->d_exp2, (void*)p->d_fast, (void*)p->d_ew2, (void*)p->d_bk2})
+                      (void*)p->d_exp2, (void*)p->d_fast, (void*)p->d_ew2, (void*)p->d_ew2f, (void*)p->d_bk2})
         cached_free(ptr);
     for (auto& t : p->probes)
         for (void* ptr : {(void*)t.d_rules, (void*)t.d_offset, (void*)t.d_fast, (void*)t.d_pc, (void*)t.d_bk2, (void*)t.d_imgkind}) cached_free(ptr);
@@ -1328,6 +1368,28 @@ extern "C" int ceg_plan_uniform_class(const ceg_plan_t* p)
 {
     if (!p) return 0;
     return p->nprobes > 0 ? p->probes[0].uni.cls : p->uni.cls;
+}
+
+extern "C" int ceg_plan_ew2_fine(const ceg_plan_t* p) { return (p && p->ew2f) ? 1 : 0; }
+
+// host only: the r^2-indexed Ewald table a plan with these parameters builds, coarse (fine == 0) or fine layout
+extern "C" int ceg_ew2_table(double alpha, double r_exact2, double cutoff2, int32_t fine, double* table, int64_t capacity, int32_t* base,
+                             int32_t* ni, int32_t* stride, double* worst)
+{
+    const Ew2Layout& lay = fine ? EW2_FINE : EW2_COARSE;
+    std::vector<double> t;
+    int32_t b = 0, n = 0;
+    double w = 0.0;
+    const bool ok = build_ew2_table(alpha, r_exact2, cutoff2, lay, t, &b, &n, &w);
+    if (base) *base = b;
+    if (ni) *ni = n;
+    if (stride) *stride = t.empty() ? 0 : lay.stride();
+    if (worst) *worst = w;
+    if (table && !t.empty()) {          // (a fit that misses the tolerance is still returned: its errors are what a test looks at)
+        if (capacity < (int64_t)t.size()) return fail(CEG_ERR_INVALID, "table needs %lld doubles, capacity %lld", (long long)t.size(), (long long)capacity);
+        memcpy(table, t.data(), t.size() * sizeof(double));
+    }
+    return ok ? 1 : 0;
 }
 
 // host only: the classification of convert_rules + detect_uniform_class on a caller's tables
@@ -1401,7 +1463,7 @@ int run(ceg_plan* p, int mode, const Output& out, const Points& pts, bool culled
         // (the uniform class of the plan or of probe 0: these calls only; ceg_plan_build_multi keeps the per-candidate records, so that
         //  a grid does not depend on how that call cuts a request into launches)
         e = launch_culled(mode, probe0 ? p->probes[0].d_pc : p->d_pc, p->g, probe0 ? p->probes[0].vdwk : p->vdwk,
-                          p->ew2 ? 2 : (p->fast_ewald ? 1 : 0), out, pts, stream, probe0 ? p->probes[0].uni.cls : p->uni.cls);
+                          p->ew2 ? (p->ew2f ? 3 : 2) : (p->fast_ewald ? 1 : 0), out, pts, stream, probe0 ? p->probes[0].uni.cls : p->uni.cls);
     } else {
         AtomTable at{p->d_atoms, p->has_rules ? p->d_kind : nullptr, p->natoms};
         e = launch_bruteforce(mode, p->g, at, rt, out, pts, stream);
@@ -1501,7 +1563,9 @@ extern "C" int ceg_plan_build_multi(ceg_plan_t* p, double lambda_vdw, double thr
     if (!guard.ok) return fail(CEG_ERR_HIP, "hipSetDevice(%d) failed", p->device);
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipSuccess;
-    const int ewk = p->ew2 ? 2 : (p->fast_ewald ? 1 : 0);        // real-space Ewald arithmetic available to this plan
+    // real-space Ewald arithmetic available to this plan (never the fine table: the fused multi-probe variants cannot hold it, and the
+    // Coulomb grid must not depend on how this call cuts a request into launches)
+    const int ewk = p->ew2 ? 2 : (p->fast_ewald ? 1 : 0);
     auto single = [&](int mode, int q) {          // one probe (q >= 0) and / or the Coulomb grid: the single-probe kernels of the probe's class
         Output o = base;
         o.vdw = q >= 0 ? d_out_vdw[q] : nullptr;

@@ -145,6 +145,10 @@ struct PlanConst {
     // multi-probe plans (all probes Lennard-Jones-only): per probe the rule table (exact path) and the per-kind fast records
     RuleTable rtm[CEG_MAX_PROBES];
     const FastVdw* fastm[CEG_MAX_PROBES];
+    // the two functions of ew2_tab on the fine layout (EWK = 3, CEG_EW2F_*): [ew2f_ni][CEG_EW2F_STRIDE]; null / 0 when the plan has none
+    const double* ew2f_tab;
+    int32_t ew2f_ni;           // intervals in the table (<= CEG_EW2F_NI_MAX)
+    int32_t ew2f_base;         // key of the first interval: hi32(r_exact2) >> CEG_EW2F_SHIFT
 };
 
 // shared between the host table builder and the kernels
@@ -168,6 +172,22 @@ constexpr int CEG_EW2_STRIDE = 14;                             // doubles per in
 #define CEG_EW2_LDS_STRIDE 14                                   // LDS stride of the record in the single-probe kernels (15: see k_culled)
 #endif
 constexpr int CEG_EW2_NI_MAX = 176;                            // cutoff 12 A from r_exact 2 A: 165 intervals
+// Fine layout (EWK = 3): 64 intervals per octave, two degree-5 polynomials, 6 + 6 coefficients = 96 B.  Halving the intervals buys
+// back what the lower degree loses (the last octave before a 12 A cutoff: 1.2e-11 against degree 6's 9.9e-12 on 32 per octave) and
+// each Horner chain is one step and the record one 16-byte read shorter.  Twice the intervals: 330 x 96 B for 12 A, which only the
+// variants with 48-byte candidate records can hold beside their staging arrays (k_culled).  The LDS stride is a build-time
+// choice between 12 doubles (96 B: records start on 8 of the 16 bank groups) and 14 (112 B: on all 16, 5.5 KB more).  Measured
+// on the roofline workload (profiles/ew2_fine_ab.txt): at 96 B the bank conflicts eat the gain (fused 12.65 ms like the parent,
+// Coulomb 10.99 against 10.46 ms), at 112 B fused 12.25 and Coulomb 10.02 ms.
+constexpr int CEG_EW2F_LOGM = 6;
+constexpr int CEG_EW2F_SHIFT = 20 - CEG_EW2F_LOGM;
+constexpr int CEG_EW2F_ND = 6;                                 // coefficients per polynomial (degree 5)
+constexpr int CEG_EW2F_STRIDE = 2 * CEG_EW2F_ND;               // doubles per interval record
+#ifndef CEG_EW2F_LDS_STRIDE
+#define CEG_EW2F_LDS_STRIDE 14                                  // LDS stride of the fine record: 12 or 14 doubles
+#endif
+static_assert(CEG_EW2F_LDS_STRIDE == 12 || CEG_EW2F_LDS_STRIDE == 14, "fine records are read with 16-byte loads");
+constexpr int CEG_EW2F_NI_MAX = 352;                           // cutoff 12 A from r_exact 2 A: 330 intervals
 // Single Buckingham class: G0(s)/C = (A/C) exp(-B sqrt(s)) on the SAME intervals as the Ewald pair (one key and one t per
 // candidate serve both tables), one degree-7 polynomial per interval (64 B).  Round 2 used degree 5 on 64 intervals per octave
 // (3e-13 of the pair energy: up to 77 ULP in stored values where the attractive and repulsive sums of a channel cancel);
@@ -187,7 +207,7 @@ constexpr double CEG_BK2_TOL = 2e-14;                          // of G0 + C/s^3,
 hipError_t launch_bruteforce(int mode, const Geom& g, const AtomTable& atoms, const RuleTable& rt,
                              const Output& out, const Points& pts, hipStream_t stream);
 // ewk: real-space Ewald arithmetic of the hot loop -- 0 libm-grade erfc / exp, 1 erfcx table + exp (alpha*cutoff <= 5),
-// 2 r^2-indexed tables
+// 2 r^2-indexed tables, 3 the plan also has the fine r^2-indexed table (used by the variants that can hold it, else as 2)
 // uni: the plan's uniform class (PlanConst::uni_class of d_pc; 0 keeps the per-candidate records).  It selects VDWK = 4 / 5 for
 // single-probe Lennard-Jones launches (vdwk == 1), see launch_cull_flags.
 hipError_t launch_culled(int mode, const PlanConst* d_pc, const Geom& g, int vdwk, int ewk,

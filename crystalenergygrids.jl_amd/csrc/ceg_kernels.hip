@@ -399,7 +399,7 @@ constexpr int culled_nw(int mode, int vdwk, int ewk, int np = 1)
 {
     // multi-probe records are 48 + 32 np bytes; VdW-only: 4 waves x 64 x (112 .. 176) B, three or four workgroups per CU
     return np > 1 ? (mode == 2 ? CEG_NW_MULTI_FUSED : CEG_WG / 64)
-                  : ((mode != 0 && ewk == 2) || (mode != 1 && vdwk == 3)) ? CEG_NW_EW2 : CEG_WG / 64;
+                  : ((mode != 0 && ewk >= 2) || (mode != 1 && vdwk == 3)) ? CEG_NW_EW2 : CEG_WG / 64;
 }
 [[maybe_unused]] constexpr double R_EXACT2 = CEG_R_EXACT2;
 static_assert(ERFCX_TAB_N == CEG_ERFCX_TAB_N, "table size mismatch");
@@ -580,7 +580,9 @@ __device__ __forceinline__ void set_lj_record(CandRecS&, int, Quad) {}
 //   (EWK replaces round 1's FASTEW flag; FASTEW = EWK != 0 below: the erfcx-polynomial slow path is valid)
 //           polynomial, no division); otherwise libm-style erfc/exp
 //   EWK     real-space Ewald term: 0 libm-style erfc / exp; 1 (alpha*cutoff <= ERFCX_XMAX) one table exp + erfcx table,
-//           no division; 2 B0(r^2), C(r^2) from r^2-indexed polynomial tables + the B_n recurrence, no sqrt / exp / erfc
+//           no division; 2 B0(r^2), C(r^2) from r^2-indexed polynomial tables + the B_n recurrence, no sqrt / exp / erfc;
+//           3: 2 on the fine layout (64 intervals per octave, degree 5: one Horner step per chain and one 16-byte read fewer per
+//           pair).  Its table is twice as long: only beside the 48-byte candidate records (VDWK 4 / 5 fused, Coulomb mode)
 //   NP      probes per launch (multi-probe plans: NP > 1 needs VDWK = 1, grid mode, EWK = 2): NP VdW accumulator sets, the
 //           candidate record carries the Lennard-Jones parameters of its kind for each probe; distance, 1/r^2, products and
 //           the Coulomb part are shared.  The per-pair arithmetic and the order of the sums are those of the NP = 1 kernel:
@@ -592,11 +594,14 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
     static_assert(NP >= 1 && NP <= CEG_MAX_PROBES && (NP == 1 || (VDWK == 1 && !POINTS && EWK == 2 && MODE != MODE_COULOMB)), "multi-probe variant");
     constexpr bool MULTI = NP > 1;
     constexpr bool FASTEW = EWK != 0;
-    constexpr bool EW2 = EWK == 2 && MODE != MODE_VDW;
+    constexpr bool EW2 = EWK >= 2 && MODE != MODE_VDW;
+    constexpr bool EW2F = EWK == 3 && MODE != MODE_VDW;           // fine layout of the r^2-indexed tables
+    static_assert(EWK >= 0 && EWK <= 3 && (EWK != 3 || (NP == 1 && VDWK != 3 && MODE != MODE_VDW)), "the fine Ewald table never meets the Buckingham table or multi-probe records");
+    static_assert(EWK != 3 || MODE == MODE_COULOMB || (MODE == MODE_FUSED && vdwk_uniform(VDWK)), "the fine Ewald table fits beside 48-byte candidate records only");
     constexpr int WG = 64 * culled_nw(MODE, VDWK, EWK, NP);
     constexpr bool BK2 = VDWK == 3 && MODE != MODE_COULOMB;       // one Buckingham class, G0(r^2) tabulated
     constexpr bool UNI = vdwk_uniform(VDWK) && MODE != MODE_COULOMB;        // one Lennard-Jones record for every VdW-active image
-    constexpr bool UNIQ = VDWK == 5 && MODE == MODE_FUSED && EWK == 2;      // and one charge
+    constexpr bool UNIQ = VDWK == 5 && MODE == MODE_FUSED && EWK >= 2;      // and one charge
     static_assert(!vdwk_uniform(VDWK) || (NP == 1 && MODE != MODE_COULOMB && (VDWK == 4 || UNIQ)), "uniform variants");
     // One workgroup = CEG_WG/64 waves; each wave owns one tile and its own slice of the staging
     // arrays (waves never touch each other's slice, so no workgroup barrier inside the loops --
@@ -615,8 +620,13 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
     // apart meet in the same banks, and a wave spans 10-40 intervals -- 30 % of the LDS-active cycles of the fused kernel were conflict
     // cycles) or 15 (120 B = 30 banks: 32 intervals apart; the record is then read as 8-byte pairs).  Single-probe
     // variants only: the multi-probe variants have no 1.4 KB of LDS to spare.
-    constexpr int EW2_LS = (NP == 1) ? CEG_EW2_LDS_STRIDE : CEG_EW2_STRIDE;
-    __shared__ __attribute__((aligned(16))) double s_ew2[EW2 ? CEG_EW2_NI_MAX * EW2_LS : 2];
+    // Fine layout: 12 doubles as built (96 B: records start on 8 of the 16 bank groups) or 14 (112 B: on all 16 -- the one that
+    // is faster than the ordinary table, ceg_internal.h), CEG_EW2F_LDS_STRIDE.
+    constexpr int EW2_TS = EW2F ? CEG_EW2F_STRIDE : CEG_EW2_STRIDE;                     // record of the table as it is built
+    constexpr int EW2_LS = EW2F ? CEG_EW2F_LDS_STRIDE : (NP == 1) ? CEG_EW2_LDS_STRIDE : CEG_EW2_STRIDE;
+    constexpr int EW2_NI = EW2F ? CEG_EW2F_NI_MAX : CEG_EW2_NI_MAX;
+    constexpr int EW2_SH = EW2F ? CEG_EW2F_SHIFT : CEG_EW2_SHIFT;                       // bits of the high word below the interval key
+    __shared__ __attribute__((aligned(16))) double s_ew2[EW2 ? EW2_NI * EW2_LS : 2];
     __shared__ __attribute__((aligned(16))) double s_bk2[BK2 ? CEG_BK2_NI_MAX * CEG_BK2_STRIDE : 2];
     __shared__ double s_exp2[64];
     __shared__ int32_t s_org[NW][4];             // tile origins for the output transpose (grid mode)
@@ -629,8 +639,10 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
 
     constexpr bool FASTVDW = VDWK != 0;
     if (EW2) {
-        const int nt = pc->ew2_ni * CEG_EW2_STRIDE;
-        for (int t = threadIdx.x; t < nt; t += WG) s_ew2[(t / CEG_EW2_STRIDE) * EW2_LS + t % CEG_EW2_STRIDE] = pc->ew2_tab[t];
+        const double* __restrict__ tab = EW2F ? pc->ew2f_tab : pc->ew2_tab;
+        const int ni = EW2F ? pc->ew2f_ni : pc->ew2_ni;
+        const int nt = (ni < EW2_NI ? ni : EW2_NI) * EW2_TS;
+        for (int t = threadIdx.x; t < nt; t += WG) s_ew2[(t / EW2_TS) * EW2_LS + t % EW2_TS] = tab[t];
     } else if (FASTEW && MODE != MODE_VDW) {
         for (int t = threadIdx.x; t < ERFCX_TAB_N * 6; t += WG) s_erfcx[t] = pc->erfcx_tab[t];
     }
@@ -740,7 +752,7 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
     const int hi_cut = __builtin_amdgcn_readfirstlane(__double2hiint(cut_hi));
     const double int_lo = uniform(r_exact2 * (1.0 + 4e-6)), int_hi = uniform(reg_hi * (1.0 - 4e-6));
     // r^2-indexed tables: record of the interval with key k starts at s_ew2 + (k - ew2_base) * STRIDE
-    const int ew2_off = EW2 ? __builtin_amdgcn_readfirstlane(-pc->ew2_base * (EW2_LS * 8)) : 0;
+    const int ew2_off = EW2 ? __builtin_amdgcn_readfirstlane(-(EW2F ? pc->ew2f_base : pc->ew2_base) * (EW2_LS * 8)) : 0;
     int ew2_stride = EW2_LS * 8;              // kept in a VGPR: v_mad_u32_u24 reads one scalar operand (ew2_off)
     asm volatile("" : "+v"(ew2_stride));
     const double ew_k3 = pc->ew_k3, ew_k15 = pc->ew_k15;       // 2 alpha^2 / 3, 4 alpha^4 / 15
@@ -945,10 +957,10 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
                 // interval of s = r2 in the r^2-indexed tables: key = exponent + leading mantissa bits, t = s - start of the interval
                 int key = 0;
                 double t = 0.0;
-                static_assert(CEG_BK2_SHIFT == CEG_EW2_SHIFT, "the Buckingham table shares the interval key of the Ewald tables");
+                static_assert(CEG_BK2_SHIFT == CEG_EW2_SHIFT && !(BK2 && EW2F), "the Buckingham table shares the interval key of the Ewald tables");
                 if (EW2 || (BK2 && WITH_VDW)) {
-                    key = (int)((unsigned)hi >> CEG_EW2_SHIFT);
-                    t = r2 - __hiloint2double(hi & (int)(0xffffffffu << CEG_EW2_SHIFT), 0);
+                    key = (int)((unsigned)hi >> EW2_SH);
+                    t = r2 - __hiloint2double(hi & (int)(0xffffffffu << EW2_SH), 0);
                 }
                 if constexpr (WITH_VDW && MULTI) {
                     // the LJ branch below, once per probe: 1/r^2 and its powers are shared, the expressions are the same
@@ -1073,6 +1085,21 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
                         //   B1 = (B0 + C)/s,  B2 = (3 B1 + 2 alpha^2 C)/s,  B3 = (5 B2 + 4 alpha^4 C)/s
                         //   v = q B0,  p1 = -q B1,  p2 = q B2,  p3 = -q B3
                         const char* recp = reinterpret_cast<const char*>(s_ew2) + mad_u24(key, ew2_stride, ew2_off);
+                        double b0, cc;
+                        if constexpr (EW2F) {                               // two degree-5 polynomials: a0..a5, c0..c5
+                            const double2* rec = reinterpret_cast<const double2*>(recp);
+                            const double2 a01 = rec[0], a23 = rec[1], a45 = rec[2], c01 = rec[3], c23 = rec[4], c45 = rec[5];
+                            b0 = __builtin_fma(a45.y, t, a45.x);
+                            cc = __builtin_fma(c45.y, t, c45.x);
+                            b0 = __builtin_fma(b0, t, a23.y);
+                            cc = __builtin_fma(cc, t, c23.y);
+                            b0 = __builtin_fma(b0, t, a23.x);
+                            cc = __builtin_fma(cc, t, c23.x);
+                            b0 = __builtin_fma(b0, t, a01.y);
+                            cc = __builtin_fma(cc, t, c01.y);
+                            b0 = __builtin_fma(b0, t, a01.x);
+                            cc = __builtin_fma(cc, t, c01.x);
+                        } else {
                         double2 a01, a23, a45, a6c0, c12, c34, c56;
                         if (EW2_LS % 2 == 0) {
                             const double2* rec = reinterpret_cast<const double2*>(recp);
@@ -1083,8 +1110,8 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
                             a6c0 = make_double2(rec[6], rec[7]); c12 = make_double2(rec[8], rec[9]); c34 = make_double2(rec[10], rec[11]);
                             c56 = make_double2(rec[12], rec[13]);
                         }
-                        double b0 = __builtin_fma(a6c0.x, t, a45.y);
-                        double cc = __builtin_fma(c56.y, t, c56.x);
+                        b0 = __builtin_fma(a6c0.x, t, a45.y);
+                        cc = __builtin_fma(c56.y, t, c56.x);
                         b0 = __builtin_fma(b0, t, a45.x);
                         cc = __builtin_fma(cc, t, c34.y);
                         b0 = __builtin_fma(b0, t, a23.y);
@@ -1095,6 +1122,7 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
                         cc = __builtin_fma(cc, t, c12.x);
                         b0 = __builtin_fma(b0, t, a01.x);
                         cc = __builtin_fma(cc, t, a6c0.y);
+                        }
                         // accumulated as B2/3 and B3/15 (one FMA + one product per step); the factors are applied once per tile
                         // (uniform charge: the VdW-active group in units of q; the record of a Coulomb-only candidate holds q_i / q)
                         const double qb0 = (UNIQ && WITH_VDW) ? b0 : A.w * b0, qc = (UNIQ && WITH_VDW) ? cc : A.w * cc;
@@ -1358,19 +1386,28 @@ static hipError_t launch_cull_flags(int vdwk, int ewk, int uni, hipStream_t stre
     //   VDW       (1, any), uni >= 1    <4, 1>               one Lennard-Jones record for the whole plan (PlanConst::uni_class): constants deferred
     //   FUSED     (1, 2), uni 1 | 2     <4, 2> <5, 2>        the same beside the r^2-indexed tables; 5: the charge of the VdW-active images deferred too
     //   FUSED     (1, 1) (1, 0), uni    <1, 1> <1, 0>        the uniform variants are instantiated beside EWK = 2 only
+    //   FUSED     (1, 3), uni 1 | 2     <4, 3> <5, 3>        the plan has the fine r^2-indexed table and the 48-byte records leave room for it
+    //   COULOMB   (any, 3)              <1, 3>               the same: charge-only records
+    //   any       (v, 3) otherwise      as (v, 2)            80-byte and multi-probe records, the Buckingham table: the coarse table stays
     // Multi-probe launches (launch_multi_t) are <1, 2, NP> only: Lennard-Jones probes on the r^2-indexed tables.
     if (MODE == MODE_VDW) ewk = 1;
     if (MODE == MODE_COULOMB) vdwk = 1;
+    const bool fine = ewk == 3;
+    if (fine) ewk = 2;
     if (ewk == 2 && vdwk == 0) ewk = 1;          // the generic rule interpreter keeps the erfcx variant
     if (vdwk == 3 && MODE == MODE_FUSED && ewk != 2) vdwk = 2;     // the tabulated Buckingham class is instantiated beside EWK = 2 only
     if (vdwk == 1 && uni > 0 && MODE == MODE_VDW) vdwk = 4;
     if (vdwk == 1 && uni > 0 && MODE == MODE_FUSED && ewk == 2) vdwk = uni == 2 ? 5 : 4;
+    if (fine && ewk == 2 && (MODE == MODE_COULOMB || (MODE == MODE_FUSED && (vdwk == 4 || vdwk == 5)))) ewk = 3;
     const int nw = culled_nw(MODE, vdwk, ewk);
     const int64_t nblocks = (ntiles + nw - 1) / nw;
     if (nblocks > 0x7fffffffLL) return hipErrorInvalidValue;
     const dim3 grid((unsigned)nblocks), block(64 * nw);
 #define CEG_LAUNCH(V, F) hipLaunchKernelGGL((k_culled<MODE, POINTS, V, F>), grid, block, 0, stream, pc, out, pts, tj, tk, ntiles)
-    if (ewk == 2 && MODE != MODE_VDW) {
+    if (ewk == 3) {
+        if constexpr (MODE == MODE_COULOMB) CEG_LAUNCH(1, 3);
+        else if constexpr (MODE == MODE_FUSED) { if (vdwk == 4) CEG_LAUNCH(4, 3); else CEG_LAUNCH(5, 3); }
+    } else if (ewk == 2 && MODE != MODE_VDW) {
         if (vdwk == 1) CEG_LAUNCH(1, 2); else if (vdwk == 3) CEG_LAUNCH(3, 2);
         else if (vdwk == 4) { if constexpr (MODE == MODE_FUSED) CEG_LAUNCH(4, 2); }
         else if (vdwk == 5) { if constexpr (MODE == MODE_FUSED) CEG_LAUNCH(5, 2); }

@@ -234,6 +234,26 @@ CEG_API int ceg_plan_uniform_class(const ceg_plan_t* plan);
 CEG_API int ceg_uniform_class(const int64_t* atomkind, const double* charge, int64_t natoms, const ceg_rule_t* rules,
                               const int32_t* rule_offset, int32_t nkinds, double cutoff2, double constants[4]);
 
+/* 1 if the plan holds the fine r^2-indexed table of the real-space Ewald functions (64 intervals per octave of r^2, two degree-5
+ * polynomials per interval) beside the ordinary one (32 per octave, degree 6), else 0.  The fused builds of uniform class 1 / 2 and
+ * the Coulomb build and point evaluation of a single-probe plan then read the fine table (one Horner step per function and one
+ * 16-byte read fewer per pair); every other launch, ceg_plan_build_multi included, keeps the ordinary table.  A plan has none
+ * without an Ewald term, when cutoff^2 lies more than 352 intervals above the radius of the exact path (12 A: 330), or with
+ * CEG_HIP_EW2_FINE=0 in the environment at plan creation (one library runs both paths: tests, A/B).  Results of the two tables agree
+ * within the fit's error: below 1.5e-11 of the pair term at a 12 A cutoff, where the ordinary table is at 1e-11. */
+CEG_API int ceg_plan_ew2_fine(const ceg_plan_t* plan);
+/* The table such a plan builds, without a device (diagnostics, CPU tests): fine = 0 the ordinary layout, 1 the fine one; r_exact2 the
+ * squared radius of the exact path (4.0 unless a hard sphere reaches further).  Interval k (0-based) covers the r^2 whose high
+ * 32 bits shifted right by 20 - log2(intervals per octave) equal base + k; its record is stride doubles, the coefficients of B0(s) =
+ * erfc(alpha sqrt(s))/sqrt(s) and then of C(s) = 2 alpha/sqrt(pi) exp(-alpha^2 s) in ascending powers of t = s - (start of the
+ * interval).  Returns 1 when a plan would use the table, 0 when it would not -- the range needs more intervals than the kernels hold
+ * (352 fine, 176 ordinary: no table is built, stride = 0, ni receives the number needed), the fit misses 5e-11 somewhere (the table is built and
+ * returned all the same), or the arguments are out of range (stride = 0, ni = 0) --, negative on error.  table (NULL = query) receives
+ * ni * stride doubles, capacity is its size in doubles; worst receives the largest relative error of the fit at 17 points per
+ * interval.  Any output may be NULL. */
+CEG_API int ceg_ew2_table(double alpha, double r_exact2, double cutoff2, int32_t fine, double* table, int64_t capacity, int32_t* base,
+                          int32_t* ni, int32_t* stride, double* worst);
+
 /* number of lattice images kept by the culled algorithm (0 before first use) */
 CEG_API int64_t ceg_plan_num_images(const ceg_plan_t* plan);
 /* The plan's lattice-image list copied to the host (diagnostics / tests: the list is built on the device since round 4 and must be
