@@ -48,6 +48,16 @@ class ReciprocalEwald:
                                                          enc, static, _abi.dptr(out)))
         return out
 
+    def launch_shape(self, natoms: int, n: int):
+        """``ceg_recip_launch_shape`` (host side only): the launch :meth:`energies` gives ``n`` placements of a molecule of
+        ``natoms`` atoms -> (waves per workgroup, constants in LDS (bool), placements per wave, dynamic LDS bytes)."""
+        ijk = np.ascontiguousarray(self.ef.kvec_ijk, dtype=np.int32).reshape(-1)
+        ks = np.asarray(self.ef.kspace.ks, dtype=np.int32)
+        out = np.zeros(4, dtype=np.int32)
+        _abi.check(self._lib, self._lib.ceg_recip_launch_shape(_abi.i32ptr(ijk), len(ijk) // 3, _abi.i32ptr(ks), int(natoms), int(n),
+                                                               _abi.i32ptr(out)))
+        return int(out[0]), bool(out[1]), int(out[2]), int(out[3])
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.ceg_recip_destroy(self._h)

@@ -184,6 +184,52 @@ extern "C" int ceg_recip_layout(const int32_t* kvec_ijk, int64_t nk, const int32
     return CEG_OK;
 }
 
+// The launch the kernel gets for a k-space box, its row layout (nrounds, ns), a molecule of `natoms` atoms and `n` placements:
+// which k_recip<C_IN_LDS, WAVES>, how many placements a wave walks, the dynamic LDS and the grid.  One place, so that
+// ceg_recip_energy_device and ceg_recip_launch_shape (host only) cannot drift apart.
+struct LaunchShape {
+    int tab_stride, waves, per_wave;
+    bool c_in_lds;
+    size_t tab_bytes, lds;
+    int64_t nblocks;
+};
+
+static int launch_shape(const int32_t ks[3], int nrounds, int ns, int32_t natoms, int64_t n, LaunchShape& s)
+{
+    if (natoms > MAX_ATOMS) return rerr(CEG_ERR_UNSUPPORTED, "molecule has more atoms than the kernel holds in LDS (16)");
+    s.tab_stride = ks[0] + 1 + 2 * ks[1] + 1 + 2 * ks[2] + 1;
+    s.waves = MAX_WAVES;
+    while (s.waves > 1 && sizeof(double2) * (size_t)s.waves * natoms * s.tab_stride > 40 * 1024) s.waves >>= 1;
+    s.tab_bytes = sizeof(double2) * (size_t)s.waves * natoms * s.tab_stride;
+    if (s.tab_bytes > 64 * 1024) return rerr(CEG_ERR_UNSUPPORTED, "tables do not fit in LDS");
+    // k-vector constants in LDS when they fit beside the tables (every placement reads all of them)
+    const size_t c_bytes = sizeof(double) * 3 * (size_t)ns * 64 + sizeof(int32_t) * ((((size_t)nrounds * 64) + 3) & ~(size_t)3);
+    s.c_in_lds = s.tab_bytes + c_bytes <= 64 * 1024;
+    s.lds = s.tab_bytes + (s.c_in_lds ? c_bytes : 0);
+    // placements per wave: amortise the staging of the constants, but keep >= ~4 workgroups per CU in flight
+    s.per_wave = 1;
+    if (s.c_in_lds) {
+        s.per_wave = 8;
+        while (s.per_wave > 1 && n / ((int64_t)s.per_wave * s.waves) < 2048) s.per_wave >>= 1;
+    }
+    s.nblocks = (n + (int64_t)s.waves * s.per_wave - 1) / ((int64_t)s.waves * s.per_wave);
+    return CEG_OK;
+}
+
+extern "C" int ceg_recip_launch_shape(const int32_t* kvec_ijk, int64_t nk, const int32_t ks[3], int32_t natoms, int64_t n, int32_t out[4])
+{
+    if (!ks || nk < 0 || (nk > 0 && !kvec_ijk) || natoms < 1 || n < 0 || !out) return rerr(CEG_ERR_INVALID, "bad argument");
+    if (int rc = check_kspace(kvec_ijk, nk, ks)) return rc;
+    const Layout l = choose_layout(kvec_ijk, nk, ks);
+    LaunchShape s;
+    if (int rc = launch_shape(ks, l.nrounds, l.ns, natoms, n, s)) return rc;
+    out[0] = s.waves;
+    out[1] = s.c_in_lds ? 1 : 0;
+    out[2] = s.per_wave;
+    out[3] = (int32_t)s.lds;
+    return CEG_OK;
+}
+
 extern "C" int ceg_recip_create(ceg_recip_t** handle, int32_t device, const int32_t* kvec_ijk, const double* kfactors,
                                 const double* sf_re, const double* sf_im, int64_t nk, const int32_t ks[3],
                                 const double invmat[9])
@@ -266,22 +312,12 @@ extern "C" int ceg_recip_energy_device(ceg_recip_t* h, const double* d_positions
     for (int a = 0; a < natoms; ++a) g.q[a] = charges[a];
     g.energy_net_charges = energy_net_charges;
     g.static_contribution = static_contribution;
-    const int tab_stride = h->ks[0] + 1 + 2 * h->ks[1] + 1 + 2 * h->ks[2] + 1;
-    int waves = MAX_WAVES;
-    while (waves > 1 && sizeof(double2) * (size_t)waves * natoms * tab_stride > 40 * 1024) waves >>= 1;
-    const size_t tab_bytes = sizeof(double2) * (size_t)waves * natoms * tab_stride;
-    if (tab_bytes > 64 * 1024) return rerr(CEG_ERR_UNSUPPORTED, "tables do not fit in LDS");
-    // k-vector constants in LDS when they fit beside the tables (every placement reads all of them)
-    const size_t c_bytes = sizeof(double) * 3 * (size_t)h->ns * 64 + sizeof(int32_t) * ((((size_t)h->nrounds * 64) + 3) & ~(size_t)3);
-    const bool c_in_lds = tab_bytes + c_bytes <= 64 * 1024;
-    const size_t lds = tab_bytes + (c_in_lds ? c_bytes : 0);
-    // placements per wave: amortise the staging of the constants, but keep >= ~4 workgroups per CU in flight
-    int per_wave = 1;
-    if (c_in_lds) {
-        per_wave = 8;
-        while (per_wave > 1 && n / ((int64_t)per_wave * waves) < 2048) per_wave >>= 1;
-    }
-    const int64_t nblocks = (n + (int64_t)waves * per_wave - 1) / ((int64_t)waves * per_wave);
+    LaunchShape ls;
+    if (int rc = launch_shape(h->ks, h->nrounds, h->ns, natoms, n, ls)) return rc;
+    const int tab_stride = ls.tab_stride, waves = ls.waves, per_wave = ls.per_wave;
+    const bool c_in_lds = ls.c_in_lds;
+    const size_t lds = ls.lds;
+    const int64_t nblocks = ls.nblocks;
     if (nblocks > 0x7fffffffLL) return rerr(CEG_ERR_INVALID, "too many placements");
     int prev = -1;
     (void)hipGetDevice(&prev);

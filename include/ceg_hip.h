@@ -430,6 +430,13 @@ CEG_API int ceg_recip_destroy(ceg_recip_t* handle);
  *  desc    [nrounds * 64]  (may be NULL; size it from a first call) i0 | (j + ky) << 9 | (k + kz) << 18 | round length << 27 */
 CEG_API int ceg_recip_layout(const int32_t* kvec_ijk, int64_t nk, const int32_t ks[3], int32_t* nrounds, int32_t* nslots,
                              int64_t* slot_of, int32_t* desc);
+/* Host side only (works without a device): the launch ceg_recip_energy* would give these k-vectors, a molecule of `natoms` atoms
+ * and `n` placements -- for diagnostics and for tests that must know which kernel variant they exercise.
+ *  out = { waves per workgroup (8, 4, 2, 1), 1 when the k-vector constants are staged in LDS else 0,
+ *          placements a wave walks (1, 2, 4, 8), dynamic LDS bytes }
+ * Refusals as at the launch: natoms > 16 and tables above 64 KiB CEG_ERR_UNSUPPORTED; the k-space checks of ceg_recip_create. */
+CEG_API int ceg_recip_launch_shape(const int32_t* kvec_ijk, int64_t nk, const int32_t ks[3], int32_t natoms, int64_t n,
+                                   int32_t out[4]);
 /* positions [n][natoms][3] A, charges [natoms] e, out [n] K -- host memory, synchronous.
  * energy_net_charges / static_contribution: the two EwaldContext constants (src/ewald.jl:497-544). */
 CEG_API int ceg_recip_energy(ceg_recip_t* handle, const double* positions, const double* charges,
