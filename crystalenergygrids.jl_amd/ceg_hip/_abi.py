@@ -65,6 +65,11 @@ assert (C.sizeof(GcmcParams), GCMC_SPECIES_DTYPE.itemsize, GCMC_STATS_DTYPE.item
 MC_BLOCK_DTYPE = np.dtype([('mask', '<u8'), ('dims', '<i4', (3,)), ('_pad', '<i4'), ('size', '<f8', (3,)), ('shift', '<f8', (3,)),
                            ('offset', '<f8', (3,)), ('mat', '<f8', (9,)), ('invmat', '<f8', (9,))], align=True)
 assert MC_BLOCK_DTYPE.itemsize == 240
+# ``ceg_mc_baseline_t`` (one record per chain) and the flag of ``ceg_mc_baseline`` / ``ceg_mc_group_baseline``
+MC_BASELINE_DTYPE = np.dtype([('framework_vdw', '<f8'), ('framework_direct', '<f8'), ('inter', '<f8'), ('recip_framework', '<f8'),
+                              ('recip_guests', '<f8'), ('nmol', '<i4'), ('natoms', '<i4')], align=True)
+assert MC_BASELINE_DTYPE.itemsize == 48
+MC_BASELINE_REFRESH = 1      # CEG_MC_BASELINE_REFRESH
 
 c_double_p = C.POINTER(C.c_double)
 c_float_p = C.POINTER(C.c_float)
@@ -205,6 +210,8 @@ PROTOTYPES = {
     "ceg_mc_group_sweep_gcmc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ceg_mc_group_set_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "ceg_mc_group_block_counts": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
+    "ceg_mc_baseline": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "ceg_mc_group_baseline": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ceg_energy_grid": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, c_double_p, c_double_p, C.c_int32,
                                   c_double_p, C.c_int32, c_double_p, c_int32_p,
                                   C.c_void_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p,

@@ -494,10 +494,67 @@ class DeviceMonteCarlo:
                         kind[q] = d
         return last
 
-    def baseline_energy(self):
-        """baseline_energy (montecarlo.jl:530-542) from the device-resident state: framework and guest-guest terms from row 0 of one
-        trial launch per molecule (every pair is seen from both sides, hence the 1/2), the reciprocal term from the total guest
-        structure factor kept on the device and the two EwaldContext constants (ewald.jl:497-544)."""
+    def ewald_constants(self):
+        """``(energy_net_charges, static_contribution)`` of the EwaldContext (ewald.jl:497-544) for the species counts of the DEVICE
+        state (``_slot``), not for ``mc.positions``: right after ``sweep_gcmc(..., positions=False)`` has changed the counts.  The
+        molecules are rigid, so the intramolecular term of a species comes from ``mc.models`` (or, without a model, from any molecule
+        of that species whose coordinates the host holds).  ``(0.0, 0.0)`` without Ewald summation.  The pair is kept for the
+        counts it was computed for: a run that asks again with the same counts pays for it once."""
+        from .hostmirror.ewald import ewald_context_constants
+        from .hostmirror.raspa import RASPASystem
+        mc = self.mc
+        if mc.ewald.alpha == 0.0:
+            return 0.0, 0.0
+        key = (id(mc.ewald), tuple(len(kind) for kind in self._slot))
+        kept = getattr(self, "_ewald_constants", None)
+        if kept is not None and kept[0] == key:
+            return kept[1]
+        systems = []
+        for i, kind in enumerate(self._slot):
+            if not kind:
+                continue
+            m = len(mc.ffidx[i])
+            shape = np.asarray(mc.models[i], dtype=np.float64).reshape(-1, 3) if len(getattr(mc, "models", ())) > i else None
+            if shape is None or len(shape) != m:
+                shape = next((np.asarray(p, dtype=np.float64).reshape(-1, 3) for p in mc.positions[i] if p is not None), None)
+            if shape is None:
+                raise ValueError(f"species {i}: neither a model nor a molecule with coordinates on the host (pull_positions() first)")
+            q = np.array([mc.charges[ix] for ix in mc.ffidx[i]], dtype=np.float64)
+            systems.append([RASPASystem(mc.mat, shape, [""] * m, np.zeros(m), q, True)] * len(kind))
+        self._ewald_constants = (key, ewald_context_constants(mc.ewald, systems))
+        return self._ewald_constants[1]
+
+    def _baseline_report(self, rec):
+        """One ``ceg_mc_baseline_t`` record into the reference's report: the two constants and the tail correction stay on the host."""
+        from .hostmirror import montecarlo as M
+        reciprocal = 0.0
+        if self.mc.ewald.alpha != 0.0:
+            enc, static = self.ewald_constants()
+            reciprocal = 2 * (float(rec["recip_framework"]) + enc) + float(rec["recip_guests"]) + static
+        return M.BaselineEnergyReport(float(rec["framework_vdw"]), float(rec["framework_direct"]), float(rec["inter"]), reciprocal,
+                                      self.mc.tailcorrection)
+
+    def baseline_record(self, refresh: bool = False) -> np.ndarray:
+        """``ceg_mc_baseline``: the raw ``_abi.MC_BASELINE_DTYPE`` record (framework, guest-guest and the two k-space sums, the
+        molecules and atoms summed) in two launches, four with ``refresh`` (every structure factor recomputed from the positions
+        first, as ``compute_ewald(::IncrementalEwaldContext)`` does)."""
+        rec = np.zeros(1, dtype=_abi.MC_BASELINE_DTYPE)
+        _abi.check(self._lib, self._lib.ceg_mc_baseline(self._h, _abi.MC_BASELINE_REFRESH if refresh else 0, rec.ctypes.data))
+        return rec[0]
+
+    def baseline_energy(self, route: str = "rows", refresh: bool = False):
+        """baseline_energy (montecarlo.jl:530-542) from the device-resident state.
+
+        ``route="rows"`` (the default): framework and guest-guest terms from row 0 of one trial launch per molecule (every pair is
+        seen from both sides, hence the 1/2), the reciprocal term from the total guest structure factor kept on the device and the
+        two EwaldContext constants (ewald.jl:497-544).  ``route="device"``: ``ceg_mc_baseline`` -- the whole state walked once on the
+        device, every pair once; ``refresh`` (this route only) recomputes the structure factors from the positions first."""
+        if route == "device":
+            return self._baseline_report(self.baseline_record(refresh))
+        if route != "rows":
+            raise ValueError(f"unknown route {route!r} (rows or device)")
+        if refresh:
+            raise ValueError("refresh belongs to route='device'")
         from .hostmirror import montecarlo as M
         from .hostmirror.ewald import ewald_context_constants
         mc = self.mc
@@ -629,6 +686,18 @@ class DeviceMonteCarloGroup:
         pocket, attempts = np.zeros(len(self.chains), dtype=np.int64), np.zeros(len(self.chains), dtype=np.int64)
         _abi.check(self._lib, self._lib.ceg_mc_group_block_counts(self._h, _abi.i64ptr(pocket), _abi.i64ptr(attempts)))
         return pocket, attempts
+
+    def baseline_records(self, refresh: bool = False) -> np.ndarray:
+        """``ceg_mc_group_baseline``: one ``_abi.MC_BASELINE_DTYPE`` record per chain, all chains in one pass (two launches, four with
+        ``refresh``); member ``c`` gets the bytes :meth:`DeviceMonteCarlo.baseline_record` gives for that chain."""
+        rec = np.zeros(len(self.chains), dtype=_abi.MC_BASELINE_DTYPE)
+        _abi.check(self._lib, self._lib.ceg_mc_group_baseline(self._h, _abi.MC_BASELINE_REFRESH if refresh else 0, rec.ctypes.data))
+        return rec
+
+    def baseline_energies(self, refresh: bool = False):
+        """baseline_energy (montecarlo.jl:530-542) of every chain -> list of ``BaselineEnergyReport``; the two Ewald constants come
+        from each chain's current species counts, the tail correction from its setup."""
+        return [chain._baseline_report(r) for chain, r in zip(self.chains, self.baseline_records(refresh))]
 
     def trial(self, moves):
         """One trial per chain: ``moves[c]`` is ``("move", idx, positions[n, m, 3])`` (rows: n + 1, row 0 where the molecule is now;

@@ -499,39 +499,13 @@ __global__ __launch_bounds__(MC_THREADS) void k_mc_accept(McView v, int32_t mole
 // sums[:, ij+1] of every molecule from its current positions (one workgroup per molecule)
 __global__ __launch_bounds__(MC_THREADS) void k_mc_sf_molecules(McView v, int stride)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-    __shared__ double s_pos[MC_MAX_ATOMS * 3];
-    __shared__ double s_q[MC_MAX_ATOMS];
-    const int tid = threadIdx.x, molecule = blockIdx.x;
-    const int first = v.mol[molecule].x, m = v.mol[molecule].y;
-    if (tid < m) {
-        const double4 A = v.atoms[first + tid];
-        int kind, mol;
-        unpack(A.w, kind, mol);
-        s_q[tid] = v.kind_charge[kind];
-        s_pos[3 * tid] = A.x; s_pos[3 * tid + 1] = A.y; s_pos[3 * tid + 2] = A.z;
-    }
-    __syncthreads();
-    double2* tab = reinterpret_cast<double2*>(s_raw);
-    fill_tables(v, s_pos, m, tab, stride, tid, MC_THREADS, s_q);
-    __syncthreads();
-    double2* mine = v.sf_mol + (size_t)molecule * v.nk;
-    rows_structure_factor(v, tab, stride, m, tid >> 6, MC_THREADS / 64, tid & 63,
-                          [&](int q, double sr, double si) { mine[q] = make_double2(sr, si); });
+    mc_sf_molecule_body(v, (int)blockIdx.x, stride);
 }
 
 // sums[:, 1] = sum over the molecules, in molecule order
 __global__ void k_mc_sf_total(McView v)
 {
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= v.nk) return;
-    double sr = 0.0, si = 0.0;
-    for (int j = 0; j < v.nmol; ++j) {
-        const double2 s = v.sf_mol[(size_t)j * v.nk + q];
-        sr += s.x;
-        si += s.y;
-    }
-    v.sf_tot[q] = make_double2(sr, si);
+    mc_sf_total_body(v, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 __global__ __launch_bounds__(MC_THREADS) void k_mc_insert(McView v, int32_t molecule, int32_t first, McMolecule nm, McPositions np, McCellOps ops, int stride)
@@ -730,7 +704,7 @@ extern "C" int ceg_mc_destroy(ceg_mc_t* h)
     if (guard.ok) {
         if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
         for (void* p : {(void*)h->d_vdw, (void*)h->d_charge, (void*)h->d_rules, (void*)h->d_offset, (void*)h->d_ijk, (void*)h->d_kf,
-                        (void*)h->d_fw, (void*)h->d_tot, (void*)h->d_mol, (void*)h->d_atoms, (void*)h->d_molidx, (void*)h->d_in, (void*)h->d_out, (void*)h->d_cells, (void*)h->d_cell_count, (void*)h->d_etab})
+                        (void*)h->d_fw, (void*)h->d_tot, (void*)h->d_mol, (void*)h->d_atoms, (void*)h->d_molidx, (void*)h->d_in, (void*)h->d_out, (void*)h->d_cells, (void*)h->d_cell_count, (void*)h->d_etab, (void*)h->d_baseline})
             if (p) (void)hipFree(p);
         if (h->h_in) (void)hipHostFree(h->h_in);
         if (h->h_out) (void)hipHostFree(h->h_out);

@@ -680,6 +680,8 @@ struct ceg_mc_group {
     std::vector<uint8_t*> d_masks;
     int blk_species = 0, blk_kinds = 0;
     std::vector<int64_t> pockets;                // [2K] of the last GCMC sweep: pocket-blocked steps, sum of the attempt indices
+    unsigned char* d_baseline = nullptr;         // partial sums and results of ceg_mc_group_baseline (ceg_mc_baseline.hip); only grows
+    size_t baseline_cap = 0;
 };
 
 namespace {
@@ -703,6 +705,7 @@ void group_free(ceg_mc_group* g)
     if (g->d_views) (void)hipFree(g->d_views);
     if (g->d_done) (void)hipFree(g->d_done);
     if (g->d_scratch) (void)hipFree(g->d_scratch);
+    if (g->d_baseline) (void)hipFree(g->d_baseline);
     for (void* p : {(void*)g->h_views, (void*)g->h_in, (void*)g->h_out, (void*)g->h_acc, (void*)g->h_flag})
         if (p) (void)hipHostFree(p);
     delete g;
@@ -713,11 +716,6 @@ int chain_err(int code, int c, const char* sep, const char* what)        // "cha
     char msg[160];
     std::snprintf(msg, sizeof msg, "chain %d%s%s", c, sep, what);
     return merr(code, msg);
-}
-
-int group_refuse_poisoned(int c)
-{
-    return chain_err(CEG_ERR_HIP, c, " of the group is inconsistent after an earlier failure of accept / insert / remove: call ceg_mc_set_guests on it", "");
 }
 
 int group_bad(int c, const char* what) { return chain_err(CEG_ERR_INVALID, c, ": ", what); }
@@ -741,6 +739,24 @@ bool group_upload_views(ceg_mc_group* g, const std::vector<char>& used)
 }
 
 }  // namespace
+
+int ceg_mcs::group_refuse_poisoned(int c)
+{
+    return chain_err(CEG_ERR_HIP, c, " of the group is inconsistent after an earlier failure of accept / insert / remove: call ceg_mc_set_guests on it", "");
+}
+
+ceg_mcs::GroupRef ceg_mcs::group_ref(ceg_mc_group* g)
+{
+    return GroupRef{g->device, g->stream, g->chains.data(), (int)g->chains.size(), g->d_views, &g->d_baseline, &g->baseline_cap};
+}
+
+bool ceg_mcs::group_views_current(ceg_mc_group* g) { return group_upload_views(g, std::vector<char>(g->chains.size(), 1)); }
+
+void ceg_mcs::group_stream_idle(ceg_mc_group* g)
+{
+    g->accept_pending = false;
+    g->uploads_pending = false;
+}
 
 extern "C" int ceg_mc_group_create(ceg_mc_group_t** group, ceg_mc_t* const* chains, int32_t k)
 {

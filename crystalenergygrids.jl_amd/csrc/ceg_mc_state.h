@@ -1,6 +1,7 @@
-// ceg_mc_state.h -- what ceg_mc.hip (ceg_mc_*) and ceg_mc_group.hip (ceg_mc_group_*) share: the kernel-side view of a handle, the
-// bodies of the trial row and of the three updates, and the host-side handle with its cell mirror.  Two translation units include
-// this, so the names live in namespace ceg_mcs; the kernels stay in the anonymous namespaces of the two files.
+// ceg_mc_state.h -- what ceg_mc.hip (ceg_mc_*), ceg_mc_group.hip (ceg_mc_group_*) and ceg_mc_baseline.hip (ceg_mc_baseline,
+// ceg_mc_group_baseline) share: the kernel-side view of a handle, the bodies of the trial row, of the three updates and of the
+// structure-factor rebuild, and the host-side handle with its cell mirror.  Several translation units include this, so the names live
+// in namespace ceg_mcs; the kernels stay in the anonymous namespaces of the files.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -565,6 +566,44 @@ __device__ __forceinline__ void mc_remove_body(const McView& v, int32_t molecule
     if (tid == 0 && last != molecule) v.mol[molecule] = moved;
 }
 
+// compute_ewald(::IncrementalEwaldContext) (ewald.jl:630-652), first half: sums[:, ij+1] of molecule `molecule` from its current
+// positions (one workgroup of MC_THREADS; dynamic LDS: the [m][stride] tables)
+__device__ __forceinline__ void mc_sf_molecule_body(const McView& v, int molecule, int stride)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    __shared__ double s_pos[MC_MAX_ATOMS * 3];
+    __shared__ double s_q[MC_MAX_ATOMS];
+    const int tid = threadIdx.x;
+    const int first = v.mol[molecule].x, m = v.mol[molecule].y;
+    if (tid < m) {
+        const double4 A = v.atoms[first + tid];
+        int kind, mol;
+        unpack(A.w, kind, mol);
+        s_q[tid] = v.kind_charge[kind];
+        s_pos[3 * tid] = A.x; s_pos[3 * tid + 1] = A.y; s_pos[3 * tid + 2] = A.z;
+    }
+    __syncthreads();
+    double2* tab = reinterpret_cast<double2*>(s_raw);
+    fill_tables(v, s_pos, m, tab, stride, tid, MC_THREADS, s_q);
+    __syncthreads();
+    double2* mine = v.sf_mol + (size_t)molecule * v.nk;
+    rows_structure_factor(v, tab, stride, m, tid >> 6, MC_THREADS / 64, tid & 63,
+                          [&](int q, double sr, double si) { mine[q] = make_double2(sr, si); });
+}
+
+// second half: sums[q, 1] = sum over the molecules, in molecule order
+__device__ __forceinline__ void mc_sf_total_body(const McView& v, int64_t q)
+{
+    if (q >= v.nk) return;
+    double sr = 0.0, si = 0.0;
+    for (int j = 0; j < v.nmol; ++j) {
+        const double2 s = v.sf_mol[(size_t)j * v.nk + q];
+        sr += s.x;
+        si += s.y;
+    }
+    v.sf_tot[q] = make_double2(sr, si);
+}
+
 inline int merr(int code, const char* msg)
 {
     ceg_set_last_error_(msg);
@@ -721,6 +760,8 @@ struct ceg_mc {
     uint64_t v_version = 1;                      // bumped wherever `v` is written (a group re-uploads its copy of `v` when this moved)
     ceg_mc_group* group = nullptr;               // the chain group this handle belongs to (its work then runs on the group's stream)
     hipStream_t own_stream = nullptr;            // the handle's own stream while it is in a group
+    unsigned char* d_baseline = nullptr;         // partial sums and result of ceg_mc_baseline (ceg_mc_baseline.hip); only grows
+    size_t baseline_cap = 0;
 };
 
 namespace ceg_mcs {
@@ -744,5 +785,20 @@ int ensure_capacity(ceg_mc* h, int64_t natoms, int64_t nmol);       // grow the 
 int rebuild_cells(ceg_mc* h);                                       // the device cell arrays from the host lists; leaves the stream idle
 bool accept_cell_ops(ceg_mc* h, int32_t molecule, const double* positions, McCellOps& ops);
 int check_molecule(const ceg_mc* h, const int32_t* kinds, int32_t m, McMolecule* nm);
+
+// defined in ceg_mc_group.hip: what ceg_mc_baseline.hip needs of a group
+struct GroupRef {
+    int device;
+    hipStream_t stream;
+    ceg_mc* const* chains;
+    int k;
+    const McView* d_views;                       // [k], current in stream order once group_views_current has returned true
+    unsigned char** d_baseline;                  // the group's counterpart of ceg_mc::d_baseline / baseline_cap
+    size_t* baseline_cap;
+};
+GroupRef group_ref(ceg_mc_group* g);
+bool group_views_current(ceg_mc_group* g);       // every member's view into d_views where it changed since its last upload
+void group_stream_idle(ceg_mc_group* g);         // the caller has synchronised the group's stream
+int group_refuse_poisoned(int c);                // CEG_ERR_HIP, "chain <c> of the group is inconsistent ..."
 
 }  // namespace ceg_mcs

@@ -776,6 +776,46 @@ function mc_group_block_counts(g::Ptr{Cvoid}, k::Integer)
     pocket, attempts
 end
 
+# `ceg_mc_baseline_t` of include/ceg_hip.h (48 bytes)
+struct McBaseline
+    framework_vdw::Float64
+    framework_direct::Float64
+    inter::Float64
+    recip_framework::Float64
+    recip_guests::Float64
+    nmol::Int32
+    natoms::Int32
+end
+const MC_BASELINE_REFRESH = Int32(1)
+
+"`ceg_mc_baseline`: the sums of `baseline_energy` (src/montecarlo.jl:530-542) over the device state of one chain, in K; `refresh` recomputes every structure factor from the positions first, as `compute_ewald(::IncrementalEwaldContext)` does"
+function mc_baseline(h::Ptr{Cvoid}; refresh::Bool=false)
+    out = Vector{McBaseline}(undef, 1)
+    GC.@preserve out _check(ccall((:ceg_mc_baseline, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Cvoid}),
+                                  h, refresh ? MC_BASELINE_REFRESH : Int32(0), pointer(out)))
+    out[1]
+end
+
+"`ceg_mc_group_baseline`: the same for the `k` chains of a group in one pass; entry `c` holds what `mc_baseline` gives for chain `c`"
+function mc_group_baseline(g::Ptr{Cvoid}, k::Integer; refresh::Bool=false)
+    out = Vector{McBaseline}(undef, k)
+    GC.@preserve out _check(ccall((:ceg_mc_group_baseline, LIB[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Cvoid}),
+                                  g, refresh ? MC_BASELINE_REFRESH : Int32(0), pointer(out)))
+    out
+end
+
+"""
+`baseline_energy(mc)` (src/montecarlo.jl:530-542) from the device state behind `h` (`mc_handle(mc, ...)`): the sums come from
+`ceg_mc_baseline`, the two constants of the Ewald context (`energy_net_charges`, `static_contribution`, src/ewald.jl:555-577) and
+the tail correction from `mc`, whose species counts must be those of the device state.
+"""
+function baseline_energy(h::Ptr{Cvoid}, mc::CEG.MonteCarloSetup; refresh::Bool=false)
+    b = mc_baseline(h; refresh)
+    ctx = mc.ewald.ctx
+    reciprocal = CEG.isdefined_ewald(ctx) ? 2*(b.recip_framework*u"K" + ctx.energy_net_charges) + b.recip_guests*u"K" + ctx.static_contribution[] : 0.0u"K"
+    CEG.BaselineEnergyReport(b.framework_vdw*u"K", b.framework_direct*u"K", b.inter*u"K", reciprocal, mc.tailcorrection[])
+end
+
 "`ceg_mc_group_destroy`: the chains get their own streams back and stay valid"
 function mc_group_close(g::Ptr{Cvoid})
     _check(ccall((:ceg_mc_group_destroy, LIB[]), Cint, (Ptr{Cvoid},), g))

@@ -872,6 +872,41 @@ CEG_API int ceg_mc_group_set_blocks(ceg_mc_group_t* group, const ceg_mc_block_t*
                                     const ceg_mc_block_t* atom_blocks, int32_t nkinds);
 CEG_API int ceg_mc_group_block_counts(ceg_mc_group_t* group, int64_t* pocket_out /*[K]*/, int64_t* attempts_out /*[K]*/);
 
+/* ---- baseline_energy (src/montecarlo.jl:530-542) of one chain, or of every chain of a group, from the resident state ----
+ * What run_montecarlo! asks for at its start, at the first production cycle, after a move that risks underflow and for its final
+ * drift check (src/simulation.jl:643,789,850-853; montecarlo.jl:364).  Synchronous; `out` is host memory ([K] for a group, member
+ * order).  The work is ordered on the handle's (the group's) stream behind everything enqueued so far, and takes a fixed number of
+ * launches -- two, four with CEG_MC_BASELINE_REFRESH -- whatever the number of chains and molecules.
+ *  framework_vdw, framework_direct  sum of framework_interactions over every atom of every molecule in the system, atom by atom as
+ *                    row 0 of ceg_mc_trial computes it; the 1e100 rules are the same (a blocked VdW value is kept and summed, a
+ *                    Coulomb value of exactly 1e100 is added without the charge); a NULL grid gives 0.
+ *  inter             compute_vdw (src/energy.jl:355-383): every unordered pair of atoms of DIFFERENT molecules with d^2 < cutoff^2,
+ *                    once, with the pair distance (fast wrap where the cell allows it, the reference's order otherwise), cutoff test
+ *                    and rule energies of the trial rows: 1/2 the sum of column 2 of row 0 over the molecules.  Free atom slots are
+ *                    skipped.  A handle that keeps neighbour cells is accepted: the atom records are authoritative, and the loop over
+ *                    them is exhaustive.
+ *  recip_framework   sum_k kf Re(conj(S_fw) S),  recip_guests  sum_k kf |S|^2,  S = sums[:, 1] as resident.  The caller composes
+ *                    2 (recip_framework + energy_net_charges) + recip_guests + static_contribution (src/ewald.jl:555-577): the two
+ *                    constants depend on the species counts and stay on the host, like the tail correction.  nk = 0: both 0.
+ *  nmol, natoms      the molecules and the occupied atom slots that were summed.
+ * CEG_MC_BASELINE_REFRESH: before the sums, every sums[:, ij+1] and sums[:, 1] is recomputed from the current positions and stored,
+ *   as compute_ewald(::IncrementalEwaldContext) (src/ewald.jl:630-652) does inside the reference's baseline_energy -- the rounding
+ *   accumulated by the incremental updates is gone afterwards.  Without the flag nothing in the state is written.
+ * Determinism: no floating-point atomics; partial sums are combined in an order fixed by the chain's own atom-slot layout.  Repeated
+ *   calls on an unchanged state return identical bytes, and ceg_mc_group_baseline returns for member c exactly the bytes
+ *   ceg_mc_baseline returns for that handle alone.  An empty box gives zeros.
+ * Errors: NULL handle / group / out or unknown flag bits -> CEG_ERR_INVALID before anything is launched; a handle (member) marked
+ *   inconsistent -> CEG_ERR_HIP (with the chain's index in ceg_last_error() for a group) and no member's state is touched; a failure
+ *   after a refresh has been launched marks the handle (every member) inconsistent. */
+typedef struct ceg_mc_baseline {
+    double framework_vdw, framework_direct, inter;   /* K */
+    double recip_framework, recip_guests;            /* K */
+    int32_t nmol, natoms;
+} ceg_mc_baseline_t;
+#define CEG_MC_BASELINE_REFRESH 1
+CEG_API int ceg_mc_baseline(ceg_mc_t* handle, int32_t flags, ceg_mc_baseline_t* out);
+CEG_API int ceg_mc_group_baseline(ceg_mc_group_t* group, int32_t flags, ceg_mc_baseline_t* out /* [K] */);
+
 /* ---- blocking masks on the grid lattice ----------------------------- */
 /*
  * BlockFile(g::EnergyGrid), src/grids.jl:188-204: a lattice cell (i, j, k), i < dims[0] etc., whose
