@@ -531,6 +531,46 @@ __device__ __forceinline__ double wave_max(double x)
     return x;
 }
 
+// Lane `l`'s value of x as a wave-uniform FP64 value in an SGPR pair (two v_readlane; see uniform() for the empty asm)
+__device__ __forceinline__ double lane_value(double x, int l)
+{
+    int lo = __double2loint(x), hi = __double2hiint(x);
+    asm("" : "+v"(lo));
+    asm("" : "+v"(hi));
+    return __hiloint2double(__builtin_amdgcn_readlane(hi, l), __builtin_amdgcn_readlane(lo, l));
+}
+
+// Inclusive scans over the 64 lanes on the DPP path (no LDS-pipe permutes, no lane addresses): four row_shr steps inside each row
+// of 16 lanes, then row_bcast15 into rows 1 and 3 and row_bcast31 into rows 2 and 3.  A lane without a source keeps `old` = 0, the
+// identity of both operations on the non-negative integers they are used for.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int dpp_or_zero(int x)
+{
+    return __builtin_amdgcn_update_dpp(0, x, CTRL, ROW_MASK, 0xf, false);
+}
+__device__ __forceinline__ int wave_scan_add(int x)
+{
+    x += dpp_or_zero<0x111, 0xf>(x);          // row_shr:1
+    x += dpp_or_zero<0x112, 0xf>(x);          // row_shr:2
+    x += dpp_or_zero<0x114, 0xf>(x);          // row_shr:4
+    x += dpp_or_zero<0x118, 0xf>(x);          // row_shr:8
+    x += dpp_or_zero<0x142, 0xa>(x);          // row_bcast:15
+    x += dpp_or_zero<0x143, 0xc>(x);          // row_bcast:31
+    return x;
+}
+__device__ __forceinline__ int wave_scan_max(int x_)      // x >= 0 (unsigned max: 0 is its identity, so each step is one DPP instruction)
+{
+    unsigned x = (unsigned)x_;
+    x = max(x, (unsigned)dpp_or_zero<0x111, 0xf>((int)x));
+    x = max(x, (unsigned)dpp_or_zero<0x112, 0xf>((int)x));
+    x = max(x, (unsigned)dpp_or_zero<0x114, 0xf>((int)x));
+    x = max(x, (unsigned)dpp_or_zero<0x118, 0xf>((int)x));
+    x = max(x, (unsigned)dpp_or_zero<0x142, 0xa>((int)x));
+    x = max(x, (unsigned)dpp_or_zero<0x143, 0xc>((int)x));
+    return (int)x;
+}
+typedef int32_t __attribute__((may_alias)) ceg_i32_alias;      // a second view of the per-wave s_odd slice (see the row map of k_culled)
+
 static_assert(sizeof(CandRec) == 80, "candidate record layout");
 // the same without the per-candidate VdW parameters (Coulomb-only builds, generic rules, the single tabulated Buckingham class)
 struct __attribute__((aligned(16))) CandRecS {
@@ -709,9 +749,16 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
     }
 
     // ---- tile box (exact hull of the lanes' points)
-    const double blx = uniform(wave_min(px)), bhx = uniform(wave_max(px));
-    const double bly = uniform(wave_min(py)), bhy = uniform(wave_max(py));
-    const double blz = uniform(wave_min(pz)), bhz = uniform(wave_max(pz));
+    // Grid mode needs no reduction.  grid_coord is a chain of correctly rounded *, /, + with a positive cell edge and a positive
+    // divisor: each step is monotone (non-decreasing) in its first operand, so the coordinate is monotone in the index and the
+    // smallest / largest coordinate over the lanes is bit for bit the coordinate of the smallest / largest (clamped) index.  Lane 0
+    // holds (i0, j0, k0), the smallest index on all three axes (the tile's first point is always valid: never clamped); lane 63
+    // holds (i0 + 3, j0 + 3, k0 + 3) clamped to the last valid plane / row / column, the largest clamped index on all three.
+    // Partial tiles and inactive waves (which run the last tile's indices in every lane) are covered by the same argument.
+    constexpr bool BOX_FROM_CORNERS = !POINTS;          // point lists keep the reductions
+    const double blx = BOX_FROM_CORNERS ? lane_value(px, 0) : uniform(wave_min(px)), bhx = BOX_FROM_CORNERS ? lane_value(px, 63) : uniform(wave_max(px));
+    const double bly = BOX_FROM_CORNERS ? lane_value(py, 0) : uniform(wave_min(py)), bhy = BOX_FROM_CORNERS ? lane_value(py, 63) : uniform(wave_max(py));
+    const double blz = BOX_FROM_CORNERS ? lane_value(pz, 0) : uniform(wave_min(pz)), bhz = BOX_FROM_CORNERS ? lane_value(pz, 63) : uniform(wave_max(pz));
     const double cx = uniform(0.5 * (blx + bhx)), cy = uniform(0.5 * (bly + bhy)), cz = uniform(0.5 * (blz + bhz));
     const double hx = uniform(0.5 * (bhx - blx)), hy = uniform(0.5 * (bhy - bly)), hz = uniform(0.5 * (bhz - blz));
     // cutoff with a rounding margin: anything a lane can see with r2 < cutoff2 is kept
@@ -790,27 +837,45 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
                 count = ib.bin_start[rowbase + bz1 + 1] - start;
             }
         }
-        // inclusive scan of counts over the wave.  The lane id is made opaque here: the permute addresses and the two LDS
-        // addresses below are loop invariants that the compiler otherwise hoists out of the tile loop and, at the VGPR limit
-        // of the hot loops, parks in scratch (stores + reloads per tile that showed up as HBM traffic)
+        // inclusive scan of counts over the wave (DPP: integer adds in another order, the same sums).  The lane id is made opaque
+        // here: the two LDS addresses below are loop invariants that the compiler otherwise hoists out of the tile loop and, at
+        // the VGPR limit of the hot loops, parks in scratch (stores + reloads per tile that showed up as HBM traffic)
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        int incl = count;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int up = __builtin_amdgcn_ds_bpermute((ln - o) << 2, incl);      // lanes < o read a wrapped lane and ignore it
-            if (ln >= o) incl += up;
-        }
+        const int incl = wave_scan_add(count);
         __builtin_amdgcn_wave_barrier();                       // previous batch's readers are done
         s_rowstart[ln] = start;
         s_rowprefix[ln + 1] = incl;
         if (ln == 0) s_rowprefix[0] = 0;
         __builtin_amdgcn_wave_barrier();
         const int total = __builtin_amdgcn_readfirstlane(s_rowprefix[64]);
+        int row_carry = 0;                         // wave-uniform: the row of flat index cbase - 1
 
         for (int cbase = 0; cbase < total; cbase += 64) {
             // -- stage: lane loads one image of the flattened row list and tests it against the tile
             const int t = cbase + lane;
+            // Row of flat index t = the largest lo with prefix[lo] <= t, i.e. the NON-EMPTY row with prefix[lo] <= t < prefix[lo + 1]
+            // (an empty row before it has the same prefix but a smaller number, one after it has prefix[lo + 1] > t).  Instead of a
+            // binary search per lane: lane r, as owner of row r, writes r at position prefix[r] - cbase of a 64-entry map when its
+            // row is non-empty and starts inside this chunk; an inclusive max-scan over the map then hands every position the last
+            // row that started at or before it -- row numbers grow with their prefix -- and positions before the first start of the
+            // chunk take the row of the previous chunk's last position (a row that straddles the chunk boundary).
+            // The map is the wave's s_odd slice: the pair loops and slow_pairs of the previous chunk are done with it, and the
+            // LDS operations of a wave complete in order.
+            int trow;
+            {
+                int lc = lane;
+                asm volatile("" : "+v"(lc));           // opaque: the three LDS addresses below are not hoisted out of the loops (see `ln`)
+                ceg_i32_alias* s_map = reinterpret_cast<ceg_i32_alias*>(s_odd);
+                const int excl = s_rowprefix[lc], incl_r = s_rowprefix[lc + 1];
+                __builtin_amdgcn_wave_barrier();
+                s_map[lc] = 0;
+                const unsigned e = (unsigned)(excl - cbase);
+                if (e < 64u && incl_r > excl) s_map[e] = lc;
+                __builtin_amdgcn_wave_barrier();
+                trow = max(wave_scan_max(s_map[lc]), row_carry);
+                row_carry = __builtin_amdgcn_readlane(trow, 63);
+            }
             bool keep = false, interior = false;
             double4 P = make_double4(0, 0, 0, 0);
             double4 LJ = make_double4(0, 0, 0, 0);
@@ -819,12 +884,7 @@ __global__ __launch_bounds__(64 * culled_nw(MODE, VDWK, EWK, NP), culled_waves(M
             for (int p = 0; p < NP; ++p) LJM[p] = make_double4(0, 0, 0, 0);
             int meta = 0, aidx = 0;
             if (t < total) {
-                int lo = 0, hi = 64;           // largest lo with prefix[lo] <= t
-#pragma unroll
-                for (int s = 0; s < 6; ++s) {
-                    const int mid = (lo + hi) >> 1;
-                    if (s_rowprefix[mid] <= t) lo = mid; else hi = mid;
-                }
+                const int lo = trow;
                 const int img = s_rowstart[lo] + (t - s_rowprefix[lo]);
                 P = ib.xyzq[img];
                 aidx = ib.atom[img];
