@@ -70,6 +70,20 @@ MC_BASELINE_DTYPE = np.dtype([('framework_vdw', '<f8'), ('framework_direct', '<f
                               ('recip_guests', '<f8'), ('nmol', '<i4'), ('natoms', '<i4')], align=True)
 assert MC_BASELINE_DTYPE.itemsize == 48
 MC_BASELINE_REFRESH = 1      # CEG_MC_BASELINE_REFRESH
+MC_SAMPLER_MAX_SYM = 191     # CEG_MC_SAMPLER_MAX_SYM
+
+
+class MC_SAMPLER(C.Structure):
+    """``ceg_mc_sampler_t`` (``unit_invmat`` column-major; the three arrays in host memory, copied by ``ceg_mc_group_set_sampler``)"""
+    _fields_ = [("every", C.c_int64), ("from_step", C.c_int64), ("series_capacity", C.c_int64), ("dims", C.c_int32 * 3),
+                ("nmaps", C.c_int32), ("nchannels", C.c_int32), ("nkinds", C.c_int32), ("nsym", C.c_int32), ("_pad", C.c_int32),
+                ("unit_invmat", C.c_double * 9), ("chain_map", C.c_void_p), ("kind_channel", C.c_void_p), ("sym", C.c_void_p)]
+
+
+# ``ceg_mc_sample_record_t``: one record per (frame, chain) of the sampler's series
+MC_SAMPLE_RECORD_DTYPE = np.dtype([('step', '<i8'), ('nmol', '<i4'), ('natoms', '<i4'), ('count', '<i4', (GCMC_MAX_SPECIES,)),
+                                   ('delta_moves', '<f8'), ('delta_swaps', '<f8')], align=True)
+assert (C.sizeof(MC_SAMPLER), MC_SAMPLE_RECORD_DTYPE.itemsize) == (152, 64)
 
 c_double_p = C.POINTER(C.c_double)
 c_float_p = C.POINTER(C.c_float)
@@ -210,6 +224,10 @@ PROTOTYPES = {
     "ceg_mc_group_sweep_gcmc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ceg_mc_group_set_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "ceg_mc_group_block_counts": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
+    "ceg_mc_group_set_sampler": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ceg_mc_group_sample": (C.c_int, [C.c_void_p]),
+    "ceg_mc_group_sampler_read": (C.c_int, [C.c_void_p, c_int64_p, C.c_void_p, c_int64_p]),
+    "ceg_mc_group_sampler_reset": (C.c_int, [C.c_void_p]),
     "ceg_mc_baseline": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ceg_mc_group_baseline": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ceg_energy_grid": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, c_double_p, c_double_p, C.c_int32,

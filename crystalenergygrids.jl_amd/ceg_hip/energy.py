@@ -643,6 +643,7 @@ class DeviceMonteCarloGroup:
         for c in self.chains:
             c._group = self
         self._blocks = None           # what set_blocks installed: (species blocks, atom blocks)
+        self.sampler = None           # what set_sampler installed (its geometry and tables, for the host restatement)
 
     def __repr__(self):
         return f"DeviceMonteCarloGroup(k={len(self.chains)})"
@@ -902,6 +903,104 @@ class DeviceMonteCarloGroup:
             if positions:
                 chain.pull_positions()
         return (stats, records) if log else stats
+
+    def set_sampler(self, every: Optional[int], from_step: int = 0, step: Optional[float] = None, dims=None, supercell=(1, 1, 1), channels=None,
+                    chain_map=None, symmetries=(), series_capacity: int = 0) -> None:
+        """``ceg_mc_group_set_sampler``: from now on :meth:`sweep` and :meth:`sweep_gcmc` take a frame after every absolute step ``s``
+        with ``s >= from_step`` and ``(s + 1) % every == 0`` -- one more launch that bins every atom of every chain as
+        ``bin_trajectory`` does (averageclusters.jl:154-202) and appends one record per chain (molecule counts, running energy
+        change) to the series; :meth:`sampler_read` fetches both.  ``every=None`` removes the sampler.
+
+        The map lives on the unit cell: the MC cell with its columns divided by ``supercell``.  ``dims = (na, nb, nc)``, or from
+        ``step`` (A) as ``floor(cell_lengths(unit cell) / step)`` (:169); neither: no map, the series only.  ``channels``: the channel
+        of every force-field kind -- a dict from kind (0-based index, or the force field's symbol) to channel, kinds not named are
+        not binned; or one entry per kind with -1 for "not binned"; default: every kind into channel 0.  ``chain_map``: the map of
+        every chain, -1 for a chain that is not binned (default: all chains pooled in map 0).  ``symmetries``: operations
+        ``(R[3, 3], t[3])`` on the fractional coordinates of the unit cell, each adding one count per atom (:185-188).
+        ``series_capacity``: the frames the series can hold; a sweep (or :meth:`sample`) whose frames would not fit is refused.
+        What was installed is kept in ``self.sampler`` (``unit_invmat``, ``dims``, ``channels``, ``chain_map``, ``symmetries``,
+        ``supercell``) for :func:`ceg_hip.mcrng.bin_positions`."""
+        if every is None:
+            _abi.check(self._lib, self._lib.ceg_mc_group_set_sampler(self._h, None))
+            self.sampler = None
+            return
+        k = len(self.chains)
+        mc = self.chains[0].mc
+        nkinds = mc.ff.nkinds
+        supercell = tuple(int(x) for x in supercell)
+        if len(supercell) != 3 or min(supercell) < 1:
+            raise ValueError("supercell: three integers >= 1")
+        unit = np.asarray(mc.mat, dtype=np.float64) / np.asarray(supercell, dtype=np.float64)[None, :]
+        unit_invmat = np.linalg.inv(unit)
+        if dims is None and step is not None:
+            dims = np.floor(np.linalg.norm(unit, axis=0) / float(step)).astype(np.int64)
+        with_map = dims is not None
+        dims = np.ascontiguousarray(dims if with_map else (0, 0, 0), dtype=np.int32)
+        if dims.shape != (3,):
+            raise ValueError("dims: (na, nb, nc)")
+        if channels is None:
+            kind_channel = np.zeros(nkinds, dtype=np.int32)
+        elif isinstance(channels, dict):
+            kind_channel = np.full(nkinds, -1, dtype=np.int32)
+            for key, ch in channels.items():
+                kind_channel[mc.ff.sdict[key] - 1 if isinstance(key, str) else int(key)] = ch
+        else:
+            kind_channel = np.ascontiguousarray(channels, dtype=np.int32)
+            if kind_channel.shape != (nkinds,):
+                raise ValueError(f"channels: one entry per force-field kind ({nkinds})")
+        cmap = np.ascontiguousarray(np.zeros(k) if chain_map is None else chain_map, dtype=np.int32)
+        if cmap.shape != (k,):
+            raise ValueError(f"chain_map: one entry per chain ({k})")
+        if with_map and (cmap.max() < 0 or kind_channel.max(initial=-1) < 0):
+            raise ValueError("a map needs at least one chain with a map (chain_map >= 0) and one kind with a channel (channels >= 0)")
+        sym = np.zeros((len(symmetries), 3, 4), dtype=np.float64)
+        for q, op in enumerate(symmetries):
+            if len(op) == 2:
+                sym[q, :, :3], sym[q, :, 3] = np.asarray(op[0], dtype=np.float64).reshape(3, 3), np.asarray(op[1], dtype=np.float64).reshape(3)
+            else:
+                sym[q] = np.asarray(op, dtype=np.float64).reshape(3, 4)
+        spec = _abi.MC_SAMPLER(int(every), int(from_step), int(series_capacity), (C.c_int32 * 3)(*[int(d) for d in dims]),
+                               int(cmap.max()) + 1 if with_map else 0, int(kind_channel.max()) + 1 if with_map else 0, nkinds, len(sym), 0,
+                               (C.c_double * 9)(*unit_invmat.T.reshape(-1)), cmap.ctypes.data, kind_channel.ctypes.data, sym.ctypes.data if len(sym) else None)
+        _abi.check(self._lib, self._lib.ceg_mc_group_set_sampler(self._h, C.addressof(spec)))
+        self.sampler = dict(every=int(every), from_step=int(from_step), series_capacity=int(series_capacity), dims=tuple(int(d) for d in dims),
+                            nmaps=int(spec.nmaps), nchannels=int(spec.nchannels), unit_invmat=unit_invmat, supercell=supercell,
+                            channels=kind_channel, chain_map=cmap, symmetries=sym)
+
+    def _sampler(self):
+        s = getattr(self, "sampler", None)
+        if s is None:
+            raise RuntimeError("no sampler installed: set_sampler first")
+        return s
+
+    def sample(self) -> None:
+        """``ceg_mc_group_sample``: one frame of the resident state, now (asynchronous, ordered with the group's other calls) -- for
+        runs driven through :meth:`trial` / :meth:`accept`.  Its records carry ``step == -1``."""
+        self._sampler()
+        _abi.check(self._lib, self._lib.ceg_mc_group_sample(self._h))
+
+    def sampler_read(self):
+        """``ceg_mc_group_sampler_read`` -> ``(bins, series, total)``: ``bins`` int64 ``[nmaps, nchannels, nc, nb, na]`` (``None`` without
+        a map), ``series`` ``[frames, K]`` of ``_abi.MC_SAMPLE_RECORD_DTYPE``, and ``total[map] = frames * (1 + nsym) * prod(supercell) *
+        chains on that map``: the ``total`` of ``bin_trajectories`` over the chains' trajectories (averageclusters.jl:196,233-234), so that
+        ``bins[map, channel] / total[map]`` is the density map."""
+        s = self._sampler()
+        frames = C.c_int64(0)
+        _abi.check(self._lib, self._lib.ceg_mc_group_sampler_read(self._h, None, None, C.byref(frames)))
+        k = len(self.chains)
+        na, nb, nc = s["dims"]
+        bins = np.zeros((s["nmaps"], s["nchannels"], nc, nb, na), dtype=np.int64) if s["nmaps"] else None
+        series = np.zeros((int(frames.value), k), dtype=_abi.MC_SAMPLE_RECORD_DTYPE)
+        _abi.check(self._lib, self._lib.ceg_mc_group_sampler_read(self._h, _abi.i64ptr(bins.reshape(-1)) if bins is not None else None,
+                                                                  series.ctypes.data if series.size else None, None))
+        per_frame = (1 + len(s["symmetries"])) * int(np.prod(s["supercell"]))
+        total = np.array([int(frames.value) * per_frame * int((s["chain_map"] == m).sum()) for m in range(s["nmaps"])], dtype=np.int64)
+        return bins, series, total
+
+    def sampler_reset(self) -> None:
+        """``ceg_mc_group_sampler_reset``: bins, series and frame count back to zero."""
+        self._sampler()
+        _abi.check(self._lib, self._lib.ceg_mc_group_sampler_reset(self._h))
 
     def close(self) -> None:
         if getattr(self, "_h", None):

@@ -388,3 +388,82 @@ def swap_rule(row, u: float, temperature: float, n_species: int, phiPV_div_k: fl
     if insertion and row[0] >= 1e90:
         return False
     return bool(u < swap_threshold(row, temperature, n_species, phiPV_div_k, self_reciprocal, tc, insertion)[1])
+
+
+# ---- the sampler of a chain group (``ceg_mc_group_set_sampler``): the bin of a position as bin_trajectory computes it
+# (averageclusters.jl:154-202), the frames of a sweep, and the positions of a chain followed through a sweep's log
+def bin_index(unit_invmat, dims, p) -> np.ndarray:
+    """0-based bin (i_a, i_b, i_c) of the position(s) ``p[..., 3]`` on a map of ``dims = (na, nb, nc)`` bins over the unit cell
+    whose inverse matrix is ``unit_invmat`` (3x3, ``y = unit_invmat @ p``), in the device's operation order:
+    ``y_r = (I[r,0] p_x + I[r,1] p_y) + I[r,2] p_z``, ``u = y - floor(y)``, ``i = ceil(u n) + (u == 0) - 1`` (:182-184), clamped to
+    ``[0, n - 1]``."""
+    return bin_index_fractional(fractional(unit_invmat, p), dims)
+
+
+def fractional(unit_invmat, p) -> np.ndarray:
+    """``y[..., 3]`` of :func:`bin_index`: the unfloored fractional coordinates, each a sum of three products left to right"""
+    I = np.asarray(unit_invmat, dtype=np.float64).reshape(3, 3)
+    p = np.asarray(p, dtype=np.float64)
+    return np.stack([(I[r, 0] * p[..., 0] + I[r, 1] * p[..., 1]) + I[r, 2] * p[..., 2] for r in range(3)], axis=-1)
+
+
+def bin_index_fractional(y, dims) -> np.ndarray:
+    y = np.asarray(y, dtype=np.float64)
+    n = np.asarray(dims, dtype=np.int64).reshape(3)
+    u = y - np.floor(y)
+    i = np.ceil(u * n.astype(np.float64)).astype(np.int64) + (u == 0.0) - 1
+    return np.clip(i, 0, n - 1)
+
+
+def bin_positions(bins, unit_invmat, positions, symmetries=()) -> np.ndarray:
+    """Add the positions ``[n, 3]`` to ``bins[nc, nb, na]`` (one (map, channel) block of the sampler: ``a`` fastest), each once as it
+    is and once per symmetry operation ``(R[3, 3], t[3])`` -- or row block ``[3, 4] = (R | t)`` -- applied to the unfloored
+    fractional coordinates: ``y'_r = ((R[r,0] y_0 + R[r,1] y_1) + R[r,2] y_2) + t_r`` (:185-188).  -> ``bins``."""
+    nc, nb, na = bins.shape
+    y = fractional(unit_invmat, np.asarray(positions, dtype=np.float64).reshape(-1, 3))
+    images = [y]
+    for op in symmetries:
+        S = np.concatenate([np.asarray(op[0], dtype=np.float64).reshape(3, 3), np.asarray(op[1], dtype=np.float64).reshape(3, 1)], axis=1) \
+            if len(op) == 2 else np.asarray(op, dtype=np.float64).reshape(3, 4)
+        images.append(np.stack([((S[r, 0] * y[:, 0] + S[r, 1] * y[:, 1]) + S[r, 2] * y[:, 2]) + S[r, 3] for r in range(3)], axis=-1))
+    for img in images:
+        i = bin_index_fractional(img, (na, nb, nc))
+        np.add.at(bins, (i[:, 2], i[:, 1], i[:, 0]), 1)
+    return bins
+
+
+def sampler_frames(first_step: int, nsteps: int, every: int, from_step: int = 0) -> list:
+    """The absolute steps after which a sweep of ``nsteps`` steps from ``first_step`` takes a frame: ``s >= from_step`` and
+    ``(s + 1) % every == 0``, in step order."""
+    if every < 1 or from_step < 0:
+        raise ValueError("every >= 1 and from_step >= 0")
+    lo = max(int(first_step), int(from_step))
+    s = lo + (-(lo + 1)) % every                   # the first s >= lo with (s + 1) % every == 0
+    return list(range(s, int(first_step) + max(int(nsteps), 0), every))
+
+
+def replay_positions(start_positions, records, atoms_per_species=None, start_species=None):
+    """Follow one chain through the log of a sweep (``records``: the chain's column of the log of ``sweep`` or ``sweep_gcmc``) from
+    ``start_positions`` (one ``[m, 3]`` array per molecule, device molecule order): an accepted displacement replaces the molecule's
+    atoms by the logged placement, an accepted insertion appends ``atoms_per_species[species]`` atoms as the last molecule, an
+    accepted deletion moves the last molecule into the hole.  Yields, after every step, the list of the molecules' positions --
+    with ``start_species`` (the species of every molecule) pairs ``(species, positions)``."""
+    mols = [np.array(p, dtype=np.float64).reshape(-1, 3) for p in start_positions]
+    spec = None if start_species is None else [int(s) for s in start_species]
+    gcmc = "species" in (records.dtype.names or ())
+    for rec in records:
+        kind, d = int(rec["kind"]), int(rec["molecule"])
+        if rec["accepted"]:
+            if gcmc and kind == SWAP_INSERTION:
+                mols.append(np.array(rec["positions"][:int(atoms_per_species[int(rec["species"])])], dtype=np.float64))
+                if spec is not None:
+                    spec.append(int(rec["species"]))
+            elif gcmc and kind == SWAP_DELETION:
+                mols[d] = mols[-1]
+                mols.pop()
+                if spec is not None:
+                    spec[d] = spec[-1]
+                    spec.pop()
+            else:
+                mols[d] = np.array(rec["positions"][:len(mols[d])], dtype=np.float64)
+        yield list(mols) if spec is None else (list(spec), list(mols))

@@ -682,6 +682,7 @@ struct ceg_mc_group {
     std::vector<int64_t> pockets;                // [2K] of the last GCMC sweep: pocket-blocked steps, sum of the attempt indices
     unsigned char* d_baseline = nullptr;         // partial sums and results of ceg_mc_group_baseline (ceg_mc_baseline.hip); only grows
     size_t baseline_cap = 0;
+    GroupSampler* sampler = nullptr;             // density maps and series taken during sweeps (ceg_mc_sample.hip); nullptr: none
 };
 
 namespace {
@@ -702,6 +703,7 @@ void group_free(ceg_mc_group* g)
 {
     if (g->stream) { (void)hipStreamSynchronize(g->stream); (void)hipStreamDestroy(g->stream); }
     group_free_blocks(g);
+    sampler_free(g->sampler);
     if (g->d_views) (void)hipFree(g->d_views);
     if (g->d_done) (void)hipFree(g->d_done);
     if (g->d_scratch) (void)hipFree(g->d_scratch);
@@ -747,7 +749,7 @@ int ceg_mcs::group_refuse_poisoned(int c)
 
 ceg_mcs::GroupRef ceg_mcs::group_ref(ceg_mc_group* g)
 {
-    return GroupRef{g->device, g->stream, g->chains.data(), (int)g->chains.size(), g->d_views, &g->d_baseline, &g->baseline_cap};
+    return GroupRef{g->device, g->stream, g->chains.data(), (int)g->chains.size(), g->d_views, &g->d_baseline, &g->baseline_cap, &g->sampler};
 }
 
 bool ceg_mcs::group_views_current(ceg_mc_group* g) { return group_upload_views(g, std::vector<char>(g->chains.size(), 1)); }
@@ -1128,9 +1130,10 @@ int sweep_failed(ceg_mc_group* g)                        // some steps may have 
 // `stage` (lay.total bytes, all but the launch lists filled in) into the group's block, then nsteps steps of trial(fast, grid, lds, list,
 // table_ok, step) per class present and accept(grid, lds, step, record), back to back on the group's stream; afterwards the block from
 // `o_back` on is back in `stage` and the records are in log_out.  A failure once the steps have started marks every chain inconsistent.
-template <class Record, class Trial, class Accept>
+// With a sampler installed, frame(step) follows the accept launch of every step the sampler takes a frame after.
+template <class Record, class Trial, class Accept, class Frame>
 int run_sweep(ceg_mc_group* g, const SweepPlan& plan, const SweepLayout& lay, std::vector<unsigned char>& stage, size_t o_back, uint64_t first_step,
-              int64_t nsteps, Record* log_out, Trial&& trial, Accept&& accept)
+              int64_t nsteps, Record* log_out, Trial&& trial, Accept&& accept, Frame&& frame)
 {
     const size_t k = g->chains.size();
     size_t lds_trial[2];
@@ -1163,12 +1166,18 @@ int run_sweep(ceg_mc_group* g, const SweepPlan& plan, const SweepLayout& lay, st
     // ---- the steps: nothing between them but the stream's own order (no chain with a molecule and no log: nothing to do)
     const int32_t* d_list = sweep_at<const int32_t>(g, lay.list);
     const unsigned n0 = (unsigned)plan.list[0].size(), n1 = (unsigned)plan.list[1].size();
+    // (with every chain empty and no log the steps launch nothing; a sampler still takes its frames, and only those are launched)
     bool launched = true;
-    for (int64_t s = 0; s < nsteps && launched && (n0 + n1 > 0 || d_log); ++s) {
+    const bool work = n0 + n1 > 0 || d_log;
+    const int64_t frames_before = g->sampler ? sampler_frames_taken(g->sampler) : 0;
+    for (int64_t s = 0; s < nsteps && launched && (work || g->sampler); ++s) {
         const uint64_t step = first_step + (uint64_t)s;
+        const bool framed = g->sampler && sampler_frame_after(g->sampler, step);
+        if (!work && !framed) continue;
         if (n0) trial(false, dim3(2u * n0, 3u), lds_trial[0], d_list, table_ok[0], step);
         if (n1) trial(true, dim3(2u * n1, 3u), lds_trial[1], d_list + n0, table_ok[1], step);
-        accept(dim3((unsigned)k), plan.lds_accept, step, d_log ? d_log + (size_t)s * k : nullptr);
+        if (work) accept(dim3((unsigned)k), plan.lds_accept, step, d_log ? d_log + (size_t)s * k : nullptr);
+        if (framed) frame(step);
         launched = hipGetLastError() == hipSuccess;
     }
     const bool ok = hipStreamSynchronize(g->stream) == hipSuccess && launched &&
@@ -1177,6 +1186,7 @@ int run_sweep(ceg_mc_group* g, const SweepPlan& plan, const SweepLayout& lay, st
     g->accept_pending = false;
     g->uploads_pending = false;
     if (d_log) (void)hipFree(d_log);
+    if (!ok && g->sampler) sampler_rollback(g->sampler, g->stream, frames_before);
     return ok ? CEG_OK : sweep_failed(g);
 }
 
@@ -1218,6 +1228,8 @@ extern "C" int ceg_mc_group_sweep(ceg_mc_group_t* g, const ceg_mc_sweep_params_t
         if (h->v.nmol == 0) continue;                    // (an empty chain is in no launch list: its steps are idle)
         if (int rc = plan.add(c, h, mmax)) return rc;
     }
+    if (g->sampler)
+        if (int rc = sampler_admit(g->sampler, p->first_step, nsteps)) return rc;
     for (int c = 0; c < k; ++c) stats_out[c] = ceg_mc_sweep_stats_t{};
     if (nsteps == 0) return CEG_OK;
     SweepLayout lay((size_t)k, sizeof(McSweepChain));
@@ -1233,7 +1245,13 @@ extern "C" int ceg_mc_group_sweep(ceg_mc_group_t* g, const ceg_mc_sweep_params_t
         hipLaunchKernelGGL(k_mcg_sweep_accept, grid, dim3(MC_THREADS), lds, g->stream, g->d_views, sweep_at<const McSweepChain>(g, lay.par), p->seed, step,
                            sweep_at<const McPositions>(g, lay.prop), sweep_at<const double>(g, lay.rows), sweep_at<ceg_mc_sweep_stats_t>(g, o_stats), rec);
     };
-    if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept)) return rc;
+    int32_t max_slots = 0;
+    for (const ceg_mc* h : g->chains) max_slots = std::max(max_slots, h->v.natoms);
+    auto frame = [&](uint64_t step) {                     // (the molecule table does not change: counts from the views)
+        const SampleSource src{nullptr, 0, 0, &sweep_at<const ceg_mc_sweep_stats_t>(g, o_stats)->delta, nullptr, (int32_t)sizeof(ceg_mc_sweep_stats_t), max_slots};
+        sampler_enqueue(g->sampler, g->stream, g->d_views, k, (int64_t)step, src);
+    };
+    if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame)) return rc;
     memcpy(stats_out, stage.data() + o_stats, sizeof(ceg_mc_sweep_stats_t) * (size_t)k);
     return CEG_OK;
 }
@@ -1352,6 +1370,8 @@ extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_para
         stats_out[c].nmol = D.nmol;
         if (p->molecule_species_out && D.nmol > 0) memcpy(p->molecule_species_out + out_off[(size_t)c], ms, sizeof(int32_t) * (size_t)D.nmol);
     };
+    if (g->sampler)
+        if (int rc = sampler_admit(g->sampler, p->first_step, nsteps)) return rc;
     for (int c = 0; c < k; ++c) stats_out[c] = ceg_mc_gcmc_stats_t{};
     g->pockets.assign(2 * (size_t)k, 0);
     if (nsteps == 0) {
@@ -1402,7 +1422,17 @@ extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_para
                            sweep_at<int32_t>(g, o_free), p->seed, step, blocks ? sweep_at<const int32_t>(g, o_res) : nullptr, sweep_at<int64_t>(g, o_pock),
                            sweep_at<const McPositions>(g, lay.prop), sweep_at<const double>(g, lay.rows), sweep_at<ceg_mc_gcmc_stats_t>(g, o_stats), rec);
     };
-    if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept)) return rc;
+    static_assert(offsetof(McGcmcTable, nmol) == 0 && offsetof(McGcmcTable, natoms) == 4 && offsetof(McGcmcTable, count) == 8 && sizeof(McGcmcTable) % 4 == 0,
+                  "the head of a chain's table as SampleSource describes it");
+    int32_t max_slots = 0;
+    for (const McGcmcChain& P : pc) max_slots = std::max(max_slots, P.atoms_cap);
+    auto frame = [&](uint64_t step) {                     // (counts from the device's table: the views' nmol / natoms are stale during the sweep)
+        const ceg_mc_gcmc_stats_t* st = sweep_at<const ceg_mc_gcmc_stats_t>(g, o_stats);
+        const SampleSource src{&sweep_at<const McGcmcTable>(g, o_tab)->nmol, (int32_t)(sizeof(McGcmcTable) / 4), ns, &st->delta_moves, &st->delta_swaps,
+                               (int32_t)sizeof(ceg_mc_gcmc_stats_t), max_slots};
+        sampler_enqueue(g->sampler, g->stream, g->d_views, k, (int64_t)step, src);
+    };
+    if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame)) return rc;
     memcpy(g->pockets.data(), stage.data() + o_pock, sizeof(int64_t) * 2 * (size_t)k);
     // ---- the host mirrors from the device: molecule table, kinds, freed runs, counts and high-water mark of every chain that swapped
     const ceg_mc_gcmc_stats_t* st = reinterpret_cast<const ceg_mc_gcmc_stats_t*>(stage.data() + o_stats);

@@ -786,7 +786,27 @@ int rebuild_cells(ceg_mc* h);                                       // the devic
 bool accept_cell_ops(ceg_mc* h, int32_t molecule, const double* positions, McCellOps& ops);
 int check_molecule(const ceg_mc* h, const int32_t* kinds, int32_t m, McMolecule* nm);
 
-// defined in ceg_mc_group.hip: what ceg_mc_baseline.hip needs of a group
+// defined in ceg_mc_sample.hip: the sampler of a group (ceg_mc_group_set_sampler).  The group owns it and frees it; a sweep asks it
+// before its first launch whether its frames fit, and after the accept launch of a frame step enqueues the frame.
+struct GroupSampler;
+// where a frame finds what the views do not hold during a sweep, per chain c: counts + c * counts_stride = (molecules, high-water
+// mark of the atom slots, molecules per species [ncount]) in device memory (nullptr: nmol / natoms of the views, no species);
+// delta_moves / delta_swaps + c * stats_stride bytes: the running sums of the sweep's statistics (nullptr: 0)
+struct SampleSource {
+    const int32_t* counts;
+    int32_t counts_stride, ncount;
+    const double *delta_moves, *delta_swaps;
+    int32_t stats_stride;
+    int32_t max_slots;                           // no chain's high-water mark exceeds this while the frame runs
+};
+void sampler_free(GroupSampler* s);
+int sampler_admit(const GroupSampler* s, uint64_t first_step, int64_t nsteps);      // CEG_ERR_INVALID: the sweep's frames do not fit
+bool sampler_frame_after(const GroupSampler* s, uint64_t step);
+void sampler_enqueue(GroupSampler* s, hipStream_t stream, const McView* d_views, int k, int64_t step, const SampleSource& src);
+int64_t sampler_frames_taken(const GroupSampler* s);
+void sampler_rollback(GroupSampler* s, hipStream_t stream, int64_t frames);        // back to `frames` frames after a failed sweep
+
+// defined in ceg_mc_group.hip: what ceg_mc_baseline.hip and ceg_mc_sample.hip need of a group
 struct GroupRef {
     int device;
     hipStream_t stream;
@@ -795,6 +815,7 @@ struct GroupRef {
     const McView* d_views;                       // [k], current in stream order once group_views_current has returned true
     unsigned char** d_baseline;                  // the group's counterpart of ceg_mc::d_baseline / baseline_cap
     size_t* baseline_cap;
+    GroupSampler** sampler;                      // nullptr behind it: no sampler installed
 };
 GroupRef group_ref(ceg_mc_group* g);
 bool group_views_current(ceg_mc_group* g);       // every member's view into d_views where it changed since its last upload

@@ -776,6 +776,97 @@ function mc_group_block_counts(g::Ptr{Cvoid}, k::Integer)
     pocket, attempts
 end
 
+# `ceg_mc_sampler_t` (152 bytes) and `ceg_mc_sample_record_t` (64 bytes) of include/ceg_hip.h
+struct McSampler
+    every::Int64
+    from_step::Int64
+    series_capacity::Int64
+    dims::NTuple{3,Int32}            # na, nb, nc; all zero: the series only
+    nmaps::Int32
+    nchannels::Int32
+    nkinds::Int32
+    nsym::Int32
+    _pad::Int32
+    unit_invmat::NTuple{9,Float64}   # column-major
+    chain_map::Ptr{Int32}
+    kind_channel::Ptr{Int32}
+    sym::Ptr{Float64}
+end
+struct McSampleRecord
+    step::Int64                      # the step the frame follows; -1 from mc_group_sample!
+    nmol::Int32
+    natoms::Int32
+    count::NTuple{8,Int32}           # molecules per species (GCMC sweeps)
+    delta_moves::Float64
+    delta_swaps::Float64
+end
+
+# what mc_group_sampler_read needs to shape its result: (na, nb, nc, nchannels, nmaps), K, the factor of `total` per frame and map
+const SAMPLERS = Dict{Ptr{Cvoid},Tuple{NTuple{5,Int},Int,Vector{Int}}}()
+
+"""
+`ceg_mc_group_set_sampler`: from now on `mc_group_sweep!` and `mc_group_sweep_gcmc!` take a frame after every absolute step `s` with
+`s ≥ from_step` and `(s + 1) % every == 0`: every atom binned as `bin_trajectory` bins it (src/averageclusters.jl:154-202) and one
+record per chain (the `Ns` of `GCMCRecorder`, src/parameterinputs.jl:232-249, and the running energy change) appended to the series.
+`mat` is the MC cell (`mc.ewald.mat` without units, Å); the map lives on `mat ./ supercell'`, with `dims` bins or
+`floor.(Int, cell_lengths ./ step)` (:169); neither: the series only.  `kind_channel[k]` is the 0-based channel of force-field index
+`k` (-1: not binned), `chain_map[c]` the 0-based map of chain `c` (-1: not binned), `symmetries` the `eq(y) = R*y + t` of
+`bin_trajectory` as `(R, t)` pairs.  Never executed here (no Julia in the image).
+"""
+function mc_group_set_sampler!(g::Ptr{Cvoid}, k::Integer, mat::AbstractMatrix{Float64}, every::Integer; from_step::Integer=0, step=nothing,
+                               dims=nothing, supercell=(1, 1, 1), kind_channel::Vector{Int32}=Int32[], chain_map::Vector{Int32}=zeros(Int32, k),
+                               symmetries=[], series_capacity::Integer=0)
+    unit = mat ./ collect(Float64, supercell)'
+    if dims === nothing && step !== nothing
+        dims = Tuple(floor.(Int, [norm(unit[:, j]) for j in 1:3] ./ (step isa Real ? step : ustrip(u"Å", step))))
+    end
+    withmap = dims !== nothing
+    d = withmap ? NTuple{3,Int32}(Int32.(dims)) : (Int32(0), Int32(0), Int32(0))
+    nmaps = withmap ? Int(maximum(chain_map)) + 1 : 0
+    nchannels = withmap ? Int(maximum(kind_channel; init=Int32(-1))) + 1 : 0
+    sym = Float64[]
+    for (R, t) in symmetries, r in 1:3
+        append!(sym, (R[r, 1], R[r, 2], R[r, 3], t[r]))
+    end
+    GC.@preserve chain_map kind_channel sym begin
+        spec = Ref(McSampler(every, from_step, series_capacity, d, nmaps, nchannels, length(kind_channel), length(symmetries), 0,
+                             Tuple(vec(inv(unit))), pointer(chain_map), pointer(kind_channel), isempty(sym) ? Ptr{Float64}(C_NULL) : pointer(sym)))
+        _check(ccall((:ceg_mc_group_set_sampler, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), g, spec))
+    end
+    per_frame = [(1 + length(symmetries))*prod(supercell)*count(==(m - 1), chain_map) for m in 1:nmaps]
+    SAMPLERS[g] = ((Int(d[1]), Int(d[2]), Int(d[3]), nchannels, nmaps), Int(k), per_frame)
+    nothing
+end
+
+"`ceg_mc_group_sample`: one frame of the resident state, now (asynchronous), for runs driven through `mc_group_trial!` / `mc_group_accept!`"
+function mc_group_sample!(g::Ptr{Cvoid})
+    _check(ccall((:ceg_mc_group_sample, LIB[]), Cint, (Ptr{Cvoid},), g))
+    nothing
+end
+
+"""
+`ceg_mc_group_sampler_read` -> `(bins, totals, series)`: `bins::Array{Int,5}` of size `(na, nb, nc, nchannels, nmaps)` --
+`bins[:, :, :, ch, m]` is the `Array{Int,3}` of `bin_trajectory` for channel `ch` of map `m` --, `totals[m]` the `total` of
+`bin_trajectories` summed over the chains of map `m` (src/averageclusters.jl:196,233-234), and `series`, a `K x frames` matrix of
+`McSampleRecord` (chain-fastest): `[r.nmol for r in series[c, :]]` is the `Ns` of chain `c`'s `GCMCRecorder`.
+"""
+function mc_group_sampler_read(g::Ptr{Cvoid})
+    shape, k, per_frame = SAMPLERS[g]
+    frames = Ref{Int64}(0)
+    _check(ccall((:ceg_mc_group_sampler_read, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}), g, C_NULL, C_NULL, frames))
+    bins = zeros(Int64, shape)
+    series = Matrix{McSampleRecord}(undef, k, frames[])
+    GC.@preserve bins series _check(ccall((:ceg_mc_group_sampler_read, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}),
+                                          g, isempty(bins) ? C_NULL : pointer(bins), frames[] > 0 ? pointer(series) : C_NULL, C_NULL))
+    bins, frames[] .* per_frame, series
+end
+
+"`ceg_mc_group_sampler_reset`: bins, series and the frame count back to zero"
+function mc_group_sampler_reset!(g::Ptr{Cvoid})
+    _check(ccall((:ceg_mc_group_sampler_reset, LIB[]), Cint, (Ptr{Cvoid},), g))
+    nothing
+end
+
 # `ceg_mc_baseline_t` of include/ceg_hip.h (48 bytes)
 struct McBaseline
     framework_vdw::Float64
@@ -818,6 +909,7 @@ end
 
 "`ceg_mc_group_destroy`: the chains get their own streams back and stay valid"
 function mc_group_close(g::Ptr{Cvoid})
+    delete!(SAMPLERS, g)                 # (the sampler dies with the group: a later group at this address starts without one)
     _check(ccall((:ceg_mc_group_destroy, LIB[]), Cint, (Ptr{Cvoid},), g))
     nothing
 end

@@ -872,6 +872,70 @@ CEG_API int ceg_mc_group_set_blocks(ceg_mc_group_t* group, const ceg_mc_block_t*
                                     const ceg_mc_block_t* atom_blocks, int32_t nkinds);
 CEG_API int ceg_mc_group_block_counts(ceg_mc_group_t* group, int64_t* pocket_out /*[K]*/, int64_t* attempts_out /*[K]*/);
 
+/* ---- sampler of a group: density maps and the per-cycle series, taken on the device while a sweep runs ----
+ * What a run produces besides its final state: the counts of bin_trajectory (src/averageclusters.jl:154-202), the input of
+ * average_clusters and of the site analysis, and the series of GCMCRecorder (Ns after every cycle, src/parameterinputs.jl:232-249)
+ * and of run_montecarlo! (the running energy, src/simulation.jl:784-799).  With a sampler installed, both sweeps take a FRAME after
+ * every absolute step s with s >= from_step and (s + 1) % every == 0, in step order: one more launch (k_mcg_sample) enqueued on the
+ * group's stream behind the accept launch of that step.  A frame bins every occupied atom slot of every chain and appends one record
+ * per chain to the series.  The sampler only reads chain state: statistics, logs and final states of a sweep are byte-identical
+ * with and without it, and with no sampler installed a sweep enqueues exactly the launches it enqueues without this section.
+ *
+ * Bins: int64 [nmaps][nchannels][nc][nb][na], a fastest -- one (map, channel) block is a Julia Array{Int,3}(na, nb, nc).  Zeroed by
+ *   set_sampler and by sampler_reset; frames accumulate.  dims = (0, 0, 0): no map, the series only.
+ * Bin of a position p, in FP64 without contraction and in this order (I = unit_invmat, column-major; n = dims):
+ *     y_r = (I[r] p_x + I[r+3] p_y) + I[r+6] p_z;   u_r = y_r - floor(y_r);   i_r = (int)ceil(u_r n_r) + (u_r == 0) - 1
+ *   (averageclusters.jl:182-184, 0-based), then clamped to [0, n_r - 1] for memory safety only.  The map lives on the UNIT cell (the
+ *   MC cell with its columns divided by the supercell): folding a supercell image onto it is the "- floor".
+ *   Every symmetry operation q adds one count more (:185-188): y'_r = ((R_r0 y_0 + R_r1 y_1) + R_r2 y_2) + t_r on the unfloored y, with
+ *   sym[q][r] = (R_r0, R_r1, R_r2, t_r), then the same index rule, into the same (map, channel).
+ * What is binned: the occupied atom slots (molecule >= 0 in the atom record) of the chains with chain_map[c] >= 0, into map
+ *   chain_map[c] and channel kind_channel[kind]; an atom of kind >= nkinds or with kind_channel[kind] == -1 is skipped.
+ * Atomics: integer atomics only, so bins and records do not depend on the order in which workgroups or lanes arrive.
+ * Series: one 64-byte record per (frame, chain), binned or not; series_out is [frames][K].  step: the step the frame follows;
+ *   nmol: the chain's molecules; natoms: the occupied atom slots counted in the atom records (an empty chain: 0, 0, nothing binned);
+ *   count: molecules per species during a GCMC sweep, zeros otherwise; delta_moves, delta_swaps: the sums of the sweep's statistics
+ *   as they stand after that step's accept launch (a plain sweep: its `delta` and 0; ceg_mc_group_sample: zeros).  During a GCMC sweep
+ *   molecule count, high-water mark of the slots and count[] are read from the device's own table, otherwise from the chains' views.
+ * A sweep whose frames (countable from first_step, nsteps, every, from_step) exceed what is left of series_capacity, or whose steps
+ *   reach beyond 2^63 - 1, returns CEG_ERR_INVALID before anything is launched or changed.
+ * set_sampler: installs (replacing the earlier one; NULL removes it); synchronises the group.  CEG_ERR_INVALID with nothing changed
+ *   -- the earlier sampler stays -- for: every < 1; from_step or series_capacity < 0; dims neither all zero nor all >= 1; with a map:
+ *   nmaps or nchannels < 1, nkinds < 0, an entry of chain_map outside [-1, nmaps) or of kind_channel outside [-1, nchannels), a
+ *   unit_invmat or sym entry that is not finite, a missing array, more than CEG_MC_SAMPLER_MAX_BINS bins over all maps and channels (8 GiB of counts); with or
+ *   without a map: nsym outside [0, CEG_MC_SAMPLER_MAX_SYM].  Without a map, nmaps, nchannels, nkinds, unit_invmat and the arrays
+ *   are ignored.
+ * A frame whose launch fails is not counted, and a sweep that fails after it has enqueued frames takes none of them: the frame
+ *   count, the series and `total` never include a record that was not written.
+ * sample: one frame of the resident state, now (step = -1): asynchronous, ordered on the group's stream behind everything enqueued
+ *   so far; for the host-driven trial / accept route.  Members that keep neighbour cells are accepted: the atom records are
+ *   authoritative.  No sampler or a full series -> CEG_ERR_INVALID; a member marked inconsistent -> CEG_ERR_HIP.
+ * sampler_read: synchronises the group; bins_out (all bins), series_out ([frames][K]) and frames_out may each be NULL.
+ * sampler_reset: zeroes bins, series and the frame count. */
+#define CEG_MC_SAMPLER_MAX_SYM 191
+#define CEG_MC_SAMPLER_MAX_BINS 1073741824
+typedef struct ceg_mc_sampler {
+    int64_t every;             /* >= 1: a frame after absolute step s iff s >= from_step && (s + 1) % every == 0 */
+    int64_t from_step;         /* >= 0 (the ninit cycles of a run are not sampled) */
+    int64_t series_capacity;   /* >= 0 frames kept in the series */
+    int32_t dims[3];           /* na, nb, nc >= 1; all three 0: no density map, series only */
+    int32_t nmaps, nchannels, nkinds, nsym, _pad;
+    double  unit_invmat[9];    /* inverse of the UNIT cell the map lives on (MC cell ./ supercell), column-major */
+    const int32_t* chain_map;    /* [K]      map of chain c in [0, nmaps), or -1: not binned */
+    const int32_t* kind_channel; /* [nkinds] channel of atoms of ff kind k in [0, nchannels), or -1: not binned */
+    const double*  sym;          /* [nsym][3][4] rows (R_r0 R_r1 R_r2 t_r), fractional, unit cell; nsym <= MAX_SYM */
+} ceg_mc_sampler_t;
+typedef struct ceg_mc_sample_record {   /* 64 bytes */
+    int64_t step;              /* absolute step the frame follows; -1 for ceg_mc_group_sample */
+    int32_t nmol, natoms;      /* molecules, occupied atom slots */
+    int32_t count[CEG_MC_GCMC_MAX_SPECIES];  /* GCMC sweep: molecules per species; otherwise zeros */
+    double  delta_moves, delta_swaps;        /* the sweep's stats sums as they stand after that step */
+} ceg_mc_sample_record_t;
+CEG_API int ceg_mc_group_set_sampler(ceg_mc_group_t* group, const ceg_mc_sampler_t* spec);
+CEG_API int ceg_mc_group_sample(ceg_mc_group_t* group);
+CEG_API int ceg_mc_group_sampler_read(ceg_mc_group_t* group, int64_t* bins_out, ceg_mc_sample_record_t* series_out, int64_t* frames_out);
+CEG_API int ceg_mc_group_sampler_reset(ceg_mc_group_t* group);
+
 /* ---- baseline_energy (src/montecarlo.jl:530-542) of one chain, or of every chain of a group, from the resident state ----
  * What run_montecarlo! asks for at its start, at the first production cycle, after a move that risks underflow and for its final
  * drift check (src/simulation.jl:643,789,850-853; montecarlo.jl:364).  Synchronous; `out` is host memory ([K] for a group, member
