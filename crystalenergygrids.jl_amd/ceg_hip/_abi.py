@@ -84,6 +84,21 @@ class MC_SAMPLER(C.Structure):
 MC_SAMPLE_RECORD_DTYPE = np.dtype([('step', '<i8'), ('nmol', '<i4'), ('natoms', '<i4'), ('count', '<i4', (GCMC_MAX_SPECIES,)),
                                    ('delta_moves', '<f8'), ('delta_swaps', '<f8')], align=True)
 assert (C.sizeof(MC_SAMPLER), MC_SAMPLE_RECORD_DTYPE.itemsize) == (152, 64)
+MC_ADAPT_DMAX, MC_ADAPT_THETAMAX = 1, 2      # CEG_MC_ADAPT_*
+MC_CYCLES_MAX_RECORDS = 16777216             # CEG_MC_CYCLES_MAX_RECORDS
+
+
+class McCycles(C.Structure):
+    """``ceg_mc_cycles_t`` (``temperatures`` [ncycles][K] and ``prior`` [K][4] in host memory, either may be NULL)"""
+    _fields_ = [("ncycles", C.c_int64), ("steps_per_cycle", C.c_int64), ("cycle0", C.c_int64), ("adapt", C.c_int32), ("_pad", C.c_int32),
+                ("temperatures", C.c_void_p), ("prior", C.c_void_p)]
+
+
+# ``ceg_mc_cycle_record_t``: one record per (cycle, chain) of ``ceg_mc_group_sweep_cycles`` / ``ceg_mc_group_sweep_gcmc_cycles``
+MC_CYCLE_RECORD_DTYPE = np.dtype([('temperature', '<f8'), ('dmax', '<f8'), ('thetamax', '<f8'), ('dmax_next', '<f8'), ('thetamax_next', '<f8'),
+                                  ('delta_moves', '<f8'), ('delta_swaps', '<f8'), ('translation_trials', '<i8'), ('translation_accepted', '<i8'),
+                                  ('rotation_trials', '<i8'), ('rotation_accepted', '<i8'), ('nmol', '<i4'), ('_pad', '<i4')], align=True)
+assert (C.sizeof(McCycles), MC_CYCLE_RECORD_DTYPE.itemsize) == (48, 96)
 
 c_double_p = C.POINTER(C.c_double)
 c_float_p = C.POINTER(C.c_float)
@@ -222,6 +237,8 @@ PROTOTYPES = {
     "ceg_mc_group_accept": (C.c_int, [C.c_void_p, c_int32_p, c_double_p]),
     "ceg_mc_group_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ceg_mc_group_sweep_gcmc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ceg_mc_group_sweep_cycles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ceg_mc_group_sweep_gcmc_cycles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ceg_mc_group_set_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "ceg_mc_group_block_counts": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
     "ceg_mc_group_set_sampler": (C.c_int, [C.c_void_p, C.c_void_p]),

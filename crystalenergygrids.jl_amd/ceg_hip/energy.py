@@ -620,12 +620,28 @@ class DeviceMonteCarlo:
             pass
 
 
+class MonteCarloDrift(RuntimeError):
+    """The drift check at the end of ``run_montecarlo!`` (simulation.jl:850-853) failed: recorded and actual energy differ."""
+
+
+class MonteCarloRun(NamedTuple):
+    """What :meth:`DeviceMonteCarloGroup.run_montecarlo` returns"""
+    initial_energies: np.ndarray      # [ninit, K] K, after every initialisation cycle
+    energies: np.ndarray              # [ncycles, K] K, after every production cycle
+    cycles: np.ndarray                # [ninit + ncycles, K] _abi.MC_CYCLE_RECORD_DTYPE
+    stats: tuple                      # (the init call's stats or None, the production call's or None)
+    baselines: tuple                  # baseline_energies() at the start, at the first production cycle, at the end
+    recorded: np.ndarray              # [K] K, what the drift check compared with the final baseline (energies[-1] + the swaps' bookkeeping)
+
+
 class DeviceMonteCarloGroup:
     """K :class:`DeviceMonteCarlo` chains on one device stepped in lockstep (``ceg_mc_group_*``): one launch evaluates the trials
     of every chain, one launch applies every accepted move -- the way ``make_isotherm`` (parameterinputs.jl:316-329) runs one
     ``run_gcmc`` per pressure, with the launch cost shared by the chains.  With ``trial`` / ``accept`` the acceptance rule stays
     with the caller; ``sweep`` runs whole sweeps of translations and rotations on the device, ``sweep_gcmc`` whole sweeps of all six
-    move kinds of ``MCMoves``, insertions and deletions included.  While
+    move kinds of ``MCMoves``, insertions and deletions included; ``sweep_cycles`` / ``sweep_gcmc_cycles`` run either over whole cycles
+    with the temperature schedule and the step-size adaptation of ``run_montecarlo!`` on the device, and ``run_montecarlo`` composes
+    the reference's whole run from them.  While
     grouped the chains' own methods remain usable (insert, remove, single trials ...) and are ordered with the group calls; the
     group and its chains are driven from one thread.  Usable as a context manager; ``close()`` gives the chains back."""
 
@@ -772,8 +788,52 @@ class DeviceMonteCarloGroup:
         -> stats (structured array [K]: trials / acceptances per move kind, blocked trials, ``delta`` = sum of after - before over
         the accepted moves), and with ``log=True`` also the log [nsteps, K] (molecule in the DEVICE's molecule order, move kind,
         accepted flag, ``u``, the two rows, the proposed positions).  The host-side ``mc.positions`` are NOT touched: read
-        :meth:`DeviceMonteCarlo.state`.  The adaptation of ``dmax`` / ``thetamax`` (simulation.jl:820-825) stays with the caller,
-        between sweeps."""
+        :meth:`DeviceMonteCarlo.state`."""
+        return self._sweep(nsteps, None, seed, first_step, temperature=temperature, dmax=dmax, thetamax=thetamax, p_rotation=p_rotation,
+                           stream_id=stream_id, bead=bead, degrees=degrees, log=log)
+
+    def _cycles(self, ncycles: int, steps_per_cycle: int, temperature, adapt, cycle0: int, prior):
+        """The ``ceg_mc_cycles_t`` of a ``*_cycles`` call -> (struct, what it points to, the per-chain temperature of the sweep's own
+        parameters or None with a table, the records [ncycles, K] to fill)."""
+        k = len(self.chains)
+        names = {"dmax": _abi.MC_ADAPT_DMAX, "thetamax": _abi.MC_ADAPT_THETAMAX}
+        bits = int(adapt) if isinstance(adapt, (int, np.integer)) else sum(names[a] for a in set(adapt))
+        table = None
+        if np.ndim(temperature) == 2:
+            table = np.ascontiguousarray(temperature, dtype=np.float64)
+            if table.shape != (int(ncycles), k):
+                raise ValueError(f"temperature: a scalar, one per chain ({k}) or a table [{int(ncycles)}, {k}]")
+            temperature = None
+        pr = None
+        if prior is not None:
+            pr = np.ascontiguousarray(prior, dtype=np.int64)
+            if pr.shape != (k, 4):
+                raise ValueError(f"prior: [{k}, 4] translation trials, accepted, rotation trials, accepted")
+        fits = 0 <= int(ncycles) * k <= _abi.MC_CYCLES_MAX_RECORDS            # (beyond it the library refuses the call: nothing to hold)
+        records = np.zeros((int(ncycles) if fits else 1, k), dtype=_abi.MC_CYCLE_RECORD_DTYPE)
+        cyc = _abi.McCycles(int(ncycles), int(steps_per_cycle), int(cycle0), bits, 0, table.ctypes.data if table is not None else None,
+                            pr.ctypes.data if pr is not None else None)
+        return cyc, (table, pr), temperature, records
+
+    def sweep_cycles(self, ncycles: int, steps_per_cycle: int, seed: int, first_step: int = 0, *, temperature, dmax, thetamax,
+                     adapt=("dmax", "thetamax"), cycle0: int = 1, prior=None, p_rotation=0.5, stream_id=None, bead=None, degrees: bool = False,
+                     log: bool = False):
+        """``ceg_mc_group_sweep_cycles``: ``ncycles`` whole cycles of ``steps_per_cycle`` steps of :meth:`sweep` in one call, with the
+        end-of-cycle block of ``run_montecarlo!`` (simulation.jl:727-728, 818-827) on the device: ``temperature`` -- a scalar, one per
+        chain or a table ``[ncycles, K]`` whose row ``j`` is in force during cycle ``j`` (``simu.temperatures``) -- and the adaptation
+        of ``dmax`` / ``thetamax`` from the cumulative acceptance ratios after every cycle (``adapt``: the names to adapt, or the
+        ``CEG_MC_ADAPT_*`` bits).  ``cycle0``: the reference's ``counter_cycle`` of the first cycle of this call; ``prior`` ``[K, 4]``: the
+        translation trials, accepted, rotation trials, accepted before this call.  To continue a run pass ``first_step`` and ``cycle0``
+        advanced, ``prior`` = the last record's counters and ``dmax`` / ``thetamax`` = its ``dmax_next`` / ``thetamax_next``
+        (:func:`ceg_hip.mcrng.cycle_records` restates the records).  The other arguments as :meth:`sweep`.
+
+        -> (stats, cycles ``_abi.MC_CYCLE_RECORD_DTYPE`` [ncycles, K][, log [ncycles * steps_per_cycle, K]])."""
+        cycles = self._cycles(ncycles, steps_per_cycle, temperature, adapt, cycle0, prior)
+        return self._sweep(int(ncycles) * int(steps_per_cycle), cycles, seed, first_step, temperature=cycles[2], dmax=dmax, thetamax=thetamax,
+                           p_rotation=p_rotation, stream_id=stream_id, bead=bead, degrees=degrees, log=log)
+
+    def _sweep(self, nsteps, cycles, seed, first_step, *, temperature, dmax, thetamax, p_rotation, stream_id, bead, degrees, log):
+        """:meth:`sweep` (``cycles`` None) and :meth:`sweep_cycles` (``cycles`` from :meth:`_cycles`; ``temperature`` None with a table)"""
         from . import mcrng
         k = len(self.chains)
 
@@ -783,7 +843,8 @@ class DeviceMonteCarloGroup:
                 raise ValueError(f"{what}: one value or one per chain ({k})")
             return a
 
-        T, dm, pr = per_chain(temperature, "temperature"), per_chain(dmax, "dmax"), per_chain(p_rotation, "p_rotation")
+        T = None if temperature is None else per_chain(temperature, "temperature")
+        dm, pr = per_chain(dmax, "dmax"), per_chain(p_rotation, "p_rotation")
         th = per_chain(thetamax, "thetamax")
         if degrees:
             th = np.ascontiguousarray(np.deg2rad(th))
@@ -799,13 +860,17 @@ class DeviceMonteCarloGroup:
             by_device = {d: per_kind[i] for i, kind in enumerate(chain._slot) for d in kind}
             beads += [by_device[d] for d in sorted(by_device)]
         beads = np.ascontiguousarray(beads if beads else [0], dtype=np.int32)
-        params = _abi.SweepParams(int(seed), int(first_step), sid.ctypes.data, T.ctypes.data, dm.ctypes.data, th.ctypes.data,
-                                  pr.ctypes.data, beads.ctypes.data)
+        params = _abi.SweepParams(int(seed), int(first_step), sid.ctypes.data, T.ctypes.data if T is not None else None, dm.ctypes.data,
+                                  th.ctypes.data, pr.ctypes.data, beads.ctypes.data)
         stats = np.zeros(k, dtype=_abi.SWEEP_STATS_DTYPE)
         records = np.zeros((max(int(nsteps), 0), k), dtype=_abi.SWEEP_RECORD_DTYPE) if log else None
-        _abi.check(self._lib, self._lib.ceg_mc_group_sweep(self._h, C.addressof(params), int(nsteps), stats.ctypes.data,
-                                                           records.ctypes.data if log and records.size else None))
-        return (stats, records) if log else stats
+        log_ptr = records.ctypes.data if log and records.size else None
+        if cycles is None:
+            _abi.check(self._lib, self._lib.ceg_mc_group_sweep(self._h, C.addressof(params), int(nsteps), stats.ctypes.data, log_ptr))
+            return (stats, records) if log else stats
+        _abi.check(self._lib, self._lib.ceg_mc_group_sweep_cycles(self._h, C.addressof(params), C.addressof(cycles[0]), stats.ctypes.data,
+                                                                  cycles[3].ctypes.data if cycles[3].size else None, log_ptr))
+        return (stats, cycles[3], records) if log else (stats, cycles[3])
 
     def gcmc_species(self, moves, phiPV_div_k, self_reciprocal=None, bead=None) -> np.ndarray:
         """The species table of ``ceg_mc_group_sweep_gcmc`` (``_abi.GCMC_SPECIES_DTYPE``) from the first chain's setup: one species
@@ -863,6 +928,24 @@ class DeviceMonteCarloGroup:
         the coordinates (one synchronisation and copy per chain): ``mc.positions`` then holds one ``None`` per molecule, which is
         all the device entry points need, until :meth:`DeviceMonteCarlo.pull_positions` fills them in -- for runs of many sweeps
         that look at the coordinates only now and then."""
+        return self._sweep_gcmc(nsteps, None, seed, first_step, temperature=temperature, dmax=dmax, thetamax=thetamax, moves=moves,
+                                phiPV_div_k=phiPV_div_k, max_molecules=max_molecules, species=species, self_reciprocal=self_reciprocal,
+                                stream_id=stream_id, bead=bead, degrees=degrees, log=log, positions=positions)
+
+    def sweep_gcmc_cycles(self, ncycles: int, steps_per_cycle: int, seed: int, first_step: int = 0, *, temperature, dmax, thetamax,
+                          adapt=("dmax", "thetamax"), cycle0: int = 1, prior=None, moves=None, phiPV_div_k=None, max_molecules, species=None,
+                          self_reciprocal=None, stream_id=None, bead=None, degrees: bool = False, log: bool = False, positions: bool = True):
+        """``ceg_mc_group_sweep_gcmc_cycles``: :meth:`sweep_cycles` for :meth:`sweep_gcmc` -- a whole GCMC production run of K chains
+        in one call.  A temperature table must be constant per chain where a species swaps (simulation.jl:688).  The host mirrors are
+        rebuilt and the coordinates read back once, at the end.  -> (stats, cycles[, log])."""
+        cycles = self._cycles(ncycles, steps_per_cycle, temperature, adapt, cycle0, prior)
+        return self._sweep_gcmc(int(ncycles) * int(steps_per_cycle), cycles, seed, first_step, temperature=cycles[2], dmax=dmax, thetamax=thetamax,
+                                moves=moves, phiPV_div_k=phiPV_div_k, max_molecules=max_molecules, species=species, self_reciprocal=self_reciprocal,
+                                stream_id=stream_id, bead=bead, degrees=degrees, log=log, positions=positions)
+
+    def _sweep_gcmc(self, nsteps, cycles, seed, first_step, *, temperature, dmax, thetamax, moves, phiPV_div_k, max_molecules, species,
+                    self_reciprocal, stream_id, bead, degrees, log, positions):
+        """:meth:`sweep_gcmc` (``cycles`` None) and :meth:`sweep_gcmc_cycles`, as :meth:`_sweep`"""
         k = len(self.chains)
 
         def per_chain(x, what, dtype=np.float64):
@@ -871,7 +954,8 @@ class DeviceMonteCarloGroup:
                 raise ValueError(f"{what}: one value or one per chain ({k})")
             return a
 
-        T, dm, th = per_chain(temperature, "temperature"), per_chain(dmax, "dmax"), per_chain(thetamax, "thetamax")
+        T = None if temperature is None else per_chain(temperature, "temperature")
+        dm, th = per_chain(dmax, "dmax"), per_chain(thetamax, "thetamax")
         if degrees:
             th = np.ascontiguousarray(np.deg2rad(th))
         cap = per_chain(max_molecules, "max_molecules", np.int32)
@@ -888,12 +972,16 @@ class DeviceMonteCarloGroup:
             given += [by_device[d] for d in sorted(by_device)]
         given = np.ascontiguousarray(given if given else [0], dtype=np.int32)
         out = np.full(max(int(np.clip(cap, 0, None).sum()), 1), -1, dtype=np.int32)
-        params = _abi.GcmcParams(int(seed), int(first_step), sid.ctypes.data, T.ctypes.data, dm.ctypes.data, th.ctypes.data, len(table), 0,
-                                 table.ctypes.data, given.ctypes.data, cap.ctypes.data, out.ctypes.data)
+        params = _abi.GcmcParams(int(seed), int(first_step), sid.ctypes.data, T.ctypes.data if T is not None else None, dm.ctypes.data,
+                                 th.ctypes.data, len(table), 0, table.ctypes.data, given.ctypes.data, cap.ctypes.data, out.ctypes.data)
         stats = np.zeros(k, dtype=_abi.GCMC_STATS_DTYPE)
         records = np.zeros((max(int(nsteps), 0), k), dtype=_abi.GCMC_RECORD_DTYPE) if log else None
-        _abi.check(self._lib, self._lib.ceg_mc_group_sweep_gcmc(self._h, C.addressof(params), int(nsteps), stats.ctypes.data,
-                                                                records.ctypes.data if log and records.size else None))
+        log_ptr = records.ctypes.data if log and records.size else None
+        if cycles is None:
+            _abi.check(self._lib, self._lib.ceg_mc_group_sweep_gcmc(self._h, C.addressof(params), int(nsteps), stats.ctypes.data, log_ptr))
+        else:
+            _abi.check(self._lib, self._lib.ceg_mc_group_sweep_gcmc_cycles(self._h, C.addressof(params), C.addressof(cycles[0]), stats.ctypes.data,
+                                                                           cycles[3].ctypes.data if cycles[3].size else None, log_ptr))
         # the chains' host side from the reported table: _slot[i] = the device indices of species i in device order
         offsets = np.concatenate([[0], np.cumsum(np.clip(cap, 0, None))])
         for c, chain in enumerate(self.chains):
@@ -902,7 +990,146 @@ class DeviceMonteCarloGroup:
             chain.mc.positions = [[None] * len(kind) for kind in chain._slot]
             if positions:
                 chain.pull_positions()
+        if cycles is not None:
+            return (stats, cycles[3], records) if log else (stats, cycles[3])
         return (stats, records) if log else stats
+
+    def numsteps(self, moves=None):
+        """The reference's steps per cycle (``numsteps``, simulation.jl:683-700) of every chain: 50 per leading species with a swap
+        probability > 0, then the molecule count of the first species without one.  ``moves``: one :class:`ceg_hip.mcrng.MoveTable`
+        per species, or None (no swaps)."""
+        out = []
+        for chain in self.chains:
+            n = 0
+            for i, kind in enumerate(chain._slot):
+                if moves is None or moves[i].swap == 0:
+                    n += len(kind)
+                    break
+                n += 50
+            out.append(n)
+        return out
+
+    def run_montecarlo(self, temperatures, ncycles: int, ninit: int = 0, *, seed: int = 0, steps_per_cycle: Optional[int] = None, gcmc=None,
+                       dmax=1.3, thetamax=math.radians(30.0), adapt=("dmax", "thetamax"), p_rotation=0.5, stream_id=None, bead=None,
+                       positions: bool = True):
+        """The shape of ``run_montecarlo!`` (simulation.jl:640-860) for the K chains: ``baseline_energy``, the ``ninit`` cycles in one
+        :meth:`sweep_cycles` / :meth:`sweep_gcmc_cycles` call, ``baseline_energy`` again (the precise energy at the first production
+        cycle, :788-790), the ``ncycles`` production cycles in one call that continues ``cycle0``, the counters and the step sizes, the
+        final ``baseline_energy`` and the reference's drift check ``isapprox(recorded, actual, rtol=1e-9)`` (:850-853), raised as
+        :class:`MonteCarloDrift` where it fails.
+
+        ``temperatures``: a scalar, one per chain, or ``[ninit + ncycles, K]`` (``simu.temperatures`` per chain).  ``steps_per_cycle``
+        defaults to :meth:`numsteps` of the first chain; a chain whose ``numsteps`` differs is refused (it belongs in another group).
+        ``gcmc``: None for translations and rotations only, else the keywords of :meth:`sweep_gcmc` that describe the species
+        (``moves`` and ``phiPV_div_k``, or ``species``; ``max_molecules``; ``self_reciprocal``).  ``dmax`` / ``thetamax`` (radians) start
+        at the reference's 1.3 A and 30 degrees (``MoveStatistics(1.3u"Å", 30.0u"°")``).
+
+        -> :class:`MonteCarloRun`: ``initial_energies`` [ninit, K] and ``energies`` [ncycles, K] (the baseline of the phase + the
+        records' deltas, K), ``cycles`` [ninit + ncycles, K], ``stats`` (the init call's or None, the production call's or None),
+        ``baselines`` (start, first production cycle, end), each a list of ``BaselineEnergyReport``, and ``recorded`` [K], the energy
+        the drift check holds against the final baseline.
+
+        Swaps: the records' ``delta_swaps`` sums what ``compute_accept_move_swap`` calls ``diff``, +-(E - self_reciprocal) + tc, while
+        the state gains or loses E and the two Ewald constants move with the species counts.  ``recorded`` is therefore
+        ``energies[-1]`` plus, per species, (count now - count at the first production cycle) * self_reciprocal, minus the tail
+        correction's change as the species table holds it, plus the change of ``2 energy_net_charges + static_contribution`` and of
+        ``mc.tailcorrection`` -- all functions of the counts alone.  Without swaps it is ``energies[-1]``."""
+        from . import mcrng
+        k = len(self.chains)
+        ninit, ncycles = int(ninit), int(ncycles)
+        if ninit < 0 or ncycles < 0:
+            raise ValueError("ninit and ncycles must be >= 0")
+        moves = table = None
+        if gcmc is not None:                         # the species table once, for both calls and for the bookkeeping of the swaps
+            gcmc = dict(gcmc)
+            given = gcmc.pop("species", None)
+            described = (gcmc.pop("moves", None), gcmc.pop("phiPV_div_k", None), gcmc.pop("self_reciprocal", None))
+            table = np.ascontiguousarray(given if given is not None else self.gcmc_species(described[0], described[1], described[2], bead))
+            gcmc["species"] = table
+            moves = [mcrng.MoveTable(cumulatives=row["cumulative"]) for row in table]
+        per_chain = self.numsteps(moves)
+        L = per_chain[0] if steps_per_cycle is None else int(steps_per_cycle)
+        if steps_per_cycle is None and any(n != L for n in per_chain):
+            raise ValueError(f"the chains' steps per cycle differ ({per_chain}): chains whose cycle lengths differ belong in different groups")
+        if L < 1:
+            raise ValueError("empty simulation: no step per cycle (simulation.jl:718)")
+        T = np.asarray(temperatures, dtype=np.float64)
+        if T.ndim == 2 and T.shape != (ninit + ncycles, k):
+            raise ValueError(f"temperatures: a scalar, one per chain ({k}) or a table [{ninit + ncycles}, {k}]")
+        dm = np.broadcast_to(np.asarray(dmax, dtype=np.float64), (k,)).copy()
+        th = np.broadcast_to(np.asarray(thetamax, dtype=np.float64), (k,)).copy()
+        prior = np.zeros((k, 4), dtype=np.int64)
+        done = [0]                                   # cycles run so far
+        common = dict(adapt=adapt, stream_id=stream_id, bead=bead)
+
+        def retail(before):                          # mc.tailcorrection follows the species counts (modify_species!, montecarlo.jl:814,858)
+            from .hostmirror.montecarlo import modify_species_dryrun
+            for chain, old in zip(self.chains, before):
+                mc = chain.mc
+                if mc.tail_cross is None:
+                    continue
+                counts = list(old)
+                for i, kind in enumerate(chain._slot):
+                    while counts[i] != len(kind):
+                        num = 1 if counts[i] < len(kind) else -1
+                        mc.tailcorrection += modify_species_dryrun(mc.tail_framework, mc.tail_cross, counts, i, num)
+                        counts[i] += num
+
+        def phase(n, last):
+            rows = T[done[0]:done[0] + n] if T.ndim == 2 else T
+            args = dict(temperature=rows, dmax=dm, thetamax=th, cycle0=1 + done[0], prior=prior, **common)
+            if gcmc is None:
+                stats, cyc = self.sweep_cycles(n, L, seed, done[0] * L, p_rotation=p_rotation, **args)
+            else:
+                before = [[len(kind) for kind in chain._slot] for chain in self.chains]
+                stats, cyc = self.sweep_gcmc_cycles(n, L, seed, done[0] * L, positions=positions and last, **gcmc, **args)
+                retail(before)
+            if n > 0:
+                dm[:], th[:] = cyc[-1]["dmax_next"], cyc[-1]["thetamax_next"]
+                for q, name in enumerate(("translation_trials", "translation_accepted", "rotation_trials", "rotation_accepted")):
+                    prior[:, q] = cyc[-1][name]
+            done[0] += n
+            return stats, cyc
+
+        start = self.baseline_energies()
+        base = np.array([float(r) for r in start])
+        stats_init = stats = None
+        cycles = np.zeros((0, k), dtype=_abi.MC_CYCLE_RECORD_DTYPE)
+        initial_energies = np.zeros((0, k))
+        production = start
+        if ninit > 0:
+            stats_init, cycles = phase(ninit, ncycles == 0)
+            initial_energies = base[None, :] + cycles["delta_moves"] + cycles["delta_swaps"]
+            production = self.baseline_energies()
+            base = np.array([float(r) for r in production])
+        energies = np.zeros((0, k))
+        recorded = base.copy()
+        if ncycles > 0:
+            counts0 = [[len(kind) for kind in chain._slot] for chain in self.chains]
+            consts0 = [chain.ewald_constants() for chain in self.chains]
+            tail0 = [chain.mc.tailcorrection for chain in self.chains]
+            stats, cyc = phase(ncycles, True)
+            energies = base[None, :] + cyc["delta_moves"] + cyc["delta_swaps"]
+            cycles = np.concatenate([cycles, cyc])
+            recorded = energies[-1].copy()
+            for c, chain in enumerate(self.chains if table is not None else []):
+                counts, ns = list(counts0[c]), len(table)
+                for i, kind in enumerate(chain._slot):
+                    while counts[i] != len(kind):
+                        num = 1 if counts[i] < len(kind) else -1
+                        recorded[c] += num * float(table[i]["self_reciprocal"]) - mcrng.tail_change(table[i]["tail_framework"], table[i]["tail_cross"][:ns],
+                                                                                                     counts, i, num)
+                        counts[i] += num
+                (enc0, static0), (enc1, static1) = consts0[c], chain.ewald_constants()
+                recorded[c] += ((2 * enc1 + static1) - (2 * enc0 + static0)) + (chain.mc.tailcorrection - tail0[c])
+        end = start
+        if ninit + ncycles > 0:                      # (not a single-point computation, simulation.jl:849)
+            end = self.baseline_energies()
+            for c, (rec, actual) in enumerate(zip(recorded, (float(r) for r in end))):
+                if not abs(rec - actual) <= 1e-9 * max(abs(rec), abs(actual)):
+                    raise MonteCarloDrift(f"chain {c}: energy deviation observed between actual ({actual!r}) and recorded ({rec!r}): "
+                                          "the simulation results are wrong")
+        return MonteCarloRun(initial_energies, energies, cycles, (stats_init, stats), (start, production, end), recorded)
 
     def set_sampler(self, every: Optional[int], from_step: int = 0, step: Optional[float] = None, dims=None, supercell=(1, 1, 1), channels=None,
                     chain_map=None, symmetries=(), series_capacity: int = 0) -> None:

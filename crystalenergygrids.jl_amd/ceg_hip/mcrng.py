@@ -23,6 +23,10 @@ Purposes for stream ``c`` at the absolute step ``s`` (key = seed low / high word
 Block pockets (``ceg_mc_group_set_blocks``; ``propose_gcmc(..., blocks=...)``): attempt ``t = 0..999`` of a proposal that ``choose_step!``
 retries (simulation.jl:299-320) draws purposes 6-8 with counter word 3 = ``purpose | (t << 8)`` (:func:`draw_attempt`); attempt 0 is the
 plain purpose.  :func:`block_lookup` is ``BlockFile`` getindex (coordinates.jl:58-66,97-101) in the device's operation order.
+
+Cycles (``ceg_mc_group_sweep_cycles`` / ``ceg_mc_group_sweep_gcmc_cycles``): :func:`adapt_dmax`, :func:`adapt_thetamax` and
+:func:`cycle_records` restate the end-of-cycle adaptation of ``statistics.dmax`` / ``θmax`` (simulation.jl:818-827) in the operation
+order of ``k_mcg_cycle_end``, ``thetamax`` in radians.
 """
 from __future__ import annotations
 
@@ -467,3 +471,61 @@ def replay_positions(start_positions, records, atoms_per_species=None, start_spe
             else:
                 mols[d] = np.array(rec["positions"][:len(mols[d])], dtype=np.float64)
         yield list(mols) if spec is None else (list(spec), list(mols))
+
+
+# ---- cycles (``ceg_mc_group_sweep_cycles`` / ``ceg_mc_group_sweep_gcmc_cycles``): the end-of-cycle block of run_montecarlo!
+# (simulation.jl:818-827) in the operation order of ``k_mcg_cycle_end``, thetamax in radians as the ABI holds it
+ADAPT_DMAX, ADAPT_THETAMAX = 1, 2
+DMAX_MIN, DMAX_MAX = 0.1, 3.0
+THETAMAX_MIN, THETAMAX_MAX, THETAMAX_GAIN = 0.17453292519943295, 3.141592653589793, 2.0943951023931953      # 10, 180 and 120 degrees
+
+
+def _clamp(x: float, lo: float, hi: float) -> float:
+    return hi if x > hi else (lo if x < lo else x)
+
+
+def adapt_dmax(dmax: float, accepted: int, trials: int, cc: int) -> float:
+    """``statistics.dmax`` after cycle ``cc`` (the reference's ``counter_cycle``, >= 1) from the cumulative translation counters
+    (simulation.jl:818-822); unchanged with zero trials (the reference's NaN ratio)."""
+    if trials <= 0:
+        return float(dmax)
+    r = float(accepted) / float(trials)
+    q = 10.0 / float(99 + cc)
+    s = math.sqrt(q)
+    f = (r - 0.25) * s
+    g = 1.0 + f
+    return _clamp(float(dmax) * g, DMAX_MIN, DMAX_MAX)
+
+
+def adapt_thetamax(thetamax: float, accepted: int, trials: int, cc: int) -> float:
+    """``statistics.θmax`` in radians after cycle ``cc`` from the cumulative rotation counters (simulation.jl:823-826); unchanged with
+    zero trials.  A restatement in radians: not bit-equal to the reference's arithmetic in degrees."""
+    if trials <= 0:
+        return float(thetamax)
+    r = float(accepted) / float(trials)
+    a = (r - 0.5) / float(cc)
+    b = a * THETAMAX_GAIN
+    return _clamp(float(thetamax) + b, THETAMAX_MIN, THETAMAX_MAX)
+
+
+def cycle_records(temperatures, dmax: float, thetamax: float, counters, nmol, delta_moves=None, delta_swaps=None, *, cycle0: int = 1,
+                  adapt: int = ADAPT_DMAX | ADAPT_THETAMAX, prior=(0, 0, 0, 0)) -> np.ndarray:
+    """The records (``_abi.MC_CYCLE_RECORD_DTYPE`` [ncycles]) ``k_mcg_cycle_end`` writes for ONE chain that starts the call with
+    ``dmax`` / ``thetamax``: ``temperatures[j]`` in force during cycle ``j``, ``counters[j]`` = the CALL's (translation trials, accepted,
+    rotation trials, accepted) as they stand at the end of cycle ``j`` (``prior`` is added), ``nmol[j]`` the chain's molecules then,
+    ``delta_moves[j]`` / ``delta_swaps[j]`` the call's sums then (None: zeros).  A chain without molecules at a cycle end, a kind with
+    zero trials and a clear ``adapt`` bit carry the value over."""
+    from ._abi import MC_CYCLE_RECORD_DTYPE
+    n = len(temperatures)
+    out = np.zeros(n, dtype=MC_CYCLE_RECORD_DTYPE)
+    d, t = float(dmax), float(thetamax)
+    for j in range(n):
+        tt, ta, rt, ra = (int(p) + int(x) for p, x in zip(prior, counters[j]))
+        cc = int(cycle0) + j
+        live = int(nmol[j]) > 0
+        dn = adapt_dmax(d, ta, tt, cc) if live and adapt & ADAPT_DMAX else d
+        tn = adapt_thetamax(t, ra, rt, cc) if live and adapt & ADAPT_THETAMAX else t
+        out[j] = (float(temperatures[j]), d, t, dn, tn, 0.0 if delta_moves is None else float(delta_moves[j]),
+                  0.0 if delta_swaps is None else float(delta_swaps[j]), tt, ta, rt, ra, int(nmol[j]), 0)
+        d, t = dn, tn
+    return out

@@ -3,6 +3,8 @@
 //   ceg_mc_group_sweep             S steps of translations and rotations: proposal, Metropolis rule and update on the device
 //   ceg_mc_group_sweep_gcmc        the same with all six move kinds, swaps included, and the molecule table owned by the device
 //   ceg_mc_group_set_blocks        block pockets: inblockpocket and the retry loop of choose_step!, resolved inside the GCMC trial launch
+//   ceg_mc_group_sweep_cycles      either sweep over whole cycles: the same body (sweep_plain / sweep_gcmc) with a ceg_mc_cycles_t, one
+//   ceg_mc_group_sweep_gcmc_cycles   launch of ceg_mc_cycles.hip behind the last step of every cycle (temperature table, dmax / thetamax)
 // The two sweeps have their own kernels, per-chain parameters and read-back, and share one host driver (run_sweep).
 #include "ceg_mc_state.h"
 
@@ -1076,10 +1078,11 @@ int sweep_refuse_chain(const ceg_mc* h, int c)
 }
 
 // temperature and step sizes of chain c (Params: either sweep's parameters)
+// (temperature: the call's [K] values, or those of the first cycle of a table; nullptr: a table without rows, nothing to check)
 template <class Params>
-int sweep_check_steps(const Params* p, int c)
+int sweep_check_steps(const Params* p, const double* temperature, int c)
 {
-    if (!std::isfinite(p->temperature[c]) || !(p->temperature[c] > 0.0)) return group_bad(c, "the temperature must be finite and > 0");
+    if (temperature && (!std::isfinite(temperature[c]) || !(temperature[c] > 0.0))) return group_bad(c, "the temperature must be finite and > 0");
     if (!std::isfinite(p->dmax[c]) || p->dmax[c] < 0.0) return group_bad(c, "dmax must be finite and >= 0");
     if (!std::isfinite(p->thetamax[c]) || p->thetamax[c] < 0.0) return group_bad(c, "thetamax must be finite and >= 0");
     return CEG_OK;
@@ -1130,10 +1133,11 @@ int sweep_failed(ceg_mc_group* g)                        // some steps may have 
 // `stage` (lay.total bytes, all but the launch lists filled in) into the group's block, then nsteps steps of trial(fast, grid, lds, list,
 // table_ok, step) per class present and accept(grid, lds, step, record), back to back on the group's stream; afterwards the block from
 // `o_back` on is back in `stage` and the records are in log_out.  A failure once the steps have started marks every chain inconsistent.
-// With a sampler installed, frame(step) follows the accept launch of every step the sampler takes a frame after.
-template <class Record, class Trial, class Accept, class Frame>
+// With a sampler installed, frame(step) follows the accept launch of every step the sampler takes a frame after.  With cycle_len > 0,
+// cycle_end(j) follows the last step of cycle j of the call (step s of the call with (s + 1) % cycle_len == 0), behind its frame.
+template <class Record, class Trial, class Accept, class Frame, class CycleEnd>
 int run_sweep(ceg_mc_group* g, const SweepPlan& plan, const SweepLayout& lay, std::vector<unsigned char>& stage, size_t o_back, uint64_t first_step,
-              int64_t nsteps, Record* log_out, Trial&& trial, Accept&& accept, Frame&& frame)
+              int64_t nsteps, Record* log_out, Trial&& trial, Accept&& accept, Frame&& frame, int64_t cycle_len, CycleEnd&& cycle_end)
 {
     const size_t k = g->chains.size();
     size_t lds_trial[2];
@@ -1170,14 +1174,16 @@ int run_sweep(ceg_mc_group* g, const SweepPlan& plan, const SweepLayout& lay, st
     bool launched = true;
     const bool work = n0 + n1 > 0 || d_log;
     const int64_t frames_before = g->sampler ? sampler_frames_taken(g->sampler) : 0;
-    for (int64_t s = 0; s < nsteps && launched && (work || g->sampler); ++s) {
+    for (int64_t s = 0; s < nsteps && launched && (work || g->sampler || cycle_len > 0); ++s) {
         const uint64_t step = first_step + (uint64_t)s;
         const bool framed = g->sampler && sampler_frame_after(g->sampler, step);
-        if (!work && !framed) continue;
+        const bool ends = cycle_len > 0 && (s + 1) % cycle_len == 0;
+        if (!work && !framed && !ends) continue;
         if (n0) trial(false, dim3(2u * n0, 3u), lds_trial[0], d_list, table_ok[0], step);
         if (n1) trial(true, dim3(2u * n1, 3u), lds_trial[1], d_list + n0, table_ok[1], step);
         if (work) accept(dim3((unsigned)k), plan.lds_accept, step, d_log ? d_log + (size_t)s * k : nullptr);
         if (framed) frame(step);
+        if (ends) cycle_end(s / cycle_len);
         launched = hipGetLastError() == hipSuccess;
     }
     const bool ok = hipStreamSynchronize(g->stream) == hipSuccess && launched &&
@@ -1190,18 +1196,56 @@ int run_sweep(ceg_mc_group* g, const SweepPlan& plan, const SweepLayout& lay, st
     return ok ? CEG_OK : sweep_failed(g);
 }
 
-}  // namespace
+// the cycles of a call (ceg_mc_cycles.hip) on the host: `cycled` -- the call came through a *_cycles entry point, cy as it was given
+struct SweepCycles {
+    bool cycled;
+    const ceg_mc_cycles_t* cy;
+    ceg_mc_cycle_record_t* out;
+    bool table() const { return cycled && cy->temperatures; }
+    // the temperatures the first step runs at: the table's first row, nullptr for a table without rows, else the parameters' own
+    const double* first_row(const double* temperature) const { return table() ? (cy->ncycles > 0 ? cy->temperatures : nullptr) : temperature; }
+    // the three segments of the group's block the cycle ends use, behind the statistics (read back with them); none without cycles
+    size_t o_rec = 0, o_table = 0, o_prior = 0;
+    void layout(SweepLayout& lay, size_t k)
+    {
+        if (!cycled) return;
+        o_rec = lay.segment(sizeof(ceg_mc_cycle_record_t) * (size_t)cy->ncycles * k);
+        o_table = lay.segment(table() ? sizeof(double) * (size_t)cy->ncycles * k : 0);
+        o_prior = lay.segment(sizeof(int64_t) * 4 * k);
+    }
+    void fill(std::vector<unsigned char>& stage, size_t k) const
+    {
+        if (!cycled) return;
+        if (table()) memcpy(stage.data() + o_table, cy->temperatures, sizeof(double) * (size_t)cy->ncycles * k);
+        if (cy->prior) memcpy(stage.data() + o_prior, cy->prior, sizeof(int64_t) * 4 * k);
+    }
+    CycleRun run(const ceg_mc_group* g) const
+    {
+        return CycleRun{cy->ncycles, cy->steps_per_cycle, cy->cycle0, cy->adapt, sweep_at<const int64_t>(g, o_prior),
+                        table() ? sweep_at<const double>(g, o_table) : nullptr, sweep_at<ceg_mc_cycle_record_t>(g, o_rec)};
+    }
+    void read_back(const std::vector<unsigned char>& stage, size_t k) const
+    {
+        if (cycled && cy->ncycles > 0) memcpy(out, stage.data() + o_rec, sizeof(ceg_mc_cycle_record_t) * (size_t)cy->ncycles * k);
+    }
+};
 
-extern "C" int ceg_mc_group_sweep(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nsteps, ceg_mc_sweep_stats_t* stats_out,
-                                  ceg_mc_sweep_record_t* log_out)
+// ceg_mc_group_sweep (C.cycled false: nsteps as given) and ceg_mc_group_sweep_cycles (nsteps from the cycles)
+int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nsteps, SweepCycles C, ceg_mc_sweep_stats_t* stats_out,
+                ceg_mc_sweep_record_t* log_out)
 {
     static_assert(sizeof(ceg_mc_sweep_record_t) == 472 && sizeof(ceg_mc_sweep_stats_t) == 48, "layouts the bindings restate");
     static_assert(sizeof(((ceg_mc_sweep_record_t*)nullptr)->positions) == sizeof(McPositions), "a record holds one placement");
-    if (!g || !p || !stats_out || !p->stream_id || !p->temperature || !p->dmax || !p->thetamax || !p->p_rotation)
+    static_assert(offsetof(McSweepChain, dmax) == offsetof(McSweepChain, temperature) + 8 && offsetof(McSweepChain, thetamax) == offsetof(McSweepChain, temperature) + 16,
+                  "temperature, dmax, thetamax adjacent, as CycleSource describes them");
+    if (!g || !p || !stats_out || !p->stream_id || (!p->temperature && !(C.cycled && C.cy && C.cy->temperatures)) || !p->dmax || !p->thetamax || !p->p_rotation)
         return merr(CEG_ERR_INVALID, "bad argument");
     if (nsteps < 0) return merr(CEG_ERR_INVALID, "negative number of steps");
     if (g->d_blocks) return merr(CEG_ERR_UNSUPPORTED, "the group has block masks installed: only ceg_mc_group_sweep_gcmc tests block pockets");
     const int k = (int)g->chains.size();
+    if (C.cycled)
+        if (int rc = cycles_check(C.cy, k, p->first_step, false, C.out, &nsteps)) return rc;
+    const double* temperature = C.first_row(p->temperature);
     // ---- every refusal before anything is launched or changed, chain by chain
     std::vector<McSweepChain> pc((size_t)k);
     std::vector<int32_t> beads;
@@ -1209,14 +1253,14 @@ extern "C" int ceg_mc_group_sweep(ceg_mc_group_t* g, const ceg_mc_sweep_params_t
     for (int c = 0; c < k; ++c) {
         ceg_mc* h = g->chains[c];
         if (int rc = sweep_refuse_chain(h, c)) return rc;
-        if (int rc = sweep_check_steps(p, c)) return rc;
+        if (int rc = sweep_check_steps(p, temperature, c)) return rc;
         if (!(p->p_rotation[c] >= 0.0 && p->p_rotation[c] <= 1.0)) return group_bad(c, "p_rotation must lie in [0, 1]");
         if (int rc = sweep_check_stream_id(p->stream_id, c)) return rc;
         McSweepChain& P = pc[(size_t)c];
         P.stream_id = p->stream_id[c];
         P.bead_off = (int32_t)beads.size();
         P.stride = h->stride;
-        P.temperature = p->temperature[c]; P.dmax = p->dmax[c]; P.thetamax = p->thetamax[c]; P.p_rotation = p->p_rotation[c];
+        P.temperature = temperature ? temperature[c] : 0.0; P.dmax = p->dmax[c]; P.thetamax = p->thetamax[c]; P.p_rotation = p->p_rotation[c];
         if (h->v.nmol > 0 && !p->bead) return merr(CEG_ERR_INVALID, "bad argument");
         int mmax = 0;
         for (int j = 0; j < h->v.nmol; ++j) {
@@ -1234,7 +1278,9 @@ extern "C" int ceg_mc_group_sweep(ceg_mc_group_t* g, const ceg_mc_sweep_params_t
     if (nsteps == 0) return CEG_OK;
     SweepLayout lay((size_t)k, sizeof(McSweepChain));
     const size_t o_bead = lay.segment(sizeof(int32_t) * beads.size()), o_stats = lay.segment(sizeof(ceg_mc_sweep_stats_t) * (size_t)k);
+    C.layout(lay, (size_t)k);
     std::vector<unsigned char> stage(lay.total, 0);
+    C.fill(stage, (size_t)k);
     memcpy(stage.data() + lay.par, pc.data(), sizeof(McSweepChain) * (size_t)k);
     if (!beads.empty()) memcpy(stage.data() + o_bead, beads.data(), sizeof(int32_t) * beads.size());
     auto trial = [&](bool fast, dim3 grid, size_t lds, const int32_t* list, int table_ok, uint64_t step) {
@@ -1251,20 +1297,32 @@ extern "C" int ceg_mc_group_sweep(ceg_mc_group_t* g, const ceg_mc_sweep_params_t
         const SampleSource src{nullptr, 0, 0, &sweep_at<const ceg_mc_sweep_stats_t>(g, o_stats)->delta, nullptr, (int32_t)sizeof(ceg_mc_sweep_stats_t), max_slots};
         sampler_enqueue(g->sampler, g->stream, g->d_views, k, (int64_t)step, src);
     };
-    if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame)) return rc;
+    auto cycle_end = [&](int64_t j) {                     // (the molecule table does not change: counts from the views)
+        const ceg_mc_sweep_stats_t* st = sweep_at<const ceg_mc_sweep_stats_t>(g, o_stats);
+        const CycleSource src{&st->translation_trials, &st->translation_accepted, &st->rotation_trials, &st->rotation_accepted, &st->delta, nullptr, nullptr,
+                              &sweep_at<McSweepChain>(g, lay.par)->temperature, (int32_t)sizeof(ceg_mc_sweep_stats_t), 0, (int32_t)sizeof(McSweepChain), 0};
+        cycles_enqueue(g->stream, g->d_views, k, C.run(g), j, src);
+    };
+    if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame, C.cycled ? C.cy->steps_per_cycle : 0, cycle_end))
+        return rc;
     memcpy(stats_out, stage.data() + o_stats, sizeof(ceg_mc_sweep_stats_t) * (size_t)k);
+    C.read_back(stage, (size_t)k);
     return CEG_OK;
 }
 
-extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps, ceg_mc_gcmc_stats_t* stats_out,
-                                       ceg_mc_gcmc_record_t* log_out)
+// ceg_mc_group_sweep_gcmc and ceg_mc_group_sweep_gcmc_cycles, as sweep_plain
+int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps, SweepCycles C, ceg_mc_gcmc_stats_t* stats_out,
+               ceg_mc_gcmc_record_t* log_out)
 {
     static_assert(sizeof(ceg_mc_gcmc_species_t) == 584 && sizeof(ceg_mc_gcmc_params_t) == 88 && sizeof(ceg_mc_gcmc_stats_t) == 192 &&
                       sizeof(ceg_mc_gcmc_record_t) == 488,
                   "layouts the bindings restate");
     static_assert(sizeof(((ceg_mc_gcmc_record_t*)nullptr)->positions) == sizeof(McPositions), "a record holds one placement");
     static_assert(CEG_MC_GCMC_MAX_SPECIES >= 4, "the documented minimum");
-    if (!g || !p || !stats_out || !p->stream_id || !p->temperature || !p->dmax || !p->thetamax || !p->species || !p->max_molecules)
+    static_assert(offsetof(McGcmcChain, dmax) == offsetof(McGcmcChain, temperature) + 8 && offsetof(McGcmcChain, thetamax) == offsetof(McGcmcChain, temperature) + 16,
+                  "temperature, dmax, thetamax adjacent, as CycleSource describes them");
+    if (!g || !p || !stats_out || !p->stream_id || (!p->temperature && !(C.cycled && C.cy && C.cy->temperatures)) || !p->dmax || !p->thetamax || !p->species ||
+        !p->max_molecules)
         return merr(CEG_ERR_INVALID, "bad argument");
     if (nsteps < 0) return merr(CEG_ERR_INVALID, "negative number of steps");
     const int k = (int)g->chains.size();
@@ -1302,6 +1360,9 @@ extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_para
         mmax = std::max(mmax, (int)S.m);
         if (swaps) swap_atoms += S.m;
     }
+    if (C.cycled)                                        // (a varying temperature only where no species swaps, simulation.jl:688)
+        if (int rc = cycles_check(C.cy, k, p->first_step, swap_atoms > 0, C.out, &nsteps)) return rc;
+    const double* temperature = C.first_row(p->temperature);
     if (g->d_blocks) {                                   // block pockets: the masks must be those of this species table
         if (ns != g->blk_species) return merr(CEG_ERR_INVALID, "nspecies differs from the nspecies of ceg_mc_group_set_blocks");
         for (int i = 0; i < ns && g->blk_kinds > 0; ++i)
@@ -1315,7 +1376,7 @@ extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_para
     std::vector<size_t> out_off((size_t)k, 0);           // chain c of molecule_species_out: the sum of max_molecules[0..c), as documented
     for (int c = 0; c < k; ++c) {
         ceg_mc* h = g->chains[c];
-        if (int rc = sweep_check_steps(p, c)) return rc;
+        if (int rc = sweep_check_steps(p, temperature, c)) return rc;
         if (int rc = sweep_check_stream_id(p->stream_id, c)) return rc;
         for (int i = 0; i < ns; ++i)
             for (int a = 0; a < p->species[i].m; ++a)
@@ -1343,7 +1404,7 @@ extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_para
         P.stream_id = p->stream_id[c];
         P.stride = h->stride;
         P.max_molecules = maxmol;
-        P.temperature = p->temperature[c]; P.dmax = p->dmax[c]; P.thetamax = p->thetamax[c];
+        P.temperature = temperature ? temperature[c] : 0.0; P.dmax = p->dmax[c]; P.thetamax = p->thetamax[c];
         // freed runs of the host mirror: the runs of m atoms go to the first species with m atoms
         int most = 0;
         for (int i = 0; i < ns; ++i) {
@@ -1395,9 +1456,11 @@ extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_para
                  o_stats = lay.segment(sizeof(ceg_mc_gcmc_stats_t) * (size_t)k), o_tab = lay.segment(sizeof(McGcmcTable) * (size_t)k),
                  o_ms = lay.segment(sizeof(int32_t) * nspec_total), o_free = lay.segment(sizeof(int32_t) * nfree_total),
                  o_pock = lay.segment(sizeof(int64_t) * 2 * (size_t)k);
+    C.layout(lay, (size_t)k);
     const ceg_mc_block_t* blocks = g->d_blocks;          // NULL: no masks, the kernels take the path without the resolve stage
     const int block_kinds = g->blk_kinds;
     std::vector<unsigned char> stage(lay.total, 0);
+    C.fill(stage, (size_t)k);
     memcpy(stage.data() + lay.par, pc.data(), sizeof(McGcmcChain) * (size_t)k);
     memcpy(stage.data() + o_spec, p->species, sizeof(ceg_mc_gcmc_species_t) * (size_t)ns);
     memcpy(stage.data() + o_tab, tab.data(), sizeof(McGcmcTable) * (size_t)k);
@@ -1432,7 +1495,16 @@ extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_para
                                (int32_t)sizeof(ceg_mc_gcmc_stats_t), max_slots};
         sampler_enqueue(g->sampler, g->stream, g->d_views, k, (int64_t)step, src);
     };
-    if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame)) return rc;
+    auto cycle_end = [&](int64_t j) {                     // (the molecule count from the device's table, as the frames)
+        const ceg_mc_gcmc_stats_t* st = sweep_at<const ceg_mc_gcmc_stats_t>(g, o_stats);
+        const CycleSource src{&st->trials[0], &st->accepted[0], &st->trials[1], &st->accepted[1], &st->delta_moves, &st->delta_swaps,
+                              &sweep_at<const McGcmcTable>(g, o_tab)->nmol, &sweep_at<McGcmcChain>(g, lay.par)->temperature,
+                              (int32_t)sizeof(ceg_mc_gcmc_stats_t), (int32_t)sizeof(McGcmcTable), (int32_t)sizeof(McGcmcChain), 0};
+        cycles_enqueue(g->stream, g->d_views, k, C.run(g), j, src);
+    };
+    if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame, C.cycled ? C.cy->steps_per_cycle : 0, cycle_end))
+        return rc;
+    C.read_back(stage, (size_t)k);
     memcpy(g->pockets.data(), stage.data() + o_pock, sizeof(int64_t) * 2 * (size_t)k);
     // ---- the host mirrors from the device: molecule table, kinds, freed runs, counts and high-water mark of every chain that swapped
     const ceg_mc_gcmc_stats_t* st = reinterpret_cast<const ceg_mc_gcmc_stats_t*>(stage.data() + o_stats);
@@ -1464,4 +1536,30 @@ extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_para
         fill_counts(c, nt[c], ms + pc[(size_t)c].spec_off);
     }
     return CEG_OK;
+}
+
+}  // namespace
+
+extern "C" int ceg_mc_group_sweep(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nsteps, ceg_mc_sweep_stats_t* stats_out,
+                                  ceg_mc_sweep_record_t* log_out)
+{
+    return sweep_plain(g, p, nsteps, SweepCycles{false, nullptr, nullptr}, stats_out, log_out);
+}
+
+extern "C" int ceg_mc_group_sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps, ceg_mc_gcmc_stats_t* stats_out,
+                                       ceg_mc_gcmc_record_t* log_out)
+{
+    return sweep_gcmc(g, p, nsteps, SweepCycles{false, nullptr, nullptr}, stats_out, log_out);
+}
+
+extern "C" int ceg_mc_group_sweep_cycles(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, const ceg_mc_cycles_t* cy, ceg_mc_sweep_stats_t* stats_out,
+                                         ceg_mc_cycle_record_t* cycles_out, ceg_mc_sweep_record_t* log_out)
+{
+    return sweep_plain(g, p, 0, SweepCycles{true, cy, cycles_out}, stats_out, log_out);
+}
+
+extern "C" int ceg_mc_group_sweep_gcmc_cycles(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, const ceg_mc_cycles_t* cy, ceg_mc_gcmc_stats_t* stats_out,
+                                              ceg_mc_cycle_record_t* cycles_out, ceg_mc_gcmc_record_t* log_out)
+{
+    return sweep_gcmc(g, p, 0, SweepCycles{true, cy, cycles_out}, stats_out, log_out);
 }

@@ -806,6 +806,29 @@ void sampler_enqueue(GroupSampler* s, hipStream_t stream, const McView* d_views,
 int64_t sampler_frames_taken(const GroupSampler* s);
 void sampler_rollback(GroupSampler* s, hipStream_t stream, int64_t frames);        // back to `frames` frames after a failed sweep
 
+// defined in ceg_mc_cycles.hip: the cycle end of ceg_mc_group_sweep_cycles / ceg_mc_group_sweep_gcmc_cycles (k_mcg_cycle_end).
+// Where the launch finds, per chain c, what it reads and writes (all device memory): the four counters and the one or two sums of
+// the call's statistics at + c * stats_stride bytes (delta_swaps nullptr: 0); the molecule count at nmol + c * nmol_stride bytes
+// (nullptr: nmol of the views); the chain's (temperature, dmax, thetamax), three adjacent doubles, at triple + c * triple_stride bytes.
+struct CycleSource {
+    const int64_t *translation_trials, *translation_accepted, *rotation_trials, *rotation_accepted;
+    const double *delta_moves, *delta_swaps;
+    const int32_t* nmol;
+    double* triple;
+    int32_t stats_stride, nmol_stride, triple_stride, _pad;
+};
+// the cycles of one call: what cycles_check has admitted, and the three segments of the group's block the launches use
+struct CycleRun {
+    int64_t ncycles, steps_per_cycle, cycle0;
+    int32_t adapt;
+    const int64_t* d_prior;                      // [K][4]
+    const double* d_table;                       // [ncycles][K], or nullptr: no table
+    ceg_mc_cycle_record_t* d_records;            // [ncycles][K]
+};
+// CEG_ERR_INVALID for every refusal of the header that the cycles themselves give; *nsteps = ncycles * steps_per_cycle
+int cycles_check(const ceg_mc_cycles_t* cy, int k, uint64_t first_step, bool constant_columns, const void* cycles_out, int64_t* nsteps);
+void cycles_enqueue(hipStream_t stream, const McView* d_views, int k, const CycleRun& run, int64_t j, const CycleSource& src);
+
 // defined in ceg_mc_group.hip: what ceg_mc_baseline.hip and ceg_mc_sample.hip need of a group
 struct GroupRef {
     int device;

@@ -625,8 +625,7 @@ end
 for every chain of the group, proposals and Metropolis rule on the device, one synchronisation at the end.  `temperature` (K),
 `dmax` (Å), `thetamax` (unitful angle or radians) and `p_rotation` per chain; `bead[c]` the 1-based reference atom of every species
 of chain `c` in Ewald order (`mc.bead[i]` of its kind); step `s` of the call is step `first_step + s` of the counter-based stream.
-Returns the statistics per chain and, with `log=true`, the `nsteps x K` records (stored chain-fastest).  The adaptation of
-`statistics.dmax` / `θmax` (src/simulation.jl:820-825) stays with the caller, between sweeps.
+Returns the statistics per chain and, with `log=true`, the `nsteps x K` records (stored chain-fastest).
 """
 function mc_group_sweep!(g::Ptr{Cvoid}, nsteps::Integer, seed::Integer, first_step::Integer, temperature::Vector, dmax::Vector,
                          thetamax::Vector, p_rotation::Vector{Float64}, bead::Vector{Vector{Int}};
@@ -727,6 +726,110 @@ function mc_group_sweep_gcmc!(g::Ptr{Cvoid}, nsteps::Integer, seed::Integer, fir
     offsets = cumsum(vcat(0, max_molecules))
     final = [out[offsets[c]+1:offsets[c]+stats[c].nmol] for c in 1:k]
     log ? (stats, final, records) : (stats, final)
+end
+
+# `ceg_mc_cycles_t` and `ceg_mc_cycle_record_t` of include/ceg_hip.h (48 and 96 bytes)
+const MC_ADAPT_DMAX = Int32(1)
+const MC_ADAPT_THETAMAX = Int32(2)
+struct McCycles
+    ncycles::Int64
+    steps_per_cycle::Int64
+    cycle0::Int64                    # counter_cycle of the first cycle of this call (>= 1)
+    adapt::Int32                     # MC_ADAPT_* bits
+    _pad::Int32
+    temperatures::Ptr{Float64}       # K x ncycles (chain-fastest), or C_NULL: the temperature of the parameters throughout
+    prior::Ptr{Int64}                # 4 x K: translation trials, accepted, rotation trials, accepted before this call; C_NULL: zeros
+end
+struct McCycleRecord
+    temperature::Float64             # in force during the cycle
+    dmax::Float64
+    thetamax::Float64                # rad
+    dmax_next::Float64               # after the adaptation at the end of the cycle
+    thetamax_next::Float64
+    delta_moves::Float64             # the call's sums as they stand at the end of the cycle
+    delta_swaps::Float64
+    translation_trials::Int64        # prior + this call, at the end of the cycle
+    translation_accepted::Int64
+    rotation_trials::Int64
+    rotation_accepted::Int64
+    nmol::Int32
+    _pad::Int32
+end
+
+# the `ceg_mc_cycles_t` of a call and the arrays it points to (keep them alive across the ccall)
+function _mc_cycles(k::Integer, ncycles::Integer, steps_per_cycle::Integer, temperatures, adapt::Integer, cycle0::Integer, prior)
+    table = temperatures isa AbstractMatrix ? Float64[ustrip(u"K", temperatures[j, c]) for c in 1:k, j in 1:ncycles] : nothing
+    pr = prior === nothing ? nothing : Int64[prior[c][q] for q in 1:4, c in 1:k]
+    cyc = McCycles(Int64(ncycles), Int64(steps_per_cycle), Int64(cycle0), Int32(adapt), Int32(0),
+                   table === nothing ? Ptr{Float64}(C_NULL) : pointer(table), pr === nothing ? Ptr{Int64}(C_NULL) : pointer(pr))
+    cyc, table, pr
+end
+
+"""
+`ceg_mc_group_sweep_cycles`: `ncycles` whole cycles of `steps_per_cycle` steps of `mc_group_sweep!` with the end-of-cycle block of
+`run_montecarlo!` (src/simulation.jl:727-728, 818-827) on the device: `temperatures` is a vector (one per chain, in force throughout) or
+an `ncycles x K` matrix whose row `j` is in force during cycle `j` (`simu.temperatures`), and `statistics.dmax` / `θmax` are adapted
+from the cumulative acceptance ratios after every cycle (`adapt`: `MC_ADAPT_*` bits).  `cycle0` is the `counter_cycle` of the first
+cycle of this call, `prior[c]` the (translation trials, accepted, rotation trials, accepted) of chain `c` before it.  Returns the
+statistics, the `ncycles x K` cycle records (stored chain-fastest) and, with `log=true`, the step records.  thetamax is held in
+radians: the adaptation is a restatement of the reference's degree arithmetic, equal to rounding.  Never executed here (no Julia in
+the image).
+"""
+function mc_group_sweep_cycles!(g::Ptr{Cvoid}, ncycles::Integer, steps_per_cycle::Integer, seed::Integer, first_step::Integer, temperatures,
+                                dmax::Vector, thetamax::Vector, p_rotation::Vector{Float64}, bead::Vector{Vector{Int}};
+                                adapt::Integer=MC_ADAPT_DMAX | MC_ADAPT_THETAMAX, cycle0::Integer=1, prior=nothing,
+                                stream_id::Vector{UInt32}=UInt32.(0:length(dmax)-1), log::Bool=false)
+    k = length(dmax)
+    cyc, table, pr = _mc_cycles(k, ncycles, steps_per_cycle, temperatures, adapt, cycle0, prior)
+    T = table === nothing ? Float64[ustrip(u"K", t) for t in temperatures] : Float64[]
+    dm = Float64[d isa Real ? d : ustrip(u"Å", d) for d in dmax]
+    th = Float64[t isa Real ? t : ustrip(u"rad", t) for t in thetamax]
+    beads = Int32[b - 1 for chain in bead for b in chain]
+    nsteps = ncycles * steps_per_cycle
+    stats = Vector{McSweepStats}(undef, k)
+    cycles = Matrix{McCycleRecord}(undef, k, ncycles)
+    records = Matrix{McSweepRecord}(undef, k, log ? nsteps : 0)
+    GC.@preserve stream_id T dm th p_rotation beads stats cycles records table pr begin
+        params = Ref(McSweepParams(UInt64(seed), UInt64(first_step), pointer(stream_id), table === nothing ? pointer(T) : Ptr{Float64}(C_NULL),
+                                   pointer(dm), pointer(th), pointer(p_rotation), pointer(beads)))
+        _check(ccall((:ceg_mc_group_sweep_cycles, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     g, params, Ref(cyc), stats, ncycles > 0 ? pointer(cycles) : C_NULL, log && nsteps > 0 ? pointer(records) : C_NULL))
+    end
+    log ? (stats, cycles, records) : (stats, cycles)
+end
+
+"""
+`ceg_mc_group_sweep_gcmc_cycles`: the same for `mc_group_sweep_gcmc!` -- a whole GCMC production run of K chains in one call.  Where a
+species has a swap probability > 0 every chain's temperature must be constant over the cycles (src/simulation.jl:688).  Returns the
+statistics, the final species of every chain's molecules, the cycle records and, with `log=true`, the step records.  Never executed
+here (no Julia in the image).
+"""
+function mc_group_sweep_gcmc_cycles!(g::Ptr{Cvoid}, ncycles::Integer, steps_per_cycle::Integer, seed::Integer, first_step::Integer, temperatures,
+                                     dmax::Vector, thetamax::Vector, species::Vector{McGcmcSpecies}, molecule_species::Vector{Vector{Int32}},
+                                     max_molecules::Vector{Int32}; adapt::Integer=MC_ADAPT_DMAX | MC_ADAPT_THETAMAX, cycle0::Integer=1,
+                                     prior=nothing, stream_id::Vector{UInt32}=UInt32.(0:length(dmax)-1), log::Bool=false)
+    k = length(dmax)
+    cyc, table, pr = _mc_cycles(k, ncycles, steps_per_cycle, temperatures, adapt, cycle0, prior)
+    T = table === nothing ? Float64[ustrip(u"K", t) for t in temperatures] : Float64[]
+    dm = Float64[d isa Real ? d : ustrip(u"Å", d) for d in dmax]
+    th = Float64[t isa Real ? t : ustrip(u"rad", t) for t in thetamax]
+    given = Int32[s for chain in molecule_species for s in chain]
+    push!(given, Int32(0))
+    out = fill(Int32(-1), max(sum(max_molecules), 1))
+    nsteps = ncycles * steps_per_cycle
+    stats = Vector{McGcmcStats}(undef, k)
+    cycles = Matrix{McCycleRecord}(undef, k, ncycles)
+    records = Matrix{McGcmcRecord}(undef, k, log ? nsteps : 0)
+    GC.@preserve stream_id T dm th species given max_molecules out stats cycles records table pr begin
+        params = Ref(McGcmcParams(UInt64(seed), UInt64(first_step), pointer(stream_id), table === nothing ? pointer(T) : Ptr{Float64}(C_NULL),
+                                  pointer(dm), pointer(th), Int32(length(species)), Int32(0), pointer(species), pointer(given),
+                                  pointer(max_molecules), pointer(out)))
+        _check(ccall((:ceg_mc_group_sweep_gcmc_cycles, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     g, params, Ref(cyc), stats, ncycles > 0 ? pointer(cycles) : C_NULL, log && nsteps > 0 ? pointer(records) : C_NULL))
+    end
+    offsets = cumsum(vcat(0, max_molecules))
+    final = [out[offsets[c]+1:offsets[c]+stats[c].nmol] for c in 1:k]
+    log ? (stats, final, cycles, records) : (stats, final, cycles)
 end
 
 # `ceg_mc_block_t` of include/ceg_hip.h (240 bytes)

@@ -715,7 +715,7 @@ CEG_API int ceg_mc_group_accept(ceg_mc_group_t* group, const int32_t* molecule, 
  * Synchronous.  Afterwards every per-handle and group entry point works on the moved state; the molecule table does not change.
  * Not covered: swap / reinsertion / random_* moves (ceg_mc_group_sweep_gcmc, below), the inblockpocket test of choose_step! (a group with
  * masks installed by ceg_mc_group_set_blocks is refused with CEG_ERR_UNSUPPORTED rather than swept without them), and the adaptation of
- * dmax / thetamax (src/simulation.jl:820-825), which stays with the caller between sweeps -- the stats hold the ratios it needs. */
+ * dmax / thetamax (src/simulation.jl:820-825): ceg_mc_group_sweep_cycles, below, runs it at every cycle end. */
 typedef struct ceg_mc_sweep_params {
     uint64_t seed, first_step;
     const uint32_t* stream_id;                 /* [K] */
@@ -791,7 +791,7 @@ CEG_API int ceg_mc_group_sweep(ceg_mc_group_t* group, const ceg_mc_sweep_params_
  *   accepted swaps.
  * Synchronous.  Afterwards the handles' host mirrors (molecule table, free atom slots, high-water mark) are rebuilt from the device and
  *   every per-handle and group entry point works on the new state.
- * Not covered: the adaptation of dmax / thetamax, the fugacity coefficient and the accessible-volume factor of GCMCData (phiPV_div_k
+ * Not covered: the fugacity coefficient and the accessible-volume factor of GCMCData (phiPV_div_k
  *   comes from the caller, as the reference takes it from Clapeyron), and chains that keep their guests in neighbour cells.
  *
  * Block pockets (ceg_mc_group_set_blocks): the inblockpocket test and the 1000-attempt retry loop of choose_step!
@@ -935,6 +935,76 @@ CEG_API int ceg_mc_group_set_sampler(ceg_mc_group_t* group, const ceg_mc_sampler
 CEG_API int ceg_mc_group_sample(ceg_mc_group_t* group);
 CEG_API int ceg_mc_group_sampler_read(ceg_mc_group_t* group, int64_t* bins_out, ceg_mc_sample_record_t* series_out, int64_t* frames_out);
 CEG_API int ceg_mc_group_sampler_reset(ceg_mc_group_t* group);
+
+/* ---- cycles: whole cycles of run_montecarlo! on the device, temperature schedule and step-size adaptation included ----
+ * The end-of-cycle block of the main loop (src/simulation.jl:727-728, 818-827): `temperature = simu.temperatures[counter_cycle]` and
+ * the adaptation of statistics.dmax / statistics.θmax from the cumulative acceptance ratios.  ceg_mc_group_sweep_cycles /
+ * ceg_mc_group_sweep_gcmc_cycles run ncycles * steps_per_cycle steps from params->first_step: checks, refusals, random stream, rows,
+ * rule, update, stats, log and final state are those of ceg_mc_group_sweep / ceg_mc_group_sweep_gcmc over that many steps, and the
+ * launches of every step are the ones that entry point enqueues, sampler frames included.  The one addition is one more launch
+ * (k_mcg_cycle_end, one workgroup, one lane per chain) after the last step of each cycle, behind that step's accept launch and behind
+ * its sampler frame if there is one.  It reads the chain's counters, writes the cycle's record and stores the next cycle's
+ * temperature, dmax and thetamax into the chain's parameters in device memory, where the next step's launches read them: stream
+ * order alone makes them visible.  The two sweeps themselves are unchanged, byte for byte and launch for launch.
+ *
+ * Temperature: with a table, row j ([K] values, K) is in force during cycle j of the call; params->temperature is then not read and
+ *   may be NULL.  Every entry must be finite and > 0.  ceg_mc_group_sweep_gcmc_cycles: if any species has a swap probability > 0
+ *   (cumulative[4] < 1), every chain's column must be constant -- the reference refuses GCMC with a varying temperature
+ *   (simulation.jl:688) and phiPV_div_k belongs to one temperature -- else CEG_ERR_INVALID.  Without a table params->temperature holds
+ *   throughout.
+ * Adaptation, at the end of cycle j of the call with cc = cycle0 + j (the reference's counter_cycle), from the CUMULATIVE counters =
+ *   prior + this call's stats as they stand then.  A blocked or pocket-blocked trial counts as a trial of its kind; translation and
+ *   rotation are kinds 0 and 1 only (the random_* kinds do not count, as in MoveStatistics).  All in FP64, without contraction, IEEE
+ *   division and square root, in this order, with clamp(x, lo, hi) = x > hi ? hi : (x < lo ? lo : x):
+ *     translation (CEG_MC_ADAPT_DMAX, only if translation_trials > 0):
+ *       r = (double)accepted / (double)trials;  q = 10.0 / (double)(99 + cc);  s = sqrt(q);
+ *       f = (r - 0.25) * s;  g = 1.0 + f;  dmax = clamp(dmax * g, 0.1, 3.0)
+ *     rotation (CEG_MC_ADAPT_THETAMAX, only if rotation_trials > 0), in radians as this ABI holds thetamax:
+ *       r = (double)accepted / (double)trials;  a = (r - 0.5) / (double)cc;  b = a * 2.0943951023931953;      (120 degrees)
+ *       thetamax = clamp(thetamax + b, 0.17453292519943295, 3.141592653589793)                               (10 and 180 degrees)
+ *   With zero trials of a kind (the reference's NaN ratio), with the bit clear, or for a chain that holds no molecule at the cycle
+ *   end, the value is carried over unchanged.  This is a restatement in radians: the reference works in degrees, so the result is
+ *   NOT bit-equal to the reference's degree arithmetic (it agrees to rounding).
+ * cycles: ncycles >= 0, steps_per_cycle >= 1, cycle0 >= 1 (the counter_cycle of the first cycle of THIS call), adapt (CEG_MC_ADAPT_*
+ *   bits), temperatures ([ncycles][K] or NULL), prior ([K][4]: translation trials, accepted, rotation trials, accepted BEFORE this
+ *   call; NULL: zeros).
+ * cycles_out [ncycles][K]: per (cycle, chain) the temperature, dmax and thetamax in force during the cycle, the two step sizes after
+ *   the adaptation at its end, the call's stats sums as they stand at the end of the cycle (plain sweep: its delta and 0), the four
+ *   cumulative counters (prior + this call) and the chain's molecule count.  log_out [ncycles * steps_per_cycle][K] or NULL.
+ * Refusals, all CEG_ERR_INVALID before anything is launched or changed: a NULL `cycles`; ncycles < 0, steps_per_cycle < 1 or
+ *   cycle0 < 1; unknown adapt bits; a table entry that is not finite and > 0 (or a varying column where GCMC forbids it); a prior
+ *   entry < 0 or accepted > trials; cycles_out NULL with ncycles > 0; ncycles * steps_per_cycle, or first_step plus it, beyond
+ *   2^63 - 1; 99 + cycle0 + ncycles not representable; more than CEG_MC_CYCLES_MAX_RECORDS records (ncycles * K) in one call.
+ *   Everything the underlying sweep refuses is refused likewise.  ncycles == 0: zero stats, nothing launched.
+ * Continuation: a run split over several calls gives the bytes of the one-call run if each call passes first_step advanced, cycle0
+ *   advanced, prior = the summed counters (the last record's) and dmax / thetamax = the last record's dmax_next / thetamax_next.
+ * Synchronous.  Not covered: one steps_per_cycle applies to the whole group (chains whose reference cycle lengths differ belong in
+ *   different groups); snapshots of the positions every `printevery` cycles; the baseline_energy at cycle 0 inside the run (a caller
+ *   composes it from two calls around ceg_mc_group_baseline). */
+#define CEG_MC_ADAPT_DMAX     1
+#define CEG_MC_ADAPT_THETAMAX 2
+#define CEG_MC_CYCLES_MAX_RECORDS 16777216
+typedef struct ceg_mc_cycles {          /* 48 bytes */
+    int64_t ncycles;                    /* >= 0 */
+    int64_t steps_per_cycle;            /* >= 1; the call runs ncycles * steps_per_cycle steps from params->first_step */
+    int64_t cycle0;                     /* >= 1: the reference's counter_cycle of the first cycle of THIS call */
+    int32_t adapt, _pad;                /* CEG_MC_ADAPT_* bits */
+    const double*  temperatures;        /* [ncycles][K] K, or NULL: params->temperature throughout */
+    const int64_t* prior;               /* [K][4] translation trials, accepted, rotation trials, accepted BEFORE this call; NULL: zeros */
+} ceg_mc_cycles_t;
+typedef struct ceg_mc_cycle_record {    /* 96 bytes */
+    double  temperature, dmax, thetamax;        /* in force during the cycle */
+    double  dmax_next, thetamax_next;           /* after the adaptation at its end */
+    double  delta_moves, delta_swaps;           /* the call's stats sums as they stand at the end of the cycle (plain sweep: delta, 0) */
+    int64_t translation_trials, translation_accepted, rotation_trials, rotation_accepted;  /* prior + this call, at the end of the cycle */
+    int32_t nmol, _pad;
+} ceg_mc_cycle_record_t;
+CEG_API int ceg_mc_group_sweep_cycles(ceg_mc_group_t* group, const ceg_mc_sweep_params_t* params, const ceg_mc_cycles_t* cycles,
+                                      ceg_mc_sweep_stats_t* stats_out, ceg_mc_cycle_record_t* cycles_out /*[ncycles][K]*/,
+                                      ceg_mc_sweep_record_t* log_out /*[ncycles * steps_per_cycle][K] or NULL*/);
+CEG_API int ceg_mc_group_sweep_gcmc_cycles(ceg_mc_group_t* group, const ceg_mc_gcmc_params_t* params, const ceg_mc_cycles_t* cycles,
+                                           ceg_mc_gcmc_stats_t* stats_out, ceg_mc_cycle_record_t* cycles_out,
+                                           ceg_mc_gcmc_record_t* log_out);
 
 /* ---- baseline_energy (src/montecarlo.jl:530-542) of one chain, or of every chain of a group, from the resident state ----
  * What run_montecarlo! asks for at its start, at the first production cycle, after a move that risks underflow and for its final
