@@ -100,6 +100,15 @@ MC_CYCLE_RECORD_DTYPE = np.dtype([('temperature', '<f8'), ('dmax', '<f8'), ('the
                                   ('rotation_trials', '<i8'), ('rotation_accepted', '<i8'), ('nmol', '<i4'), ('_pad', '<i4')], align=True)
 assert (C.sizeof(McCycles), MC_CYCLE_RECORD_DTYPE.itemsize) == (48, 96)
 
+
+class McChainPlan(C.Structure):
+    """``ceg_mc_chain_plan_t`` (``phiPV_div_k`` [K][nspecies] and ``stop_step`` [K] in host memory, either may be NULL)"""
+    _fields_ = [("nspecies", C.c_int32), ("_pad", C.c_int32), ("phiPV_div_k", C.c_void_p), ("stop_step", C.c_void_p)]
+
+
+assert C.sizeof(McChainPlan) == 24
+MC_STOPPED = -2              # record.molecule of a step a chain sat out (its stop_step reached)
+
 c_double_p = C.POINTER(C.c_double)
 c_float_p = C.POINTER(C.c_float)
 c_int32_p = C.POINTER(C.c_int32)
@@ -241,6 +250,7 @@ PROTOTYPES = {
     "ceg_mc_group_sweep_gcmc_cycles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ceg_mc_group_set_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "ceg_mc_group_block_counts": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
+    "ceg_mc_group_set_chain_plan": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ceg_mc_group_set_sampler": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ceg_mc_group_sample": (C.c_int, [C.c_void_p]),
     "ceg_mc_group_sampler_read": (C.c_int, [C.c_void_p, c_int64_p, C.c_void_p, c_int64_p]),

@@ -634,6 +634,17 @@ class MonteCarloRun(NamedTuple):
     recorded: np.ndarray              # [K] K, what the drift check compared with the final baseline (energies[-1] + the swaps' bookkeeping)
 
 
+class Isotherm(NamedTuple):
+    """What :meth:`DeviceMonteCarloGroup.make_isotherm` returns (``make_isotherm``'s isotherm, loadings, energies, per chain)"""
+    isotherm: np.ndarray              # [K] mean of the chain's loadings
+    loadings: list                    # [K] of float64[ncycles[c]]: count[0] / Π after each of the chain's own production cycles
+    energies: list                    # [K] of float64[ncycles[c]] K, after each of the chain's own production cycles
+    drift_ok: np.ndarray              # [K] bool: isapprox(recorded, actual, rtol=1e-9) (simulation.jl:850-853)
+    recorded: np.ndarray              # [K] K
+    actual: np.ndarray                # [K] K, the final baseline_energy
+    run: MonteCarloRun
+
+
 class DeviceMonteCarloGroup:
     """K :class:`DeviceMonteCarlo` chains on one device stepped in lockstep (``ceg_mc_group_*``): one launch evaluates the trials
     of every chain, one launch applies every accepted move -- the way ``make_isotherm`` (parameterinputs.jl:316-329) runs one
@@ -660,6 +671,7 @@ class DeviceMonteCarloGroup:
             c._group = self
         self._blocks = None           # what set_blocks installed: (species blocks, atom blocks)
         self.sampler = None           # what set_sampler installed (its geometry and tables, for the host restatement)
+        self.chain_plan = None        # what set_chain_plan installed: (phiPV_div_k [K, nspecies] or None, stop_step [K] or None)
 
     def __repr__(self):
         return f"DeviceMonteCarloGroup(k={len(self.chains)})"
@@ -703,6 +715,45 @@ class DeviceMonteCarloGroup:
         pocket, attempts = np.zeros(len(self.chains), dtype=np.int64), np.zeros(len(self.chains), dtype=np.int64)
         _abi.check(self._lib, self._lib.ceg_mc_group_block_counts(self._h, _abi.i64ptr(pocket), _abi.i64ptr(attempts)))
         return pocket, attempts
+
+    @staticmethod
+    def chain_plan_arrays(k: int, phiPV_div_k=None, stop_step=None):
+        """The two arrays of a chain plan for ``k`` chains as ``ceg_mc_group_set_chain_plan`` takes them -> (float64 ``[k, nspecies]``
+        or None, int64 ``[k]`` or None).  ``phiPV_div_k``: ``[k, nspecies]``, or ``[k]`` for one species; ``stop_step``: ``[k]`` integers.
+        Needs no device; the values themselves are checked by the library (a stop < 0 at once, a ``phiPV_div_k`` by the GCMC sweep)."""
+        phi = stop = None
+        if phiPV_div_k is not None:
+            phi = np.asarray(phiPV_div_k, dtype=np.float64)
+            if phi.ndim == 1:
+                phi = phi[:, None]
+            if phi.ndim != 2 or phi.shape[0] != k or not 1 <= phi.shape[1] <= _abi.GCMC_MAX_SPECIES:
+                raise ValueError(f"phiPV_div_k: [{k}, nspecies] with 1 <= nspecies <= {_abi.GCMC_MAX_SPECIES}, got shape {phi.shape}")
+            phi = np.ascontiguousarray(phi)
+        if stop_step is not None:
+            given = np.asarray(stop_step)
+            if given.shape != (k,) or given.dtype.kind not in "iu":
+                raise ValueError(f"stop_step: one integer step per chain ({k})")
+            if given.dtype.kind == "u" and given.size and int(given.max()) > np.iinfo(np.int64).max:
+                raise ValueError("stop_step: a step beyond 2^63 - 1")
+            stop = np.ascontiguousarray(given, dtype=np.int64)
+        return phi, stop
+
+    def set_chain_plan(self, phiPV_div_k=None, stop_step=None) -> None:
+        """``ceg_mc_group_set_chain_plan``: what differs between the chains of an isotherm (``make_isotherm``, parameterinputs.jl:305-334).
+        ``phiPV_div_k[c][i]`` (K) replaces the species table's value for chain ``c`` in the swap rules of :meth:`sweep_gcmc` /
+        :meth:`sweep_gcmc_cycles`; chain ``c`` takes no part in the absolute steps ``s >= stop_step[c]`` of any sweep: its state, its
+        statistics and its share of a sampler's map stay those of its own last step, and its log records are zero but for
+        ``molecule == -2``, ``kind == -1`` (and ``species == -1``).  Either may be None; ``set_chain_plan()`` removes the plan.  It stays
+        installed until it is replaced or removed; what is installed is kept in ``self.chain_plan``."""
+        phi, stop = self.chain_plan_arrays(len(self.chains), phiPV_div_k, stop_step)
+        if phi is None and stop is None:
+            _abi.check(self._lib, self._lib.ceg_mc_group_set_chain_plan(self._h, None))
+            self.chain_plan = None
+            return
+        plan = _abi.McChainPlan(phi.shape[1] if phi is not None else 0, 0, phi.ctypes.data if phi is not None else None,
+                                stop.ctypes.data if stop is not None else None)
+        _abi.check(self._lib, self._lib.ceg_mc_group_set_chain_plan(self._h, C.addressof(plan)))
+        self.chain_plan = (phi, stop)
 
     def baseline_records(self, refresh: bool = False) -> np.ndarray:
         """``ceg_mc_group_baseline``: one ``_abi.MC_BASELINE_DTYPE`` record per chain, all chains in one pass (two launches, four with
@@ -1011,12 +1062,13 @@ class DeviceMonteCarloGroup:
 
     def run_montecarlo(self, temperatures, ncycles: int, ninit: int = 0, *, seed: int = 0, steps_per_cycle: Optional[int] = None, gcmc=None,
                        dmax=1.3, thetamax=math.radians(30.0), adapt=("dmax", "thetamax"), p_rotation=0.5, stream_id=None, bead=None,
-                       positions: bool = True):
+                       positions: bool = True, check_drift: bool = True):
         """The shape of ``run_montecarlo!`` (simulation.jl:640-860) for the K chains: ``baseline_energy``, the ``ninit`` cycles in one
         :meth:`sweep_cycles` / :meth:`sweep_gcmc_cycles` call, ``baseline_energy`` again (the precise energy at the first production
         cycle, :788-790), the ``ncycles`` production cycles in one call that continues ``cycle0``, the counters and the step sizes, the
         final ``baseline_energy`` and the reference's drift check ``isapprox(recorded, actual, rtol=1e-9)`` (:850-853), raised as
-        :class:`MonteCarloDrift` where it fails.
+        :class:`MonteCarloDrift` where it fails (``check_drift=False``: not checked; the caller compares ``recorded`` with
+        ``baselines[2]``).
 
         ``temperatures``: a scalar, one per chain, or ``[ninit + ncycles, K]`` (``simu.temperatures`` per chain).  ``steps_per_cycle``
         defaults to :meth:`numsteps` of the first chain; a chain whose ``numsteps`` differs is refused (it belongs in another group).
@@ -1125,11 +1177,71 @@ class DeviceMonteCarloGroup:
         end = start
         if ninit + ncycles > 0:                      # (not a single-point computation, simulation.jl:849)
             end = self.baseline_energies()
-            for c, (rec, actual) in enumerate(zip(recorded, (float(r) for r in end))):
+            for c, (rec, actual) in enumerate(zip(recorded, (float(r) for r in end)) if check_drift else ()):
                 if not abs(rec - actual) <= 1e-9 * max(abs(rec), abs(actual)):
                     raise MonteCarloDrift(f"chain {c}: energy deviation observed between actual ({actual!r}) and recorded ({rec!r}): "
                                           "the simulation results are wrong")
         return MonteCarloRun(initial_energies, energies, cycles, (stats_init, stats), (start, production, end), recorded)
+
+    def make_isotherm(self, phiPV_div_k, ncycles, ninit: int = 0, *, temperature, max_molecules, moves=None, species=None, self_reciprocal=None,
+                      seed: int = 0, steps_per_cycle: Optional[int] = None, supercell=(1, 1, 1), dmax=1.3, thetamax=math.radians(30.0),
+                      adapt=("dmax", "thetamax"), stream_id=None, bead=None, positions: bool = True):
+        """``make_isotherm`` (parameterinputs.jl:305-334) on the device sweeps: chain ``c`` is the ``run_gcmc`` of one pressure, with its own
+        ``phiPV_div_k[c]`` (``[K, nspecies]`` K, e.g. from :func:`ceg_hip.mcrng.phiPV_div_k`) and its own run length ``ncycles[c]`` (e.g.
+        from :func:`ceg_hip.mcrng.isotherm_ncycles`); all chains run the same ``ninit`` cycles first.  Composed from what exists: a chain
+        plan (:meth:`set_chain_plan`) with ``stop_step[c] = (ninit + ncycles[c]) * steps_per_cycle``, a series-only sampler with one frame
+        per production cycle, and :meth:`run_montecarlo` over ``max(ncycles)`` production cycles -- baseline, ``ninit`` cycles, baseline,
+        production, baseline.  The call is as long as the longest chain; the others stop at their own last step and stay stopped.
+
+        ``temperature``: a scalar or one per chain (constant, as ``make_isotherm`` asserts).  ``moves`` (one
+        :class:`ceg_hip.mcrng.MoveTable` per species; ``run_gcmc`` passes the first through ``MoveTable.for_gcmc``) or a ready ``species``
+        table, whose own ``phiPV_div_k`` is not read.  ``supercell``: the unit cells of the MC cell, whose product is the ``Π`` the
+        loadings are divided by (parameterinputs.jl:244).  The other arguments as :meth:`run_montecarlo`.
+
+        Refuses to run with a sampler of the caller's installed (``RuntimeError``); a chain plan of the caller's is replaced.  Afterwards
+        neither a sampler nor a plan is installed.
+
+        -> :class:`Isotherm`: per chain the mean loading, the loadings ``count[0] / Π`` and the energies (K) after each of its OWN
+        production cycles, the outcome of the reference's drift check at rtol 1e-9 (``drift_ok``, with ``recorded`` and ``actual``), and the
+        underlying :class:`MonteCarloRun`."""
+        k = len(self.chains)
+        if self.sampler is not None:
+            raise RuntimeError("make_isotherm installs a sampler of its own: remove yours first (set_sampler(None))")
+        n = np.asarray(ncycles)
+        if n.shape != (k,) or n.dtype.kind not in "iu" or (n < 0).any():
+            raise ValueError(f"ncycles: one run length >= 0 per chain ({k})")
+        ninit = int(ninit)
+        if ninit < 0:
+            raise ValueError("ninit must be >= 0")
+        phi, _ = self.chain_plan_arrays(k, phiPV_div_k, None)
+        if phi is None:
+            raise ValueError("phiPV_div_k: one row per chain")
+        pi = int(np.prod([int(x) for x in supercell]))
+        if len(supercell) != 3 or pi < 1:
+            raise ValueError("supercell: three integers >= 1")
+        if species is None:
+            if moves is None:
+                raise ValueError("moves or species")
+            species = self.gcmc_species(moves, list(phi[0]), self_reciprocal, bead)
+        species = np.ascontiguousarray(species)
+        from . import mcrng
+        L = int(steps_per_cycle) if steps_per_cycle is not None else self.numsteps([mcrng.MoveTable(cumulatives=row["cumulative"]) for row in species])[0]
+        longest = int(n.max())
+        try:
+            self.set_chain_plan(phi, (ninit + n.astype(np.int64)) * L)
+            self.set_sampler(L, from_step=ninit * L, series_capacity=longest)
+            run = self.run_montecarlo(temperature, longest, ninit, seed=seed, steps_per_cycle=steps_per_cycle, dmax=dmax, thetamax=thetamax,
+                                      gcmc=dict(species=species, max_molecules=max_molecules), adapt=adapt, stream_id=stream_id, bead=bead,
+                                      positions=positions, check_drift=False)
+            series = self.sampler_read()[1]
+        finally:
+            self.set_sampler(None)
+            self.set_chain_plan()
+        loadings = [series["count"][:int(n[c]), c, 0] / pi for c in range(k)]
+        actual = np.array([float(r) for r in run.baselines[2]])
+        drift_ok = np.abs(run.recorded - actual) <= 1e-9 * np.maximum(np.abs(run.recorded), np.abs(actual))
+        return Isotherm(np.array([x.mean() if len(x) else np.nan for x in loadings]), loadings, [run.energies[:int(n[c]), c] for c in range(k)],
+                        drift_ok, run.recorded, actual, run)
 
     def set_sampler(self, every: Optional[int], from_step: int = 0, step: Optional[float] = None, dims=None, supercell=(1, 1, 1), channels=None,
                     chain_map=None, symmetries=(), series_capacity: int = 0) -> None:

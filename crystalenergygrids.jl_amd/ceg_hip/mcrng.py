@@ -27,6 +27,10 @@ plain purpose.  :func:`block_lookup` is ``BlockFile`` getindex (coordinates.jl:5
 Cycles (``ceg_mc_group_sweep_cycles`` / ``ceg_mc_group_sweep_gcmc_cycles``): :func:`adapt_dmax`, :func:`adapt_thetamax` and
 :func:`cycle_records` restate the end-of-cycle adaptation of ``statistics.dmax`` / ``θmax`` (simulation.jl:818-827) in the operation
 order of ``k_mcg_cycle_end``, ``thetamax`` in radians.
+
+Isotherms (``ceg_mc_group_set_chain_plan``, ``DeviceMonteCarloGroup.make_isotherm``): :func:`isotherm_ncycles`, :func:`accessible_volume`,
+:func:`phiPV_div_k` and :meth:`MoveTable.for_gcmc` restate the host arithmetic of ``make_isotherm`` / ``run_gcmc`` / ``GCMCData``
+(parameterinputs.jl:274-279,319, gcmc.jl:26-37, simulation.jl:714-715); the fugacity coefficient stays with the caller.
 """
 from __future__ import annotations
 
@@ -240,6 +244,13 @@ class MoveTable:
             if r < c:
                 return k
         return 5
+
+    def for_gcmc(self) -> "MoveTable":
+        """The table ``run_gcmc`` runs the first species with (parameterinputs.jl:274-279): a table without swap probability
+        (``cumulatives[end] ≈ 1.0``) gets every cumulative before the swap times 2/3, i.e. a swap probability of 1/3; any other is kept."""
+        if not math.isclose(self.cumulatives[-1], 1.0, rel_tol=math.sqrt(2.0 ** -52), abs_tol=0.0):
+            return self
+        return MoveTable(cumulatives=tuple(c * 2 / 3 for c in self.cumulatives))
 
     def __getitem__(self, name: str) -> float:
         k = MOVE_NAMES.index(name)
@@ -529,3 +540,33 @@ def cycle_records(temperatures, dmax: float, thetamax: float, counters, nmol, de
                   0.0 if delta_swaps is None else float(delta_swaps[j]), tt, ta, rt, ra, int(nmol[j]), 0)
         d, t = dn, tn
     return out
+
+
+# ------------------------------------------------------------------ isotherms (ceg_mc_group_set_chain_plan)
+def isotherm_ncycles(ncycles: int, pressure_pa: float) -> int:
+    """The run length ``make_isotherm`` gives the chain of one pressure (parameterinputs.jl:319):
+    ``ceil(Int, simu.ncycles * (1 + 1e3 / ustrip(u"Pa", P)))``"""
+    return int(math.ceil(int(ncycles) * (1 + 1e3 / float(pressure_pa))))
+
+
+def accessible_volume(mask, unitcell, supercell) -> float:
+    """``GCMCData.volumes[i]`` in A^3 (gcmc.jl:26-37): ``accessible_fraction * (det(unitcell) * Π)`` with ``Π`` the product of
+    ``supercell`` and ``accessible_fraction = 1 - count(block) / length(block)`` of the species' block mask (``None`` or an empty mask:
+    1).  ``unitcell``: the cell vectors as columns."""
+    M = np.asarray(unitcell, dtype=np.float64).reshape(3, 3)
+    det = (M[0, 0] * (M[1, 1] * M[2, 2] - M[1, 2] * M[2, 1]) - M[0, 1] * (M[1, 0] * M[2, 2] - M[1, 2] * M[2, 0])
+           + M[0, 2] * (M[1, 0] * M[2, 1] - M[1, 1] * M[2, 0]))
+    pi = 1
+    for x in (supercell if np.ndim(supercell) else (supercell,)):
+        pi *= int(x)
+    cellvolume = float(det) * pi
+    fraction = 1.0
+    if mask is not None and np.size(mask) > 0:
+        fraction = 1.0 - int(np.count_nonzero(mask)) / int(np.size(mask))
+    return fraction * cellvolume
+
+
+def phiPV_div_k(phi: float, pressure_pa: float, volume_A3: float) -> float:
+    """``φPV_div_k`` of one species in K (simulation.jl:714-715): ``φ * uconvert(u"K", abs(P) * V / u"k")`` with P in Pa, V in A^3
+    (1e-30 m^3) and k = 1.380649e-23 J/K.  The fugacity coefficient ``phi`` is the caller's (Clapeyron's in the reference, :707-712)."""
+    return float(phi) * (abs(float(pressure_pa)) * float(volume_A3) * 1e-30 / 1.380649e-23)

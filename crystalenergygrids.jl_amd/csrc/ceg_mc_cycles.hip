@@ -63,8 +63,9 @@ __global__ __launch_bounds__(CEG_MC_GROUP_MAX) void k_mcg_cycle_end(const McView
     const double temperature = triple[0], dmax = triple[1], thetamax = triple[2];
     const int64_t cc = R.cycle0 + E.j;
     double dmax_next = dmax, thetamax_next = thetamax;
-    if (nmol > 0 && (R.adapt & CEG_MC_ADAPT_DMAX) && tt > 0) dmax_next = cycle_adapt_dmax(dmax, ta, tt, cc);
-    if (nmol > 0 && (R.adapt & CEG_MC_ADAPT_THETAMAX) && rt > 0) thetamax_next = cycle_adapt_thetamax(thetamax, ra, rt, cc);
+    const bool adapts = nmol > 0 && !(S.stop && S.last_step >= (uint64_t)S.stop[c]);      // (not a chain that stopped in or before this cycle)
+    if (adapts && (R.adapt & CEG_MC_ADAPT_DMAX) && tt > 0) dmax_next = cycle_adapt_dmax(dmax, ta, tt, cc);
+    if (adapts && (R.adapt & CEG_MC_ADAPT_THETAMAX) && rt > 0) thetamax_next = cycle_adapt_thetamax(thetamax, ra, rt, cc);
     ceg_mc_cycle_record_t rec;
     rec.temperature = temperature; rec.dmax = dmax; rec.thetamax = thetamax;
     rec.dmax_next = dmax_next; rec.thetamax_next = thetamax_next;

@@ -5,6 +5,7 @@
 //   ceg_mc_group_set_blocks        block pockets: inblockpocket and the retry loop of choose_step!, resolved inside the GCMC trial launch
 //   ceg_mc_group_sweep_cycles      either sweep over whole cycles: the same body (sweep_plain / sweep_gcmc) with a ceg_mc_cycles_t, one
 //   ceg_mc_group_sweep_gcmc_cycles   launch of ceg_mc_cycles.hip behind the last step of every cycle (temperature table, dmax / thetamax)
+//   ceg_mc_group_set_chain_plan      per chain: the phiPV_div_k of the swap rules and the absolute step at which the chain stops (isotherms)
 // The two sweeps have their own kernels, per-chain parameters and read-back, and share one host driver (run_sweep).
 #include "ceg_mc_state.h"
 
@@ -80,6 +81,9 @@ struct McSweepChain {            // per chain, device memory
 struct McMove { int32_t molecule, kind; };       // kind 0 translation, 1 rotation; molecule -1: the chain is idle
 
 __device__ McCellOps d_mc_no_cell_ops;           // (sweeps refuse chains with neighbour cells: the accept body never reads it)
+
+// the chain plan's stop (ceg_mc_group_set_chain_plan): chain c takes no part in the absolute steps >= stop[c]; nullptr: no chain stops
+__device__ __forceinline__ bool chain_stopped(const int64_t* __restrict__ stop, int c, uint64_t step) { return stop && step >= (uint64_t)stop[c]; }
 
 __device__ __forceinline__ McMove sweep_select(const McView& v, const McSweepChain& P, uint64_t seed, uint64_t step)
 {
@@ -182,9 +186,14 @@ __device__ __forceinline__ int displacement_decision(const double* row, double u
 // one workgroup per chain: compute_accept_move (src/montecarlo.jl:702-712) on the two rows, statistics, the log record, update_mc!
 __global__ __launch_bounds__(MC_THREADS) void k_mcg_sweep_accept(const McView* __restrict__ views, const McSweepChain* __restrict__ params, uint64_t seed,
                                                                  uint64_t step, const McPositions* __restrict__ prop, const double* __restrict__ rows,
-                                                                 ceg_mc_sweep_stats_t* __restrict__ stats, ceg_mc_sweep_record_t* __restrict__ log)
+                                                                 ceg_mc_sweep_stats_t* __restrict__ stats, ceg_mc_sweep_record_t* __restrict__ log,
+                                                                 const int64_t* __restrict__ stop)
 {
     const int c = (int)blockIdx.x, tid = threadIdx.x;
+    if (chain_stopped(stop, c, step)) {                            // (ceg_mc_group_set_chain_plan: the chain sat this step out)
+        if (log && tid == 0) { log[c].molecule = -2; log[c].kind = -1; }
+        return;
+    }
     const McView& v = as_constant(views)[c];
     const McSweepChain& P = as_constant(params)[c];
     const McMove mv = sweep_select(v, P, seed, step);
@@ -526,10 +535,15 @@ __global__ __launch_bounds__(MC_THREADS) void k_mcg_gcmc_accept(const McView* __
                                                                 int32_t* molspec, int32_t* freeslots, uint64_t seed, uint64_t step,
                                                                 const int32_t* resolved, int64_t* __restrict__ pockets,
                                                                 const McPositions* __restrict__ prop, const double* __restrict__ rows,
-                                                                ceg_mc_gcmc_stats_t* __restrict__ stats, ceg_mc_gcmc_record_t* __restrict__ log)
+                                                                ceg_mc_gcmc_stats_t* __restrict__ stats, ceg_mc_gcmc_record_t* __restrict__ log,
+                                                                const double* __restrict__ chain_phi, const int64_t* __restrict__ stop)
 {
     __shared__ McMolecule s_nm;
     const int c = (int)blockIdx.x, tid = threadIdx.x;
+    if (chain_stopped(stop, c, step)) {                            // (ceg_mc_group_set_chain_plan: the chain sat this step out)
+        if (log && tid == 0) { log[c].species = -1; log[c].molecule = -2; log[c].kind = -1; }
+        return;
+    }
     const McView& v = as_constant(views)[c];
     const McGcmcChain& P = as_constant(params)[c];
     McGcmcTable* T = tables + c;
@@ -593,15 +607,17 @@ __global__ __launch_bounds__(MC_THREADS) void k_mcg_gcmc_accept(const McView* __
             }
             tc = d * n;
             const double temp = P.temperature;
+            // the chain's own phiPV_div_k where the chain plan carries one ([K][nspecies]), else the species table's
+            const double phi = chain_phi ? chain_phi[(size_t)c * (size_t)nspecies + (size_t)i] : sp.phiPV_div_k;
             if (mv.kind == 5) {
                 const double E = ((row[4] + row[5]) + row[6]) + row[7];
                 blocked = row[4] >= 1e90;
                 delta = (E - sp.self_reciprocal) + tc;
-                acc = (!blocked && u < ((sp.phiPV_div_k / temp) / (double)(mv.n_i + 1)) * exp(-delta / temp)) ? 1 : 0;
+                acc = (!blocked && u < ((phi / temp) / (double)(mv.n_i + 1)) * exp(-delta / temp)) ? 1 : 0;
             } else {
                 const double E = ((row[0] + row[1]) + row[2]) + row[3];
                 delta = -(E - sp.self_reciprocal) + tc;
-                acc = (u < (((double)mv.n_i * temp) / sp.phiPV_div_k) * exp(-delta / temp)) ? 1 : 0;
+                acc = (u < (((double)mv.n_i * temp) / phi) * exp(-delta / temp)) ? 1 : 0;
             }
         }
     }
@@ -685,6 +701,12 @@ struct ceg_mc_group {
     unsigned char* d_baseline = nullptr;         // partial sums and results of ceg_mc_group_baseline (ceg_mc_baseline.hip); only grows
     size_t baseline_cap = 0;
     GroupSampler* sampler = nullptr;             // density maps and series taken during sweeps (ceg_mc_sample.hip); nullptr: none
+    // chain plan (ceg_mc_group_set_chain_plan): the host's copy for the checks and the launch lists, the device's for the kernels
+    std::vector<double> plan_phi;                // [K][plan_species], empty: the species table's value for every chain
+    std::vector<int64_t> plan_stop;              // [K], empty: no chain stops
+    int plan_species = 0;
+    double* d_plan_phi = nullptr;
+    int64_t* d_plan_stop = nullptr;
 };
 
 namespace {
@@ -710,6 +732,8 @@ void group_free(ceg_mc_group* g)
     if (g->d_done) (void)hipFree(g->d_done);
     if (g->d_scratch) (void)hipFree(g->d_scratch);
     if (g->d_baseline) (void)hipFree(g->d_baseline);
+    if (g->d_plan_phi) (void)hipFree(g->d_plan_phi);
+    if (g->d_plan_stop) (void)hipFree(g->d_plan_stop);
     for (void* p : {(void*)g->h_views, (void*)g->h_in, (void*)g->h_out, (void*)g->h_acc, (void*)g->h_flag})
         if (p) (void)hipHostFree(p);
     delete g;
@@ -1065,6 +1089,45 @@ extern "C" int ceg_mc_group_block_counts(ceg_mc_group_t* g, int64_t* pocket_out,
     return CEG_OK;
 }
 
+// ---- chain plan of a group: both arrays go to the device once and stay there
+extern "C" int ceg_mc_group_set_chain_plan(ceg_mc_group_t* g, const ceg_mc_chain_plan_t* plan)
+{
+    static_assert(sizeof(ceg_mc_chain_plan_t) == 24, "layout the bindings restate");
+    if (!g) return merr(CEG_ERR_INVALID, "bad argument");
+    const size_t k = g->chains.size();
+    const bool phi = plan && plan->phiPV_div_k, stop = plan && plan->stop_step;
+    if (plan) {
+        if (plan->nspecies < 0 || plan->nspecies > CEG_MC_GCMC_MAX_SPECIES) return merr(CEG_ERR_INVALID, "chain plan: 0 <= nspecies <= CEG_MC_GCMC_MAX_SPECIES");
+        if (phi && plan->nspecies < 1) return merr(CEG_ERR_INVALID, "chain plan: phiPV_div_k needs nspecies >= 1");
+        for (size_t c = 0; stop && c < k; ++c)
+            if (plan->stop_step[c] < 0) return group_bad((int)c, "chain plan: stop_step must be >= 0");
+    }
+    Guard guard(g->device);
+    if (!guard.ok) return merr(CEG_ERR_HIP, "hipSetDevice failed");
+    if (hipStreamSynchronize(g->stream) != hipSuccess) return merr(CEG_ERR_HIP, "stream synchronisation failed");
+    g->accept_pending = false;
+    g->uploads_pending = false;
+    // the new arrays first: a failure leaves the earlier plan installed
+    double* d_phi = nullptr;
+    int64_t* d_stop = nullptr;
+    const size_t phi_bytes = phi ? sizeof(double) * k * (size_t)plan->nspecies : 0, stop_bytes = stop ? sizeof(int64_t) * k : 0;
+    const bool ok = (!phi || (hipMalloc((void**)&d_phi, phi_bytes) == hipSuccess && hipMemcpy(d_phi, plan->phiPV_div_k, phi_bytes, hipMemcpyHostToDevice) == hipSuccess)) &&
+                    (!stop || (hipMalloc((void**)&d_stop, stop_bytes) == hipSuccess && hipMemcpy(d_stop, plan->stop_step, stop_bytes, hipMemcpyHostToDevice) == hipSuccess));
+    if (!ok) {
+        if (d_phi) (void)hipFree(d_phi);
+        if (d_stop) (void)hipFree(d_stop);
+        return merr(CEG_ERR_HIP, "could not copy the chain plan to the device");
+    }
+    if (g->d_plan_phi) (void)hipFree(g->d_plan_phi);
+    if (g->d_plan_stop) (void)hipFree(g->d_plan_stop);
+    g->d_plan_phi = d_phi;
+    g->d_plan_stop = d_stop;
+    g->plan_species = phi ? plan->nspecies : 0;
+    if (phi) g->plan_phi.assign(plan->phiPV_div_k, plan->phiPV_div_k + k * (size_t)plan->nspecies); else g->plan_phi.clear();
+    if (stop) g->plan_stop.assign(plan->stop_step, plan->stop_step + k); else g->plan_stop.clear();
+    return CEG_OK;
+}
+
 // ---- what the two sweeps share on the host: the refusals, the launch plan, the layout of the group's device block and the driver
 namespace {
 
@@ -1161,15 +1224,23 @@ int run_sweep(ceg_mc_group* g, const SweepPlan& plan, const SweepLayout& lay, st
         if (d_log) (void)hipFree(d_log);
         return merr(CEG_ERR_HIP, what);
     };
+    // the launch lists; with stops in the chain plan each class in the order of its chains' stops, the latest first (chain order among
+    // equals), so that the chains still running at a step are the head of their list and the trial grid shrinks with them
+    const std::vector<int64_t>& stop = g->plan_stop;
+    std::vector<int32_t> order[2] = {plan.list[0], plan.list[1]};
+    if (!stop.empty())
+        for (int cl = 0; cl < 2; ++cl)
+            std::stable_sort(order[cl].begin(), order[cl].end(), [&](int32_t a, int32_t b) { return stop[(size_t)a] > stop[(size_t)b]; });
     int32_t* l = reinterpret_cast<int32_t*>(stage.data() + lay.list);
     for (int cl = 0, e = 0; cl < 2; ++cl)
-        for (int32_t c : plan.list[cl]) l[e++] = c;
+        for (int32_t c : order[cl]) l[e++] = c;
     if (hipMemcpy(g->d_scratch, stage.data(), lay.total, hipMemcpyHostToDevice) != hipSuccess) return fail("H2D failed");
     if (!group_upload_views(g, std::vector<char>(k, 1))) return fail("view upload failed");
     if (d_log && hipMemsetAsync(d_log, 0, log_bytes, g->stream) != hipSuccess) return fail("hipMemsetAsync failed");
     // ---- the steps: nothing between them but the stream's own order (no chain with a molecule and no log: nothing to do)
     const int32_t* d_list = sweep_at<const int32_t>(g, lay.list);
     const unsigned n0 = (unsigned)plan.list[0].size(), n1 = (unsigned)plan.list[1].size();
+    unsigned live0 = n0, live1 = n1;                     // chains of either class that have not stopped (the steps only go up)
     // (with every chain empty and no log the steps launch nothing; a sampler still takes its frames, and only those are launched)
     bool launched = true;
     const bool work = n0 + n1 > 0 || d_log;
@@ -1179,9 +1250,14 @@ int run_sweep(ceg_mc_group* g, const SweepPlan& plan, const SweepLayout& lay, st
         const bool framed = g->sampler && sampler_frame_after(g->sampler, step);
         const bool ends = cycle_len > 0 && (s + 1) % cycle_len == 0;
         if (!work && !framed && !ends) continue;
-        if (n0) trial(false, dim3(2u * n0, 3u), lds_trial[0], d_list, table_ok[0], step);
-        if (n1) trial(true, dim3(2u * n1, 3u), lds_trial[1], d_list + n0, table_ok[1], step);
-        if (work) accept(dim3((unsigned)k), plan.lds_accept, step, d_log ? d_log + (size_t)s * k : nullptr);
+        if (!stop.empty()) {
+            while (live0 > 0 && step >= (uint64_t)stop[(size_t)order[0][live0 - 1]]) --live0;
+            while (live1 > 0 && step >= (uint64_t)stop[(size_t)order[1][live1 - 1]]) --live1;
+        }
+        if (live0) trial(false, dim3(2u * live0, 3u), lds_trial[0], d_list, table_ok[0], step);
+        if (live1) trial(true, dim3(2u * live1, 3u), lds_trial[1], d_list + n0, table_ok[1], step);
+        // (the accept launch keeps one workgroup per chain: a stopped chain's writes its record and returns; no chain left and no log: none)
+        if (live0 + live1 > 0 || d_log) accept(dim3((unsigned)k), plan.lds_accept, step, d_log ? d_log + (size_t)s * k : nullptr);
         if (framed) frame(step);
         if (ends) cycle_end(s / cycle_len);
         launched = hipGetLastError() == hipSuccess;
@@ -1202,6 +1278,7 @@ struct SweepCycles {
     const ceg_mc_cycles_t* cy;
     ceg_mc_cycle_record_t* out;
     bool table() const { return cycled && cy->temperatures; }
+    uint64_t last_step(uint64_t first_step, int64_t j) const { return first_step + (uint64_t)(j + 1) * (uint64_t)cy->steps_per_cycle - 1; }   // of cycle j of the call
     // the temperatures the first step runs at: the table's first row, nullptr for a table without rows, else the parameters' own
     const double* first_row(const double* temperature) const { return table() ? (cy->ncycles > 0 ? cy->temperatures : nullptr) : temperature; }
     // the three segments of the group's block the cycle ends use, behind the statistics (read back with them); none without cycles
@@ -1289,18 +1366,21 @@ int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nstep
     };
     auto accept = [&](dim3 grid, size_t lds, uint64_t step, ceg_mc_sweep_record_t* rec) {
         hipLaunchKernelGGL(k_mcg_sweep_accept, grid, dim3(MC_THREADS), lds, g->stream, g->d_views, sweep_at<const McSweepChain>(g, lay.par), p->seed, step,
-                           sweep_at<const McPositions>(g, lay.prop), sweep_at<const double>(g, lay.rows), sweep_at<ceg_mc_sweep_stats_t>(g, o_stats), rec);
+                           sweep_at<const McPositions>(g, lay.prop), sweep_at<const double>(g, lay.rows), sweep_at<ceg_mc_sweep_stats_t>(g, o_stats), rec,
+                           g->d_plan_stop);
     };
     int32_t max_slots = 0;
     for (const ceg_mc* h : g->chains) max_slots = std::max(max_slots, h->v.natoms);
     auto frame = [&](uint64_t step) {                     // (the molecule table does not change: counts from the views)
-        const SampleSource src{nullptr, 0, 0, &sweep_at<const ceg_mc_sweep_stats_t>(g, o_stats)->delta, nullptr, (int32_t)sizeof(ceg_mc_sweep_stats_t), max_slots};
+        const SampleSource src{nullptr, 0, 0, &sweep_at<const ceg_mc_sweep_stats_t>(g, o_stats)->delta, nullptr, (int32_t)sizeof(ceg_mc_sweep_stats_t), max_slots,
+                               g->d_plan_stop};
         sampler_enqueue(g->sampler, g->stream, g->d_views, k, (int64_t)step, src);
     };
     auto cycle_end = [&](int64_t j) {                     // (the molecule table does not change: counts from the views)
         const ceg_mc_sweep_stats_t* st = sweep_at<const ceg_mc_sweep_stats_t>(g, o_stats);
         const CycleSource src{&st->translation_trials, &st->translation_accepted, &st->rotation_trials, &st->rotation_accepted, &st->delta, nullptr, nullptr,
-                              &sweep_at<McSweepChain>(g, lay.par)->temperature, (int32_t)sizeof(ceg_mc_sweep_stats_t), 0, (int32_t)sizeof(McSweepChain), 0};
+                              &sweep_at<McSweepChain>(g, lay.par)->temperature, (int32_t)sizeof(ceg_mc_sweep_stats_t), 0, (int32_t)sizeof(McSweepChain), 0,
+                              g->d_plan_stop, C.last_step(p->first_step, j)};
         cycles_enqueue(g->stream, g->d_views, k, C.run(g), j, src);
     };
     if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame, C.cycled ? C.cy->steps_per_cycle : 0, cycle_end))
@@ -1331,6 +1411,8 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
     for (int c = 0; c < k; ++c)
         if (int rc = sweep_refuse_chain(g->chains[c], c)) return rc;
     if (ns < 1 || ns > CEG_MC_GCMC_MAX_SPECIES) return merr(CEG_ERR_INVALID, "1 <= nspecies <= CEG_MC_GCMC_MAX_SPECIES");
+    const std::vector<double>& chain_phi = g->plan_phi;
+    if (!chain_phi.empty() && g->plan_species != ns) return merr(CEG_ERR_INVALID, "nspecies differs from the nspecies of ceg_mc_group_set_chain_plan");
     int mmax = 1;
     int64_t swap_atoms = 0;                              // atoms of one molecule of every species that can be inserted
     for (int i = 0; i < ns; ++i) {
@@ -1353,7 +1435,13 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
             prev = S.cumulative[q];
         }
         const bool swaps = S.cumulative[4] < 1.0;
-        if (swaps && !(std::isfinite(S.phiPV_div_k) && S.phiPV_div_k > 0.0)) return bad("phiPV_div_k must be finite and > 0 where the swap probability is > 0");
+        // (with per-chain values in the chain plan the table's own is not read: the plan's entries get the same check instead)
+        if (swaps && chain_phi.empty() && !(std::isfinite(S.phiPV_div_k) && S.phiPV_div_k > 0.0))
+            return bad("phiPV_div_k must be finite and > 0 where the swap probability is > 0");
+        for (int c = 0; swaps && !chain_phi.empty() && c < k; ++c) {
+            const double phi = chain_phi[(size_t)c * (size_t)ns + (size_t)i];
+            if (!(std::isfinite(phi) && phi > 0.0)) return group_bad(c, "chain plan: phiPV_div_k must be finite and > 0 for a species whose swap probability is > 0");
+        }
         if (!std::isfinite(S.self_reciprocal) || !std::isfinite(S.tail_framework)) return bad("self_reciprocal and the tail correction must be finite");
         for (int j = 0; j < ns; ++j)
             if (!std::isfinite(S.tail_cross[j])) return bad("self_reciprocal and the tail correction must be finite");
@@ -1483,7 +1571,8 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
         hipLaunchKernelGGL(k_mcg_gcmc_accept, grid, dim3(MC_THREADS), lds, g->stream, g->d_views, sweep_at<const McGcmcChain>(g, lay.par),
                            sweep_at<const ceg_mc_gcmc_species_t>(g, o_spec), ns, sweep_at<McGcmcTable>(g, o_tab), sweep_at<int32_t>(g, o_ms),
                            sweep_at<int32_t>(g, o_free), p->seed, step, blocks ? sweep_at<const int32_t>(g, o_res) : nullptr, sweep_at<int64_t>(g, o_pock),
-                           sweep_at<const McPositions>(g, lay.prop), sweep_at<const double>(g, lay.rows), sweep_at<ceg_mc_gcmc_stats_t>(g, o_stats), rec);
+                           sweep_at<const McPositions>(g, lay.prop), sweep_at<const double>(g, lay.rows), sweep_at<ceg_mc_gcmc_stats_t>(g, o_stats), rec,
+                           g->d_plan_phi, g->d_plan_stop);
     };
     static_assert(offsetof(McGcmcTable, nmol) == 0 && offsetof(McGcmcTable, natoms) == 4 && offsetof(McGcmcTable, count) == 8 && sizeof(McGcmcTable) % 4 == 0,
                   "the head of a chain's table as SampleSource describes it");
@@ -1492,14 +1581,15 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
     auto frame = [&](uint64_t step) {                     // (counts from the device's table: the views' nmol / natoms are stale during the sweep)
         const ceg_mc_gcmc_stats_t* st = sweep_at<const ceg_mc_gcmc_stats_t>(g, o_stats);
         const SampleSource src{&sweep_at<const McGcmcTable>(g, o_tab)->nmol, (int32_t)(sizeof(McGcmcTable) / 4), ns, &st->delta_moves, &st->delta_swaps,
-                               (int32_t)sizeof(ceg_mc_gcmc_stats_t), max_slots};
+                               (int32_t)sizeof(ceg_mc_gcmc_stats_t), max_slots, g->d_plan_stop};
         sampler_enqueue(g->sampler, g->stream, g->d_views, k, (int64_t)step, src);
     };
     auto cycle_end = [&](int64_t j) {                     // (the molecule count from the device's table, as the frames)
         const ceg_mc_gcmc_stats_t* st = sweep_at<const ceg_mc_gcmc_stats_t>(g, o_stats);
         const CycleSource src{&st->trials[0], &st->accepted[0], &st->trials[1], &st->accepted[1], &st->delta_moves, &st->delta_swaps,
                               &sweep_at<const McGcmcTable>(g, o_tab)->nmol, &sweep_at<McGcmcChain>(g, lay.par)->temperature,
-                              (int32_t)sizeof(ceg_mc_gcmc_stats_t), (int32_t)sizeof(McGcmcTable), (int32_t)sizeof(McGcmcChain), 0};
+                              (int32_t)sizeof(ceg_mc_gcmc_stats_t), (int32_t)sizeof(McGcmcTable), (int32_t)sizeof(McGcmcChain), 0,
+                              g->d_plan_stop, C.last_step(p->first_step, j)};
         cycles_enqueue(g->stream, g->d_views, k, C.run(g), j, src);
     };
     if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame, C.cycled ? C.cy->steps_per_cycle : 0, cycle_end))

@@ -791,13 +791,15 @@ int check_molecule(const ceg_mc* h, const int32_t* kinds, int32_t m, McMolecule*
 struct GroupSampler;
 // where a frame finds what the views do not hold during a sweep, per chain c: counts + c * counts_stride = (molecules, high-water
 // mark of the atom slots, molecules per species [ncount]) in device memory (nullptr: nmol / natoms of the views, no species);
-// delta_moves / delta_swaps + c * stats_stride bytes: the running sums of the sweep's statistics (nullptr: 0)
+// delta_moves / delta_swaps + c * stats_stride bytes: the running sums of the sweep's statistics (nullptr: 0);
+// stop: the chain plan's [K] stops (nullptr: none) -- a frame after a step >= stop[c] writes chain c's record and bins nothing of it
 struct SampleSource {
     const int32_t* counts;
     int32_t counts_stride, ncount;
     const double *delta_moves, *delta_swaps;
     int32_t stats_stride;
     int32_t max_slots;                           // no chain's high-water mark exceeds this while the frame runs
+    const int64_t* stop;
 };
 void sampler_free(GroupSampler* s);
 int sampler_admit(const GroupSampler* s, uint64_t first_step, int64_t nsteps);      // CEG_ERR_INVALID: the sweep's frames do not fit
@@ -810,12 +812,16 @@ void sampler_rollback(GroupSampler* s, hipStream_t stream, int64_t frames);     
 // Where the launch finds, per chain c, what it reads and writes (all device memory): the four counters and the one or two sums of
 // the call's statistics at + c * stats_stride bytes (delta_swaps nullptr: 0); the molecule count at nmol + c * nmol_stride bytes
 // (nullptr: nmol of the views); the chain's (temperature, dmax, thetamax), three adjacent doubles, at triple + c * triple_stride bytes.
+// stop: the chain plan's [K] stops (nullptr: none) and last_step, the absolute last step of the cycle: a chain with last_step >=
+// stop[c] gets its record with the counters as they stand and its step sizes carried over.
 struct CycleSource {
     const int64_t *translation_trials, *translation_accepted, *rotation_trials, *rotation_accepted;
     const double *delta_moves, *delta_swaps;
     const int32_t* nmol;
     double* triple;
     int32_t stats_stride, nmol_stride, triple_stride, _pad;
+    const int64_t* stop;
+    uint64_t last_step;
 };
 // the cycles of one call: what cycles_check has admitted, and the three segments of the group's block the launches use
 struct CycleRun {

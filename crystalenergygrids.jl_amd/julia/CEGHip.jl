@@ -879,6 +879,36 @@ function mc_group_block_counts(g::Ptr{Cvoid}, k::Integer)
     pocket, attempts
 end
 
+# `ceg_mc_chain_plan_t` of include/ceg_hip.h (24 bytes)
+struct McChainPlan
+    nspecies::Int32
+    _pad::Int32
+    phiPV_div_k::Ptr{Float64}        # [K][nspecies] in K, species fastest; C_NULL: the species table's value for every chain
+    stop_step::Ptr{Int64}            # [K] absolute steps; C_NULL: no chain ever stops
+end
+
+"""
+`ceg_mc_group_set_chain_plan`: what differs between the chains of `make_isotherm` (src/parameterinputs.jl:305-334).  `phiPV_div_k` is an
+`nspecies x K` matrix (`φPV_div_k[i]` of src/simulation.jl:714-715 for the pressure of chain `c` in column `c`; unitful or in K) that
+replaces the species table's value in the swap rules of `mc_group_sweep_gcmc!` / `mc_group_sweep_gcmc_cycles!`; chain `c` takes no part
+in the absolute steps `s ≥ stop_step[c]` of any sweep (its `ncycles` of :319 times `steps_per_cycle`, counted from step 0 of the run).
+Either may be `nothing`; both `nothing` removes the plan.  Never executed here (no Julia in the image).
+"""
+function mc_group_set_chain_plan!(g::Ptr{Cvoid}; phiPV_div_k::Union{Nothing,AbstractMatrix}=nothing, stop_step::Union{Nothing,AbstractVector{<:Integer}}=nothing)
+    if phiPV_div_k === nothing && stop_step === nothing
+        _check(ccall((:ceg_mc_group_set_chain_plan, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), g, C_NULL))
+        return nothing
+    end
+    phi = phiPV_div_k === nothing ? Float64[] : Float64[x isa Real ? x : ustrip(u"K", x) for x in vec(phiPV_div_k)]
+    stop = stop_step === nothing ? Int64[] : Vector{Int64}(stop_step)
+    GC.@preserve phi stop begin
+        plan = Ref(McChainPlan(phiPV_div_k === nothing ? Int32(0) : Int32(size(phiPV_div_k, 1)), Int32(0),
+                               phiPV_div_k === nothing ? Ptr{Float64}(C_NULL) : pointer(phi), stop_step === nothing ? Ptr{Int64}(C_NULL) : pointer(stop)))
+        _check(ccall((:ceg_mc_group_set_chain_plan, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), g, plan))
+    end
+    nothing
+end
+
 # `ceg_mc_sampler_t` (152 bytes) and `ceg_mc_sample_record_t` (64 bytes) of include/ceg_hip.h
 struct McSampler
     every::Int64

@@ -792,7 +792,8 @@ CEG_API int ceg_mc_group_sweep(ceg_mc_group_t* group, const ceg_mc_sweep_params_
  * Synchronous.  Afterwards the handles' host mirrors (molecule table, free atom slots, high-water mark) are rebuilt from the device and
  *   every per-handle and group entry point works on the new state.
  * Not covered: the fugacity coefficient and the accessible-volume factor of GCMCData (phiPV_div_k
- *   comes from the caller, as the reference takes it from Clapeyron), and chains that keep their guests in neighbour cells.
+ *   comes from the caller, as the reference takes it from Clapeyron), and chains that keep their guests in neighbour cells.  One
+ *   phiPV_div_k per chain and a last step per chain (an isotherm's pressures): ceg_mc_group_set_chain_plan, below.
  *
  * Block pockets (ceg_mc_group_set_blocks): the inblockpocket test and the 1000-attempt retry loop of choose_step!
  * (src/simulation.jl:271-326, src/montecarlo.jl:631-640), resolved inside the trial launch of the step (no launch is added).
@@ -979,7 +980,7 @@ CEG_API int ceg_mc_group_sampler_reset(ceg_mc_group_t* group);
  * Continuation: a run split over several calls gives the bytes of the one-call run if each call passes first_step advanced, cycle0
  *   advanced, prior = the summed counters (the last record's) and dmax / thetamax = the last record's dmax_next / thetamax_next.
  * Synchronous.  Not covered: one steps_per_cycle applies to the whole group (chains whose reference cycle lengths differ belong in
- *   different groups); snapshots of the positions every `printevery` cycles; the baseline_energy at cycle 0 inside the run (a caller
+ *   different groups; chains whose run LENGTHS differ stop at their own last step with ceg_mc_group_set_chain_plan, below); snapshots of the positions every `printevery` cycles; the baseline_energy at cycle 0 inside the run (a caller
  *   composes it from two calls around ceg_mc_group_baseline). */
 #define CEG_MC_ADAPT_DMAX     1
 #define CEG_MC_ADAPT_THETAMAX 2
@@ -1005,6 +1006,43 @@ CEG_API int ceg_mc_group_sweep_cycles(ceg_mc_group_t* group, const ceg_mc_sweep_
 CEG_API int ceg_mc_group_sweep_gcmc_cycles(ceg_mc_group_t* group, const ceg_mc_gcmc_params_t* params, const ceg_mc_cycles_t* cycles,
                                            ceg_mc_gcmc_stats_t* stats_out, ceg_mc_cycle_record_t* cycles_out,
                                            ceg_mc_gcmc_record_t* log_out);
+
+/* ---- chain plan: a fugacity term and a last step per chain (make_isotherm, src/parameterinputs.jl:305-334) ----
+ * An isotherm is one run_gcmc per pressure.  The pressure of a chain enters its run in one number, phiPV_div_k of
+ * compute_accept_move_swap (src/gcmc.jl:77-88, built at src/simulation.jl:701-715), and in its run length, ncycles =
+ * ceil(simu.ncycles (1 + 1e3 / P)) (parameterinputs.jl:319).  The plan gives a group both per chain, so that one lockstep call runs
+ * the chains of an isotherm: it is as long as the longest chain, and the others stop at their own last step and stay stopped.
+ *
+ * set_chain_plan copies both arrays (host memory) to the group's device memory and synchronises the group.  The plan stays installed
+ *   until it is replaced, removed with NULL, or the group is destroyed.
+ * phiPV_div_k [K][nspecies] K, or NULL: entry [c][i] replaces species[i].phiPV_div_k for chain c in both swap rules of
+ *   ceg_mc_group_sweep_gcmc and ceg_mc_group_sweep_gcmc_cycles (the table's own value is then neither read nor checked).  Nothing else
+ *   changes: the FP64 expressions and their order are the ones documented for ceg_mc_group_sweep_gcmc ("Rule").  Entries of species
+ *   with no swap probability are not read.  The plain sweeps ignore the array.
+ * stop_step [K] absolute steps, or NULL: chain c takes no part in the absolute steps s >= stop_step[c] of any of the four sweep entry
+ *   points.  For such a step no row is evaluated (the chain is in no trial launch: the grid shrinks), nothing of the chain's state
+ *   changes, and its statistics, spent / blocked / capacity and pocket counters count nothing.  Its log record is zero bytes except
+ *   molecule = -2 (ceg_mc_group_trial's "idle in this step"), kind = -1 and, in the GCMC record, species = -1.
+ *   Sampler: a frame taken after such a step does not bin the chain (a pooled map would otherwise count the frozen chain again and
+ *     again); the chain's series record of the frame is still written, from its frozen state, so series_out stays [frames][K].
+ *   Cycle end: the record of a cycle whose last step is >= stop_step[c] is still written, with the counters as they stand; dmax and
+ *     thetamax are carried over without adaptation, as for a chain with no molecules.
+ *   stop_step[c] <= first_step is legal: the chain sits the whole call out.  The random stream is keyed by the absolute step, so a
+ *   stopped chain can be continued later from first_step = stop_step[c], and the continuation gives the bytes of the uninterrupted run.
+ * Refusals, all CEG_ERR_INVALID before anything is launched or changed, the earlier plan staying installed: set_chain_plan with
+ *   nspecies outside [0, CEG_MC_GCMC_MAX_SPECIES], phiPV_div_k given with nspecies < 1, or a stop_step < 0; a GCMC sweep with a plan
+ *   whose phiPV_div_k has an nspecies other than params->nspecies, or with an entry that is not finite and > 0 for a species whose swap
+ *   probability is > 0.
+ * With no plan installed, or a plan whose two pointers are NULL, every sweep enqueues the launches and produces the bytes (log,
+ *   statistics, records, maps, states) it produces without this section.
+ * Not covered: the fugacity coefficient (phi comes from the caller, as the reference takes it from Clapeyron); one steps_per_cycle
+ *   applies to the whole group; chains that keep their guests in neighbour cells. */
+typedef struct ceg_mc_chain_plan {      /* 24 bytes */
+    int32_t nspecies, _pad;
+    const double*  phiPV_div_k;         /* [K][nspecies] in K, or NULL: every chain uses the species table's value */
+    const int64_t* stop_step;           /* [K] absolute steps, or NULL: no chain ever stops */
+} ceg_mc_chain_plan_t;
+CEG_API int ceg_mc_group_set_chain_plan(ceg_mc_group_t* group, const ceg_mc_chain_plan_t* plan);   /* NULL removes it */
 
 /* ---- baseline_energy (src/montecarlo.jl:530-542) of one chain, or of every chain of a group, from the resident state ----
  * What run_montecarlo! asks for at its start, at the first production cycle, after a move that risks underflow and for its final
