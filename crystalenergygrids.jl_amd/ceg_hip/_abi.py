@@ -251,6 +251,9 @@ PROTOTYPES = {
     "ceg_mc_group_set_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "ceg_mc_group_block_counts": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
     "ceg_mc_group_set_chain_plan": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ceg_mc_group_set_device_cells": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "ceg_mc_group_halted": (C.c_int, [C.c_void_p, c_int64_p]),
+    "ceg_mc_cell_lists": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, C.c_int64]),
     "ceg_mc_group_set_sampler": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ceg_mc_group_sample": (C.c_int, [C.c_void_p]),
     "ceg_mc_group_sampler_read": (C.c_int, [C.c_void_p, c_int64_p, C.c_void_p, c_int64_p]),

@@ -419,6 +419,18 @@ class DeviceMonteCarlo:
             _abi.check(self._lib, rc)
         return (tuple(int(x) for x in nb), int(cap.value)) if rc == 1 else None
 
+    def cell_lists(self, nslots: Optional[int] = None):
+        """``ceg_mc_cell_lists``: the host's cell lists of the handle -> (int32[nslots] cell, int32[nslots] entry in that cell) per atom
+        slot, -1 where the slot is in no cell, or None when the handle keeps no neighbour cells.  ``nslots`` defaults to the atom slots
+        of the guests on the device (:meth:`state`)."""
+        if nslots is None:
+            nslots = len(self.state()[0])
+        cell_of, idx_of = np.full(int(nslots), -1, dtype=np.int32), np.full(int(nslots), -1, dtype=np.int32)
+        rc = self._lib.ceg_mc_cell_lists(self._h, _abi.i32ptr(cell_of), _abi.i32ptr(idx_of), int(nslots))
+        if rc < 0:
+            _abi.check(self._lib, rc)
+        return (cell_of, idx_of) if rc == 1 else None
+
     def refresh(self) -> None:
         """Upload the guests of ``self.mc`` (initial state, or to resynchronise with the host side)."""
         pos, kinds, first = [], [], [0]
@@ -624,6 +636,14 @@ class MonteCarloDrift(RuntimeError):
     """The drift check at the end of ``run_montecarlo!`` (simulation.jl:850-853) failed: recorded and actual energy differ."""
 
 
+class MonteCarloHalted(RuntimeError):
+    """A sweep halted a chain on a full neighbour cell (:meth:`DeviceMonteCarloGroup.halted`): ``chain`` and the absolute ``step``."""
+
+    def __init__(self, chain: int, step: int):
+        super().__init__(f"chain {chain} halted at step {step} on a full neighbour cell: raise the capacity with device_cells(capacity=...)")
+        self.chain, self.step = chain, step
+
+
 class MonteCarloRun(NamedTuple):
     """What :meth:`DeviceMonteCarloGroup.run_montecarlo` returns"""
     initial_energies: np.ndarray      # [ninit, K] K, after every initialisation cycle
@@ -715,6 +735,24 @@ class DeviceMonteCarloGroup:
         pocket, attempts = np.zeros(len(self.chains), dtype=np.int64), np.zeros(len(self.chains), dtype=np.int64)
         _abi.check(self._lib, self._lib.ceg_mc_group_block_counts(self._h, _abi.i64ptr(pocket), _abi.i64ptr(attempts)))
         return pocket, attempts
+
+    def device_cells(self, on: bool = True, capacity: Optional[int] = None) -> None:
+        """``ceg_mc_group_set_device_cells``: :meth:`sweep`, :meth:`sweep_gcmc` and their ``_cycles`` forms take the chains that keep
+        their guests in neighbour cells (:meth:`DeviceMonteCarlo.neighbour_cells`); their cell lists are kept on the device during
+        a sweep.  ``capacity``: such chains get at least that many entries per cell.  ``on=False``: such chains are refused again."""
+        _abi.check(self._lib, self._lib.ceg_mc_group_set_device_cells(self._h, 1 if on else 0, int(capacity or 0)))
+
+    def halted(self) -> np.ndarray:
+        """``ceg_mc_group_halted`` -> int64[K]: the absolute step at which the last sweep call halted the chain on a full cell (nothing
+        of that step was applied; continue from it after ``device_cells(capacity=...)``), -1 where it did not."""
+        out = np.full(len(self.chains), -1, dtype=np.int64)
+        _abi.check(self._lib, self._lib.ceg_mc_group_halted(self._h, _abi.i64ptr(out)))
+        return out
+
+    def _raise_if_halted(self) -> None:
+        h = self.halted()
+        for c in np.nonzero(h >= 0)[0]:
+            raise MonteCarloHalted(int(c), int(h[c]))
 
     @staticmethod
     def chain_plan_arrays(k: int, phiPV_div_k=None, stop_step=None):
@@ -1085,7 +1123,12 @@ class DeviceMonteCarloGroup:
         the state gains or loses E and the two Ewald constants move with the species counts.  ``recorded`` is therefore
         ``energies[-1]`` plus, per species, (count now - count at the first production cycle) * self_reciprocal, minus the tail
         correction's change as the species table holds it, plus the change of ``2 energy_net_charges + static_contribution`` and of
-        ``mc.tailcorrection`` -- all functions of the counts alone.  Without swaps it is ``energies[-1]``."""
+        ``mc.tailcorrection`` -- all functions of the counts alone.  Without swaps it is ``energies[-1]``.
+
+        A chain that keeps its guests in neighbour cells takes part after :meth:`device_cells`, with or without ``gcmc``.
+        If a sweep call halts a chain on a full cell, :class:`MonteCarloHalted` names chain and step; the states are those the call
+        left (the halted chain as before that step).  Continuing a run in the middle of a cycle is out of scope: raise the capacity
+        with ``device_cells(capacity=...)`` and start the run again."""
         from . import mcrng
         k = len(self.chains)
         ninit, ncycles = int(ninit), int(ncycles)
@@ -1136,6 +1179,7 @@ class DeviceMonteCarloGroup:
                 before = [[len(kind) for kind in chain._slot] for chain in self.chains]
                 stats, cyc = self.sweep_gcmc_cycles(n, L, seed, done[0] * L, positions=positions and last, **gcmc, **args)
                 retail(before)
+            self._raise_if_halted()                  # (a chain with neighbour cells whose cell filled up: device_cells)
             if n > 0:
                 dm[:], th[:] = cyc[-1]["dmax_next"], cyc[-1]["thetamax_next"]
                 for q, name in enumerate(("translation_trials", "translation_accepted", "rotation_trials", "rotation_accepted")):

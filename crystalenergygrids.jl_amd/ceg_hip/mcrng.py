@@ -31,6 +31,9 @@ order of ``k_mcg_cycle_end``, ``thetamax`` in radians.
 Isotherms (``ceg_mc_group_set_chain_plan``, ``DeviceMonteCarloGroup.make_isotherm``): :func:`isotherm_ncycles`, :func:`accessible_volume`,
 :func:`phiPV_div_k` and :meth:`MoveTable.for_gcmc` restate the host arithmetic of ``make_isotherm`` / ``run_gcmc`` / ``GCMCData``
 (parameterinputs.jl:274-279,319, gcmc.jl:26-37, simulation.jl:714-715); the fugacity coefficient stays with the caller.
+
+Neighbour cells (``ceg_mc_group_set_device_cells``): :class:`CellBook` restates the cell lists of a chain (``CellMirror`` of
+``csrc/ceg_mc_state.h``: ``bin_of``, ``take_out``, ``put_in``, ``refresh``) and :func:`replay_cell_book` follows them through a sweep's log.
 """
 from __future__ import annotations
 
@@ -482,6 +485,111 @@ def replay_positions(start_positions, records, atoms_per_species=None, start_spe
             else:
                 mols[d] = np.array(rec["positions"][:len(mols[d])], dtype=np.float64)
         yield list(mols) if spec is None else (list(spec), list(mols))
+
+
+# ---- neighbour cells (``ceg_mc_group_set_device_cells``): the cell lists of a chain, i.e. ``CellMirror`` of csrc/ceg_mc_state.h, whose
+# sequential semantics the accept launch of csrc/ceg_mc_cells.hip replays.  The order of the entries of a cell fixes the order of the
+# pair sum of every later row, so the three operations are restated exactly.
+class CellBook:
+    """Which atom slot sits at which entry of which cell.  ``invmat``: the inverse of the MC cell matrix (``mc.invmat``, fractional =
+    invmat @ p); ``nb``: bins per axis (:meth:`ceg_hip.energy.DeviceMonteCarlo.neighbour_cells`).  ``members[c]`` lists the atom slots
+    of cell ``c`` in entry order; ``cell_of`` / ``idx_of`` map an atom slot to its cell and entry (absent: in no cell); ``max_fill``
+    is the longest list there has been (the capacity a handle needs)."""
+
+    def __init__(self, invmat, nb):
+        self.invmat = np.asarray(invmat, dtype=np.float64).reshape(3, 3)
+        self.nb = tuple(int(n) for n in nb)
+        self.members = [[] for _ in range(self.nb[0] * self.nb[1] * self.nb[2])]
+        self.cell_of, self.idx_of = {}, {}
+        self.max_fill = 0
+
+    def bin_of(self, p) -> int:
+        """``cell_of_position`` (csrc/ceg_consumers.h): f = invmat p in that order of operations, f - floor(f), the truncation of
+        ``f * nb`` and both clamps (f - floor(f) rounds to 1.0 for a tiny negative f: the upper clamp)."""
+        x, y, z = (float(v) for v in p)
+        b = []
+        for i in range(3):
+            I = self.invmat[i]
+            f = (float(I[0]) * x + float(I[1]) * y) + float(I[2]) * z
+            f -= math.floor(f)
+            q = int(f * self.nb[i])
+            b.append(0 if q < 0 else (self.nb[i] - 1 if q >= self.nb[i] else q))
+        return (b[0] * self.nb[1] + b[1]) * self.nb[2] + b[2]
+
+    def take_out(self, slot: int) -> None:
+        """the last entry of the cell moves into the hole, and its ``idx_of`` follows"""
+        slot = int(slot)
+        if slot not in self.cell_of:
+            return
+        c, i = self.cell_of.pop(slot), self.idx_of.pop(slot)
+        mem = self.members[c]
+        moved = mem[-1]
+        mem[i] = moved
+        if moved != slot:
+            self.idx_of[moved] = i
+        mem.pop()
+
+    def put_in(self, slot: int, c: int) -> None:
+        """append"""
+        mem = self.members[int(c)]
+        mem.append(int(slot))
+        self.cell_of[int(slot)], self.idx_of[int(slot)] = int(c), len(mem) - 1
+        self.max_fill = max(self.max_fill, len(mem))
+
+    def refresh(self, slot: int) -> None:
+        """the record of the atom is copied again where it sits: the lists do not change"""
+
+    def set_atoms(self, positions) -> "CellBook":
+        """``ceg_mc_set_guests``: every atom slot put in, in slot order"""
+        for slot, p in enumerate(np.asarray(positions, dtype=np.float64).reshape(-1, 3)):
+            self.put_in(slot, self.bin_of(p))
+        return self
+
+    def move(self, first: int, positions) -> int:
+        """an accepted displacement of the molecule in atom slots ``first ...`` (``accept_cell_ops``), per atom in order: refresh where
+        the bin did not change, else take-out and put-in -> the number of atoms that changed their cell"""
+        changed = 0
+        for a, p in enumerate(np.asarray(positions, dtype=np.float64).reshape(-1, 3)):
+            c = self.bin_of(p)
+            if self.cell_of.get(first + a) == c:
+                self.refresh(first + a)
+                continue
+            self.take_out(first + a)
+            self.put_in(first + a, c)
+            changed += 1
+        return changed
+
+    def insert(self, first: int, positions) -> None:
+        """an accepted insertion into the atom slots ``first ...``: put-in of the atoms in order"""
+        for a, p in enumerate(np.asarray(positions, dtype=np.float64).reshape(-1, 3)):
+            self.put_in(first + a, self.bin_of(p))
+
+    def remove(self, first: int, m: int, last_first: int = -1, last_m: int = 0) -> None:
+        """an accepted deletion of the molecule in atom slots ``first ... first + m - 1``: take-out of its atoms in order, then the
+        refresh of the atoms of the last molecule (slots ``last_first ...``) where that one takes over the index"""
+        for a in range(m):
+            self.take_out(first + a)
+        for a in range(last_m):
+            self.refresh(last_first + a)
+
+    def lists(self, nslots: int):
+        """-> (int32[nslots] cell, int32[nslots] entry), -1 where the slot is in no cell: what ``DeviceMonteCarlo.cell_lists`` returns"""
+        cell_of, idx_of = np.full(int(nslots), -1, dtype=np.int32), np.full(int(nslots), -1, dtype=np.int32)
+        for slot, c in self.cell_of.items():
+            cell_of[slot], idx_of[slot] = c, self.idx_of[slot]
+        return cell_of, idx_of
+
+
+def replay_cell_book(book: CellBook, records, first_slot, atoms) -> int:
+    """Follow one chain's cell lists through the log of a plain sweep (``records``: the chain's column of the log of ``sweep``):
+    every accepted displacement of device molecule ``d`` moves the atoms in slots ``first_slot[d] ... + atoms[d] - 1`` to the logged
+    placement.  Idle and stopped steps (molecule < 0) change nothing.  -> the number of atoms that changed their cell."""
+    changed = 0
+    for rec in records:
+        d = int(rec["molecule"])
+        if d >= 0 and rec["accepted"]:
+            changed += book.move(int(first_slot[d]), rec["positions"][:int(atoms[d])])
+    return changed
 
 
 # ---- cycles (``ceg_mc_group_sweep_cycles`` / ``ceg_mc_group_sweep_gcmc_cycles``): the end-of-cycle block of run_montecarlo!

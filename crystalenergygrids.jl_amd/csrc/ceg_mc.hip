@@ -704,7 +704,7 @@ extern "C" int ceg_mc_destroy(ceg_mc_t* h)
     if (guard.ok) {
         if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
         for (void* p : {(void*)h->d_vdw, (void*)h->d_charge, (void*)h->d_rules, (void*)h->d_offset, (void*)h->d_ijk, (void*)h->d_kf,
-                        (void*)h->d_fw, (void*)h->d_tot, (void*)h->d_mol, (void*)h->d_atoms, (void*)h->d_molidx, (void*)h->d_in, (void*)h->d_out, (void*)h->d_cells, (void*)h->d_cell_count, (void*)h->d_etab, (void*)h->d_baseline})
+                        (void*)h->d_fw, (void*)h->d_tot, (void*)h->d_mol, (void*)h->d_atoms, (void*)h->d_molidx, (void*)h->d_in, (void*)h->d_out, (void*)h->d_cells, (void*)h->d_cell_count, (void*)h->d_cell_of, (void*)h->d_idx_of, (void*)h->d_owner, (void*)h->d_etab, (void*)h->d_baseline})
             if (p) (void)hipFree(p);
         if (h->h_in) (void)hipHostFree(h->h_in);
         if (h->h_out) (void)hipHostFree(h->h_out);
@@ -773,9 +773,10 @@ int ceg_mcs::rebuild_cells(ceg_mc* h)
 {
     CellMirror& cm = h->cm;
     if (!cm.on) return CEG_OK;
+    ++cm.version;
     const int ncells = cm.ncells();
     int cap = std::max(cm.cap, 8);
-    while (cap < cm.max_fill + cm.max_fill / 2 + 2) cap *= 2;
+    while (cap < cm.max_fill + cm.max_fill / 2 + 2 || cap < cm.min_cap) cap *= 2;
     if (hipStreamSynchronize(h->stream) != hipSuccess) return merr(CEG_ERR_HIP, "stream synchronisation failed");
     if (cap != cm.cap || !h->d_cells) {
         if (h->d_cells) (void)hipFree(h->d_cells);
@@ -1301,6 +1302,19 @@ extern "C" int ceg_mc_neighbour_cells(ceg_mc_t* h, int32_t nb[3], int32_t* capac
         if (nb) nb[i] = h->cm.on ? h->cm.nb[i] : 0;
     if (capacity) *capacity = h->cm.on ? h->cm.cap : 0;
     return h->cm.on ? 1 : 0;
+}
+
+extern "C" int ceg_mc_cell_lists(ceg_mc_t* h, int32_t* cell_of, int32_t* idx_of, int64_t nslots)
+{
+    if (!h || nslots < 0 || (nslots > 0 && (!cell_of || !idx_of))) return merr(CEG_ERR_INVALID, "bad argument");
+    if (h->poisoned) return refuse_poisoned();
+    if (!h->cm.on) return 0;
+    const int64_t have = (int64_t)h->cm.cell_of.size();
+    for (int64_t s = 0; s < nslots; ++s) {
+        cell_of[s] = s < have ? h->cm.cell_of[(size_t)s] : -1;
+        idx_of[s] = s < have ? h->cm.idx_of[(size_t)s] : -1;
+    }
+    return 1;
 }
 
 extern "C" int ceg_mc_get_state(ceg_mc_t* h, double* positions, double* sf_total_re, double* sf_total_im)

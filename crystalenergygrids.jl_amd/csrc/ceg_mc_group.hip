@@ -7,7 +7,7 @@
 //   ceg_mc_group_sweep_gcmc_cycles   launch of ceg_mc_cycles.hip behind the last step of every cycle (temperature table, dmax / thetamax)
 //   ceg_mc_group_set_chain_plan      per chain: the phiPV_div_k of the swap rules and the absolute step at which the chain stops (isotherms)
 // The two sweeps have their own kernels, per-chain parameters and read-back, and share one host driver (run_sweep).
-#include "ceg_mc_state.h"
+#include "ceg_mc_gcmc.h"
 
 using namespace ceg_mcs;
 
@@ -19,18 +19,6 @@ struct McGroupRow {
     int32_t view, molecule, stride, _pad;    // view: index of the chain in the group (views[view]); molecule -1 for an insertion
     int64_t trial, out;                      // offsets of the chain's placements (doubles) and of its first row (rows)
     McLocal L;
-};
-
-struct McAtChainRow {
-    int64_t out;             // row of `out` (fetched in front of the body: at its end it would be a round trip to host memory)
-    int r;                   // row of the chain
-    unsigned n;              // workgroups of all the launches of the call
-    int table_ok;            // the call's LDS leaves room for the pair tables
-    template <bool INSERT> __device__ __forceinline__ int64_t b() const { return INSERT ? (int64_t)r + 1 : (int64_t)r; }
-    __device__ __forceinline__ double* row(double* o) const { return o + 4 * (size_t)out; }
-    __device__ __forceinline__ unsigned nblocks() const { return n; }
-    __device__ __forceinline__ bool table_in_lds(const McView& v) const { return table_ok && v.table_in_lds; }
-    __device__ __forceinline__ int natoms(const McView& v) const { return v.natoms; }
 };
 
 // workgroup x of the launch: row x - ends[c - 1] of the chain c with ends[c - 1] <= x < ends[c] (ends: row prefix of the launch)
@@ -71,77 +59,7 @@ __global__ __launch_bounds__(MC_THREADS) void k_mcg_accept(const McView* __restr
 // k_mcg_accept), back to back on the group's stream.  Every workgroup of a chain's step regenerates the chain's random numbers from
 // (seed, step, stream id, purpose) (ceg_philox.h); what a step hands from the first kernel to the second -- the proposed positions
 // and the two rows -- stays in device memory.
-struct McSweepChain {            // per chain, device memory
-    uint32_t stream_id;
-    int32_t bead_off;            // the chain's first entry of the bead array
-    int32_t stride, _pad;
-    double temperature, dmax, thetamax, p_rotation;
-};
-
-struct McMove { int32_t molecule, kind; };       // kind 0 translation, 1 rotation; molecule -1: the chain is idle
-
 __device__ McCellOps d_mc_no_cell_ops;           // (sweeps refuse chains with neighbour cells: the accept body never reads it)
-
-// the chain plan's stop (ceg_mc_group_set_chain_plan): chain c takes no part in the absolute steps >= stop[c]; nullptr: no chain stops
-__device__ __forceinline__ bool chain_stopped(const int64_t* __restrict__ stop, int c, uint64_t step) { return stop && step >= (uint64_t)stop[c]; }
-
-__device__ __forceinline__ McMove sweep_select(const McView& v, const McSweepChain& P, uint64_t seed, uint64_t step)
-{
-    const int nmol = v.nmol;
-    if (nmol <= 0) return McMove{-1, -1};
-    const ceg_philox::Block w = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::SELECT);
-    int j = (int)floor(ceg_philox::uniform(w.w[0], w.w[1]) * (double)nmol);
-    j = j < nmol - 1 ? j : nmol - 1;
-    const bool rotate = v.mol[j].y > 1 && ceg_philox::uniform(w.w[2], w.w[3]) < P.p_rotation;
-    return McMove{j, rotate ? 1 : 0};
-}
-
-// (dx, dy, dz) turned by the angle with sine s and cosine c about `axis`: the matrices of src/mcmoves.jl:155-161 (SMatrix fills column by column)
-__device__ __forceinline__ void rotate_about(int axis, double s, double c, double& dx, double& dy, double& dz)
-{
-#pragma clang fp contract(off)
-    const double x = dx, y = dy, z = dz;
-    if (axis == 0) { dy = c * y - s * z; dz = s * y + c * z; }
-    else if (axis == 1) { dx = c * x + s * z; dz = c * z - s * x; }
-    else { dx = c * x - s * y; dy = s * x + c * y; }
-}
-
-// coordinate `comp` of atom `a` of the proposed placement of molecule mv.molecule (atoms [mj.x, mj.x + mj.y)): random_translation /
-// random_rotation of src/mcmoves.jl:139-164 on the resident positions
-// (stream id, step sizes and the atom the molecule rotates about as plain arguments: ceg_mc_group_sweep takes them from its per-chain
-// parameters and bead array, ceg_mc_group_sweep_gcmc from its own parameters and species table)
-__device__ __forceinline__ double sweep_coordinate_of(const McView& v, uint32_t stream_id, double dmax, double thetamax, int bead_atom, int kind, const int2 mj,
-                                                      uint64_t seed, uint64_t step, int a, int comp)
-{
-#pragma clang fp contract(off)
-    const double4 A = v.atoms[mj.x + a];
-    const ceg_philox::Block g = ceg_philox::draw(seed, step, stream_id, ceg_philox::GEOMETRY_A);
-    if (kind == 0) {
-        uint32_t wa = g.w[0], wb = g.w[1];
-        if (comp == 1) { wa = g.w[2]; wb = g.w[3]; }
-        if (comp == 2) {
-            const ceg_philox::Block h = ceg_philox::draw(seed, step, stream_id, ceg_philox::GEOMETRY_B);
-            wa = h.w[0]; wb = h.w[1];
-        }
-        const double r = (2.0 * ceg_philox::uniform(wa, wb) - 1.0) * dmax;
-        return (comp == 0 ? A.x : (comp == 1 ? A.y : A.z)) + r;
-    }
-    const double theta = thetamax * (2.0 * ceg_philox::uniform(g.w[0], g.w[1]) - 1.0);
-    int axis = (int)floor(3.0 * ceg_philox::uniform(g.w[2], g.w[3]));
-    axis = axis < 2 ? axis : 2;
-    double s, c;
-    sincos(theta, &s, &c);
-    const double4 R = v.atoms[mj.x + bead_atom];
-    double dx = A.x - R.x, dy = A.y - R.y, dz = A.z - R.z;
-    rotate_about(axis, s, c, dx, dy, dz);
-    return comp == 0 ? R.x + dx : (comp == 1 ? R.y + dy : R.z + dz);
-}
-
-__device__ __forceinline__ double sweep_coordinate(const McView& v, const McSweepChain& P, const int32_t* __restrict__ bead, const McMove mv, const int2 mj,
-                                                   uint64_t seed, uint64_t step, int a, int comp)
-{
-    return sweep_coordinate_of(v, P.stream_id, P.dmax, P.thetamax, mv.kind == 0 ? 0 : bead[P.bead_off + mv.molecule], mv.kind, mj, seed, step, a, comp);
-}
 
 // workgroup (x, y): chain list[x / 2], row x % 2 (0 where the molecule is, 1 the proposal), term y of the row.  prop[3 chain + y]: the
 // proposal as this workgroup's trial placement (written and read by the same threads); y = 0 is the copy k_mcg_sweep_accept reads.
@@ -170,17 +88,6 @@ __global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mcg_sweep_trial(
     __syncthreads();
     const McAtChainRow at{2 * (int64_t)c + r, r, 0u, table_ok};
     mc_trial_row<FAST, false, false>(v, mv.molecule, s_L, mine->xyz, rows, P.stride, nullptr, nullptr, 0ull, at);
-}
-
-// compute_accept_move (src/montecarlo.jl:702-712) on the rows before (row[0..3]) and after (row[4..7]) a displacement: the sums in the
-// reference's order; a proposal inside the framework's hard core is blocked; delta = after - before
-__device__ __forceinline__ int displacement_decision(const double* row, double u, double temperature, bool& blocked, double& delta)
-{
-#pragma clang fp contract(off)
-    const double b = ((row[0] + row[1]) + row[2]) + row[3], a = ((row[4] + row[5]) + row[6]) + row[7];
-    blocked = row[4] >= 1e90;
-    delta = a - b;
-    return (!blocked && (a < b || u < exp((b - a) / temperature))) ? 1 : 0;
 }
 
 // one workgroup per chain: compute_accept_move (src/montecarlo.jl:702-712) on the two rows, statistics, the log record, update_mc!
@@ -231,259 +138,6 @@ __global__ __launch_bounds__(MC_THREADS) void k_mcg_sweep_accept(const McView* _
 // species, the stacks of freed atom slots -- sits in ordinary device memory (McGcmcTable and the arrays behind it), is written with
 // ordinary stores by the accept kernel and read with ordinary loads by the next launch; the nmol / natoms entries of the chains' views
 // (read through the constant address space) are not used here.
-constexpr int MC_GCMC_SPECIES = CEG_MC_GCMC_MAX_SPECIES;
-
-struct McGcmcChain {             // per chain, fixed during a sweep
-    uint32_t stream_id;
-    int32_t stride;
-    int32_t max_molecules, atoms_cap;
-    int32_t spec_off;            // the chain's first entry of the species-of-molecule array
-    int32_t free_off, free_cap;  // stack of species i: freeslots[free_off + i * free_cap ...]
-    int32_t _pad;
-    double temperature, dmax, thetamax;
-};
-
-struct McGcmcTable {             // per chain, written by k_mcg_gcmc_accept
-    int32_t nmol, natoms;        // natoms: high-water mark of the atom slots
-    int32_t count[MC_GCMC_SPECIES], nfree[MC_GCMC_SPECIES];
-};
-
-struct McGcmcMove {
-    int32_t species, kind;       // kind 0..6 (include/ceg_hip.h)
-    int32_t molecule;            // device index; an insertion: the index it takes; -1 spent
-    int32_t n_i, nmol, natoms;
-    int32_t flags;               // 1 spent, 4 capacity
-};
-
-__device__ __forceinline__ int32_t gcmc_ld(const int32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-
-// the move of chain `P` at `step`, by the whole workgroup (the j-th molecule of the species is found by a scan of the table)
-__device__ __forceinline__ McGcmcMove gcmc_select(const McGcmcChain& P, const ceg_mc_gcmc_species_t* __restrict__ spec, int nspecies,
-                                                  const McGcmcTable* T, const int32_t* molspec, uint64_t seed, uint64_t step)
-{
-    __shared__ int s_wcnt[MC_THREADS / 64], s_found;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    McGcmcMove mv;
-    mv.nmol = gcmc_ld(&T->nmol);
-    mv.natoms = gcmc_ld(&T->natoms);
-    const ceg_philox::Block w = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::GCMC_SELECT);
-    int i = (int)floor(ceg_philox::uniform(w.w[0], w.w[1]) * (double)nspecies);
-    i = i < nspecies - 1 ? i : nspecies - 1;
-    const double uk = ceg_philox::uniform(w.w[2], w.w[3]);
-    int kind = 5;
-    for (int k = 4; k >= 0; --k)
-        if (uk < spec[i].cumulative[k]) kind = k;
-    const ceg_philox::Block wm = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::GCMC_MOLECULE);
-    if (kind == 5 && ceg_philox::uniform(wm.w[2], wm.w[3]) < 0.5) kind = 6;
-    mv.species = i;
-    mv.kind = kind;
-    mv.n_i = gcmc_ld(&T->count[i]);
-    mv.flags = 0;
-    mv.molecule = -1;
-    if (kind == 5) {
-        mv.molecule = mv.nmol;
-        if (mv.nmol >= P.max_molecules) mv.flags = 4;
-        return mv;
-    }
-    if (mv.n_i <= 0) { mv.flags = 1; return mv; }
-    int j = (int)floor(ceg_philox::uniform(wm.w[0], wm.w[1]) * (double)mv.n_i);
-    j = j < mv.n_i - 1 ? j : mv.n_i - 1;
-    const int32_t* ms = molspec + P.spec_off;
-    const int chunk = (mv.nmol + MC_THREADS - 1) / MC_THREADS;
-    const int lo = tid * chunk, hi = lo + chunk < mv.nmol ? lo + chunk : mv.nmol;
-    int cnt = 0;
-    for (int t = lo; t < hi; ++t) cnt += gcmc_ld(ms + t) == i ? 1 : 0;
-    int incl = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(incl, o);
-        if (lane >= o) incl += up;
-    }
-    if (tid == 0) s_found = -1;
-    if (lane == 63) s_wcnt[wave] = incl;
-    __syncthreads();
-    int before = incl - cnt;
-    for (int q = 0; q < wave; ++q) before += s_wcnt[q];
-    if (cnt > 0 && before <= j && j < before + cnt) {
-        int seen = before;
-        for (int t = lo; t < hi; ++t)
-            if (gcmc_ld(ms + t) == i && seen++ == j) s_found = t;
-    }
-    __syncthreads();
-    mv.molecule = __builtin_amdgcn_readfirstlane(s_found);
-    if (mv.molecule < 0) mv.flags = 1;          // (the counts and the table disagree: cannot happen; the step is spent)
-    return mv;
-}
-
-// the placement of one atom by the random_* kinds and the insertion (src/mcmoves.jl:139-164 with the MC cell / 180 degrees,
-// simulation.jl:294-305) from the blocks g, h, k of purposes 6, 7, 8 of its attempt: (px, py, pz) the atom, (bx, by, bz) the bead atom
-__device__ __forceinline__ void gcmc_random_point(const double* M, int kind, int m, const ceg_philox::Block& g, const ceg_philox::Block& h,
-                                                  const ceg_philox::Block& k, double& px, double& py, double& pz, double bx, double by, double bz)
-{
-#pragma clang fp contract(off)
-    if (kind != 3) {                             // random_translation: r = mat (U3 - 0.5)
-        const double ua = ceg_philox::uniform(g.w[0], g.w[1]) - 0.5, ub = ceg_philox::uniform(g.w[2], g.w[3]) - 0.5,
-                     uc = ceg_philox::uniform(h.w[0], h.w[1]) - 0.5;
-        const double rx = (M[0] * ua + M[3] * ub) + M[6] * uc, ry = (M[1] * ua + M[4] * ub) + M[7] * uc, rz = (M[2] * ua + M[5] * ub) + M[8] * uc;
-        px += rx; py += ry; pz += rz;
-        bx += rx; by += ry; bz += rz;
-    }
-    if (kind == 2 || m == 1) return;
-    const double theta = 3.141592653589793 * (2.0 * ceg_philox::uniform(h.w[2], h.w[3]) - 1.0);
-    int axis = (int)floor(3.0 * ceg_philox::uniform(k.w[0], k.w[1]));
-    axis = axis < 2 ? axis : 2;
-    double s, c;
-    sincos(theta, &s, &c);
-    double dx = px - bx, dy = py - by, dz = pz - bz;
-    rotate_about(axis, s, c, dx, dy, dz);
-    px = bx + dx; py = by + dy; pz = bz + dz;
-}
-
-// atom `a` and the bead atom of what a random_* kind or the insertion displaces: the species' model for an insertion, else the molecule
-__device__ __forceinline__ void gcmc_random_source(const McView& v, const ceg_mc_gcmc_species_t& S, int kind, const int2 mj, int a, double& px, double& py,
-                                                   double& pz, double& bx, double& by, double& bz)
-{
-    if (kind == 5) {
-        px = S.model[a][0]; py = S.model[a][1]; pz = S.model[a][2];
-        bx = S.model[S.bead][0]; by = S.model[S.bead][1]; bz = S.model[S.bead][2];
-    } else {
-        const double4 A = v.atoms[mj.x + a], B = v.atoms[mj.x + S.bead];
-        px = A.x; py = A.y; pz = A.z;
-        bx = B.x; by = B.y; bz = B.z;
-    }
-}
-
-// coordinate `comp` of atom `a` of the proposal: kinds 0 / 1 from sweep_coordinate, the random_* kinds and the insertion from attempt
-// `attempt` of purposes 6-8 (0 wherever choose_step! does not retry)
-__device__ __forceinline__ double gcmc_coordinate(const McView& v, const McGcmcChain& P, const ceg_mc_gcmc_species_t& S, const McGcmcMove& mv, const int2 mj,
-                                                  uint64_t seed, uint64_t step, uint32_t attempt, int a, int comp)
-{
-    if (mv.kind <= 1) {
-        if (mv.kind == 1 && mj.y == 1) return comp == 0 ? v.atoms[mj.x].x : (comp == 1 ? v.atoms[mj.x].y : v.atoms[mj.x].z);
-        return sweep_coordinate_of(v, P.stream_id, P.dmax, P.thetamax, S.bead, mv.kind, mj, seed, step, a, comp);
-    }
-    double px, py, pz, bx, by, bz;
-    gcmc_random_source(v, S, mv.kind, mj, a, px, py, pz, bx, by, bz);
-    ceg_philox::Block g{}, k{};
-    const ceg_philox::Block h = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::attempt_purpose(ceg_philox::GCMC_RANDOM_B, attempt));
-    if (mv.kind != 3) g = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::attempt_purpose(ceg_philox::GCMC_RANDOM_A, attempt));
-    if (mv.kind != 2 && mj.y != 1) k = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::attempt_purpose(ceg_philox::GCMC_RANDOM_C, attempt));
-    gcmc_random_point(v.mat, mv.kind, mj.y, g, h, k, px, py, pz, bx, by, bz);
-    return comp == 0 ? px : (comp == 1 ? py : pz);
-}
-
-// ---- block pockets (ceg_mc_group_set_blocks): inblockpocket and the retry loop of choose_step! (src/simulation.jl:271-326,
-// src/montecarlo.jl:631-640), resolved by every workgroup of a chain's step in front of its row.
-// blocks[0 .. nspecies): the species blocks; blocks[nspecies + kind]: the atom blocks (nkinds == 0: none); masks in device memory.
-using McBlock = ceg_mc_block_t;
-
-// BlockFile getindex at p + offset (src/coordinates.jl:58-66,97-101; blocked_at of ceg_egrid.hip): a NULL mask is empty
-__device__ __forceinline__ bool block_holds(const McBlock& B, double px, double py, double pz)
-{
-#pragma clang fp contract(off)
-    if (!B.mask) return false;
-    px = px + B.offset[0]; py = py + B.offset[1]; pz = pz + B.offset[2];
-    const double* I = B.invmat;
-    const double* M = B.mat;
-    double a0 = (I[0] * px + I[3] * py) + I[6] * pz;
-    double a1 = (I[1] * px + I[4] * py) + I[7] * pz;
-    double a2 = (I[2] * px + I[5] * py) + I[8] * pz;
-    a0 -= floor(a0); a1 -= floor(a1); a2 -= floor(a2);
-    const double q[3] = {(M[0] * a0 + M[3] * a1) + M[6] * a2, (M[1] * a0 + M[4] * a1) + M[7] * a2, (M[2] * a0 + M[5] * a1) + M[8] * a2};
-    int idx[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double sh = (q[c] - B.shift[c]) * (double)B.dims[c] / B.size[c] + 1.0;
-        const int i = (int)rint(sh) - 1;
-        idx[c] = i < 0 ? 0 : (i > B.dims[c] ? B.dims[c] : i);                          // memory safety only
-    }
-    const size_t ny = (size_t)B.dims[1] + 1, nz = (size_t)B.dims[2] + 1;
-    return B.mask[((size_t)idx[0] * ny + idx[1]) * nz + idx[2]] != 0;
-}
-
-// what a step's trial launch hands to its accept launch, one word per chain: attempt << 2 | exhausted << 1 | pocket-blocked
-constexpr int MC_POCKET = 1, MC_EXHAUSTED = 2;
-constexpr int MC_RESOLVE_PASSES = (ceg_philox::GCMC_ATTEMPTS + 15) / 16;
-
-// The attempt of the step's proposal and whether the step is pocket-blocked, by the whole workgroup.  16 attempts per pass, one per
-// 16 lanes, lane a of an attempt on atom a: the three Philox blocks of the attempt are drawn by its lanes 0-2 and shared, every lane
-// places its atom and looks it up; a ballot gives each attempt its verdict and the lowest passing attempt of the pass ends the loop.
-// Kinds 0, 1, 3 have the one proposal (attempt 0) and pass with its verdict.
-__device__ __forceinline__ int gcmc_resolve(const McView& v, const McGcmcChain& P, const ceg_mc_gcmc_species_t& S, const McGcmcMove& mv, const int2 mj,
-                                            const McBlock* __restrict__ blocks, int nspecies, int nkinds, uint64_t seed, uint64_t step)
-{
-    static_assert(MC_THREADS == 256 && MC_MAX_ATOMS == 16, "16 attempts of 16 lanes");
-    __shared__ unsigned s_verdict[2][MC_THREADS / 64];
-    const int tid = threadIdx.x, wave = tid >> 6, a = tid & 15;
-    const bool retried = mv.kind == 2 || mv.kind == 4 || mv.kind == 5;
-    const int npass = retried ? MC_RESOLVE_PASSES : 1;
-    const McBlock& SB = blocks[mv.species];
-    const int akind = S.kinds[a < mj.y ? a : 0];
-    for (int p = 0; p < npass; ++p) {
-        const int t = 16 * p + (tid >> 4);
-        const bool live = a < mj.y && (retried ? t < (int)ceg_philox::GCMC_ATTEMPTS : t == 0);
-        double x = 0.0, y = 0.0, z = 0.0;
-        if (mv.kind <= 1) {
-            if (live) {
-                x = gcmc_coordinate(v, P, S, mv, mj, seed, step, 0u, a, 0);
-                y = gcmc_coordinate(v, P, S, mv, mj, seed, step, 0u, a, 1);
-                z = gcmc_coordinate(v, P, S, mv, mj, seed, step, 0u, a, 2);
-            }
-        } else {
-            const ceg_philox::Block mine = ceg_philox::draw(seed, step, P.stream_id, ceg_philox::attempt_purpose(ceg_philox::GCMC_RANDOM_A + (uint32_t)(a % 3), (uint32_t)t));
-            ceg_philox::Block g, h, k;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                g.w[w] = (uint32_t)__shfl((int)mine.w[w], 0, 16);
-                h.w[w] = (uint32_t)__shfl((int)mine.w[w], 1, 16);
-                k.w[w] = (uint32_t)__shfl((int)mine.w[w], 2, 16);
-            }
-            if (live) {
-                double bx, by, bz;
-                gcmc_random_source(v, S, mv.kind, mj, a, x, y, z, bx, by, bz);
-                gcmc_random_point(v.mat, mv.kind, mj.y, g, h, k, x, y, z, bx, by, bz);
-            }
-        }
-        bool in_species = false, in_any = false;
-        if (live) {
-            in_species = block_holds(SB, x, y, z);
-            in_any = in_species || (nkinds > 0 && block_holds(blocks[nspecies + akind], x, y, z));
-        }
-        const unsigned long long bs = __ballot(in_species), ba = __ballot(in_any);
-        unsigned verdict = 0;                    // bits 0-3: the wave's four attempts pass; bits 4-7: their placements lie in a pocket
-        for (int q = 0; q < 4; ++q) {
-            const unsigned s16 = (unsigned)(bs >> (16 * q)) & 0xffffu, a16 = (unsigned)(ba >> (16 * q)) & 0xffffu;
-            const int tq = 16 * p + 4 * wave + q;
-            const bool pass = retried ? tq < (int)ceg_philox::GCMC_ATTEMPTS && (mv.kind == 5 ? ((s16 >> S.bead) & 1u) == 0u : a16 == 0u) : tq == 0;
-            verdict |= (pass ? 1u : 0u) << q | (a16 != 0u ? 16u : 0u) << q;
-        }
-        if ((tid & 63) == 0) s_verdict[p & 1][wave] = verdict;
-        __syncthreads();                         // (one per pass: the buffer of pass p is next written in pass p + 2, behind the barrier of p + 1)
-        unsigned pass = 0, pocket = 0;
-        for (int w = 0; w < MC_THREADS / 64; ++w) {
-            const unsigned r = s_verdict[p & 1][w];
-            pass |= (r & 15u) << (4 * w);
-            pocket |= (r >> 4) << (4 * w);
-        }
-        pass = (unsigned)__builtin_amdgcn_readfirstlane((int)pass);
-        if (pass) {
-            const int q = __ffs((int)pass) - 1;
-            return (16 * p + q) << 2 | (((pocket >> q) & 1u) ? MC_POCKET : 0);
-        }
-    }
-    return ((int)ceg_philox::GCMC_ATTEMPTS - 1) << 2 | MC_EXHAUSTED | MC_POCKET;
-}
-
-struct McAtGcmcRow {
-    int64_t out;
-    int r;                   // 0: where the molecule is; 1: the proposal (an insertion passes 0: its only row is the proposal)
-    int table_ok, n;         // n: high-water mark of the atom slots, from the device's table
-    template <bool INSERT> __device__ __forceinline__ int64_t b() const { return INSERT ? (int64_t)r + 1 : (int64_t)r; }
-    __device__ __forceinline__ double* row(double* o) const { return o + 4 * (size_t)out; }
-    __device__ __forceinline__ unsigned nblocks() const { return 0u; }
-    __device__ __forceinline__ bool table_in_lds(const McView& v) const { return table_ok && v.table_in_lds; }
-    __device__ __forceinline__ int natoms(const McView&) const { return n; }
-};
 
 // workgroup (x, y): chain list[x / 2], row x % 2, term y of the row, as k_mcg_sweep_trial; a deletion has no row 1, an insertion no row 0
 template <bool FAST>
@@ -707,6 +361,9 @@ struct ceg_mc_group {
     int plan_species = 0;
     double* d_plan_phi = nullptr;
     int64_t* d_plan_stop = nullptr;
+    // device cells (ceg_mc_group_set_device_cells): ceg_mc_group_sweep / _cycles take the chains with neighbour cells
+    bool device_cells = false;
+    std::vector<int64_t> halted;                 // [K] of the last sweep call: the step at which a full cell halted the chain, -1: none
 };
 
 namespace {
@@ -1128,14 +785,40 @@ extern "C" int ceg_mc_group_set_chain_plan(ceg_mc_group_t* g, const ceg_mc_chain
     return CEG_OK;
 }
 
+// ---- device cells of a group: the plain sweeps take the chains with neighbour cells
+extern "C" int ceg_mc_group_set_device_cells(ceg_mc_group_t* g, int32_t on, int32_t min_capacity)
+{
+    if (!g || min_capacity < 0 || min_capacity > (1 << 20)) return merr(CEG_ERR_INVALID, "bad argument (0 <= min_capacity <= 2^20)");
+    Guard guard(g->device);
+    if (!guard.ok) return merr(CEG_ERR_HIP, "hipSetDevice failed");
+    if (hipStreamSynchronize(g->stream) != hipSuccess) return merr(CEG_ERR_HIP, "stream synchronisation failed");
+    group_stream_idle(g);
+    for (size_t c = 0; on && min_capacity > 0 && c < g->chains.size(); ++c) {
+        ceg_mc* h = g->chains[c];
+        if (!h->cm.on || h->cm.cap >= min_capacity) continue;
+        if (h->poisoned) return group_refuse_poisoned((int)c);
+        h->cm.min_cap = min_capacity;
+        if (int rc = rebuild_cells(h)) { h->poisoned = true; return rc; }
+    }
+    g->device_cells = on != 0;
+    return CEG_OK;
+}
+
+extern "C" int ceg_mc_group_halted(ceg_mc_group_t* g, int64_t* halted_step_out)
+{
+    if (!g || !halted_step_out) return merr(CEG_ERR_INVALID, "bad argument");
+    for (size_t c = 0; c < g->chains.size(); ++c) halted_step_out[c] = c < g->halted.size() ? g->halted[c] : -1;
+    return CEG_OK;
+}
+
 // ---- what the two sweeps share on the host: the refusals, the launch plan, the layout of the group's device block and the driver
 namespace {
 
 // a chain no sweep takes: inconsistent after a failure, or with its guests in neighbour cells
-int sweep_refuse_chain(const ceg_mc* h, int c)
+int sweep_refuse_chain(const ceg_mc* h, int c, bool cells_ok = false)
 {
     if (h->poisoned) return group_refuse_poisoned(c);
-    if (h->v.use_cells || h->cm.on)
+    if ((h->v.use_cells || h->cm.on) && !cells_ok)
         return chain_err(CEG_ERR_UNSUPPORTED, c, " keeps its guests in neighbour cells: sweeps take chains with the exhaustive pair loop only", "");
     return CEG_OK;
 }
@@ -1158,15 +841,16 @@ int sweep_check_stream_id(const uint32_t* stream_id, int c)
     return CEG_OK;
 }
 
-// the launches of a step: the chains by class (0: exact rule energies, 1: fast), the LDS of their trial and accept kernels;
-// add(): chain c takes part, with molecules of at most mmax atoms
+// the launches of a step: the chains by class (bit 0: fast rule energies, bit 1: neighbour cells), the LDS of their trial and
+// accept kernels; add(): chain c takes part, with molecules of at most mmax atoms
+constexpr int SWEEP_CLASSES = 4;
 struct SweepPlan {
-    std::vector<int32_t> list[2];
-    size_t lds_trial[2] = {0, 0}, pair_table[2] = {0, 0}, lds_accept = 0;
+    std::vector<int32_t> list[SWEEP_CLASSES];
+    size_t lds_trial[SWEEP_CLASSES] = {0, 0, 0, 0}, pair_table[SWEEP_CLASSES] = {0, 0, 0, 0}, lds_accept = 0;
     int add(int c, const ceg_mc* h, int mmax)
     {
         if (tables_bytes(h, mmax) > 64 * 1024) return merr(CEG_ERR_UNSUPPORTED, "k-space tables of the molecule do not fit in LDS");
-        const int cl = h->v.fast ? 1 : 0;
+        const int cl = (h->v.fast ? 1 : 0) | (h->v.use_cells ? 2 : 0);
         list[cl].push_back(c);
         lds_trial[cl] = std::max(lds_trial[cl], tables_bytes(h, mmax));
         lds_accept = std::max(lds_accept, tables_bytes(h, mmax));
@@ -1193,7 +877,7 @@ int sweep_failed(ceg_mc_group* g)                        // some steps may have 
     return merr(CEG_ERR_HIP, "a sweep kernel failed: every chain of the group is marked inconsistent");
 }
 
-// `stage` (lay.total bytes, all but the launch lists filled in) into the group's block, then nsteps steps of trial(fast, grid, lds, list,
+// `stage` (lay.total bytes, all but the launch lists filled in) into the group's block, then nsteps steps of trial(class, grid, lds, list,
 // table_ok, step) per class present and accept(grid, lds, step, record), back to back on the group's stream; afterwards the block from
 // `o_back` on is back in `stage` and the records are in log_out.  A failure once the steps have started marks every chain inconsistent.
 // With a sampler installed, frame(step) follows the accept launch of every step the sampler takes a frame after.  With cycle_len > 0,
@@ -1203,9 +887,9 @@ int run_sweep(ceg_mc_group* g, const SweepPlan& plan, const SweepLayout& lay, st
               int64_t nsteps, Record* log_out, Trial&& trial, Accept&& accept, Frame&& frame, int64_t cycle_len, CycleEnd&& cycle_end)
 {
     const size_t k = g->chains.size();
-    size_t lds_trial[2];
-    int table_ok[2];
-    for (int cl = 0; cl < 2; ++cl) {                     // the pair table in LDS only where the largest tables leave room (run_trial's rule)
+    size_t lds_trial[SWEEP_CLASSES];
+    int table_ok[SWEEP_CLASSES];
+    for (int cl = 0; cl < SWEEP_CLASSES; ++cl) {                     // the pair table in LDS only where the largest tables leave room (run_trial's rule)
         table_ok[cl] = plan.lds_trial[cl] + plan.pair_table[cl] <= 64 * 1024 ? 1 : 0;
         lds_trial[cl] = plan.lds_trial[cl] + (table_ok[cl] ? plan.pair_table[cl] : 0);
     }
@@ -1227,37 +911,42 @@ int run_sweep(ceg_mc_group* g, const SweepPlan& plan, const SweepLayout& lay, st
     // the launch lists; with stops in the chain plan each class in the order of its chains' stops, the latest first (chain order among
     // equals), so that the chains still running at a step are the head of their list and the trial grid shrinks with them
     const std::vector<int64_t>& stop = g->plan_stop;
-    std::vector<int32_t> order[2] = {plan.list[0], plan.list[1]};
+    std::vector<int32_t> order[SWEEP_CLASSES] = {plan.list[0], plan.list[1], plan.list[2], plan.list[3]};
     if (!stop.empty())
-        for (int cl = 0; cl < 2; ++cl)
+        for (int cl = 0; cl < SWEEP_CLASSES; ++cl)
             std::stable_sort(order[cl].begin(), order[cl].end(), [&](int32_t a, int32_t b) { return stop[(size_t)a] > stop[(size_t)b]; });
     int32_t* l = reinterpret_cast<int32_t*>(stage.data() + lay.list);
-    for (int cl = 0, e = 0; cl < 2; ++cl)
+    for (int cl = 0, e = 0; cl < SWEEP_CLASSES; ++cl)
         for (int32_t c : order[cl]) l[e++] = c;
     if (hipMemcpy(g->d_scratch, stage.data(), lay.total, hipMemcpyHostToDevice) != hipSuccess) return fail("H2D failed");
     if (!group_upload_views(g, std::vector<char>(k, 1))) return fail("view upload failed");
     if (d_log && hipMemsetAsync(d_log, 0, log_bytes, g->stream) != hipSuccess) return fail("hipMemsetAsync failed");
     // ---- the steps: nothing between them but the stream's own order (no chain with a molecule and no log: nothing to do)
     const int32_t* d_list = sweep_at<const int32_t>(g, lay.list);
-    const unsigned n0 = (unsigned)plan.list[0].size(), n1 = (unsigned)plan.list[1].size();
-    unsigned live0 = n0, live1 = n1;                     // chains of either class that have not stopped (the steps only go up)
+    unsigned first[SWEEP_CLASSES], live[SWEEP_CLASSES], listed = 0;       // live: chains of a class that have not stopped (the steps only go up)
+    for (int cl = 0; cl < SWEEP_CLASSES; ++cl) {
+        first[cl] = listed;
+        live[cl] = (unsigned)plan.list[cl].size();
+        listed += live[cl];
+    }
     // (with every chain empty and no log the steps launch nothing; a sampler still takes its frames, and only those are launched)
     bool launched = true;
-    const bool work = n0 + n1 > 0 || d_log;
+    const bool work = listed > 0 || d_log;
     const int64_t frames_before = g->sampler ? sampler_frames_taken(g->sampler) : 0;
     for (int64_t s = 0; s < nsteps && launched && (work || g->sampler || cycle_len > 0); ++s) {
         const uint64_t step = first_step + (uint64_t)s;
         const bool framed = g->sampler && sampler_frame_after(g->sampler, step);
         const bool ends = cycle_len > 0 && (s + 1) % cycle_len == 0;
         if (!work && !framed && !ends) continue;
-        if (!stop.empty()) {
-            while (live0 > 0 && step >= (uint64_t)stop[(size_t)order[0][live0 - 1]]) --live0;
-            while (live1 > 0 && step >= (uint64_t)stop[(size_t)order[1][live1 - 1]]) --live1;
+        unsigned running = 0;
+        for (int cl = 0; cl < SWEEP_CLASSES; ++cl) {
+            if (!stop.empty())
+                while (live[cl] > 0 && step >= (uint64_t)stop[(size_t)order[cl][live[cl] - 1]]) --live[cl];
+            if (live[cl]) trial(cl, dim3(2u * live[cl], 3u), lds_trial[cl], d_list + first[cl], table_ok[cl], step);
+            running += live[cl];
         }
-        if (live0) trial(false, dim3(2u * live0, 3u), lds_trial[0], d_list, table_ok[0], step);
-        if (live1) trial(true, dim3(2u * live1, 3u), lds_trial[1], d_list + n0, table_ok[1], step);
         // (the accept launch keeps one workgroup per chain: a stopped chain's writes its record and returns; no chain left and no log: none)
-        if (live0 + live1 > 0 || d_log) accept(dim3((unsigned)k), plan.lds_accept, step, d_log ? d_log + (size_t)s * k : nullptr);
+        if (running > 0 || d_log) accept(dim3((unsigned)k), plan.lds_accept, step, d_log ? d_log + (size_t)s * k : nullptr);
         if (framed) frame(step);
         if (ends) cycle_end(s / cycle_len);
         launched = hipGetLastError() == hipSuccess;
@@ -1307,6 +996,85 @@ struct SweepCycles {
     }
 };
 
+// the device's book of chain h's cell lists from its CellMirror, where the mirror changed since the device's copy was current:
+// cell_of / idx_of uploaded (8 bytes per atom slot), owner[] rebuilt from them by one launch on the group's stream.
+// nslots: the atom slots the sweep can reach (slots beyond the host's lists are in no cell).
+// (No sweep is in flight: every sweep ends with a synchronisation.)
+int book_upload(ceg_mc_group* g, ceg_mc* h, McCellBook& B, size_t nslots)
+{
+    const CellMirror& cm = h->cm;
+    const size_t entries = (size_t)cm.ncells() * (size_t)cm.cap;
+    B = McCellBook{h->d_cell_of, h->d_idx_of, h->d_owner, (int32_t)cm.ncells(), (int32_t)nslots};
+    if (h->book_version == cm.version && h->d_cell_of && h->d_owner && nslots <= h->book_slots && entries <= h->book_entries) return CEG_OK;
+    h->book_version = 0;
+    if (nslots > h->book_slots || !h->d_cell_of) {
+        if (h->d_cell_of) (void)hipFree(h->d_cell_of);
+        if (h->d_idx_of) (void)hipFree(h->d_idx_of);
+        h->d_cell_of = h->d_idx_of = nullptr;
+        h->book_slots = 0;
+        const size_t n = std::max<size_t>(nslots, 1);
+        if (hipMalloc((void**)&h->d_cell_of, sizeof(int32_t) * n) != hipSuccess || hipMalloc((void**)&h->d_idx_of, sizeof(int32_t) * n) != hipSuccess)
+            return merr(CEG_ERR_HIP, "could not allocate the device's cell lists");
+        h->book_slots = n;
+    }
+    if (entries > h->book_entries || !h->d_owner) {
+        if (h->d_owner) (void)hipFree(h->d_owner);
+        h->d_owner = nullptr;
+        h->book_entries = 0;
+        const size_t n = std::max<size_t>(entries, 1);
+        if (hipMalloc((void**)&h->d_owner, sizeof(int32_t) * n) != hipSuccess) return merr(CEG_ERR_HIP, "could not allocate the device's cell lists");
+        h->book_entries = n;
+    }
+    std::vector<int32_t> cof(std::max<size_t>(nslots, 1), -1), iof(std::max<size_t>(nslots, 1), -1);
+    for (size_t s = 0; s < nslots && s < cm.cell_of.size(); ++s) { cof[s] = cm.cell_of[s]; iof[s] = cm.idx_of[s]; }
+    B = McCellBook{h->d_cell_of, h->d_idx_of, h->d_owner, (int32_t)cm.ncells(), (int32_t)nslots};
+    if (hipMemcpy(h->d_cell_of, cof.data(), sizeof(int32_t) * nslots, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->d_idx_of, iof.data(), sizeof(int32_t) * nslots, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemsetAsync(h->d_owner, 0xff, sizeof(int32_t) * entries, g->stream) != hipSuccess)
+        return merr(CEG_ERR_HIP, "could not copy the cell lists to the device");
+    cells_book_fill(g->stream, h->v, B);
+    if (hipGetLastError() != hipSuccess) return merr(CEG_ERR_HIP, "could not fill the device's cell lists");
+    h->book_version = cm.version;
+    return CEG_OK;
+}
+
+// the CellMirror of chain h from the device's book after a sweep (the stream is idle); peak: the longest list the sweep's steps saw;
+// false: the book is not a set of cell lists
+bool book_read_back(ceg_mc* h, int peak)
+{
+    CellMirror& cm = h->cm;
+    const size_t nslots = (size_t)std::max(h->v.natoms, 0), ncells = (size_t)cm.ncells();
+    std::vector<int32_t> cof(std::max<size_t>(nslots, 1)), iof(std::max<size_t>(nslots, 1)), cnt(ncells);
+    if (hipMemcpy(cof.data(), h->d_cell_of, sizeof(int32_t) * nslots, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(iof.data(), h->d_idx_of, sizeof(int32_t) * nslots, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(cnt.data(), h->d_cell_count, sizeof(int32_t) * ncells, hipMemcpyDeviceToHost) != hipSuccess)
+        return false;
+    // checked on a flat copy first (every entry of every list named by exactly one atom slot), then written into the mirror's lists
+    std::vector<size_t> at(ncells + 1, 0);
+    int fill = 0;
+    for (size_t c = 0; c < ncells; ++c) {
+        if (cnt[c] < 0 || cnt[c] > cm.cap) return false;
+        at[c + 1] = at[c] + (size_t)cnt[c];
+        fill = std::max(fill, (int)cnt[c]);
+    }
+    std::vector<int32_t> flat(at[ncells], -1);
+    size_t named = 0;
+    for (size_t s = 0; s < nslots; ++s) {
+        const int32_t c = cof[s], i = iof[s];
+        if (c < 0) { cof[s] = iof[s] = -1; continue; }
+        if ((size_t)c >= ncells || i < 0 || i >= cnt[(size_t)c] || flat[at[(size_t)c] + (size_t)i] != -1) return false;
+        flat[at[(size_t)c] + (size_t)i] = (int32_t)s;
+        ++named;
+    }
+    if (named != flat.size() || cm.members.size() != ncells) return false;
+    for (size_t c = 0; c < ncells; ++c) cm.members[c].assign(flat.begin() + (std::ptrdiff_t)at[c], flat.begin() + (std::ptrdiff_t)at[c + 1]);
+    if (cm.cell_of.size() < nslots) { cm.cell_of.resize(nslots, -1); cm.idx_of.resize(nslots, -1); }
+    std::copy(cof.begin(), cof.begin() + (std::ptrdiff_t)nslots, cm.cell_of.begin());
+    std::copy(iof.begin(), iof.begin() + (std::ptrdiff_t)nslots, cm.idx_of.begin());
+    cm.max_fill = std::max(cm.max_fill, std::max(fill, peak));      // peak: the longest list within a step, as the host's put_in counts it
+    return true;
+}
+
 // ceg_mc_group_sweep (C.cycled false: nsteps as given) and ceg_mc_group_sweep_cycles (nsteps from the cycles)
 int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nsteps, SweepCycles C, ceg_mc_sweep_stats_t* stats_out,
                 ceg_mc_sweep_record_t* log_out)
@@ -1329,7 +1097,7 @@ int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nstep
     SweepPlan plan;
     for (int c = 0; c < k; ++c) {
         ceg_mc* h = g->chains[c];
-        if (int rc = sweep_refuse_chain(h, c)) return rc;
+        if (int rc = sweep_refuse_chain(h, c, g->device_cells)) return rc;
         if (int rc = sweep_check_steps(p, temperature, c)) return rc;
         if (!(p->p_rotation[c] >= 0.0 && p->p_rotation[c] <= 1.0)) return group_bad(c, "p_rotation must lie in [0, 1]");
         if (int rc = sweep_check_stream_id(p->stream_id, c)) return rc;
@@ -1352,41 +1120,87 @@ int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nstep
     if (g->sampler)
         if (int rc = sampler_admit(g->sampler, p->first_step, nsteps)) return rc;
     for (int c = 0; c < k; ++c) stats_out[c] = ceg_mc_sweep_stats_t{};
+    g->halted.assign((size_t)k, -1);
     if (nsteps == 0) return CEG_OK;
+    // chains with cells (device cells switched on): the book of each in the block, and the stops as a device array the accept launch
+    // lowers to the halting step -- what the trial launches, the sampler and the cycle ends then read as the chain's stop
+    bool with_cells = false;
+    for (const ceg_mc* h : g->chains) with_cells = with_cells || h->v.use_cells;
     SweepLayout lay((size_t)k, sizeof(McSweepChain));
-    const size_t o_bead = lay.segment(sizeof(int32_t) * beads.size()), o_stats = lay.segment(sizeof(ceg_mc_sweep_stats_t) * (size_t)k);
+    const size_t o_bead = lay.segment(sizeof(int32_t) * beads.size()), o_book = lay.segment(with_cells ? sizeof(McCellBook) * (size_t)k : 0),
+                 o_stats = lay.segment(sizeof(ceg_mc_sweep_stats_t) * (size_t)k);
     C.layout(lay, (size_t)k);
+    const size_t o_stop = lay.segment(with_cells ? sizeof(int64_t) * (size_t)k : 0), o_halt = lay.segment(with_cells ? sizeof(int64_t) * (size_t)k : 0),
+                 o_flags = lay.segment(with_cells ? sizeof(int32_t) * 2 * (size_t)k : 0);
     std::vector<unsigned char> stage(lay.total, 0);
     C.fill(stage, (size_t)k);
     memcpy(stage.data() + lay.par, pc.data(), sizeof(McSweepChain) * (size_t)k);
     if (!beads.empty()) memcpy(stage.data() + o_bead, beads.data(), sizeof(int32_t) * beads.size());
-    auto trial = [&](bool fast, dim3 grid, size_t lds, const int32_t* list, int table_ok, uint64_t step) {
-        hipLaunchKernelGGL((fast ? k_mcg_sweep_trial<true> : k_mcg_sweep_trial<false>), grid, dim3(MC_THREADS), lds, g->stream, g->d_views, sweep_at<const McSweepChain>(g, lay.par),
+    if (with_cells) {
+        Guard guard(g->device);
+        if (!guard.ok) return merr(CEG_ERR_HIP, "hipSetDevice failed");
+        McCellBook* books = reinterpret_cast<McCellBook*>(stage.data() + o_book);
+        int64_t* st = reinterpret_cast<int64_t*>(stage.data() + o_stop);
+        int64_t* ht = reinterpret_cast<int64_t*>(stage.data() + o_halt);
+        for (int c = 0; c < k; ++c) {
+            st[c] = g->plan_stop.empty() ? INT64_MAX : g->plan_stop[(size_t)c];
+            ht[c] = -1;
+            if (g->chains[c]->v.use_cells)
+                if (int rc = book_upload(g, g->chains[c], books[c], (size_t)std::max(g->chains[c]->v.natoms, 0))) return rc;
+        }
+    }
+    auto trial = [&](int cl, dim3 grid, size_t lds, const int32_t* list, int table_ok, uint64_t step) {
+        if (cl & 2)
+            cells_sweep_trial(cl & 1, grid, lds, g->stream, g->d_views, sweep_at<const McSweepChain>(g, lay.par), sweep_at<const int32_t>(g, o_bead), list, table_ok,
+                              p->seed, step, sweep_at<McPositions>(g, lay.prop), sweep_at<double>(g, lay.rows), sweep_at<const int64_t>(g, o_stop));
+        else
+            hipLaunchKernelGGL((cl & 1 ? k_mcg_sweep_trial<true> : k_mcg_sweep_trial<false>), grid, dim3(MC_THREADS), lds, g->stream, g->d_views, sweep_at<const McSweepChain>(g, lay.par),
                                sweep_at<const int32_t>(g, o_bead), list, table_ok, p->seed, step, sweep_at<McPositions>(g, lay.prop), sweep_at<double>(g, lay.rows));
     };
     auto accept = [&](dim3 grid, size_t lds, uint64_t step, ceg_mc_sweep_record_t* rec) {
+        if (with_cells) {
+            const CellSweep cs{sweep_at<const McCellBook>(g, o_book), sweep_at<int64_t>(g, o_stop), sweep_at<int64_t>(g, o_halt), sweep_at<int32_t>(g, o_flags)};
+            cells_sweep_accept(grid, lds, g->stream, g->d_views, sweep_at<const McSweepChain>(g, lay.par), cs, p->seed, step, sweep_at<const McPositions>(g, lay.prop),
+                               sweep_at<const double>(g, lay.rows), sweep_at<ceg_mc_sweep_stats_t>(g, o_stats), rec);
+            return;
+        }
         hipLaunchKernelGGL(k_mcg_sweep_accept, grid, dim3(MC_THREADS), lds, g->stream, g->d_views, sweep_at<const McSweepChain>(g, lay.par), p->seed, step,
                            sweep_at<const McPositions>(g, lay.prop), sweep_at<const double>(g, lay.rows), sweep_at<ceg_mc_sweep_stats_t>(g, o_stats), rec,
                            g->d_plan_stop);
     };
     int32_t max_slots = 0;
     for (const ceg_mc* h : g->chains) max_slots = std::max(max_slots, h->v.natoms);
+    auto stop_of = [&]() -> const int64_t* { return with_cells ? sweep_at<const int64_t>(g, o_stop) : g->d_plan_stop; };
     auto frame = [&](uint64_t step) {                     // (the molecule table does not change: counts from the views)
         const SampleSource src{nullptr, 0, 0, &sweep_at<const ceg_mc_sweep_stats_t>(g, o_stats)->delta, nullptr, (int32_t)sizeof(ceg_mc_sweep_stats_t), max_slots,
-                               g->d_plan_stop};
+                               stop_of()};
         sampler_enqueue(g->sampler, g->stream, g->d_views, k, (int64_t)step, src);
     };
     auto cycle_end = [&](int64_t j) {                     // (the molecule table does not change: counts from the views)
         const ceg_mc_sweep_stats_t* st = sweep_at<const ceg_mc_sweep_stats_t>(g, o_stats);
         const CycleSource src{&st->translation_trials, &st->translation_accepted, &st->rotation_trials, &st->rotation_accepted, &st->delta, nullptr, nullptr,
                               &sweep_at<McSweepChain>(g, lay.par)->temperature, (int32_t)sizeof(ceg_mc_sweep_stats_t), 0, (int32_t)sizeof(McSweepChain), 0,
-                              g->d_plan_stop, C.last_step(p->first_step, j)};
+                              stop_of(), C.last_step(p->first_step, j)};
         cycles_enqueue(g->stream, g->d_views, k, C.run(g), j, src);
     };
     if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame, C.cycled ? C.cy->steps_per_cycle : 0, cycle_end))
         return rc;
     memcpy(stats_out, stage.data() + o_stats, sizeof(ceg_mc_sweep_stats_t) * (size_t)k);
     C.read_back(stage, (size_t)k);
+    if (with_cells) {
+        // ---- the host's cell lists from the device's book, for every chain with cells that accepted a move; a chain whose book
+        //      failed a range check is marked inconsistent
+        memcpy(g->halted.data(), stage.data() + o_halt, sizeof(int64_t) * (size_t)k);
+        const int32_t* flags = reinterpret_cast<const int32_t*>(stage.data() + o_flags);
+        int bad = -1;
+        for (int c = 0; c < k; ++c) {
+            ceg_mc* h = g->chains[c];
+            if (!h->v.use_cells) continue;
+            const bool moved = stats_out[c].translation_accepted + stats_out[c].rotation_accepted > 0;
+            if (flags[2 * c] || (moved && !book_read_back(h, flags[2 * c + 1]))) { h->poisoned = true; bad = bad < 0 ? c : bad; }
+        }
+        if (bad >= 0) return chain_err(CEG_ERR_HIP, bad, ": the cell lists kept on the device failed a range check: the chain is marked inconsistent", "");
+    }
     return CEG_OK;
 }
 
@@ -1409,7 +1223,7 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
     const int ns = p->nspecies;
     // ---- every refusal before anything is launched or changed: the chains, the species table, then the parameters chain by chain
     for (int c = 0; c < k; ++c)
-        if (int rc = sweep_refuse_chain(g->chains[c], c)) return rc;
+        if (int rc = sweep_refuse_chain(g->chains[c], c, g->device_cells)) return rc;
     if (ns < 1 || ns > CEG_MC_GCMC_MAX_SPECIES) return merr(CEG_ERR_INVALID, "1 <= nspecies <= CEG_MC_GCMC_MAX_SPECIES");
     const std::vector<double>& chain_phi = g->plan_phi;
     if (!chain_phi.empty() && g->plan_species != ns) return merr(CEG_ERR_INVALID, "nspecies differs from the nspecies of ceg_mc_group_set_chain_plan");
@@ -1522,6 +1336,7 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
     if (g->sampler)
         if (int rc = sampler_admit(g->sampler, p->first_step, nsteps)) return rc;
     for (int c = 0; c < k; ++c) stats_out[c] = ceg_mc_gcmc_stats_t{};
+    g->halted.assign((size_t)k, -1);
     g->pockets.assign(2 * (size_t)k, 0);
     if (nsteps == 0) {
         size_t o = 0;
@@ -1545,6 +1360,11 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
                  o_ms = lay.segment(sizeof(int32_t) * nspec_total), o_free = lay.segment(sizeof(int32_t) * nfree_total),
                  o_pock = lay.segment(sizeof(int64_t) * 2 * (size_t)k);
     C.layout(lay, (size_t)k);
+    // chains with cells (device cells switched on), as in sweep_plain: the books, the stops the accept launch lowers, halt and flags
+    bool with_cells = false;
+    for (const ceg_mc* h : g->chains) with_cells = with_cells || h->v.use_cells;
+    const size_t o_stop = lay.segment(with_cells ? sizeof(int64_t) * (size_t)k : 0), o_halt = lay.segment(with_cells ? sizeof(int64_t) * (size_t)k : 0),
+                 o_flags = lay.segment(with_cells ? sizeof(int32_t) * 2 * (size_t)k : 0), o_book = lay.segment(with_cells ? sizeof(McCellBook) * (size_t)k : 0);
     const ceg_mc_block_t* blocks = g->d_blocks;          // NULL: no masks, the kernels take the path without the resolve stage
     const int block_kinds = g->blk_kinds;
     std::vector<unsigned char> stage(lay.total, 0);
@@ -1561,13 +1381,39 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
             for (int q = 0; q < tab[(size_t)c].nfree[i]; ++q)
                 fr[(size_t)P.free_off + (size_t)i * P.free_cap + q] = g->chains[c]->free_runs[(size_t)p->species[i].m][(size_t)q];
     }
-    auto trial = [&](bool fast, dim3 grid, size_t lds, const int32_t* list, int table_ok, uint64_t step) {
-        hipLaunchKernelGGL((fast ? k_mcg_gcmc_trial<true> : k_mcg_gcmc_trial<false>), grid, dim3(MC_THREADS), lds, g->stream, g->d_views, sweep_at<const McGcmcChain>(g, lay.par),
+    if (with_cells) {
+        McCellBook* books = reinterpret_cast<McCellBook*>(stage.data() + o_book);
+        int64_t* sp = reinterpret_cast<int64_t*>(stage.data() + o_stop);
+        int64_t* ht = reinterpret_cast<int64_t*>(stage.data() + o_halt);
+        for (int c = 0; c < k; ++c) {
+            sp[c] = g->plan_stop.empty() ? INT64_MAX : g->plan_stop[(size_t)c];
+            ht[c] = -1;
+            if (g->chains[c]->v.use_cells)               // (the lists cover every atom slot an insertion can take)
+                if (int rc = book_upload(g, g->chains[c], books[c], (size_t)pc[(size_t)c].atoms_cap)) return rc;
+        }
+    }
+    auto stop_of = [&]() -> const int64_t* { return with_cells ? sweep_at<const int64_t>(g, o_stop) : g->d_plan_stop; };
+    auto trial = [&](int cl, dim3 grid, size_t lds, const int32_t* list, int table_ok, uint64_t step) {
+        if (cl & 2) {
+            cells_gcmc_trial(cl & 1, grid, lds, g->stream, g->d_views, sweep_at<const McGcmcChain>(g, lay.par), sweep_at<const ceg_mc_gcmc_species_t>(g, o_spec), ns,
+                             sweep_at<const McGcmcTable>(g, o_tab), sweep_at<const int32_t>(g, o_ms), list, table_ok, p->seed, step, blocks, block_kinds,
+                             sweep_at<int32_t>(g, o_res), sweep_at<McPositions>(g, lay.prop), sweep_at<double>(g, lay.rows), stop_of());
+            return;
+        }
+        hipLaunchKernelGGL((cl & 1 ? k_mcg_gcmc_trial<true> : k_mcg_gcmc_trial<false>), grid, dim3(MC_THREADS), lds, g->stream, g->d_views, sweep_at<const McGcmcChain>(g, lay.par),
                                sweep_at<const ceg_mc_gcmc_species_t>(g, o_spec), ns, sweep_at<const McGcmcTable>(g, o_tab), sweep_at<const int32_t>(g, o_ms), list,
                                table_ok, p->seed, step, blocks, block_kinds, sweep_at<int32_t>(g, o_res), sweep_at<McPositions>(g, lay.prop),
                                sweep_at<double>(g, lay.rows));
     };
     auto accept = [&](dim3 grid, size_t lds, uint64_t step, ceg_mc_gcmc_record_t* rec) {
+        if (with_cells) {
+            const CellSweep cs{sweep_at<const McCellBook>(g, o_book), sweep_at<int64_t>(g, o_stop), sweep_at<int64_t>(g, o_halt), sweep_at<int32_t>(g, o_flags)};
+            cells_gcmc_accept(grid, lds, g->stream, g->d_views, sweep_at<const McGcmcChain>(g, lay.par), sweep_at<const ceg_mc_gcmc_species_t>(g, o_spec), ns,
+                              sweep_at<McGcmcTable>(g, o_tab), sweep_at<int32_t>(g, o_ms), sweep_at<int32_t>(g, o_free), p->seed, step,
+                              blocks ? sweep_at<const int32_t>(g, o_res) : nullptr, sweep_at<int64_t>(g, o_pock), sweep_at<const McPositions>(g, lay.prop),
+                              sweep_at<const double>(g, lay.rows), sweep_at<ceg_mc_gcmc_stats_t>(g, o_stats), rec, g->d_plan_phi, cs);
+            return;
+        }
         hipLaunchKernelGGL(k_mcg_gcmc_accept, grid, dim3(MC_THREADS), lds, g->stream, g->d_views, sweep_at<const McGcmcChain>(g, lay.par),
                            sweep_at<const ceg_mc_gcmc_species_t>(g, o_spec), ns, sweep_at<McGcmcTable>(g, o_tab), sweep_at<int32_t>(g, o_ms),
                            sweep_at<int32_t>(g, o_free), p->seed, step, blocks ? sweep_at<const int32_t>(g, o_res) : nullptr, sweep_at<int64_t>(g, o_pock),
@@ -1581,7 +1427,7 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
     auto frame = [&](uint64_t step) {                     // (counts from the device's table: the views' nmol / natoms are stale during the sweep)
         const ceg_mc_gcmc_stats_t* st = sweep_at<const ceg_mc_gcmc_stats_t>(g, o_stats);
         const SampleSource src{&sweep_at<const McGcmcTable>(g, o_tab)->nmol, (int32_t)(sizeof(McGcmcTable) / 4), ns, &st->delta_moves, &st->delta_swaps,
-                               (int32_t)sizeof(ceg_mc_gcmc_stats_t), max_slots, g->d_plan_stop};
+                               (int32_t)sizeof(ceg_mc_gcmc_stats_t), max_slots, stop_of()};
         sampler_enqueue(g->sampler, g->stream, g->d_views, k, (int64_t)step, src);
     };
     auto cycle_end = [&](int64_t j) {                     // (the molecule count from the device's table, as the frames)
@@ -1589,7 +1435,7 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
         const CycleSource src{&st->trials[0], &st->accepted[0], &st->trials[1], &st->accepted[1], &st->delta_moves, &st->delta_swaps,
                               &sweep_at<const McGcmcTable>(g, o_tab)->nmol, &sweep_at<McGcmcChain>(g, lay.par)->temperature,
                               (int32_t)sizeof(ceg_mc_gcmc_stats_t), (int32_t)sizeof(McGcmcTable), (int32_t)sizeof(McGcmcChain), 0,
-                              g->d_plan_stop, C.last_step(p->first_step, j)};
+                              stop_of(), C.last_step(p->first_step, j)};
         cycles_enqueue(g->stream, g->d_views, k, C.run(g), j, src);
     };
     if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame, C.cycled ? C.cy->steps_per_cycle : 0, cycle_end))
@@ -1624,6 +1470,19 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
     for (int c = 0; c < k; ++c) {
         stats_out[c] = st[c];
         fill_counts(c, nt[c], ms + pc[(size_t)c].spec_off);
+    }
+    if (with_cells) {                                    // the host's cell lists of every chain with cells that accepted a step, as in sweep_plain
+        memcpy(g->halted.data(), stage.data() + o_halt, sizeof(int64_t) * (size_t)k);
+        const int32_t* flags = reinterpret_cast<const int32_t*>(stage.data() + o_flags);
+        int bad = -1;
+        for (int c = 0; c < k; ++c) {
+            ceg_mc* h = g->chains[c];
+            if (!h->v.use_cells) continue;
+            int64_t moved = 0;
+            for (int q = 0; q < 7; ++q) moved += st[c].accepted[q];
+            if (flags[2 * c] || (moved > 0 && !book_read_back(h, flags[2 * c + 1]))) { h->poisoned = true; bad = bad < 0 ? c : bad; }
+        }
+        if (bad >= 0) return chain_err(CEG_ERR_HIP, bad, ": the cell lists kept on the device failed a range check: the chain is marked inconsistent", "");
     }
     return CEG_OK;
 }

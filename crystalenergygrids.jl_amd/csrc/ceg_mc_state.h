@@ -638,10 +638,12 @@ struct CellMirror {
     std::vector<std::pair<int32_t, int32_t>> touched;   // (cell, entry) whose content changed
     std::vector<int32_t> touched_cells;
     int max_fill = 0;
+    int min_cap = 0;                                    // rebuild_cells gives every cell at least this many entries (ceg_mc_group_set_device_cells)
+    uint64_t version = 1;                               // bumped by every change of the lists or of the capacity (a sweep uploads the lists to the device when it moved)
 
     int ncells() const { return nb[0] * nb[1] * nb[2]; }
     int bin_of(const double* p) const { return ceg_consumers::cell_of_position(bins, invmat, p); }
-    void begin() { touched.clear(); touched_cells.clear(); }
+    void begin() { touched.clear(); touched_cells.clear(); ++version; }
     void touch(int32_t c, int32_t i)
     {
         for (const auto& t : touched)
@@ -733,6 +735,10 @@ struct ceg_mc {
     ceg_mcs::CellMirror cm;                      // neighbour cells of the guest atoms (when the MC cell is large enough to gain)
     double4* d_cells = nullptr;
     int32_t* d_cell_count = nullptr;
+    // the device's copy of the cell lists (McCellBook of ceg_mc_sweep.h), authoritative only while a sweep of the handle's group runs
+    int32_t *d_cell_of = nullptr, *d_idx_of = nullptr, *d_owner = nullptr;
+    size_t book_slots = 0, book_entries = 0;     // allocated sizes: atom slots of d_cell_of / d_idx_of, entries of d_owner
+    uint64_t book_version = 0;                   // CellMirror::version the device's copy agrees with (0: never uploaded)
     int stride = 0;
     // row-wise k-vector layout (ceg_rows.h) and, per distinct molecule (tuple of atom kinds), the pair-table rows of its kinds
     int32_t *d_desc = nullptr, *d_qof = nullptr;

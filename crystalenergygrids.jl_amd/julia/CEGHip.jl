@@ -909,6 +909,23 @@ function mc_group_set_chain_plan!(g::Ptr{Cvoid}; phiPV_div_k::Union{Nothing,Abst
     nothing
 end
 
+"""
+`ceg_mc_group_set_device_cells`: with `on`, the four sweep entry points (`mc_group_sweep!`, `mc_group_sweep_gcmc!` and their `_cycles!`
+forms) take the chains that keep their guests in neighbour cells (their cell lists are kept on the device during a sweep);
+`capacity > 0` gives such chains at least that many entries per cell.  Never executed here (no Julia in the image).
+"""
+function mc_group_set_device_cells!(g::Ptr{Cvoid}, on::Bool=true; capacity::Integer=0)
+    _check(ccall((:ceg_mc_group_set_device_cells, LIB[]), Cint, (Ptr{Cvoid}, Int32, Int32), g, on ? 1 : 0, capacity))
+    nothing
+end
+
+"`ceg_mc_group_halted`: per chain the absolute step at which the last sweep call halted it on a full cell (continue from it with a larger capacity), -1 if it did not"
+function mc_group_halted(g::Ptr{Cvoid}, k::Integer)
+    halted = fill(Int64(-1), k)
+    _check(ccall((:ceg_mc_group_halted, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int64}), g, halted))
+    halted
+end
+
 # `ceg_mc_sampler_t` (152 bytes) and `ceg_mc_sample_record_t` (64 bytes) of include/ceg_hip.h
 struct McSampler
     every::Int64

@@ -706,7 +706,7 @@ CEG_API int ceg_mc_group_accept(ceg_mc_group_t* group, const int32_t* molecule, 
  * params: seed, first_step; per chain stream_id (pairwise distinct), temperature K (finite, > 0), dmax A and thetamax rad (finite,
  *   >= 0), p_rotation in [0, 1]; bead: one 0-based atom index per molecule of every chain, packed in chain order (molecule order of
  *   ceg_mc_set_guests / ceg_mc_insert).  A violation, nsteps < 0 or a missing pointer -> CEG_ERR_INVALID; a member that keeps its
- *   guests in neighbour cells -> CEG_ERR_UNSUPPORTED (its update needs cell operations worked out on the host); a member marked
+ *   guests in neighbour cells -> CEG_ERR_UNSUPPORTED unless ceg_mc_group_set_device_cells, below, is on (its update needs the cell lists); a member marked
  *   inconsistent -> CEG_ERR_HIP.  A refused call launches nothing and leaves every chain as it was.  nsteps == 0: zeros.
  * stats_out [K]: trials and acceptances per move kind (a blocked trial counts as a trial of its kind and in `blocked`), delta =
  *   FP64 sum of a - b over the accepted moves.
@@ -1036,13 +1036,46 @@ CEG_API int ceg_mc_group_sweep_gcmc_cycles(ceg_mc_group_t* group, const ceg_mc_g
  * With no plan installed, or a plan whose two pointers are NULL, every sweep enqueues the launches and produces the bytes (log,
  *   statistics, records, maps, states) it produces without this section.
  * Not covered: the fugacity coefficient (phi comes from the caller, as the reference takes it from Clapeyron); one steps_per_cycle
- *   applies to the whole group; chains that keep their guests in neighbour cells. */
+ *   applies to the whole group.  (Chains that keep their guests in neighbour cells take part with ceg_mc_group_set_device_cells, below.) */
 typedef struct ceg_mc_chain_plan {      /* 24 bytes */
     int32_t nspecies, _pad;
     const double*  phiPV_div_k;         /* [K][nspecies] in K, or NULL: every chain uses the species table's value */
     const int64_t* stop_step;           /* [K] absolute steps, or NULL: no chain ever stops */
 } ceg_mc_chain_plan_t;
 CEG_API int ceg_mc_group_set_chain_plan(ceg_mc_group_t* group, const ceg_mc_chain_plan_t* plan);   /* NULL removes it */
+
+/* ---- device cells: the sweeps on chains that keep their guests in neighbour cells ----
+ * A handle whose MC cell is several cut-offs wide keeps its guest atoms in neighbour cells (ceg_mc_neighbour_cells), and the host
+ * holds which atom slot sits at which entry of which cell.  The sweeps refuse such a chain (CEG_ERR_UNSUPPORTED) unless device cells
+ * are switched on for the group; then all four sweep entry points take it: its trial rows walk the cells (the body of ceg_mc_trial /
+ * ceg_mc_trial_insert with cells), and the cell operations of an accepted step are worked out in the accept launch on a device copy
+ * of the lists (cell and entry per atom slot, atom slot per entry), exactly as ceg_mc_accept / ceg_mc_insert / ceg_mc_remove work
+ * them out on the host: a displacement, atom by atom in order, refreshes where the bin is unchanged, else takes out (the last entry
+ * into the hole) and puts in (append); an insertion puts the atoms of the new slot run in, in order; a deletion takes the molecule's
+ * atoms out in order and then refreshes the atoms of the last molecule where that one takes over the index.
+ * The copy is uploaded before a sweep where the host's lists have changed, and the host's lists are rebuilt from it after a sweep
+ * that accepted a move (both cost time per call, not per step: prefer long calls), so every
+ * host-driven call works on the chain afterwards as on any other.  Log, statistics and states are those of the host-driven route
+ * with the same proposals, byte for byte; chains without cells in the same group run the kernels and give the bytes they gave before.
+ * A full cell halts the chain: an accepted displacement or insertion that would put an atom into a cell already holding `capacity` entries is
+ *   not applied -- nothing of the step is written: atoms, structure factors, cells, lists, statistics -- and from that absolute
+ *   step on the chain behaves as if the chain plan had stopped it there (log records with molecule = -2, no sampler bins, cycle
+ *   records written with the step sizes carried over; in a GCMC sweep nothing of the molecule table, the counts or the freed slots changes).  The call returns CEG_OK; ceg_mc_group_halted reports the step.  The caller
+ *   raises the capacity (set_device_cells with a larger min_capacity) and continues from first_step = that step: proposals and
+ *   decisions depend on (seed, absolute step, stream id) only and a larger capacity changes no order of entries, so the result is
+ *   that of a run that had the capacity from the start.  Continuing in the middle of a cycle of the *_cycles entry points is not
+ *   covered.
+ * Every index read from the device's lists is range-checked before it is used; a failed check halts the chain in the same way and
+ *   the call returns CEG_ERR_HIP with the chain marked inconsistent.
+ * Not covered: growing the capacity inside a call; continuing a halted chain in the middle of a cycle. */
+/* on != 0: the sweeps of this group take chains that keep their guests in neighbour cells; their cell lists are kept on the
+   device during a sweep.  min_capacity > 0: their cells are rebuilt with at least that many entries per cell (never fewer
+   than rebuild_cells would choose).  on == 0: as before (such chains are refused).  Synchronises the group's stream. */
+CEG_API int ceg_mc_group_set_device_cells(ceg_mc_group_t* group, int32_t on, int32_t min_capacity);
+/* per chain the absolute step at which the last sweep call halted it on a full cell, -1 if it did not */
+CEG_API int ceg_mc_group_halted(ceg_mc_group_t* group, int64_t* halted_step_out /* [K] */);
+/* the host's cell lists of a handle: cell and entry of every atom slot (-1: in no cell); returns 0 without neighbour cells */
+CEG_API int ceg_mc_cell_lists(ceg_mc_t* handle, int32_t* cell_of, int32_t* idx_of, int64_t nslots);
 
 /* ---- baseline_energy (src/montecarlo.jl:530-542) of one chain, or of every chain of a group, from the resident state ----
  * What run_montecarlo! asks for at its start, at the first production cycle, after a move that risks underflow and for its final
