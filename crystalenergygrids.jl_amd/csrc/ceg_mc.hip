@@ -633,12 +633,7 @@ extern "C" int ceg_mc_create(ceg_mc_t** handle, int32_t device, ceg_interp_t* co
     ok = ok && hipMemset(h->d_tot, 0, sizeof(double2) * (size_t)(nk > 0 ? nk : 1)) == hipSuccess;
     if (ok && v.fast) {   // the r^2-indexed erfc(alpha r)/r records of the fractional-coordinate pair kernel (ceg_pairfrac.h)
         double alpha = 0.0;
-        bool shared = true;
-        for (const DevRule& R : dr)
-            if (R.kind == CEG_COULOMB_EWALD_DIRECT) {
-                if (alpha == 0.0) alpha = R.p0;
-                else if (alpha != R.p0) shared = false;
-            }
+        const bool shared = ceg_pairfrac::shared_alpha(dr.data(), (size_t)(nr > 0 ? nr : 0), alpha);
         ceg_pairfrac::ErfcTable et;
         if (shared && alpha > 0.0 && cutoff2 > 1.0 && ceg_pairfrac::build_erfc_table(alpha, 1.0, cutoff2, et) && upload(&h->d_etab, et.rec.data(), et.rec.size())) {
             h->ebase = et.base; h->eni = et.ni;

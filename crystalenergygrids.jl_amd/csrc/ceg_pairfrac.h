@@ -147,16 +147,18 @@ inline bool build_erfc_table(double alpha, double s_min, double s_max, ErfcTable
     if (!(worst < 1e-13)) { out.rec.clear(); out.ni = 0; return false; }
     return true;
 }
-// the alpha the CoulombEwaldDirect terms of the records share (0: none or several)
-inline double shared_alpha(const PairFast* fast, size_t n)
+// the alpha every CoulombEwaldDirect rule of a pair table shares: false when there is no such rule or when two of them differ.  Whether a
+// rule has been seen is kept apart from the value: alpha = 0 is a legal rule (plain 1/r) and differs from every other alpha.
+inline bool shared_alpha(const DevRule* rules, size_t n, double& alpha)
 {
-    double alpha = 0.0;
-    for (size_t i = 0; i < n; ++i)
-        if (fast[i].cls && fast[i].qq != 0.0) {
-            if (alpha == 0.0) alpha = fast[i].alpha;
-            else if (alpha != fast[i].alpha) return 0.0;
+    bool seen = false;
+    alpha = 0.0;
+    for (size_t q = 0; q < n; ++q)
+        if (rules[q].kind == CEG_COULOMB_EWALD_DIRECT) {
+            if (!seen) { alpha = rules[q].p0; seen = true; }
+            else if (alpha != rules[q].p0) return false;
         }
-    return alpha;
+    return seen;
 }
 
 // host: the record of one pair-table entry (rules [q0, q1) of `rules`); `walked` rules of other kinds make it cls = 0

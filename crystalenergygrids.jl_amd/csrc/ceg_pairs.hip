@@ -395,12 +395,7 @@ extern "C" int ceg_pairs_create(ceg_pairs_t** handle, int32_t device, const doub
     h->h_offset.assign(rule_offset, rule_offset + nt + 1);
     {   // the r^2-indexed erfc(alpha r)/r records of the fractional-coordinate kernel
         double alpha = 0.0;
-        bool shared = true;
-        for (int32_t q = 0; q < nr; ++q)
-            if (dr[q].kind == CEG_COULOMB_EWALD_DIRECT) {
-                if (alpha == 0.0) alpha = dr[q].p0;
-                else if (alpha != dr[q].p0) shared = false;
-            }
+        const bool shared = ceg_pairfrac::shared_alpha(dr.data(), (size_t)(nr > 0 ? nr : 0), alpha);
         ceg_pairfrac::ErfcTable et;
         if (fast && shared && alpha > 0.0 && cutoff2 > 1.0 && ceg_pairfrac::build_erfc_table(alpha, 1.0, cutoff2, et)) {
             if (hipMalloc((void**)&h->d_etab, et.rec.size() * sizeof(double)) == hipSuccess &&
