@@ -109,6 +109,17 @@ class McChainPlan(C.Structure):
 assert C.sizeof(McChainPlan) == 24
 MC_STOPPED = -2              # record.molecule of a step a chain sat out (its stop_step reached)
 
+
+class McTempering(C.Structure):
+    """``ceg_mc_tempering_t`` (``rung`` [K] int32, may be NULL, and ``energy`` [K] float64 in host memory)"""
+    _fields_ = [("every", C.c_int64), ("record_capacity", C.c_int64), ("rung", C.c_void_p), ("energy", C.c_void_p)]
+
+
+# ``ceg_mc_exchange_record_t``: one record per (cycle, chain) while a tempering state is installed
+MC_EXCHANGE_RECORD_DTYPE = np.dtype([('rung', '<i4'), ('rung_next', '<i4'), ('partner', '<i4'), ('accepted', '<i4'), ('energy', '<f8'),
+                                     ('temperature_next', '<f8'), ('u', '<f8'), ('threshold', '<f8')], align=True)
+assert (C.sizeof(McTempering), MC_EXCHANGE_RECORD_DTYPE.itemsize) == (32, 48)
+
 c_double_p = C.POINTER(C.c_double)
 c_float_p = C.POINTER(C.c_float)
 c_int32_p = C.POINTER(C.c_int32)
@@ -254,6 +265,8 @@ PROTOTYPES = {
     "ceg_mc_group_set_device_cells": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "ceg_mc_group_halted": (C.c_int, [C.c_void_p, c_int64_p]),
     "ceg_mc_cell_lists": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, C.c_int64]),
+    "ceg_mc_group_set_tempering": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ceg_mc_group_tempering_read": (C.c_int, [C.c_void_p, c_int32_p, c_double_p, c_int64_p, C.c_void_p, c_int64_p]),
     "ceg_mc_group_set_sampler": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ceg_mc_group_sample": (C.c_int, [C.c_void_p]),
     "ceg_mc_group_sampler_read": (C.c_int, [C.c_void_p, c_int64_p, C.c_void_p, c_int64_p]),

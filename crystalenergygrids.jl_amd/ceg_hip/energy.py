@@ -665,6 +665,21 @@ class Isotherm(NamedTuple):
     run: MonteCarloRun
 
 
+class ParallelTemperingRun(NamedTuple):
+    """What :meth:`DeviceMonteCarloGroup.run_parallel_tempering` returns; "by rung": entry ``[j, r]`` belongs to the chain that sat on
+    rung ``r`` during cycle ``j``"""
+    exchanges: np.ndarray             # [ninit + ncycles, K] _abi.MC_EXCHANGE_RECORD_DTYPE, per chain
+    cycles_by_rung: np.ndarray        # [ninit + ncycles, K] _abi.MC_CYCLE_RECORD_DTYPE, re-sorted by rung
+    exchanges_by_rung: np.ndarray     # [ninit + ncycles, K] the exchange records re-sorted by rung
+    chain_of_rung: np.ndarray         # [ninit + ncycles, K] the chain on rung r during cycle j
+    acceptance: np.ndarray            # [K - 1] accepted / attempted of the rung pair (r, r + 1) over the production cycles (NaN: never tried)
+    pair_counts: np.ndarray           # [K, 2] attempted, accepted of the production cycles (row K - 1 is zeros)
+    rungs: np.ndarray                 # [K] the rung of every chain at the end
+    recorded: np.ndarray              # [K] K, the device's energy of every chain at the end, held against the final baseline
+    baselines: tuple                  # baseline_energies() at the start, at the first production cycle, at the end
+    stats: tuple                      # (the init call's stats or None, the production call's or None)
+
+
 class DeviceMonteCarloGroup:
     """K :class:`DeviceMonteCarlo` chains on one device stepped in lockstep (``ceg_mc_group_*``): one launch evaluates the trials
     of every chain, one launch applies every accepted move -- the way ``make_isotherm`` (parameterinputs.jl:316-329) runs one
@@ -692,6 +707,7 @@ class DeviceMonteCarloGroup:
         self._blocks = None           # what set_blocks installed: (species blocks, atom blocks)
         self.sampler = None           # what set_sampler installed (its geometry and tables, for the host restatement)
         self.chain_plan = None        # what set_chain_plan installed: (phiPV_div_k [K, nspecies] or None, stop_step [K] or None)
+        self.tempering = None         # what set_tempering installed: (every, capacity)
 
     def __repr__(self):
         return f"DeviceMonteCarloGroup(k={len(self.chains)})"
@@ -1226,6 +1242,131 @@ class DeviceMonteCarloGroup:
                     raise MonteCarloDrift(f"chain {c}: energy deviation observed between actual ({actual!r}) and recorded ({rec!r}): "
                                           "the simulation results are wrong")
         return MonteCarloRun(initial_energies, energies, cycles, (stats_init, stats), (start, production, end), recorded)
+
+    def set_tempering(self, every: Optional[int], energies=None, rungs=None, capacity: int = 1024) -> None:
+        """``ceg_mc_group_set_tempering``: from now on :meth:`sweep_cycles` and :meth:`sweep_gcmc_cycles` exchange replicas between
+        neighbouring rungs of the temperature ladder at the end of every cycle ``cc`` with ``cc % every == 0`` (the rule of
+        ``run_parallel_tempering``, simulation.jl:533), on the device.  Temperatures, not configurations, are exchanged: the
+        ``temperature`` argument of those calls is then indexed by RUNG (non-decreasing), and the chain on rung ``r`` runs at entry ``r``.
+        ``energies``: the total energy of every chain now (K; default: the totals of :meth:`baseline_energies`); ``rungs``: the rung of
+        every chain, a permutation (default: chain ``c`` on rung ``c``); ``capacity``: the cycles of exchange records kept.
+        ``every=None`` removes the state.  Any other call that moves a chain (``sweep``, ``accept``, ``insert`` ...) makes the stored
+        energies stale: install the state again.  :func:`ceg_hip.mcrng.exchange_round` restates a cycle end."""
+        if every is None:
+            _abi.check(self._lib, self._lib.ceg_mc_group_set_tempering(self._h, None))
+            self.tempering = None
+            return
+        k = len(self.chains)
+        if energies is None:
+            energies = [float(r) for r in self.baseline_energies()]
+        E = np.ascontiguousarray(energies, dtype=np.float64)
+        if E.shape != (k,):
+            raise ValueError(f"energies: one per chain ({k})")
+        R = None
+        if rungs is not None:
+            R = np.ascontiguousarray(rungs, dtype=np.int32)
+            if R.shape != (k,):
+                raise ValueError(f"rungs: one per chain ({k})")
+        spec = _abi.McTempering(int(every), int(capacity), R.ctypes.data if R is not None else None, E.ctypes.data)
+        _abi.check(self._lib, self._lib.ceg_mc_group_set_tempering(self._h, C.addressof(spec)))
+        self.tempering = (int(every), int(capacity))
+
+    def tempering_read(self):
+        """``ceg_mc_group_tempering_read`` -> (rungs int32[K], energies float64[K] -- as of the end of the last ``*_cycles`` call --,
+        pair counts int64[K, 2]: attempted and accepted exchanges of the rung pair (r, r + 1), records
+        ``_abi.MC_EXCHANGE_RECORD_DTYPE`` [cycles, K] of every cycle since :meth:`set_tempering`)."""
+        if self.tempering is None:
+            raise RuntimeError("the group has no tempering state (set_tempering)")
+        k = len(self.chains)
+        rung, energy, pairs = np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.float64), np.zeros((k, 2), dtype=np.int64)
+        n = C.c_int64(0)
+        _abi.check(self._lib, self._lib.ceg_mc_group_tempering_read(self._h, None, None, None, None, C.byref(n)))
+        records = np.zeros((max(int(n.value), 0), k), dtype=_abi.MC_EXCHANGE_RECORD_DTYPE)
+        _abi.check(self._lib, self._lib.ceg_mc_group_tempering_read(self._h, _abi.i32ptr(rung), _abi.dptr(energy), _abi.i64ptr(pairs.reshape(-1)),
+                                                                    records.ctypes.data if records.size else None, C.byref(n)))
+        return rung, energy, pairs, records
+
+    def run_parallel_tempering(self, ladder, ncycles: int, ninit: int = 0, *, every: int = 1, seed: int = 0, steps_per_cycle: Optional[int] = None,
+                               gcmc=None, dmax=1.3, thetamax=math.radians(30.0), adapt=("dmax", "thetamax"), p_rotation=0.5, stream_id=None,
+                               bead=None, rungs=None, positions: bool = True, check_drift: bool = True) -> ParallelTemperingRun:
+        """The shape of ``run_parallel_tempering`` (simulation.jl:461-622) for the K chains, composed like :meth:`run_montecarlo`:
+        ``baseline_energy`` and :meth:`set_tempering`, the ``ninit`` cycles in one :meth:`sweep_cycles` call, ``baseline_energy`` again and
+        the state installed again with the precise energies (the rungs carried over), the ``ncycles`` production cycles in one call, and
+        for every chain the device's recorded energy against the final ``baseline_energy`` at the reference's rtol 1e-9 (:614),
+        raised as :class:`MonteCarloDrift` where it fails (``check_drift=False``: not checked).
+
+        ``ladder``: the temperatures BY RUNG, non-decreasing: one per rung, or a table ``[ninit + ncycles, K]``.  ``every``: an exchange
+        round after every cycle ``cc`` with ``cc % every == 0``.  ``rungs``: the rung of every chain at the start (default: chain ``c`` on
+        rung ``c``).  ``gcmc``: as in :meth:`run_montecarlo`, with displacement moves only (exchanges under swaps are refused).  Step
+        sizes and counters stay with the chain, not the rung.  Afterwards no tempering state is installed.
+
+        -> :class:`ParallelTemperingRun`: the exchange records per chain, the cycle and exchange records re-sorted by rung, the
+        acceptance ratio of every rung pair over the production cycles, the final rungs and energies."""
+        k = len(self.chains)
+        ninit, ncycles = int(ninit), int(ncycles)
+        if ninit < 0 or ncycles < 0:
+            raise ValueError("ninit and ncycles must be >= 0")
+        L = self.numsteps(None)[0] if steps_per_cycle is None else int(steps_per_cycle)
+        if steps_per_cycle is None and any(n != L for n in self.numsteps(None)):
+            raise ValueError("the chains' steps per cycle differ: chains whose cycle lengths differ belong in different groups")
+        if L < 1:
+            raise ValueError("empty simulation: no step per cycle (simulation.jl:718)")
+        T = np.asarray(ladder, dtype=np.float64)
+        if T.shape not in ((k,), (ninit + ncycles, k)):
+            raise ValueError(f"ladder: one temperature per rung ({k}) or a table [{ninit + ncycles}, {k}]")
+        dm = np.broadcast_to(np.asarray(dmax, dtype=np.float64), (k,)).copy()
+        th = np.broadcast_to(np.asarray(thetamax, dtype=np.float64), (k,)).copy()
+        prior = np.zeros((k, 4), dtype=np.int64)
+        done = [0]
+
+        def phase(n, last):
+            rows = T[done[0]:done[0] + n] if T.ndim == 2 else T
+            args = dict(temperature=rows, dmax=dm, thetamax=th, cycle0=1 + done[0], prior=prior, adapt=adapt, stream_id=stream_id, bead=bead)
+            if gcmc is None:
+                stats, cyc = self.sweep_cycles(n, L, seed, done[0] * L, p_rotation=p_rotation, **args)
+            else:
+                stats, cyc = self.sweep_gcmc_cycles(n, L, seed, done[0] * L, positions=positions and last, **dict(gcmc), **args)
+            self._raise_if_halted()
+            dm[:], th[:] = cyc[-1]["dmax_next"], cyc[-1]["thetamax_next"]
+            for q, name in enumerate(("translation_trials", "translation_accepted", "rotation_trials", "rotation_accepted")):
+                prior[:, q] = cyc[-1][name]
+            done[0] += n
+            return stats, cyc
+
+        start = self.baseline_energies()
+        production = end = start
+        stats_init = stats = None
+        cycles = [np.zeros((0, k), dtype=_abi.MC_CYCLE_RECORD_DTYPE)]
+        exchanges = [np.zeros((0, k), dtype=_abi.MC_EXCHANGE_RECORD_DTYPE)]
+        rung = np.arange(k, dtype=np.int32) if rungs is None else np.ascontiguousarray(rungs, dtype=np.int32)
+        recorded = np.array([float(r) for r in start])
+        pairs = np.zeros((k, 2), dtype=np.int64)
+        try:
+            if ninit > 0:
+                self.set_tempering(every, recorded, rung, capacity=ninit)
+                stats_init, cyc = phase(ninit, ncycles == 0)
+                rung, recorded, pairs, rec = self.tempering_read()
+                cycles.append(cyc); exchanges.append(rec)
+                production = end = self.baseline_energies()
+            if ncycles > 0:
+                self.set_tempering(every, [float(r) for r in production], rung, capacity=ncycles)
+                stats, cyc = phase(ncycles, True)
+                rung, recorded, pairs, rec = self.tempering_read()
+                cycles.append(cyc); exchanges.append(rec)
+                end = self.baseline_energies()
+        finally:
+            if self.tempering is not None:
+                self.set_tempering(None)
+        for c, (rec, actual) in enumerate(zip(recorded, (float(r) for r in end)) if check_drift and ninit + ncycles > 0 else ()):
+            if not abs(rec - actual) <= 1e-9 * max(abs(rec), abs(actual)):
+                raise MonteCarloDrift(f"chain {c}: energy deviation observed between actual ({actual!r}) and recorded ({rec!r}): "
+                                      "the simulation results are wrong")
+        cycles, exchanges = np.concatenate(cycles), np.concatenate(exchanges)
+        chain_of_rung = np.argsort(exchanges["rung"], axis=1).astype(np.int32)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            acceptance = pairs[:-1, 1] / pairs[:-1, 0]
+        return ParallelTemperingRun(exchanges, np.take_along_axis(cycles, chain_of_rung, axis=1), np.take_along_axis(exchanges, chain_of_rung, axis=1),
+                                    chain_of_rung, acceptance, pairs, rung, recorded, (start, production, end), (stats_init, stats))
 
     def make_isotherm(self, phiPV_div_k, ncycles, ninit: int = 0, *, temperature, max_molecules, moves=None, species=None, self_reciprocal=None,
                       seed: int = 0, steps_per_cycle: Optional[int] = None, supercell=(1, 1, 1), dmax=1.3, thetamax=math.radians(30.0),

@@ -28,6 +28,10 @@ Cycles (``ceg_mc_group_sweep_cycles`` / ``ceg_mc_group_sweep_gcmc_cycles``): :fu
 :func:`cycle_records` restate the end-of-cycle adaptation of ``statistics.dmax`` / ``θmax`` (simulation.jl:818-827) in the operation
 order of ``k_mcg_cycle_end``, ``thetamax`` in radians.
 
+Tempering (``ceg_mc_group_set_tempering``): purpose 9 is the draw of a replica exchange, ``u = U(w0, w1)`` at the cycle's absolute last
+step on the stream of the pair's chain on the lower rung; :func:`exchange_pairs`, :func:`exchange_threshold` and :func:`exchange_round`
+restate ``k_mcg_exchange`` (the rule of ``run_parallel_tempering``, simulation.jl:533).
+
 Isotherms (``ceg_mc_group_set_chain_plan``, ``DeviceMonteCarloGroup.make_isotherm``): :func:`isotherm_ncycles`, :func:`accessible_volume`,
 :func:`phiPV_div_k` and :meth:`MoveTable.for_gcmc` restate the host arithmetic of ``make_isotherm`` / ``run_gcmc`` / ``GCMCData``
 (parameterinputs.jl:274-279,319, gcmc.jl:26-37, simulation.jl:714-715); the fugacity coefficient stays with the caller.
@@ -648,6 +652,81 @@ def cycle_records(temperatures, dmax: float, thetamax: float, counters, nmol, de
                   0.0 if delta_swaps is None else float(delta_swaps[j]), tt, ta, rt, ra, int(nmol[j]), 0)
         d, t = dn, tn
     return out
+
+
+# ------------------------------------------------------------------ tempering (ceg_mc_group_set_tempering)
+# The exchange round of ``k_mcg_exchange`` (csrc/ceg_mc_temper.hip) in its operation order: what the device is held to.
+EXCHANGE = 9              # the purpose of the exchange draw, on the stream of the pair's chain on the lower rung
+
+
+def exchange_pairs(k: int, cc: int, every: int) -> list:
+    """The rung pairs ``(r, r + 1)`` of the round at the end of cycle ``cc`` (the reference's ``counter_cycle``) of ``k`` chains: none
+    unless ``cc % every == 0``; else ``r = parity, parity + 2, ...`` with ``r + 1 < k`` and ``parity = (cc // every) & 1``."""
+    if every < 1:
+        raise ValueError("every >= 1")
+    if int(cc) % int(every) != 0:
+        return []
+    parity = (int(cc) // int(every)) & 1
+    return [(r, r + 1) for r in range(parity, int(k) - 1, 2)]
+
+
+def exchange_threshold(E_a: float, E_b: float, T_a: float, T_b: float) -> float:
+    """``e`` of the rule for the chain ``a`` on the lower and ``b`` on the upper rung (simulation.jl:533), every operation rounded to
+    FP64 in this order: ``ia = 1 / T_a; ib = 1 / T_b; d = ia - ib; Tp = 1 / d; x = (E_a - E_b) / Tp; e = exp(x)``.  Equal temperatures
+    give ``Tp = inf`` and ``e = 1``; NaN energies give NaN."""
+    with np.errstate(all="ignore"):
+        ia = np.float64(1.0) / np.float64(T_a)
+        ib = np.float64(1.0) / np.float64(T_b)
+        d = ia - ib
+        Tp = np.float64(1.0) / d
+        x = float((np.float64(E_a) - np.float64(E_b)) / Tp)
+    try:
+        return math.exp(x)
+    except OverflowError:
+        return math.inf
+
+
+def exchange_rule(E_a: float, E_b: float, u: float, threshold: float) -> bool:
+    """``E_b < E_a || u < e``: NaN energies reject"""
+    return bool(E_b < E_a or u < threshold)
+
+
+def exchange_round(rung, energy, temperatures_by_rung, stopped, seed: int, step: int, stream_id, cc: int, every: int,
+                   next_temperatures_by_rung=None):
+    """One cycle end of ``k_mcg_exchange`` for K chains: ``rung[c]`` the rung of chain ``c`` during the ended cycle, ``energy[c]`` its
+    energy at the end, ``temperatures_by_rung[r]`` the temperature in force on rung ``r`` during the ended cycle, ``stopped[c]`` whether
+    the chain is stopped at ``step``, the cycle's absolute last step; ``cc`` the cycle's counter.  ``next_temperatures_by_rung``: the next
+    cycle's (default: the same).  A pair is attempted if the round is due and neither chain is stopped; the draw is
+    ``U(w0, w1)`` of ``draw(seed, step, stream_id[a], EXCHANGE)``.
+    -> (the rungs of the next cycle int32[K], records ``_abi.MC_EXCHANGE_RECORD_DTYPE`` [K])"""
+    from ._abi import MC_EXCHANGE_RECORD_DTYPE
+    k = len(rung)
+    rung = [int(r) for r in rung]
+    if sorted(rung) != list(range(k)):
+        raise ValueError("rung: a permutation of 0..K-1")
+    T = [float(t) for t in temperatures_by_rung]
+    Tn = T if next_temperatures_by_rung is None else [float(t) for t in next_temperatures_by_rung]
+    chain = [0] * k
+    for c, r in enumerate(rung):
+        chain[r] = c
+    new = list(rung)
+    rec = np.zeros(k, dtype=MC_EXCHANGE_RECORD_DTYPE)
+    rec["rung"], rec["partner"], rec["accepted"], rec["energy"] = rung, -1, -1, [float(e) for e in energy]
+    for r, _ in exchange_pairs(k, cc, every):
+        a, b = chain[r], chain[r + 1]
+        if stopped[a] or stopped[b]:
+            continue
+        w = draw(seed, step, int(stream_id[a]), EXCHANGE)
+        u = uniform(w[0], w[1])
+        e = exchange_threshold(float(energy[a]), float(energy[b]), T[r], T[r + 1])
+        acc = exchange_rule(float(energy[a]), float(energy[b]), u, e)
+        for me, other in ((a, b), (b, a)):
+            rec[me]["partner"], rec[me]["accepted"], rec[me]["u"], rec[me]["threshold"] = other, int(acc), u, e
+        if acc:
+            new[a], new[b] = r + 1, r
+    rec["rung_next"] = new
+    rec["temperature_next"] = [Tn[r] for r in new]
+    return np.array(new, dtype=np.int32), rec
 
 
 # ------------------------------------------------------------------ isotherms (ceg_mc_group_set_chain_plan)

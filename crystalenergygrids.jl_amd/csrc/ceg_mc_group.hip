@@ -6,6 +6,7 @@
 //   ceg_mc_group_sweep_cycles      either sweep over whole cycles: the same body (sweep_plain / sweep_gcmc) with a ceg_mc_cycles_t, one
 //   ceg_mc_group_sweep_gcmc_cycles   launch of ceg_mc_cycles.hip behind the last step of every cycle (temperature table, dmax / thetamax)
 //   ceg_mc_group_set_chain_plan      per chain: the phiPV_div_k of the swap rules and the absolute step at which the chain stops (isotherms)
+//   ceg_mc_group_set_tempering       (ceg_mc_temper.hip) the *_cycles sweeps enqueue one exchange launch behind every cycle end
 // The two sweeps have their own kernels, per-chain parameters and read-back, and share one host driver (run_sweep).
 #include "ceg_mc_gcmc.h"
 
@@ -355,6 +356,7 @@ struct ceg_mc_group {
     unsigned char* d_baseline = nullptr;         // partial sums and results of ceg_mc_group_baseline (ceg_mc_baseline.hip); only grows
     size_t baseline_cap = 0;
     GroupSampler* sampler = nullptr;             // density maps and series taken during sweeps (ceg_mc_sample.hip); nullptr: none
+    GroupTempering* tempering = nullptr;         // rungs, energies and exchange records of the *_cycles sweeps (ceg_mc_temper.hip); nullptr: none
     // chain plan (ceg_mc_group_set_chain_plan): the host's copy for the checks and the launch lists, the device's for the kernels
     std::vector<double> plan_phi;                // [K][plan_species], empty: the species table's value for every chain
     std::vector<int64_t> plan_stop;              // [K], empty: no chain stops
@@ -363,6 +365,7 @@ struct ceg_mc_group {
     int64_t* d_plan_stop = nullptr;
     // device cells (ceg_mc_group_set_device_cells): ceg_mc_group_sweep / _cycles take the chains with neighbour cells
     bool device_cells = false;
+    bool sweep_enqueued = false;                 // the last run_sweep got as far as its steps (a failure before that has launched and changed nothing)
     std::vector<int64_t> halted;                 // [K] of the last sweep call: the step at which a full cell halted the chain, -1: none
 };
 
@@ -385,6 +388,7 @@ void group_free(ceg_mc_group* g)
     if (g->stream) { (void)hipStreamSynchronize(g->stream); (void)hipStreamDestroy(g->stream); }
     group_free_blocks(g);
     sampler_free(g->sampler);
+    temper_free(g->tempering);
     if (g->d_views) (void)hipFree(g->d_views);
     if (g->d_done) (void)hipFree(g->d_done);
     if (g->d_scratch) (void)hipFree(g->d_scratch);
@@ -432,7 +436,7 @@ int ceg_mcs::group_refuse_poisoned(int c)
 
 ceg_mcs::GroupRef ceg_mcs::group_ref(ceg_mc_group* g)
 {
-    return GroupRef{g->device, g->stream, g->chains.data(), (int)g->chains.size(), g->d_views, &g->d_baseline, &g->baseline_cap, &g->sampler};
+    return GroupRef{g->device, g->stream, g->chains.data(), (int)g->chains.size(), g->d_views, &g->d_baseline, &g->baseline_cap, &g->sampler, &g->tempering};
 }
 
 bool ceg_mcs::group_views_current(ceg_mc_group* g) { return group_upload_views(g, std::vector<char>(g->chains.size(), 1)); }
@@ -887,6 +891,7 @@ int run_sweep(ceg_mc_group* g, const SweepPlan& plan, const SweepLayout& lay, st
               int64_t nsteps, Record* log_out, Trial&& trial, Accept&& accept, Frame&& frame, int64_t cycle_len, CycleEnd&& cycle_end)
 {
     const size_t k = g->chains.size();
+    g->sweep_enqueued = false;
     size_t lds_trial[SWEEP_CLASSES];
     int table_ok[SWEEP_CLASSES];
     for (int cl = 0; cl < SWEEP_CLASSES; ++cl) {                     // the pair table in LDS only where the largest tables leave room (run_trial's rule)
@@ -921,6 +926,7 @@ int run_sweep(ceg_mc_group* g, const SweepPlan& plan, const SweepLayout& lay, st
     if (hipMemcpy(g->d_scratch, stage.data(), lay.total, hipMemcpyHostToDevice) != hipSuccess) return fail("H2D failed");
     if (!group_upload_views(g, std::vector<char>(k, 1))) return fail("view upload failed");
     if (d_log && hipMemsetAsync(d_log, 0, log_bytes, g->stream) != hipSuccess) return fail("hipMemsetAsync failed");
+    g->sweep_enqueued = true;
     // ---- the steps: nothing between them but the stream's own order (no chain with a molecule and no log: nothing to do)
     const int32_t* d_list = sweep_at<const int32_t>(g, lay.list);
     unsigned first[SWEEP_CLASSES], live[SWEEP_CLASSES], listed = 0;       // live: chains of a class that have not stopped (the steps only go up)
@@ -972,6 +978,18 @@ struct SweepCycles {
     const double* first_row(const double* temperature) const { return table() ? (cy->ncycles > 0 ? cy->temperatures : nullptr) : temperature; }
     // the three segments of the group's block the cycle ends use, behind the statistics (read back with them); none without cycles
     size_t o_rec = 0, o_table = 0, o_prior = 0;
+    // tempering (ceg_mc_temper.hip), only for a call through a *_cycles entry point: the state, and without a table the segment of
+    // the ladder (params->temperature, [K] by rung) that the exchange launch reads the next cycle's temperatures from
+    GroupTempering* temper = nullptr;
+    size_t o_ladder = 0;
+    void ladder_layout(SweepLayout& lay, size_t k) { o_ladder = lay.segment(temper && !table() ? sizeof(double) * k : 0); }
+    // the chain's first temperature: the caller's values are indexed by rung while a tempering state is installed
+    double first_temperature(const double* temperature, int c) const { return !temperature ? 0.0 : temperature[temper ? temper_rungs(temper)[c] : c]; }
+    // [K] by rung in device memory: what cycle j + 1 runs at (the call's last cycle: what it ran at)
+    const double* next_row(const ceg_mc_group* g, int64_t j, size_t k) const
+    {
+        return table() ? sweep_at<const double>(g, o_table) + (size_t)std::min(j + 1, cy->ncycles - 1) * k : sweep_at<const double>(g, o_ladder);
+    }
     void layout(SweepLayout& lay, size_t k)
     {
         if (!cycled) return;
@@ -979,9 +997,10 @@ struct SweepCycles {
         o_table = lay.segment(table() ? sizeof(double) * (size_t)cy->ncycles * k : 0);
         o_prior = lay.segment(sizeof(int64_t) * 4 * k);
     }
-    void fill(std::vector<unsigned char>& stage, size_t k) const
+    void fill(std::vector<unsigned char>& stage, size_t k, const double* ladder) const
     {
         if (!cycled) return;
+        if (temper && !table()) memcpy(stage.data() + o_ladder, ladder, sizeof(double) * k);
         if (table()) memcpy(stage.data() + o_table, cy->temperatures, sizeof(double) * (size_t)cy->ncycles * k);
         if (cy->prior) memcpy(stage.data() + o_prior, cy->prior, sizeof(int64_t) * 4 * k);
     }
@@ -1090,6 +1109,7 @@ int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nstep
     const int k = (int)g->chains.size();
     if (C.cycled)
         if (int rc = cycles_check(C.cy, k, p->first_step, false, C.out, &nsteps)) return rc;
+    C.temper = C.cycled ? g->tempering : nullptr;        // (the plain sweep ignores a tempering state)
     const double* temperature = C.first_row(p->temperature);
     // ---- every refusal before anything is launched or changed, chain by chain
     std::vector<McSweepChain> pc((size_t)k);
@@ -1105,7 +1125,7 @@ int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nstep
         P.stream_id = p->stream_id[c];
         P.bead_off = (int32_t)beads.size();
         P.stride = h->stride;
-        P.temperature = temperature ? temperature[c] : 0.0; P.dmax = p->dmax[c]; P.thetamax = p->thetamax[c]; P.p_rotation = p->p_rotation[c];
+        P.temperature = C.first_temperature(temperature, c); P.dmax = p->dmax[c]; P.thetamax = p->thetamax[c]; P.p_rotation = p->p_rotation[c];
         if (h->v.nmol > 0 && !p->bead) return merr(CEG_ERR_INVALID, "bad argument");
         int mmax = 0;
         for (int j = 0; j < h->v.nmol; ++j) {
@@ -1117,6 +1137,8 @@ int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nstep
         if (h->v.nmol == 0) continue;                    // (an empty chain is in no launch list: its steps are idle)
         if (int rc = plan.add(c, h, mmax)) return rc;
     }
+    if (C.temper)
+        if (int rc = temper_admit(C.temper, C.cy, p->temperature, k, false)) return rc;
     if (g->sampler)
         if (int rc = sampler_admit(g->sampler, p->first_step, nsteps)) return rc;
     for (int c = 0; c < k; ++c) stats_out[c] = ceg_mc_sweep_stats_t{};
@@ -1127,13 +1149,14 @@ int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nstep
     bool with_cells = false;
     for (const ceg_mc* h : g->chains) with_cells = with_cells || h->v.use_cells;
     SweepLayout lay((size_t)k, sizeof(McSweepChain));
-    const size_t o_bead = lay.segment(sizeof(int32_t) * beads.size()), o_book = lay.segment(with_cells ? sizeof(McCellBook) * (size_t)k : 0),
-                 o_stats = lay.segment(sizeof(ceg_mc_sweep_stats_t) * (size_t)k);
+    const size_t o_bead = lay.segment(sizeof(int32_t) * beads.size()), o_book = lay.segment(with_cells ? sizeof(McCellBook) * (size_t)k : 0);
+    C.ladder_layout(lay, (size_t)k);
+    const size_t o_stats = lay.segment(sizeof(ceg_mc_sweep_stats_t) * (size_t)k);
     C.layout(lay, (size_t)k);
     const size_t o_stop = lay.segment(with_cells ? sizeof(int64_t) * (size_t)k : 0), o_halt = lay.segment(with_cells ? sizeof(int64_t) * (size_t)k : 0),
                  o_flags = lay.segment(with_cells ? sizeof(int32_t) * 2 * (size_t)k : 0);
     std::vector<unsigned char> stage(lay.total, 0);
-    C.fill(stage, (size_t)k);
+    C.fill(stage, (size_t)k, p->temperature);
     memcpy(stage.data() + lay.par, pc.data(), sizeof(McSweepChain) * (size_t)k);
     if (!beads.empty()) memcpy(stage.data() + o_bead, beads.data(), sizeof(int32_t) * beads.size());
     if (with_cells) {
@@ -1173,7 +1196,7 @@ int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nstep
     auto stop_of = [&]() -> const int64_t* { return with_cells ? sweep_at<const int64_t>(g, o_stop) : g->d_plan_stop; };
     auto frame = [&](uint64_t step) {                     // (the molecule table does not change: counts from the views)
         const SampleSource src{nullptr, 0, 0, &sweep_at<const ceg_mc_sweep_stats_t>(g, o_stats)->delta, nullptr, (int32_t)sizeof(ceg_mc_sweep_stats_t), max_slots,
-                               stop_of()};
+                               stop_of(), C.temper ? temper_device_rungs(C.temper) : nullptr};
         sampler_enqueue(g->sampler, g->stream, g->d_views, k, (int64_t)step, src);
     };
     auto cycle_end = [&](int64_t j) {                     // (the molecule table does not change: counts from the views)
@@ -1182,9 +1205,15 @@ int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nstep
                               &sweep_at<McSweepChain>(g, lay.par)->temperature, (int32_t)sizeof(ceg_mc_sweep_stats_t), 0, (int32_t)sizeof(McSweepChain), 0,
                               stop_of(), C.last_step(p->first_step, j)};
         cycles_enqueue(g->stream, g->d_views, k, C.run(g), j, src);
+        if (C.temper)
+            temper_enqueue(C.temper, g->stream, k, C.run(g), j, src,
+                           TemperSource{&sweep_at<const McSweepChain>(g, lay.par)->stream_id, (int32_t)sizeof(McSweepChain), 0, p->seed, C.next_row(g, j, (size_t)k)});
     };
-    if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame, C.cycled ? C.cy->steps_per_cycle : 0, cycle_end))
+    if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame, C.cycled ? C.cy->steps_per_cycle : 0, cycle_end)) {
+        if (C.temper && g->sweep_enqueued) temper_fail(C.temper);       // (a failure before the steps has changed nothing: the state stays)
         return rc;
+    }
+    if (C.temper && !temper_commit(C.temper, C.cy->ncycles)) return merr(CEG_ERR_HIP, "D2H of the rungs failed: the tempering state is stale");
     memcpy(stats_out, stage.data() + o_stats, sizeof(ceg_mc_sweep_stats_t) * (size_t)k);
     C.read_back(stage, (size_t)k);
     if (with_cells) {
@@ -1264,6 +1293,7 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
     }
     if (C.cycled)                                        // (a varying temperature only where no species swaps, simulation.jl:688)
         if (int rc = cycles_check(C.cy, k, p->first_step, swap_atoms > 0, C.out, &nsteps)) return rc;
+    C.temper = C.cycled ? g->tempering : nullptr;        // (the plain sweep ignores a tempering state)
     const double* temperature = C.first_row(p->temperature);
     if (g->d_blocks) {                                   // block pockets: the masks must be those of this species table
         if (ns != g->blk_species) return merr(CEG_ERR_INVALID, "nspecies differs from the nspecies of ceg_mc_group_set_blocks");
@@ -1306,7 +1336,7 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
         P.stream_id = p->stream_id[c];
         P.stride = h->stride;
         P.max_molecules = maxmol;
-        P.temperature = temperature ? temperature[c] : 0.0; P.dmax = p->dmax[c]; P.thetamax = p->thetamax[c];
+        P.temperature = C.first_temperature(temperature, c); P.dmax = p->dmax[c]; P.thetamax = p->thetamax[c];
         // freed runs of the host mirror: the runs of m atoms go to the first species with m atoms
         int most = 0;
         for (int i = 0; i < ns; ++i) {
@@ -1333,6 +1363,8 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
         stats_out[c].nmol = D.nmol;
         if (p->molecule_species_out && D.nmol > 0) memcpy(p->molecule_species_out + out_off[(size_t)c], ms, sizeof(int32_t) * (size_t)D.nmol);
     };
+    if (C.temper)
+        if (int rc = temper_admit(C.temper, C.cy, p->temperature, k, swap_atoms > 0)) return rc;
     if (g->sampler)
         if (int rc = sampler_admit(g->sampler, p->first_step, nsteps)) return rc;
     for (int c = 0; c < k; ++c) stats_out[c] = ceg_mc_gcmc_stats_t{};
@@ -1355,8 +1387,9 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
     // ---- added to the common segments: [ns] species | [K] resolved attempts | [K] statistics | [K] tables | species of the molecules |
     //      stacks of freed slots | [2K] pocket counters (from the statistics on: read back after the sweep)
     SweepLayout lay((size_t)k, sizeof(McGcmcChain));
-    const size_t o_spec = lay.segment(sizeof(ceg_mc_gcmc_species_t) * (size_t)ns), o_res = lay.segment(sizeof(int32_t) * (size_t)k),
-                 o_stats = lay.segment(sizeof(ceg_mc_gcmc_stats_t) * (size_t)k), o_tab = lay.segment(sizeof(McGcmcTable) * (size_t)k),
+    const size_t o_spec = lay.segment(sizeof(ceg_mc_gcmc_species_t) * (size_t)ns), o_res = lay.segment(sizeof(int32_t) * (size_t)k);
+    C.ladder_layout(lay, (size_t)k);
+    const size_t o_stats = lay.segment(sizeof(ceg_mc_gcmc_stats_t) * (size_t)k), o_tab = lay.segment(sizeof(McGcmcTable) * (size_t)k),
                  o_ms = lay.segment(sizeof(int32_t) * nspec_total), o_free = lay.segment(sizeof(int32_t) * nfree_total),
                  o_pock = lay.segment(sizeof(int64_t) * 2 * (size_t)k);
     C.layout(lay, (size_t)k);
@@ -1368,7 +1401,7 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
     const ceg_mc_block_t* blocks = g->d_blocks;          // NULL: no masks, the kernels take the path without the resolve stage
     const int block_kinds = g->blk_kinds;
     std::vector<unsigned char> stage(lay.total, 0);
-    C.fill(stage, (size_t)k);
+    C.fill(stage, (size_t)k, p->temperature);
     memcpy(stage.data() + lay.par, pc.data(), sizeof(McGcmcChain) * (size_t)k);
     memcpy(stage.data() + o_spec, p->species, sizeof(ceg_mc_gcmc_species_t) * (size_t)ns);
     memcpy(stage.data() + o_tab, tab.data(), sizeof(McGcmcTable) * (size_t)k);
@@ -1427,7 +1460,7 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
     auto frame = [&](uint64_t step) {                     // (counts from the device's table: the views' nmol / natoms are stale during the sweep)
         const ceg_mc_gcmc_stats_t* st = sweep_at<const ceg_mc_gcmc_stats_t>(g, o_stats);
         const SampleSource src{&sweep_at<const McGcmcTable>(g, o_tab)->nmol, (int32_t)(sizeof(McGcmcTable) / 4), ns, &st->delta_moves, &st->delta_swaps,
-                               (int32_t)sizeof(ceg_mc_gcmc_stats_t), max_slots, stop_of()};
+                               (int32_t)sizeof(ceg_mc_gcmc_stats_t), max_slots, stop_of(), C.temper ? temper_device_rungs(C.temper) : nullptr};
         sampler_enqueue(g->sampler, g->stream, g->d_views, k, (int64_t)step, src);
     };
     auto cycle_end = [&](int64_t j) {                     // (the molecule count from the device's table, as the frames)
@@ -1437,9 +1470,15 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
                               (int32_t)sizeof(ceg_mc_gcmc_stats_t), (int32_t)sizeof(McGcmcTable), (int32_t)sizeof(McGcmcChain), 0,
                               stop_of(), C.last_step(p->first_step, j)};
         cycles_enqueue(g->stream, g->d_views, k, C.run(g), j, src);
+        if (C.temper)
+            temper_enqueue(C.temper, g->stream, k, C.run(g), j, src,
+                           TemperSource{&sweep_at<const McGcmcChain>(g, lay.par)->stream_id, (int32_t)sizeof(McGcmcChain), 0, p->seed, C.next_row(g, j, (size_t)k)});
     };
-    if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame, C.cycled ? C.cy->steps_per_cycle : 0, cycle_end))
+    if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame, C.cycled ? C.cy->steps_per_cycle : 0, cycle_end)) {
+        if (C.temper && g->sweep_enqueued) temper_fail(C.temper);       // (a failure before the steps has changed nothing: the state stays)
         return rc;
+    }
+    if (C.temper && !temper_commit(C.temper, C.cy->ncycles)) return merr(CEG_ERR_HIP, "D2H of the rungs failed: the tempering state is stale");
     C.read_back(stage, (size_t)k);
     memcpy(g->pockets.data(), stage.data() + o_pock, sizeof(int64_t) * 2 * (size_t)k);
     // ---- the host mirrors from the device: molecule table, kinds, freed runs, counts and high-water mark of every chain that swapped

@@ -63,7 +63,9 @@ __global__ __launch_bounds__(MC_THREADS) void k_mcg_sample(const McView* __restr
         occupied = mol >= 0;
         // (a chain that had stopped by the frame's step -- ceg_mc_group_set_chain_plan -- is counted into its record and not binned)
         const bool frozen = src.stop && step >= src.stop[c];
-        const int map = (M.bins && !frozen) ? M.chain_map[c] : -1;
+        // (tempering: the map of the rung the chain holds, so that a map belongs to a temperature; a permutation of the chains)
+        const int of = src.rung ? src.rung[c] : c;
+        const int map = (M.bins && !frozen && (unsigned)of < gridDim.x) ? M.chain_map[of] : -1;
         const int channel = (M.bins && kind >= 0 && kind < M.nkinds) ? M.kind_channel[kind] : -1;
         if (occupied && map >= 0 && channel >= 0) {
 #pragma clang fp contract(off)
@@ -237,7 +239,8 @@ extern "C" int ceg_mc_group_sample(ceg_mc_group_t* g)
     Guard guard(r.device);
     if (!guard.ok) return merr(CEG_ERR_HIP, "hipSetDevice failed");
     if (!group_views_current(g)) return merr(CEG_ERR_HIP, "view upload failed");
-    sampler_enqueue(s, r.stream, r.d_views, r.k, -1, SampleSource{nullptr, 0, 0, nullptr, nullptr, 0, max_slots, nullptr});
+    sampler_enqueue(s, r.stream, r.d_views, r.k, -1, SampleSource{nullptr, 0, 0, nullptr, nullptr, 0, max_slots, nullptr,
+                                                                    *r.tempering ? temper_device_rungs(*r.tempering) : nullptr});
     if (hipGetLastError() != hipSuccess) return merr(CEG_ERR_HIP, "sample kernel launch failed");
     return CEG_OK;                       // asynchronous: ordered on the group's stream
 }

@@ -806,6 +806,7 @@ struct SampleSource {
     int32_t stats_stride;
     int32_t max_slots;                           // no chain's high-water mark exceeds this while the frame runs
     const int64_t* stop;
+    const int32_t* rung;                         // [K] tempering: chain c is binned into the map of rung[c]; nullptr: of c
 };
 void sampler_free(GroupSampler* s);
 int sampler_admit(const GroupSampler* s, uint64_t first_step, int64_t nsteps);      // CEG_ERR_INVALID: the sweep's frames do not fit
@@ -841,6 +842,27 @@ struct CycleRun {
 int cycles_check(const ceg_mc_cycles_t* cy, int k, uint64_t first_step, bool constant_columns, const void* cycles_out, int64_t* nsteps);
 void cycles_enqueue(hipStream_t stream, const McView* d_views, int k, const CycleRun& run, int64_t j, const CycleSource& src);
 
+// defined in ceg_mc_temper.hip: the tempering state of a group (ceg_mc_group_set_tempering) and the exchange launch (k_mcg_exchange)
+// that the *_cycles sweeps enqueue behind cycles_enqueue.  The group owns the state and frees it.
+struct GroupTempering;
+// what the exchange launch needs beside the cycle end's own arguments: the chains' stream ids (stream_id + c * param_stride bytes),
+// the seed of the call, and the [K] temperatures by rung of the NEXT cycle in device memory (the call's last cycle: of the ended one)
+struct TemperSource {
+    const uint32_t* stream_id;
+    int32_t param_stride, _pad;
+    uint64_t seed;
+    const double* next_row;
+};
+void temper_free(GroupTempering* t);
+// CEG_ERR_INVALID where a *_cycles call cannot run with the state: stale, too few record slots left, a row (of the table, else the
+// ladder) that decreases, swaps.  ladder: params->temperature, [K] by rung (read where the cycles have no table)
+int temper_admit(const GroupTempering* t, const ceg_mc_cycles_t* cy, const double* ladder, int k, bool swaps);
+const int32_t* temper_rungs(const GroupTempering* t);                // [K] the host's copy
+const int32_t* temper_device_rungs(const GroupTempering* t);         // [K] device memory
+void temper_enqueue(GroupTempering* t, hipStream_t stream, int k, const CycleRun& run, int64_t j, const CycleSource& src, const TemperSource& ts);
+bool temper_commit(GroupTempering* t, int64_t ncycles);              // a call has ended well (stream idle): its records count, the host's rungs follow
+void temper_fail(GroupTempering* t);                                 // a call failed once enqueued: the state is stale
+
 // defined in ceg_mc_group.hip: what ceg_mc_baseline.hip and ceg_mc_sample.hip need of a group
 struct GroupRef {
     int device;
@@ -851,6 +873,7 @@ struct GroupRef {
     unsigned char** d_baseline;                  // the group's counterpart of ceg_mc::d_baseline / baseline_cap
     size_t* baseline_cap;
     GroupSampler** sampler;                      // nullptr behind it: no sampler installed
+    GroupTempering** tempering;                  // nullptr behind it: no tempering installed
 };
 GroupRef group_ref(ceg_mc_group* g);
 bool group_views_current(ceg_mc_group* g);       // every member's view into d_views where it changed since its last upload

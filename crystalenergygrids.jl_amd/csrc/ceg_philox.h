@@ -52,6 +52,8 @@ enum : uint32_t { GCMC_SELECT = 4, GCMC_MOLECULE = 5, GCMC_RANDOM_A = 6, GCMC_RA
 // attempt 0 is the plain purpose
 constexpr uint32_t GCMC_ATTEMPTS = 1000;
 CEG_PHILOX_HD uint32_t attempt_purpose(uint32_t purpose, uint32_t attempt) { return purpose | (attempt << 8); }
+// ceg_mc_group_set_tempering: the draw of a replica exchange, on the stream of the pair's chain on the lower rung
+enum : uint32_t { EXCHANGE = 9 };
 
 }  // namespace ceg_philox
 

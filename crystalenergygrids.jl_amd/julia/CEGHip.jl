@@ -926,6 +926,64 @@ function mc_group_halted(g::Ptr{Cvoid}, k::Integer)
     halted
 end
 
+# `ceg_mc_tempering_t` (32 bytes) and `ceg_mc_exchange_record_t` (48 bytes) of include/ceg_hip.h
+struct McTempering
+    every::Int64
+    record_capacity::Int64
+    rung::Ptr{Int32}                 # [K] 0-based, a permutation; C_NULL: chain c on rung c
+    energy::Ptr{Float64}             # [K] in K
+end
+
+struct McExchangeRecord
+    rung::Int32                      # 0-based, during the ended cycle
+    rung_next::Int32
+    partner::Int32                   # 0-based chain, -1: none
+    accepted::Int32                  # 1, 0, or -1: no attempt
+    energy::Float64
+    temperature_next::Float64
+    u::Float64
+    threshold::Float64
+end
+
+"""
+`ceg_mc_group_set_tempering`: replica exchange between the chains on neighbouring rungs of the temperature ladder at the end of every
+cycle `cc` with `cc % every == 0` of `mc_group_sweep_cycles!` / `mc_group_sweep_gcmc_cycles!` (`run_parallel_tempering`,
+src/simulation.jl:461-622; the rule of :533).  Temperatures are exchanged, not configurations: the temperatures of those calls are then
+indexed by rung.  `energy`: the total energy of every chain now (unitful or in K); `rung`: 0-based, `nothing` for the identity;
+`energy === nothing` removes the state.  UNVERIFIED: never executed.
+"""
+function mc_group_set_tempering!(g::Ptr{Cvoid}, energy::Union{Nothing,AbstractVector}; every::Integer=1, capacity::Integer=1024,
+                                 rung::Union{Nothing,AbstractVector{<:Integer}}=nothing)
+    if energy === nothing
+        _check(ccall((:ceg_mc_group_set_tempering, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), g, C_NULL))
+        return nothing
+    end
+    e = Float64[x isa Real ? x : ustrip(u"K", x) for x in energy]
+    r = rung === nothing ? Int32[] : Vector{Int32}(rung)
+    GC.@preserve e r begin
+        spec = Ref(McTempering(Int64(every), Int64(capacity), rung === nothing ? Ptr{Int32}(C_NULL) : pointer(r), pointer(e)))
+        _check(ccall((:ceg_mc_group_set_tempering, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), g, spec))
+    end
+    nothing
+end
+
+"""
+`ceg_mc_group_tempering_read` for a group of `k` chains -> (rungs (0-based), energies (K), pair counts `2 x k`: attempted and accepted of
+the rung pair (r, r + 1) in column r, records `k x cycles`).  UNVERIFIED: never executed.
+"""
+function mc_group_tempering_read(g::Ptr{Cvoid}, k::Integer)
+    n = Ref{Int64}(0)
+    _check(ccall((:ceg_mc_group_tempering_read, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}),
+                 g, C_NULL, C_NULL, C_NULL, C_NULL, n))
+    rung = zeros(Int32, k)
+    energy = zeros(Float64, k)
+    pairs = zeros(Int64, 2, k)
+    records = Matrix{McExchangeRecord}(undef, k, n[])
+    _check(ccall((:ceg_mc_group_tempering_read, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}),
+                 g, rung, energy, pairs, records, n))
+    rung, energy, pairs, records
+end
+
 # `ceg_mc_sampler_t` (152 bytes) and `ceg_mc_sample_record_t` (64 bytes) of include/ceg_hip.h
 struct McSampler
     every::Int64

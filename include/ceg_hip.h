@@ -1077,6 +1077,81 @@ CEG_API int ceg_mc_group_halted(ceg_mc_group_t* group, int64_t* halted_step_out 
 /* the host's cell lists of a handle: cell and entry of every atom slot (-1: in no cell); returns 0 without neighbour cells */
 CEG_API int ceg_mc_cell_lists(ceg_mc_t* handle, int32_t* cell_of, int32_t* idx_of, int64_t nslots);
 
+/* ---- tempering: replica exchange between the chains of a group at cycle ends (run_parallel_tempering, src/simulation.jl:461-622) ----
+ * K chains of one group on a ladder of temperatures exchange with their neighbours on the ladder at the end of a cycle, inside
+ * ceg_mc_group_sweep_cycles / ceg_mc_group_sweep_gcmc_cycles, with no host round trip.  What is exchanged is the TEMPERATURE, not the
+ * configuration: a chain keeps its state, random stream, step sizes, statistics and log; what moves is the RUNG of the ladder it
+ * sits on.  The rule is the reference's (:533): compute_accept_move(E_i, E_{i+1}, inv(inv(T_i) - inv(T_{i+1}))).
+ * One more launch per cycle (k_mcg_exchange, one workgroup, one lane per chain) follows k_mcg_cycle_end on the group's stream; plain
+ * loads and stores, stream order is the only synchronisation.  The two plain sweeps (ceg_mc_group_sweep / _sweep_gcmc) ignore an
+ * installed tempering state.
+ *
+ * set_tempering copies `rung` and `energy` (host memory) to the group's device memory and synchronises the group; NULL removes the
+ *   state.  every >= 1; record_capacity >= 0 cycles of records kept; rung [K] a permutation of 0..K-1 (NULL: chain c on rung c);
+ *   energy [K] the total energy of every chain NOW (e.g. ceg_mc_group_baseline's total), finite.
+ * While installed, for both *_cycles entry points:
+ *   Temperatures by rung: every temperature the caller passes is indexed by rung -- params->temperature[r] and column r of
+ *     cycles->temperatures -- and the chain on rung r runs at it.  Every row must be non-decreasing in r.
+ *   Energy at the end of cycle j of a call: energy at the call's start + the call's delta_moves as it stands then, and in the GCMC
+ *     entry point (that + delta_moves) + delta_swaps; FP64, in this order, no contraction.  After the last cycle of a call it becomes
+ *     the next call's start value.  The rungs likewise persist on the device; the host's copy is refreshed at the end of each call.
+ *   Round: with cc = cycle0 + j, an exchange round happens iff cc % every == 0; parity = (cc / every) & 1; the rung pairs are
+ *     (r, r + 1) for r = parity, parity + 2, ... with r + 1 < K.  A pair is attempted only if neither chain is stopped at the cycle's
+ *     last step (last_step >= its stop: the chain plan's, or the step at which a full cell halted it); else both get partner = -1,
+ *     accepted = -1.
+ *   Rule: a the chain on the lower rung, b on the upper, T_a and T_b the temperatures in force during the ended cycle (the cycle
+ *     record's).  In FP64, without contraction, IEEE division:
+ *       ia = 1 / T_a;  ib = 1 / T_b;  d = ia - ib;  Tp = 1 / d;  x = (E_a - E_b) / Tp;  e = exp(x);   accept iff E_b < E_a || u < e
+ *     Equal temperatures give Tp = +inf, e = 1 and an accepted exchange; NaN energies reject.  exp is the device library's.
+ *   Draw: u = U(w0, w1) of the Philox block (seed of the call, absolute last step of the cycle, stream id of chain a, purpose 9).
+ *   After the round -- at EVERY cycle end, round or not -- chain c's temperature for the next cycle is row_{j+1}[rung_next[c]]: the
+ *     table's next row, or params->temperature where there is no table; after the call's last cycle the ended cycle's row.  One
+ *     ceg_mc_exchange_record_t is written per (cycle, chain).
+ *   Sampler: a density map's chain_map is indexed by rung (chain c is binned into chain_map[rung[c]], the rung it held during the
+ *     frame's cycle), so maps belong to temperatures; the series records stay per chain.  A frame of ceg_mc_group_sample is binned
+ *     by the rungs as they stand on the device then.
+ * tempering_read synchronises the group and copies what is asked for (each pointer may be NULL): the rung and the energy of every
+ *   chain, attempted and accepted exchanges of the rung pair (r, r + 1) in row r (row K - 1 is zeros), the records of all cycles since
+ *   set_tempering and their number.
+ * Refusals, all CEG_ERR_INVALID before anything is launched or changed, the earlier state staying: set_tempering with every < 1, a
+ *   negative (or absurd, > 2^32) record_capacity, a rung that is no permutation, a missing or non-finite energy; a *_cycles call whose
+ *   ncycles exceeds what is left of record_capacity, with a row that decreases, or -- ceg_mc_group_sweep_gcmc_cycles -- with any
+ *   species whose swap probability is > 0 (phiPV_div_k belongs to one temperature).
+ * A sweep that fails (CEG_ERR_HIP) once its steps have been enqueued takes none of its records and marks the tempering state stale:
+ *   the next *_cycles call is refused (CEG_ERR_INVALID) until set_tempering is called again.  A failure before that (the device
+ *   cannot be selected, an allocation or the copy of the call's block fails) has launched and changed nothing: the state stays.
+ * Continuation: a run split over several calls (first_step, cycle0, prior and the step sizes advanced as for the cycles above; with
+ *   a table each call gets its own rows) gives the one-call run's logs, states, rungs, partners, draws, decisions and pair counts.
+ *   Two entries cannot be equal in their bytes, by the definitions above.  Energy: a later call starts from the ROUNDED sum of the
+ *   earlier one and its delta_moves starts at zero, so the same terms are added in another association; energies, and the
+ *   thresholds computed from them, agree to rounding (one rounding of at most half an ulp of the largest partial sum per step; a
+ *   decision could differ only where u lies that close to the threshold).  temperature_next of a call's last cycle: the call cannot
+ *   see the row that follows, so it is the ENDED cycle's row at the chain's next rung; the next call starts every chain at its rung's
+ *   entry of its own first row, so the temperatures the chains run at are the one-call run's.
+ * Not enforced: any other call that moves a chain (the plain sweeps, accept, insert, remove, set_guests) makes the stored energies
+ *   stale; the caller installs the state again.
+ * With no tempering installed every entry point enqueues exactly the launches and produces the bytes it produces without this section.
+ * Not covered: step sizes and the cumulative counters stay with the chain, not the rung; exchanges under GCMC swaps; any pair
+ *   schedule other than the alternating one; snapshots; exchanging configurations; SiteHopping. */
+typedef struct ceg_mc_tempering {       /* 32 bytes */
+    int64_t every;                      /* >= 1: a round at the end of every cycle cc with cc % every == 0 */
+    int64_t record_capacity;            /* >= 0: cycles of records kept */
+    const int32_t* rung;                /* [K] a permutation of 0..K-1, or NULL: chain c on rung c */
+    const double*  energy;              /* [K] K: the total energy of every chain now, finite */
+} ceg_mc_tempering_t;
+typedef struct ceg_mc_exchange_record { /* 48 bytes */
+    int32_t rung, rung_next;            /* during the ended cycle, during the next */
+    int32_t partner;                    /* the other chain of the pair, -1: none */
+    int32_t accepted;                   /* 1, 0, or -1: no attempt */
+    double  energy;                     /* of the chain at the end of the cycle */
+    double  temperature_next;           /* the chain's temperature during the next cycle */
+    double  u, threshold;               /* the draw and e of the rule (0 without an attempt) */
+} ceg_mc_exchange_record_t;
+CEG_API int ceg_mc_group_set_tempering(ceg_mc_group_t* group, const ceg_mc_tempering_t* tempering);   /* NULL removes it */
+CEG_API int ceg_mc_group_tempering_read(ceg_mc_group_t* group, int32_t* rung_out /*[K]*/, double* energy_out /*[K]*/,
+                                        int64_t* pair_counts_out /*[K][2]*/, ceg_mc_exchange_record_t* records_out /*[cycles][K]*/,
+                                        int64_t* cycles_out);
+
 /* ---- baseline_energy (src/montecarlo.jl:530-542) of one chain, or of every chain of a group, from the resident state ----
  * What run_montecarlo! asks for at its start, at the first production cycle, after a move that risks underflow and for its final
  * drift check (src/simulation.jl:643,789,850-853; montecarlo.jl:364).  Synchronous; `out` is host memory ([K] for a group, member
