@@ -119,6 +119,20 @@ class McTempering(C.Structure):
 MC_EXCHANGE_RECORD_DTYPE = np.dtype([('rung', '<i4'), ('rung_next', '<i4'), ('partner', '<i4'), ('accepted', '<i4'), ('energy', '<f8'),
                                      ('temperature_next', '<f8'), ('u', '<f8'), ('threshold', '<f8')], align=True)
 assert (C.sizeof(McTempering), MC_EXCHANGE_RECORD_DTYPE.itemsize) == (32, 48)
+MC_RECORDER_MAX_BYTES = 8 << 30      # CEG_MC_RECORDER_MAX_BYTES
+MC_SNAPSHOT_NO_BODY, MC_SNAPSHOT_STOPPED = 1, 2      # flags of a snapshot record
+
+
+class McRecorder(C.Structure):
+    """``ceg_mc_recorder_t`` (``energy`` [K] float64 in host memory, copied by ``ceg_mc_group_set_recorder``)"""
+    _fields_ = [("every", C.c_int64), ("origin", C.c_int64), ("frame_capacity", C.c_int64), ("max_atoms", C.c_int32),
+                ("max_molecules", C.c_int32), ("track_min", C.c_int32), ("_pad", C.c_int32), ("energy", C.c_void_p)]
+
+
+# ``ceg_mc_snapshot_record_t``: one record per (frame, chain) of the recorder, and one per chain for the minimum
+MC_SNAPSHOT_RECORD_DTYPE = np.dtype([('cycle', '<i8'), ('step', '<i8'), ('energy', '<f8'), ('nmol', '<i4'), ('natoms', '<i4'),
+                                     ('flags', '<i4'), ('_pad', '<i4')], align=True)
+assert (C.sizeof(McRecorder), MC_SNAPSHOT_RECORD_DTYPE.itemsize) == (48, 40)
 
 c_double_p = C.POINTER(C.c_double)
 c_float_p = C.POINTER(C.c_float)
@@ -267,6 +281,11 @@ PROTOTYPES = {
     "ceg_mc_cell_lists": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, C.c_int64]),
     "ceg_mc_group_set_tempering": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ceg_mc_group_tempering_read": (C.c_int, [C.c_void_p, c_int32_p, c_double_p, c_int64_p, C.c_void_p, c_int64_p]),
+    "ceg_mc_group_set_recorder": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ceg_mc_group_snapshot": (C.c_int, [C.c_void_p]),
+    "ceg_mc_group_recorder_rebase": (C.c_int, [C.c_void_p, c_double_p]),
+    "ceg_mc_group_recorder_read": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, c_double_p, c_int32_p, c_int32_p, c_int32_p, c_int64_p]),
+    "ceg_mc_group_recorder_min": (C.c_int, [C.c_void_p, c_int64_p, c_double_p, C.c_void_p, c_double_p, c_int32_p, c_int32_p, c_int32_p]),
     "ceg_mc_group_set_sampler": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ceg_mc_group_sample": (C.c_int, [C.c_void_p]),
     "ceg_mc_group_sampler_read": (C.c_int, [C.c_void_p, c_int64_p, C.c_void_p, c_int64_p]),

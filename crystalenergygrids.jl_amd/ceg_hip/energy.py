@@ -708,6 +708,7 @@ class DeviceMonteCarloGroup:
         self.sampler = None           # what set_sampler installed (its geometry and tables, for the host restatement)
         self.chain_plan = None        # what set_chain_plan installed: (phiPV_div_k [K, nspecies] or None, stop_step [K] or None)
         self.tempering = None         # what set_tempering installed: (every, capacity)
+        self.recorder = None          # what set_recorder installed: dict(every, origin, capacity, track_min, max_atoms, max_molecules)
 
     def __repr__(self):
         return f"DeviceMonteCarloGroup(k={len(self.chains)})"
@@ -1205,6 +1206,8 @@ class DeviceMonteCarloGroup:
 
         start = self.baseline_energies()
         base = np.array([float(r) for r in start])
+        if self.recorder is not None:                # the recorder's energies are the reference's `energy`: the baseline + the deltas
+            self.recorder_rebase(base)
         stats_init = stats = None
         cycles = np.zeros((0, k), dtype=_abi.MC_CYCLE_RECORD_DTYPE)
         initial_energies = np.zeros((0, k))
@@ -1214,6 +1217,8 @@ class DeviceMonteCarloGroup:
             initial_energies = base[None, :] + cycles["delta_moves"] + cycles["delta_swaps"]
             production = self.baseline_energies()
             base = np.array([float(r) for r in production])
+            if self.recorder is not None:            # (the precise energy at the first production cycle, simulation.jl:788-790)
+                self.recorder_rebase(base)
         energies = np.zeros((0, k))
         recorded = base.copy()
         if ncycles > 0:
@@ -1525,6 +1530,151 @@ class DeviceMonteCarloGroup:
         """``ceg_mc_group_sampler_reset``: bins, series and frame count back to zero."""
         self._sampler()
         _abi.check(self._lib, self._lib.ceg_mc_group_sampler_reset(self._h))
+
+    def set_recorder(self, every: Optional[int], origin: int = 0, capacity: int = 1024, energies=None, track_min: bool = False,
+                     max_atoms: Optional[int] = None, max_molecules: Optional[int] = None) -> None:
+        """``ceg_mc_group_set_recorder``: from now on :meth:`sweep_cycles` and :meth:`sweep_gcmc_cycles` copy every chain's configuration
+        into device memory at the end of every cycle ``cc`` with ``cc >= origin and (cc - origin) % every == 0`` (``every=0``: no
+        periodic frames) -- the trajectory ``run_montecarlo!`` writes every ``printevery`` cycles (simulation.jl:784-799) -- and, with
+        ``track_min``, keep per chain the lowest-energy configuration seen at any cycle end (``RMinimumEnergy``,
+        parameterinputs.jl:86-108), with no host round trip; :meth:`recorder_read` / :meth:`recorder_minimum` read everything once,
+        after the run.  ``energies``: the total energy of every chain now (K; default: the totals of :meth:`baseline_energies`);
+        ``capacity``: the frames kept; ``max_atoms`` / ``max_molecules``: the room of a frame per chain, by default what the largest
+        chain holds now -- for GCMC pass the sweep's ``max_molecules``, and ``max_atoms`` follows from the largest species.
+        ``every=None`` removes the recorder.  :meth:`run_montecarlo` rebases an installed recorder at its two baselines.  Any other call
+        that moves a chain (``sweep``, ``accept``, ``insert``, :meth:`restore` ...) makes the running energies stale:
+        :meth:`recorder_rebase`.  ``track_min`` is refused under GCMC swaps (``delta_swaps`` is the rule's ``diff``, not the state's
+        energy change).  :func:`ceg_hip.mcrng.snapshot_cycles` / :func:`ceg_hip.mcrng.track_minimum` restate the schedule and the rule."""
+        if every is None:
+            _abi.check(self._lib, self._lib.ceg_mc_group_set_recorder(self._h, None))
+            self.recorder = None
+            return
+        k = len(self.chains)
+        if energies is None:
+            energies = [float(r) for r in self.baseline_energies()]
+        E = np.ascontiguousarray(energies, dtype=np.float64)
+        if E.shape != (k,):
+            raise ValueError(f"energies: one per chain ({k})")
+        largest = max((len(ids) for chain in self.chains for ids in chain.mc.ffidx), default=1)
+        if max_molecules is None:
+            max_molecules = max(sum(len(kind) for kind in chain._slot) for chain in self.chains)
+            if max_atoms is None:
+                max_atoms = max(sum(len(chain.mc.ffidx[i]) * len(kind) for i, kind in enumerate(chain._slot)) for chain in self.chains)
+        elif max_atoms is None:
+            max_atoms = int(max_molecules) * largest
+        max_atoms, max_molecules = max(int(max_atoms), 1), max(int(max_molecules), 1)
+        spec = _abi.McRecorder(int(every), int(origin), int(capacity), max_atoms, max_molecules, 1 if track_min else 0, 0, E.ctypes.data)
+        _abi.check(self._lib, self._lib.ceg_mc_group_set_recorder(self._h, C.addressof(spec)))
+        self.recorder = dict(every=int(every), origin=int(origin), capacity=int(capacity), track_min=bool(track_min), max_atoms=max_atoms,
+                             max_molecules=max_molecules)
+
+    def _recorder(self):
+        r = getattr(self, "recorder", None)
+        if r is None:
+            raise RuntimeError("no recorder installed: set_recorder first")
+        return r
+
+    def snapshot(self) -> None:
+        """``ceg_mc_group_snapshot``: one frame of the resident state, now (asynchronous, ordered with the group's other calls).  Its
+        records carry ``cycle == step == -1`` and the recorder's running energy; the species of its molecules are -1."""
+        self._recorder()
+        _abi.check(self._lib, self._lib.ceg_mc_group_snapshot(self._h))
+
+    def recorder_rebase(self, energies) -> None:
+        """``ceg_mc_group_recorder_rebase``: replace the recorder's running energies (K, one per chain) -- the precise energy at the
+        first production cycle (simulation.jl:788-790).  The minimum is neither tested nor reset."""
+        self._recorder()
+        E = np.ascontiguousarray(energies, dtype=np.float64)
+        if E.shape != (len(self.chains),):
+            raise ValueError(f"energies: one per chain ({len(self.chains)})")
+        _abi.check(self._lib, self._lib.ceg_mc_group_recorder_rebase(self._h, _abi.dptr(E)))
+
+    @staticmethod
+    def _recorder_bodies(records, xyz, kind, first, species):
+        """[n, K] records and the four padded arrays -> per record (positions, kinds, mol_first, species) trimmed to the counts (empty
+        where the record carries no body)"""
+        out = []
+        for f in range(records.shape[0]):
+            row = []
+            for c in range(records.shape[1]):
+                r = records[f, c]
+                na, nm = (0, 0) if r["flags"] & _abi.MC_SNAPSHOT_NO_BODY else (int(r["natoms"]), int(r["nmol"]))
+                row.append((xyz[f, c, :na].copy(), kind[f, c, :na].copy(), first[f, c, :nm + 1].copy(), species[f, c, :nm].copy()))
+            out.append(row)
+        return out
+
+    def recorder_read(self, first_frame: int = 0, nframes: Optional[int] = None):
+        """``ceg_mc_group_recorder_read`` -> ``(records, frames)``: ``records`` ``[n, K]`` of ``_abi.MC_SNAPSHOT_RECORD_DTYPE`` for the
+        frames ``first_frame .. first_frame + nframes`` (default: all from ``first_frame``), and ``frames[f][c]`` = (positions
+        ``[natoms, 3]``, kinds int32 ``[natoms]`` 0-based, mol_first int32 ``[nmol + 1]``, species int32 ``[nmol]``) of chain ``c`` in
+        molecule order -- what ``ceg_mc_get_state`` returns and ``ceg_mc_set_guests`` takes (:meth:`restore`).  A record with flag 1
+        (the chain did not fit ``max_atoms`` / ``max_molecules``) has the true counts and an empty body."""
+        s = self._recorder()
+        taken = C.c_int64(0)
+        _abi.check(self._lib, self._lib.ceg_mc_group_recorder_read(self._h, 0, 0, None, None, None, None, None, C.byref(taken)))
+        first_frame = int(first_frame)
+        n = int(taken.value) - first_frame if nframes is None else int(nframes)
+        k, ma, mm = len(self.chains), s["max_atoms"], s["max_molecules"]
+        records = np.zeros((max(n, 0), k), dtype=_abi.MC_SNAPSHOT_RECORD_DTYPE)
+        xyz, kind = np.zeros((max(n, 0), k, ma, 3)), np.zeros((max(n, 0), k, ma), dtype=np.int32)
+        first, species = np.zeros((max(n, 0), k, mm + 1), dtype=np.int32), np.zeros((max(n, 0), k, mm), dtype=np.int32)
+        some = n > 0
+        _abi.check(self._lib, self._lib.ceg_mc_group_recorder_read(self._h, first_frame, n, records.ctypes.data if some else None,
+                                                                   _abi.dptr(xyz.reshape(-1)) if some else None, _abi.i32ptr(kind.reshape(-1)) if some else None,
+                                                                   _abi.i32ptr(first.reshape(-1)) if some else None,
+                                                                   _abi.i32ptr(species.reshape(-1)) if some else None, None))
+        return records, self._recorder_bodies(records, xyz, kind, first, species)
+
+    def recorder_minimum(self):
+        """``ceg_mc_group_recorder_min`` -> ``(mink int64[K], mine float64[K], records [K], bodies)``: per chain the cycle at whose end
+        the lowest energy was seen (-1: the state at :meth:`set_recorder`), that energy, its record and ``bodies[c]`` = (positions,
+        kinds, mol_first, species) as :meth:`recorder_read` gives them."""
+        s = self._recorder()
+        k, ma, mm = len(self.chains), s["max_atoms"], s["max_molecules"]
+        mink, mine = np.zeros(k, dtype=np.int64), np.zeros(k)
+        records = np.zeros((1, k), dtype=_abi.MC_SNAPSHOT_RECORD_DTYPE)
+        xyz, kind = np.zeros((1, k, ma, 3)), np.zeros((1, k, ma), dtype=np.int32)
+        first, species = np.zeros((1, k, mm + 1), dtype=np.int32), np.zeros((1, k, mm), dtype=np.int32)
+        _abi.check(self._lib, self._lib.ceg_mc_group_recorder_min(self._h, _abi.i64ptr(mink), _abi.dptr(mine), records.ctypes.data, _abi.dptr(xyz.reshape(-1)),
+                                                                  _abi.i32ptr(kind.reshape(-1)), _abi.i32ptr(first.reshape(-1)), _abi.i32ptr(species.reshape(-1))))
+        return mink, mine, records[0], self._recorder_bodies(records, xyz, kind, first, species)[0]
+
+    def restore(self, chain_index: int, frame) -> None:
+        """Put a frame of :meth:`recorder_read` / :meth:`recorder_minimum` -- (positions, kinds, mol_first, species) -- back into chain
+        ``chain_index`` through ``ceg_mc_set_guests`` and refresh the chain's host side (``mc.positions``, the molecule order, the tail
+        correction where the counts change).  Species of -1 (a frame of the plain entry point) are taken from the molecules' kinds.
+        The recorder's and a tempering state's energies of that chain are stale afterwards."""
+        chain = self.chains[int(chain_index)]
+        mc = chain.mc
+        pos, kinds, first, species = frame
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+        first = np.ascontiguousarray(first, dtype=np.int32)
+        if len(first) < 1 or first[-1] != len(kinds) or len(pos) != len(kinds):
+            raise ValueError("the frame has no body (a record with flag 1?) or its arrays disagree")
+        nmol = len(first) - 1
+        by_kinds = {}
+        for i, ids in enumerate(mc.ffidx):
+            by_kinds.setdefault(tuple(int(q) - 1 for q in ids), i)
+        spec = []
+        for j in range(nmol):
+            i = int(species[j]) if len(species) > j and species[j] >= 0 else by_kinds.get(tuple(int(q) for q in kinds[first[j]:first[j + 1]]))
+            if i is None or not 0 <= i < len(mc.ffidx) or tuple(int(q) - 1 for q in mc.ffidx[i]) != tuple(int(q) for q in kinds[first[j]:first[j + 1]]):
+                raise ValueError(f"molecule {j} of the frame matches no species of the chain")
+            spec.append(i)
+        _abi.check(self._lib, self._lib.ceg_mc_set_guests(chain._h, _abi.dptr(pos.reshape(-1)) if len(pos) else None, _abi.i32ptr(kinds) if len(kinds) else None,
+                                                          _abi.i32ptr(first), nmol))
+        before = [len(kind) for kind in chain._slot]
+        chain._slot = [[j for j in range(nmol) if spec[j] == i] for i in range(len(mc.positions))]
+        mc.positions = [[pos[first[j]:first[j + 1]].copy() for j in kind] for kind in chain._slot]
+        if mc.tail_cross is not None:                # mc.tailcorrection follows the species counts (modify_species!, montecarlo.jl:814,858)
+            from .hostmirror.montecarlo import modify_species_dryrun
+            counts = list(before)
+            for i, kind in enumerate(chain._slot):
+                while counts[i] != len(kind):
+                    num = 1 if counts[i] < len(kind) else -1
+                    mc.tailcorrection += modify_species_dryrun(mc.tail_framework, mc.tail_cross, counts, i, num)
+                    counts[i] += num
 
     def close(self) -> None:
         if getattr(self, "_h", None):

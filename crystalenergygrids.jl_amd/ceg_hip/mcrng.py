@@ -464,6 +464,35 @@ def sampler_frames(first_step: int, nsteps: int, every: int, from_step: int = 0)
     return list(range(s, int(first_step) + max(int(nsteps), 0), every))
 
 
+# The recorder of ``ceg_mc_group_set_recorder`` (csrc/ceg_mc_record.hip): when a frame is due and how the minimum is followed.
+def snapshot_due(cc: int, origin: int, every: int) -> bool:
+    """A frame at the end of cycle ``cc``: ``every > 0 and cc >= origin and (cc - origin) % every == 0``."""
+    if every < 0 or origin < 0:
+        raise ValueError("every >= 0 and origin >= 0")
+    return every > 0 and cc >= origin and (cc - origin) % every == 0
+
+
+def snapshot_cycles(cycle0: int, ncycles: int, origin: int, every: int) -> list:
+    """The cycles ``cc`` of a call (``cycle0 <= cc < cycle0 + ncycles``) at whose end a frame is due, in order."""
+    return [cc for cc in range(int(cycle0), int(cycle0) + max(int(ncycles), 0)) if snapshot_due(cc, origin, every)]
+
+
+def track_minimum(energies, e0, stopped=None, cycle0: int = 1):
+    """``RMinimumEnergy`` per chain over ``energies`` [ncycles, K] (row j: the end of cycle ``cycle0 + j``) from the initial
+    minimum ``e0`` [K] (``mink`` = -1): ``if e < mine`` -- strict, so a tie keeps the earlier cycle, and a NaN never wins.
+    ``stopped`` [ncycles, K] bool: the chain is not tested at that cycle end.  -> (mink int64[K], mine float64[K])."""
+    E = np.asarray(energies, dtype=np.float64)
+    mine = np.array(e0, dtype=np.float64, copy=True).reshape(-1)
+    E = E.reshape(-1, len(mine))
+    mink = np.full(len(mine), -1, dtype=np.int64)
+    S = np.zeros(E.shape, dtype=bool) if stopped is None else np.asarray(stopped, dtype=bool).reshape(E.shape)
+    for j in range(E.shape[0]):
+        for c in range(E.shape[1]):
+            if not S[j, c] and E[j, c] < mine[c]:
+                mine[c], mink[c] = E[j, c], int(cycle0) + j
+    return mink, mine
+
+
 def replay_positions(start_positions, records, atoms_per_species=None, start_species=None):
     """Follow one chain through the log of a sweep (``records``: the chain's column of the log of ``sweep`` or ``sweep_gcmc``) from
     ``start_positions`` (one ``[m, 3]`` array per molecule, device molecule order): an accepted displacement replaces the molecule's

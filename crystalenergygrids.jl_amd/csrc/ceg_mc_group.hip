@@ -7,6 +7,7 @@
 //   ceg_mc_group_sweep_gcmc_cycles   launch of ceg_mc_cycles.hip behind the last step of every cycle (temperature table, dmax / thetamax)
 //   ceg_mc_group_set_chain_plan      per chain: the phiPV_div_k of the swap rules and the absolute step at which the chain stops (isotherms)
 //   ceg_mc_group_set_tempering       (ceg_mc_temper.hip) the *_cycles sweeps enqueue one exchange launch behind every cycle end
+//   ceg_mc_group_set_recorder        (ceg_mc_record.hip) the *_cycles sweeps enqueue one snapshot launch behind the cycle ends it wants
 // The two sweeps have their own kernels, per-chain parameters and read-back, and share one host driver (run_sweep).
 #include "ceg_mc_gcmc.h"
 
@@ -357,6 +358,7 @@ struct ceg_mc_group {
     size_t baseline_cap = 0;
     GroupSampler* sampler = nullptr;             // density maps and series taken during sweeps (ceg_mc_sample.hip); nullptr: none
     GroupTempering* tempering = nullptr;         // rungs, energies and exchange records of the *_cycles sweeps (ceg_mc_temper.hip); nullptr: none
+    GroupRecorder* recorder = nullptr;           // frames and minimum taken at the cycle ends of the *_cycles sweeps (ceg_mc_record.hip); nullptr: none
     // chain plan (ceg_mc_group_set_chain_plan): the host's copy for the checks and the launch lists, the device's for the kernels
     std::vector<double> plan_phi;                // [K][plan_species], empty: the species table's value for every chain
     std::vector<int64_t> plan_stop;              // [K], empty: no chain stops
@@ -389,6 +391,7 @@ void group_free(ceg_mc_group* g)
     group_free_blocks(g);
     sampler_free(g->sampler);
     temper_free(g->tempering);
+    recorder_free(g->recorder);
     if (g->d_views) (void)hipFree(g->d_views);
     if (g->d_done) (void)hipFree(g->d_done);
     if (g->d_scratch) (void)hipFree(g->d_scratch);
@@ -436,7 +439,7 @@ int ceg_mcs::group_refuse_poisoned(int c)
 
 ceg_mcs::GroupRef ceg_mcs::group_ref(ceg_mc_group* g)
 {
-    return GroupRef{g->device, g->stream, g->chains.data(), (int)g->chains.size(), g->d_views, &g->d_baseline, &g->baseline_cap, &g->sampler, &g->tempering};
+    return GroupRef{g->device, g->stream, g->chains.data(), (int)g->chains.size(), g->d_views, &g->d_baseline, &g->baseline_cap, &g->sampler, &g->tempering, &g->recorder};
 }
 
 bool ceg_mcs::group_views_current(ceg_mc_group* g) { return group_upload_views(g, std::vector<char>(g->chains.size(), 1)); }
@@ -983,6 +986,15 @@ struct SweepCycles {
     GroupTempering* temper = nullptr;
     size_t o_ladder = 0;
     void ladder_layout(SweepLayout& lay, size_t k) { o_ladder = lay.segment(temper && !table() ? sizeof(double) * k : 0); }
+    // recorder (ceg_mc_record.hip), likewise only for a *_cycles call: the recorder and the segment of the chains' energies at the call's start
+    GroupRecorder* recorder = nullptr;
+    size_t o_energy = 0;
+    void recorder_layout(SweepLayout& lay, std::vector<unsigned char>& stage, size_t k)
+    {
+        o_energy = lay.segment(recorder ? sizeof(double) * k : 0);
+        stage.assign(lay.total, 0);
+        if (recorder) recorder_energies(recorder, reinterpret_cast<double*>(stage.data() + o_energy));
+    }
     // the chain's first temperature: the caller's values are indexed by rung while a tempering state is installed
     double first_temperature(const double* temperature, int c) const { return !temperature ? 0.0 : temperature[temper ? temper_rungs(temper)[c] : c]; }
     // [K] by rung in device memory: what cycle j + 1 runs at (the call's last cycle: what it ran at)
@@ -1110,6 +1122,7 @@ int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nstep
     if (C.cycled)
         if (int rc = cycles_check(C.cy, k, p->first_step, false, C.out, &nsteps)) return rc;
     C.temper = C.cycled ? g->tempering : nullptr;        // (the plain sweep ignores a tempering state)
+    C.recorder = C.cycled ? g->recorder : nullptr;       // (and a recorder)
     const double* temperature = C.first_row(p->temperature);
     // ---- every refusal before anything is launched or changed, chain by chain
     std::vector<McSweepChain> pc((size_t)k);
@@ -1139,6 +1152,8 @@ int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nstep
     }
     if (C.temper)
         if (int rc = temper_admit(C.temper, C.cy, p->temperature, k, false)) return rc;
+    if (C.recorder)
+        if (int rc = recorder_admit(C.recorder, C.cy, k, false)) return rc;
     if (g->sampler)
         if (int rc = sampler_admit(g->sampler, p->first_step, nsteps)) return rc;
     for (int c = 0; c < k; ++c) stats_out[c] = ceg_mc_sweep_stats_t{};
@@ -1155,7 +1170,8 @@ int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nstep
     C.layout(lay, (size_t)k);
     const size_t o_stop = lay.segment(with_cells ? sizeof(int64_t) * (size_t)k : 0), o_halt = lay.segment(with_cells ? sizeof(int64_t) * (size_t)k : 0),
                  o_flags = lay.segment(with_cells ? sizeof(int32_t) * 2 * (size_t)k : 0);
-    std::vector<unsigned char> stage(lay.total, 0);
+    std::vector<unsigned char> stage;
+    C.recorder_layout(lay, stage, (size_t)k);
     C.fill(stage, (size_t)k, p->temperature);
     memcpy(stage.data() + lay.par, pc.data(), sizeof(McSweepChain) * (size_t)k);
     if (!beads.empty()) memcpy(stage.data() + o_bead, beads.data(), sizeof(int32_t) * beads.size());
@@ -1208,10 +1224,21 @@ int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nstep
         if (C.temper)
             temper_enqueue(C.temper, g->stream, k, C.run(g), j, src,
                            TemperSource{&sweep_at<const McSweepChain>(g, lay.par)->stream_id, (int32_t)sizeof(McSweepChain), 0, p->seed, C.next_row(g, j, (size_t)k)});
+        if (C.recorder && recorder_wants(C.recorder, C.cy->cycle0 + j))
+            recorder_enqueue(C.recorder, g->stream, g->d_views, k, C.cy->cycle0 + j,
+                             RecordSource{nullptr, 0, (int32_t)sizeof(ceg_mc_sweep_stats_t), &st->delta, nullptr, nullptr, nullptr, 0, 0, stop_of(), src.last_step,
+                                          sweep_at<const double>(g, C.o_energy)});
     };
     if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame, C.cycled ? C.cy->steps_per_cycle : 0, cycle_end)) {
         if (C.temper && g->sweep_enqueued) temper_fail(C.temper);       // (a failure before the steps has changed nothing: the state stays)
+        if (C.recorder && g->sweep_enqueued) recorder_fail(C.recorder, g->stream);
         return rc;
+    }
+    if (C.recorder) {                                    // the energies after the call's last cycle, formed as the launch forms them
+        const double* e0 = reinterpret_cast<const double*>(stage.data() + C.o_energy);
+        std::vector<double> e((size_t)k);
+        for (int c = 0; c < k; ++c) e[(size_t)c] = e0[c] + reinterpret_cast<const ceg_mc_sweep_stats_t*>(stage.data() + o_stats)[c].delta;
+        recorder_commit(C.recorder, e.data());
     }
     if (C.temper && !temper_commit(C.temper, C.cy->ncycles)) return merr(CEG_ERR_HIP, "D2H of the rungs failed: the tempering state is stale");
     memcpy(stats_out, stage.data() + o_stats, sizeof(ceg_mc_sweep_stats_t) * (size_t)k);
@@ -1231,6 +1258,13 @@ int sweep_plain(ceg_mc_group_t* g, const ceg_mc_sweep_params_t* p, int64_t nstep
         if (bad >= 0) return chain_err(CEG_ERR_HIP, bad, ": the cell lists kept on the device failed a range check: the chain is marked inconsistent", "");
     }
     return CEG_OK;
+}
+
+// (energy + delta_moves) + delta_swaps in FP64, in this order: the energy of a chain after a GCMC call as k_mcg_snapshot forms it
+double recorder_sum(double energy, const ceg_mc_gcmc_stats_t& st)
+{
+    const double moved = energy + st.delta_moves;
+    return moved + st.delta_swaps;
 }
 
 // ceg_mc_group_sweep_gcmc and ceg_mc_group_sweep_gcmc_cycles, as sweep_plain
@@ -1294,6 +1328,7 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
     if (C.cycled)                                        // (a varying temperature only where no species swaps, simulation.jl:688)
         if (int rc = cycles_check(C.cy, k, p->first_step, swap_atoms > 0, C.out, &nsteps)) return rc;
     C.temper = C.cycled ? g->tempering : nullptr;        // (the plain sweep ignores a tempering state)
+    C.recorder = C.cycled ? g->recorder : nullptr;       // (and a recorder)
     const double* temperature = C.first_row(p->temperature);
     if (g->d_blocks) {                                   // block pockets: the masks must be those of this species table
         if (ns != g->blk_species) return merr(CEG_ERR_INVALID, "nspecies differs from the nspecies of ceg_mc_group_set_blocks");
@@ -1365,6 +1400,8 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
     };
     if (C.temper)
         if (int rc = temper_admit(C.temper, C.cy, p->temperature, k, swap_atoms > 0)) return rc;
+    if (C.recorder)
+        if (int rc = recorder_admit(C.recorder, C.cy, k, swap_atoms > 0)) return rc;
     if (g->sampler)
         if (int rc = sampler_admit(g->sampler, p->first_step, nsteps)) return rc;
     for (int c = 0; c < k; ++c) stats_out[c] = ceg_mc_gcmc_stats_t{};
@@ -1400,7 +1437,8 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
                  o_flags = lay.segment(with_cells ? sizeof(int32_t) * 2 * (size_t)k : 0), o_book = lay.segment(with_cells ? sizeof(McCellBook) * (size_t)k : 0);
     const ceg_mc_block_t* blocks = g->d_blocks;          // NULL: no masks, the kernels take the path without the resolve stage
     const int block_kinds = g->blk_kinds;
-    std::vector<unsigned char> stage(lay.total, 0);
+    std::vector<unsigned char> stage;
+    C.recorder_layout(lay, stage, (size_t)k);
     C.fill(stage, (size_t)k, p->temperature);
     memcpy(stage.data() + lay.par, pc.data(), sizeof(McGcmcChain) * (size_t)k);
     memcpy(stage.data() + o_spec, p->species, sizeof(ceg_mc_gcmc_species_t) * (size_t)ns);
@@ -1473,10 +1511,22 @@ int sweep_gcmc(ceg_mc_group_t* g, const ceg_mc_gcmc_params_t* p, int64_t nsteps,
         if (C.temper)
             temper_enqueue(C.temper, g->stream, k, C.run(g), j, src,
                            TemperSource{&sweep_at<const McGcmcChain>(g, lay.par)->stream_id, (int32_t)sizeof(McGcmcChain), 0, p->seed, C.next_row(g, j, (size_t)k)});
+        if (C.recorder && recorder_wants(C.recorder, C.cy->cycle0 + j))      // (counts and species from the device's table, as the frames)
+            recorder_enqueue(C.recorder, g->stream, g->d_views, k, C.cy->cycle0 + j,
+                             RecordSource{&sweep_at<const McGcmcTable>(g, o_tab)->nmol, (int32_t)(sizeof(McGcmcTable) / 4), (int32_t)sizeof(ceg_mc_gcmc_stats_t),
+                                          &st->delta_moves, &st->delta_swaps, sweep_at<const int32_t>(g, o_ms), &sweep_at<const McGcmcChain>(g, lay.par)->spec_off,
+                                          (int32_t)sizeof(McGcmcChain), 0, stop_of(), src.last_step, sweep_at<const double>(g, C.o_energy)});
     };
     if (int rc = run_sweep(g, plan, lay, stage, o_stats, p->first_step, nsteps, log_out, trial, accept, frame, C.cycled ? C.cy->steps_per_cycle : 0, cycle_end)) {
         if (C.temper && g->sweep_enqueued) temper_fail(C.temper);       // (a failure before the steps has changed nothing: the state stays)
+        if (C.recorder && g->sweep_enqueued) recorder_fail(C.recorder, g->stream);
         return rc;
+    }
+    if (C.recorder) {                                    // the energies after the call's last cycle, formed as the launch forms them
+        const double* e0 = reinterpret_cast<const double*>(stage.data() + C.o_energy);
+        std::vector<double> e((size_t)k);
+        for (int c = 0; c < k; ++c) e[(size_t)c] = recorder_sum(e0[c], reinterpret_cast<const ceg_mc_gcmc_stats_t*>(stage.data() + o_stats)[c]);
+        recorder_commit(C.recorder, e.data());
     }
     if (C.temper && !temper_commit(C.temper, C.cy->ncycles)) return merr(CEG_ERR_HIP, "D2H of the rungs failed: the tempering state is stale");
     C.read_back(stage, (size_t)k);

@@ -863,6 +863,33 @@ void temper_enqueue(GroupTempering* t, hipStream_t stream, int k, const CycleRun
 bool temper_commit(GroupTempering* t, int64_t ncycles);              // a call has ended well (stream idle): its records count, the host's rungs follow
 void temper_fail(GroupTempering* t);                                 // a call failed once enqueued: the state is stale
 
+// defined in ceg_mc_record.hip: the recorder of a group (ceg_mc_group_set_recorder) and the snapshot launch (k_mcg_snapshot) that the
+// *_cycles sweeps enqueue behind cycles_enqueue / temper_enqueue at the cycle ends the recorder wants.  The group owns it and frees it.
+struct GroupRecorder;
+// where the launch finds, per chain c, what the views do not hold during a sweep (all device memory): counts + c * counts_stride =
+// (molecules, high-water mark of the atom slots) as SampleSource describes them (nullptr: nmol / natoms of the views); the running
+// sums of the call's statistics at delta_* + c * stats_stride bytes (nullptr: 0); the species of the chain's molecule j at
+// molspec[*(spec_off + c * spec_stride bytes) + j] (molspec nullptr: -1); stop and last_step as in CycleSource; energy: [K] the
+// chains' energies at the call's start
+struct RecordSource {
+    const int32_t* counts;
+    int32_t counts_stride, stats_stride;
+    const double *delta_moves, *delta_swaps;
+    const int32_t *molspec, *spec_off;
+    int32_t spec_stride, _pad;
+    const int64_t* stop;
+    uint64_t last_step;
+    const double* energy;
+};
+void recorder_free(GroupRecorder* r);
+// CEG_ERR_INVALID where a *_cycles call cannot run with the recorder: stale, its due frames exceed the room left, track_min under swaps
+int recorder_admit(const GroupRecorder* r, const ceg_mc_cycles_t* cy, int k, bool swaps);
+bool recorder_wants(const GroupRecorder* r, int64_t cc);            // a launch at the end of cycle cc (a frame is due, or track_min)
+void recorder_energies(const GroupRecorder* r, double* out);        // [K] the running energies (what a call stages as RecordSource::energy)
+void recorder_enqueue(GroupRecorder* r, hipStream_t stream, const McView* d_views, int k, int64_t cc, const RecordSource& src);
+void recorder_commit(GroupRecorder* r, const double* energy);       // a call has ended well: its frames count, [K] the energies after its last cycle
+void recorder_fail(GroupRecorder* r, hipStream_t stream);           // a call failed once enqueued: none of its frames, the recorder is stale
+
 // defined in ceg_mc_group.hip: what ceg_mc_baseline.hip and ceg_mc_sample.hip need of a group
 struct GroupRef {
     int device;
@@ -874,6 +901,7 @@ struct GroupRef {
     size_t* baseline_cap;
     GroupSampler** sampler;                      // nullptr behind it: no sampler installed
     GroupTempering** tempering;                  // nullptr behind it: no tempering installed
+    GroupRecorder** recorder;                    // nullptr behind it: no recorder installed
 };
 GroupRef group_ref(ceg_mc_group* g);
 bool group_views_current(ceg_mc_group* g);       // every member's view into d_views where it changed since its last upload

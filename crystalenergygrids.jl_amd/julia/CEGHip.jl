@@ -984,6 +984,97 @@ function mc_group_tempering_read(g::Ptr{Cvoid}, k::Integer)
     rung, energy, pairs, records
 end
 
+# `ceg_mc_recorder_t` (48 bytes) and `ceg_mc_snapshot_record_t` (40 bytes) of include/ceg_hip.h
+struct McRecorder
+    every::Int64                     # 0: no periodic frames
+    origin::Int64
+    frame_capacity::Int64
+    max_atoms::Int32
+    max_molecules::Int32
+    track_min::Int32
+    _pad::Int32
+    energy::Ptr{Float64}             # [K] in K
+end
+
+struct McSnapshotRecord
+    cycle::Int64                     # -1: mc_group_snapshot!, or the state at installation
+    step::Int64
+    energy::Float64
+    nmol::Int32
+    natoms::Int32
+    flags::Int32                     # 1: does not fit, no body; 2: stopped or halted
+    _pad::Int32
+end
+
+"""
+`ceg_mc_group_set_recorder`: from now on `mc_group_sweep_cycles!` / `mc_group_sweep_gcmc_cycles!` take a frame of every chain's
+positions at the end of cycle `cc` iff `every > 0 && cc >= origin && (cc - origin) % every == 0` (the trajectory of `run_montecarlo!`,
+src/simulation.jl:784-799) and, with `track_min`, keep the lowest-energy configuration per chain (`RMinimumEnergy`,
+src/parameterinputs.jl:86-108), on the device.  `energy`: the total energy of every chain now (unitful or in K);
+`energy === nothing` removes the recorder.  UNVERIFIED: never executed.
+"""
+function mc_group_set_recorder!(g::Ptr{Cvoid}, energy::Union{Nothing,AbstractVector}; every::Integer=1, origin::Integer=0,
+                                capacity::Integer=1024, max_atoms::Integer=1, max_molecules::Integer=1, track_min::Bool=false)
+    if energy === nothing
+        _check(ccall((:ceg_mc_group_set_recorder, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), g, C_NULL))
+        return nothing
+    end
+    e = Float64[x isa Real ? x : ustrip(u"K", x) for x in energy]
+    GC.@preserve e begin
+        spec = Ref(McRecorder(Int64(every), Int64(origin), Int64(capacity), Int32(max_atoms), Int32(max_molecules), Int32(track_min), Int32(0),
+                              pointer(e)))
+        _check(ccall((:ceg_mc_group_set_recorder, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), g, spec))
+    end
+    nothing
+end
+
+"""
+`ceg_mc_group_snapshot`: one frame of the resident state now, asynchronous on the group's stream.  UNVERIFIED: never executed.
+"""
+function mc_group_snapshot!(g::Ptr{Cvoid})
+    _check(ccall((:ceg_mc_group_snapshot, LIB[]), Cint, (Ptr{Cvoid},), g))
+    nothing
+end
+
+"""
+`ceg_mc_group_recorder_read` for a group of `k` chains whose recorder was installed with `max_atoms` / `max_molecules` -> (records
+`k x frames`, xyz `3 x max_atoms x k x frames` in Å, kinds (0-based) `max_atoms x k x frames`, mol_first (0-based)
+`(max_molecules + 1) x k x frames`, species (0-based, -1: unknown) `max_molecules x k x frames`).  UNVERIFIED: never executed.
+"""
+function mc_group_recorder_read(g::Ptr{Cvoid}, k::Integer, max_atoms::Integer, max_molecules::Integer)
+    n = Ref{Int64}(0)
+    _check(ccall((:ceg_mc_group_recorder_read, LIB[]), Cint,
+                 (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}),
+                 g, Int64(0), Int64(0), C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, n))
+    records = Matrix{McSnapshotRecord}(undef, k, n[])
+    xyz = zeros(Float64, 3, max_atoms, k, n[])
+    kinds = zeros(Int32, max_atoms, k, n[])
+    first = zeros(Int32, max_molecules + 1, k, n[])
+    species = zeros(Int32, max_molecules, k, n[])
+    _check(ccall((:ceg_mc_group_recorder_read, LIB[]), Cint,
+                 (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}),
+                 g, Int64(0), n[], records, xyz, kinds, first, species, n))
+    records, xyz, kinds, first, species
+end
+
+"""
+`ceg_mc_group_recorder_min` -> (mink, mine (K), records `k`, xyz, kinds, mol_first, species as `mc_group_recorder_read` lays them out,
+without the frame axis).  UNVERIFIED: never executed.
+"""
+function mc_group_recorder_min(g::Ptr{Cvoid}, k::Integer, max_atoms::Integer, max_molecules::Integer)
+    mink = zeros(Int64, k)
+    mine = zeros(Float64, k)
+    records = Vector{McSnapshotRecord}(undef, k)
+    xyz = zeros(Float64, 3, max_atoms, k)
+    kinds = zeros(Int32, max_atoms, k)
+    first = zeros(Int32, max_molecules + 1, k)
+    species = zeros(Int32, max_molecules, k)
+    _check(ccall((:ceg_mc_group_recorder_min, LIB[]), Cint,
+                 (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                 g, mink, mine, records, xyz, kinds, first, species))
+    mink, mine, records, xyz, kinds, first, species
+end
+
 # `ceg_mc_sampler_t` (152 bytes) and `ceg_mc_sample_record_t` (64 bytes) of include/ceg_hip.h
 struct McSampler
     every::Int64

@@ -980,8 +980,9 @@ CEG_API int ceg_mc_group_sampler_reset(ceg_mc_group_t* group);
  * Continuation: a run split over several calls gives the bytes of the one-call run if each call passes first_step advanced, cycle0
  *   advanced, prior = the summed counters (the last record's) and dmax / thetamax = the last record's dmax_next / thetamax_next.
  * Synchronous.  Not covered: one steps_per_cycle applies to the whole group (chains whose reference cycle lengths differ belong in
- *   different groups; chains whose run LENGTHS differ stop at their own last step with ceg_mc_group_set_chain_plan, below); snapshots of the positions every `printevery` cycles; the baseline_energy at cycle 0 inside the run (a caller
- *   composes it from two calls around ceg_mc_group_baseline). */
+ *   different groups; chains whose run LENGTHS differ stop at their own last step with ceg_mc_group_set_chain_plan, below); the baseline_energy at cycle 0 inside the run (a caller
+ *   composes it from two calls around ceg_mc_group_baseline).  The positions every `printevery` cycles and the minimum-energy
+ *   configuration: ceg_mc_group_set_recorder, below. */
 #define CEG_MC_ADAPT_DMAX     1
 #define CEG_MC_ADAPT_THETAMAX 2
 #define CEG_MC_CYCLES_MAX_RECORDS 16777216
@@ -1132,7 +1133,7 @@ CEG_API int ceg_mc_cell_lists(ceg_mc_t* handle, int32_t* cell_of, int32_t* idx_o
  *   stale; the caller installs the state again.
  * With no tempering installed every entry point enqueues exactly the launches and produces the bytes it produces without this section.
  * Not covered: step sizes and the cumulative counters stay with the chain, not the rung; exchanges under GCMC swaps; any pair
- *   schedule other than the alternating one; snapshots; exchanging configurations; SiteHopping. */
+ *   schedule other than the alternating one; exchanging configurations; SiteHopping. */
 typedef struct ceg_mc_tempering {       /* 32 bytes */
     int64_t every;                      /* >= 1: a round at the end of every cycle cc with cc % every == 0 */
     int64_t record_capacity;            /* >= 0: cycles of records kept */
@@ -1151,6 +1152,88 @@ CEG_API int ceg_mc_group_set_tempering(ceg_mc_group_t* group, const ceg_mc_tempe
 CEG_API int ceg_mc_group_tempering_read(ceg_mc_group_t* group, int32_t* rung_out /*[K]*/, double* energy_out /*[K]*/,
                                         int64_t* pair_counts_out /*[K][2]*/, ceg_mc_exchange_record_t* records_out /*[cycles][K]*/,
                                         int64_t* cycles_out);
+
+/* ---- recorder: position snapshots and a minimum-energy record at cycle ends (src/simulation.jl:784-799, parameterinputs.jl:86-108) ----
+ * The trajectory of run_montecarlo! (put!(output, o) every `printevery` cycles) and RMinimumEnergy (the lowest-energy configuration
+ * seen at any cycle end) for the K chains of a group, taken inside ceg_mc_group_sweep_cycles / ceg_mc_group_sweep_gcmc_cycles with no
+ * host round trip: while a recorder is installed those two calls enqueue one more launch (k_mcg_snapshot, one workgroup per chain) at
+ * the cycle ends where the recorder wants one, behind k_mcg_cycle_end and, with tempering, behind k_mcg_exchange.  The launch reads
+ * chain state and writes only memory the recorder owns; everything is read once, after the run.  Plain loads and stores; stream
+ * order is the only synchronisation; the bytes do not depend on the order in which workgroups or lanes arrive.
+ *
+ * set_recorder copies `energy` (host memory), allocates the store (frame_capacity frames, zeroed) and synchronises the group; NULL
+ *   removes the recorder.  With track_min it also copies every chain's state NOW into the chain's best slot, with the given energy
+ *   and mink = -1 (one launch), so it needs every member consistent.
+ * Frame: at the end of cycle cc = cycle0 + j of a *_cycles call iff every > 0 && cc >= origin && (cc - origin) % every == 0.  With
+ *   cycle0 counted as run_montecarlo does (1 + the cycles run so far), origin = ninit gives the reference's idx_cycle % printevery == 0.
+ * Body of a frame, per (frame, chain), in four arrays [frame][chain][...]:
+ *   double  xyz[max_atoms][3], int32 kind[max_atoms]   in MOLECULE order: the atoms of molecule 0, then 1, ..., each molecule's atoms
+ *                                                      in slot order -- the bytes and the order of ceg_mc_get_state;
+ *   int32   mol_first[max_molecules + 1]               first atom of every molecule and the atom count, as ceg_mc_set_guests takes it;
+ *   int32   species[max_molecules]                     ceg_mc_group_sweep_gcmc_cycles: the species of molecule j from the device's own
+ *                                                      table; -1 in the plain entry point, in ceg_mc_group_snapshot and at installation.
+ *   Entries beyond the counts are zero.  During a GCMC call nmol, the high-water mark of the atom slots and the species come from the
+ *   device's molecule table (the views' counts are stale there).
+ * Record: one ceg_mc_snapshot_record_t per (frame, chain).  A chain whose nmol > max_molecules or natoms > max_atoms, or whose
+ *   molecule table fails a range check (a molecule outside [1, 16] atoms or outside the atom slots in use), gets flags |= 1, the counts
+ *   as they are in the chain (natoms: the sum of the molecules' counts) and NO body (zeros); that is not an error.  flags |= 2: the
+ *   chain was stopped (chain plan) or halted (full cell) at `step`: the frame repeats the frozen state.
+ * Energy at the end of cycle j of a call: energy at the call's start + the call's delta_moves as it stands then, and in the GCMC
+ *   entry point (that + delta_moves) + delta_swaps; FP64, in this order, no contraction (the definition tempering uses; the recorder
+ *   keeps its own copy).  After a call that ended well the value after its last cycle is the next call's start value.  Under swaps
+ *   delta_swaps is compute_accept_move_swap's `diff`, not the state's energy change, so `energy` is that bookkeeping value.
+ * Minimum (track_min != 0): the launch runs at EVERY cycle end and implements `if Float64(e) < Float64(record.mine)` per chain:
+ *   strict, so ties keep the earlier cycle, and a NaN never wins.  The chain's record and body go to the chain's best slot (its tail
+ *   zeroed; a chain that does not fit: flags 1 and a zeroed body), mine = e, mink = cc.  A chain stopped or halted at the cycle's
+ *   last step is not tested.  Neither ceg_mc_group_snapshot nor recorder_rebase tests or resets the minimum.
+ * snapshot: one frame of the resident state now (cycle = step = -1, energy = the recorder's running energy), asynchronous on the
+ *   group's stream like ceg_mc_group_sample.
+ * recorder_rebase replaces the running energies ([K], host memory, finite): the precise energy at idx_cycle == 0
+ *   (simulation.jl:788-790).  Synchronises the group.
+ * recorder_read synchronises and copies frames [first_frame, first_frame + nframes) of what is asked for (every pointer may be
+ *   NULL): records [nframes][K], xyz [nframes][K][max_atoms][3], kind [nframes][K][max_atoms], mol_first
+ *   [nframes][K][max_molecules + 1], species [nframes][K][max_molecules]; *frames_out = the frames taken so far.
+ * recorder_min synchronises and copies per chain mink, mine, the best record and body ([K][...] as above), every pointer optional.
+ * Refusals, all before anything is launched or changed, the earlier recorder staying installed: CEG_ERR_INVALID for every < 0,
+ *   origin < 0, frame_capacity < 0, max_atoms < 1, max_molecules < 1, a missing or non-finite energy, a store (frame_capacity + 1
+ *   best slot) * K * bytes per chain above CEG_MC_RECORDER_MAX_BYTES; a *_cycles call whose due frames exceed the room left, or on a
+ *   stale recorder; ceg_mc_group_sweep_gcmc_cycles with track_min and any species whose swap probability is > 0; snapshot on a full
+ *   store, a stale recorder or without one; a read window outside the frames taken; recorder_min without track_min or on a stale
+ *   recorder.  CEG_ERR_HIP, with the chain's index in ceg_last_error(), for snapshot, or set_recorder with track_min, on a group
+ *   with an inconsistent member.
+ * A sweep that fails (CEG_ERR_HIP) once its steps have been enqueued takes none of its frames (they are zeroed again) and marks the
+ *   recorder stale until set_recorder is called again; the frames taken before stay readable, the minimum does not (the failed
+ *   call's launches may have written it).
+ * With no recorder installed every entry point enqueues exactly the launches and produces the bytes it produces without this
+ *   section; with one installed, no frame due and no track_min, no launch is added; logs, statistics, records and final states are
+ *   the same bytes with and without it.  The two plain sweeps (ceg_mc_group_sweep / _sweep_gcmc) ignore the recorder, and like any
+ *   other call that moves a chain they make its running energies stale: rebase.
+ * Out of scope: the PDB / stream / zst / restart file formats of output.jl; restoring a frame on the device (the host route through
+ *   ceg_mc_set_guests is the one provided); a minimum per rung; ShootingStarMinimizer's spawned quenches (a caller composes them
+ *   from TRamp / TAnneal temperature tables, this minimum and ceg_mc_set_guests). */
+#define CEG_MC_RECORDER_MAX_BYTES ((int64_t)8 << 30)
+typedef struct ceg_mc_recorder {        /* 48 bytes */
+    int64_t every;                      /* >= 0; 0: no periodic frames */
+    int64_t origin;                     /* >= 0 */
+    int64_t frame_capacity;             /* >= 0 frames kept */
+    int32_t max_atoms, max_molecules;   /* per chain and frame, >= 1 */
+    int32_t track_min, _pad;            /* != 0: RMinimumEnergy per chain */
+    const double* energy;               /* [K] K: the total energy of every chain now, finite */
+} ceg_mc_recorder_t;
+typedef struct ceg_mc_snapshot_record { /* 40 bytes */
+    int64_t cycle, step;                /* cc and the absolute last step of the cycle; -1, -1: snapshot, or the state at installation */
+    double  energy;
+    int32_t nmol, natoms;               /* as they are in the chain, also when they do not fit */
+    int32_t flags, _pad;                /* 1: does not fit, no body; 2: the chain was stopped or halted at `step` */
+} ceg_mc_snapshot_record_t;
+CEG_API int ceg_mc_group_set_recorder(ceg_mc_group_t* group, const ceg_mc_recorder_t* recorder);   /* NULL removes it */
+CEG_API int ceg_mc_group_snapshot(ceg_mc_group_t* group);
+CEG_API int ceg_mc_group_recorder_rebase(ceg_mc_group_t* group, const double* energy /*[K]*/);
+CEG_API int ceg_mc_group_recorder_read(ceg_mc_group_t* group, int64_t first_frame, int64_t nframes, ceg_mc_snapshot_record_t* records_out,
+                                       double* xyz_out, int32_t* kind_out, int32_t* mol_first_out, int32_t* species_out, int64_t* frames_out);
+CEG_API int ceg_mc_group_recorder_min(ceg_mc_group_t* group, int64_t* mink_out /*[K]*/, double* mine_out /*[K]*/,
+                                      ceg_mc_snapshot_record_t* record_out /*[K]*/, double* xyz_out, int32_t* kind_out, int32_t* mol_first_out,
+                                      int32_t* species_out);
 
 /* ---- baseline_energy (src/montecarlo.jl:530-542) of one chain, or of every chain of a group, from the resident state ----
  * What run_montecarlo! asks for at its start, at the first production cycle, after a move that risks underflow and for its final
