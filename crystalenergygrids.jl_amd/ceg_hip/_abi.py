@@ -134,6 +134,34 @@ MC_SNAPSHOT_RECORD_DTYPE = np.dtype([('cycle', '<i8'), ('step', '<i8'), ('energy
                                      ('flags', '<i4'), ('_pad', '<i4')], align=True)
 assert (C.sizeof(McRecorder), MC_SNAPSHOT_RECORD_DTYPE.itemsize) == (48, 40)
 
+SITE_MAX_MOLECULES = 4096    # CEG_SITE_MAX_MOLECULES
+SITE_FRAME_TAKEN, SITE_FRAME_DROPPED, SITE_NEW_MINIMUM = 1, 2, 4      # flags of a site cycle record
+
+
+class SiteParams(C.Structure):
+    """``ceg_site_params_t`` (``stream_id`` [K] uint32 in host memory, or NULL)"""
+    _fields_ = [("seed", C.c_uint64), ("first_step", C.c_uint64), ("stream_id", C.c_void_p)]
+
+
+class SiteCycles(C.Structure):
+    """``ceg_site_cycles_t`` (``temperature`` [ncycles][K] float64 in host memory)"""
+    _fields_ = [("ncycles", C.c_int64), ("steps_per_cycle", C.c_int64), ("cycle0", C.c_int64), ("temperature", C.c_void_p)]
+
+
+class SiteRecorder(C.Structure):
+    """``ceg_site_recorder_t``"""
+    _fields_ = [("every", C.c_int64), ("origin", C.c_int64), ("frame_capacity", C.c_int64), ("track_min", C.c_int32), ("_pad", C.c_int32)]
+
+
+SITE_STATS_DTYPE = np.dtype([('attempted', '<i8'), ('accepted', '<i8'), ('delta', '<f8'), ('energy', '<f8')], align=True)
+SITE_CYCLE_RECORD_DTYPE = np.dtype([('cycle', '<i8'), ('temperature', '<f8'), ('energy', '<f8'), ('delta', '<f8'), ('attempted', '<i8'),
+                                    ('accepted', '<i8'), ('flags', '<i4'), ('_pad', '<i4')], align=True)
+SITE_RECORD_DTYPE = np.dtype([('molecule', '<i4'), ('old_site', '<i4'), ('new_site', '<i4'), ('accepted', '<i4'), ('before', '<f8'),
+                              ('after', '<f8'), ('u', '<f8')], align=True)
+SITE_FRAME_RECORD_DTYPE = np.dtype([('cycle', '<i8'), ('energy', '<f8')], align=True)
+assert (C.sizeof(SiteParams), C.sizeof(SiteCycles), C.sizeof(SiteRecorder), SITE_STATS_DTYPE.itemsize, SITE_CYCLE_RECORD_DTYPE.itemsize,
+        SITE_RECORD_DTYPE.itemsize, SITE_FRAME_RECORD_DTYPE.itemsize) == (24, 32, 32, 32, 56, 40, 16)
+
 c_double_p = C.POINTER(C.c_double)
 c_float_p = C.POINTER(C.c_float)
 c_int32_p = C.POINTER(C.c_int32)
@@ -301,6 +329,20 @@ PROTOTYPES = {
                                           C.c_void_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                           C.c_double, C.c_double, c_double_p, C.c_int32, c_double_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ceg_site_tables": (C.c_int, [C.c_void_p, c_int32_p, C.c_int32, c_double_p, C.c_int32, C.c_double, C.c_double, c_double_p, c_double_p, c_double_p]),
+    "ceg_site_tables_device": (C.c_int, [C.c_void_p, c_int32_p, C.c_int32, c_double_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "ceg_site_group_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_double,
+                                        C.POINTER(C.c_void_p)]),
+    "ceg_site_group_destroy": (C.c_int, [C.c_void_p]),
+    "ceg_site_group_sweep_cycles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ceg_site_group_baseline": (C.c_int, [C.c_void_p, c_double_p]),
+    "ceg_site_group_rebase": (C.c_int, [C.c_void_p]),
+    "ceg_site_group_get_populations": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ceg_site_group_set_populations": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ceg_site_group_set_recorder": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ceg_site_group_recorder_read": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, c_int64_p]),
+    "ceg_site_group_recorder_min": (C.c_int, [C.c_void_p, c_int64_p, c_double_p, C.c_void_p]),
     "ceg_recip_energy_device": (C.c_int, [C.c_void_p, C.c_void_p, c_double_p, C.c_int32, C.c_int64, C.c_double, C.c_double,
                                           C.c_void_p, C.c_void_p]),
 }

@@ -38,6 +38,11 @@ Isotherms (``ceg_mc_group_set_chain_plan``, ``DeviceMonteCarloGroup.make_isother
 
 Neighbour cells (``ceg_mc_group_set_device_cells``): :class:`CellBook` restates the cell lists of a chain (``CellMirror`` of
 ``csrc/ceg_mc_state.h``: ``bin_of``, ``take_out``, ``put_in``, ``refresh``) and :func:`replay_cell_book` follows them through a sweep's log.
+
+Site hopping (``ceg_site_group_sweep_cycles``, ``csrc/ceg_site.hip``): purpose 10 draws the molecule and the site of a hop, purpose 3 the
+acceptance; :func:`site_propose`, :func:`site_row_sum` (the device's summation order), :func:`site_movement_energy`, :func:`site_step`
+and :func:`site_replay` restate ``k_site_sweep``, :func:`site_baseline` is ``baseline_energy(::SiteHopping)`` in extended precision, and
+:func:`site_random_population` (purpose 11, host only) draws the ``randperm`` start of a quench.  The section at the end of this file.
 """
 from __future__ import annotations
 
@@ -786,3 +791,147 @@ def phiPV_div_k(phi: float, pressure_pa: float, volume_A3: float) -> float:
     """``φPV_div_k`` of one species in K (simulation.jl:714-715): ``φ * uconvert(u"K", abs(P) * V / u"k")`` with P in Pa, V in A^3
     (1e-30 m^3) and k = 1.380649e-23 J/K.  The fugacity coefficient ``phi`` is the caller's (Clapeyron's in the reference, :707-712)."""
     return float(phi) * (abs(float(pressure_pa)) * float(volume_A3) * 1e-30 / 1.380649e-23)
+
+
+# ------------------------------------------------------------------ site hopping (ceg_site_group_*, csrc/ceg_site.hip)
+# The reference's second Monte-Carlo model (src/sitehopping.jl): m molecules on n sites, all physics in ``frameworkenergies[n]`` and
+# ``interactions[n, n]`` (symmetric, the diagonal 1e100).  Sites are 0-based here, as on the device.  The step of stream ``c`` at the
+# absolute step ``s``:
+#   10 SITE_SELECT  molecule ``i = min(floor(U(w0, w1) m), m - 1)``, site ``new = min(floor(U(w2, w3) n), n - 1)``
+#   3  acceptance   ``u = U(w0, w1)``
+#   before = framework[old] + R(old), after = framework[new] + R(new), R the row sum in the device's order (:func:`site_row_sum`);
+#   accepted iff ``after < before`` or ``u < exp((before - after) / T)``; then ``energy += after - before`` and ``population[i] = new``.
+# A hop onto an occupied site meets 1e100 and is rejected by the rule; a hop onto the own site has after == before and is accepted.
+#   11 SITE_POPULATE  :func:`site_random_population`, the host-side start of ``run_random_quenching``; never drawn on the device.
+SITE_SELECT = 10
+SITE_POPULATE = 11
+_LANES = np.arange(64)
+
+
+def site_propose(seed: int, step: int, stream_id: int, m: int, n: int):
+    """-> (molecule ``i``, site ``new``, acceptance draw ``u``) of stream ``stream_id`` at the absolute step ``step``."""
+    w = draw(seed, step, stream_id, SITE_SELECT)
+    i = min(int(math.floor(uniform(w[0], w[1]) * float(m))), m - 1)
+    new = min(int(math.floor(uniform(w[2], w[3]) * float(n))), n - 1)
+    return i, new, acceptance_draw(seed, step, stream_id)
+
+
+def site_row_sum(terms) -> float:
+    """The sum of ``terms`` [m] in the order of ``k_site_sweep``, a fixed function of m alone: lane ``l`` of 64 adds its terms
+    ``l, l + 64, l + 128, ...`` in rising order onto +0.0; then for ``o = 32, 16, 8, 4, 2, 1`` every lane replaces its sum by
+    (its sum) + (the sum of lane ``l ^ o``); the result is lane 0's.  The caller puts +0.0 where a term is left out (the same bits:
+    such a sum is never -0.0)."""
+    t = np.asarray(terms, dtype=np.float64).reshape(-1)
+    rows = -(-len(t) // 64)
+    padded = np.zeros(rows * 64, dtype=np.float64)
+    padded[:len(t)] = t
+    lanes = np.zeros(64, dtype=np.float64)
+    for r in padded.reshape(rows, 64):          # (+0.0 for the lanes whose terms have run out: bit-neutral)
+        lanes = lanes + r
+    for o in (32, 16, 8, 4, 2, 1):
+        lanes = lanes + lanes[_LANES ^ o]
+    return float(lanes[0])
+
+
+def site_movement_energy(framework, interactions, population, i: int, site=None) -> float:
+    """``movement_energy(sh, i, si)`` (sitehopping.jl:114-121) in the device's order: ``framework[site] + R(site)`` with
+    ``R = site_row_sum(interactions[site, population[j]] for j != i, +0.0 at j == i)``.  ``site=None``: where molecule ``i`` sits."""
+    pop = np.asarray(population, dtype=np.int64)
+    s = int(pop[i]) if site is None else int(site)
+    terms = np.array(np.asarray(interactions, dtype=np.float64)[s, pop], dtype=np.float64)
+    terms[i] = 0.0
+    return float(np.float64(framework[s]) + np.float64(site_row_sum(terms)))
+
+
+class SiteStep(NamedTuple):
+    molecule: int
+    old_site: int
+    new_site: int
+    before: float
+    after: float
+    u: float
+    threshold: float          # exp((before - after) / T), what u is compared with when after >= before
+    accepted: bool
+
+
+def site_step(framework, interactions, population, seed: int, step: int, stream_id: int, temperature: float, decision=None) -> SiteStep:
+    """One step of one chain; ``population`` (a mutable integer array) is updated in place when the step is accepted.
+    ``decision`` not None: that decision is followed instead of the rule's (a replay of a log across an exp that rounds
+    differently on the host).  The caller adds ``after - before`` to its running energy when the step is accepted."""
+    m, n = len(population), len(framework)
+    i, new, u = site_propose(seed, step, stream_id, m, n)
+    old = int(population[i])
+    before = site_movement_energy(framework, interactions, population, i, old)
+    after = site_movement_energy(framework, interactions, population, i, new)
+    with np.errstate(over="ignore"):
+        x = float((np.float64(before) - np.float64(after)) / np.float64(temperature))
+    try:
+        e = math.exp(x)
+    except OverflowError:
+        e = math.inf
+    ok = bool(after < before or u < e)
+    if decision is not None:
+        ok = bool(decision)
+    if ok:
+        population[i] = new
+    return SiteStep(i, old, new, before, after, u, e, ok)
+
+
+class SiteReplay(NamedTuple):
+    steps: list               # [ncycles * steps_per_cycle] SiteStep
+    population: np.ndarray    # uint16[m] at the end
+    energy: float             # the running energy at the end
+    delta: float              # the sum of the accepted changes added to ``delta``
+    cycle_energy: np.ndarray  # float64[ncycles] at the cycle ends
+    cycle_population: np.ndarray   # uint16[ncycles, m] at the cycle ends
+    accepted: int
+
+
+def site_replay(framework, interactions, population, energy: float, seed: int, first_step: int, stream_id: int, temperatures,
+                steps_per_cycle: int, log=None, delta: float = 0.0) -> SiteReplay:
+    """One chain through ``len(temperatures)`` cycles of ``steps_per_cycle`` steps from the absolute step ``first_step``, as
+    ``ceg_site_group_sweep_cycles`` runs it.  ``log`` (the chain's column of the device log, with a field ``accepted``): its
+    decisions are followed."""
+    fw = np.asarray(framework, dtype=np.float64)
+    it = np.asarray(interactions, dtype=np.float64)
+    pop = np.array(population, dtype=np.int64)
+    e, d, acc = np.float64(energy), np.float64(delta), 0
+    steps, ce, cp = [], [], []
+    t = 0
+    for T in temperatures:
+        for _ in range(int(steps_per_cycle)):
+            dec = None if log is None else bool(log["accepted"][t])
+            st = site_step(fw, it, pop, seed, int(first_step) + t, stream_id, float(T), dec)
+            if st.accepted:
+                diff = np.float64(st.after) - np.float64(st.before)
+                e, d, acc = e + diff, d + diff, acc + 1
+            steps.append(st)
+            t += 1
+        ce.append(float(e))
+        cp.append(pop.astype(np.uint16))
+    m = len(pop)
+    return SiteReplay(steps, pop.astype(np.uint16), float(e), float(d), np.array(ce, dtype=np.float64),
+                      np.array(cp, dtype=np.uint16).reshape(len(ce), m), acc)
+
+
+def site_baseline(framework, interactions, population, tailcorrection: float = 0.0):
+    """``baseline_energy(::SiteHopping)`` (sitehopping.jl:105-112) in extended precision:
+    tail correction + sum of ``framework[population]`` + sum over i < j of ``interactions[population[i], population[j]]``."""
+    pop = np.asarray(population, dtype=np.int64)
+    sub = np.asarray(interactions, dtype=np.longdouble)[np.ix_(pop, pop)]
+    inter = np.triu(sub, 1).sum(dtype=np.longdouble)
+    return np.longdouble(tailcorrection) + np.asarray(framework, dtype=np.longdouble)[pop].sum(dtype=np.longdouble) + inter
+
+
+def site_random_population(seed: int, stream_id: int, n: int, m: int) -> np.ndarray:
+    """A ``randperm``-style start (sitehopping.jl:87-88: ``resize!(randperm(n), m)``): the first ``m`` entries of a Fisher-Yates
+    shuffle of ``0..n-1`` driven by purpose 11 of stream ``stream_id``: for ``j = 0..m-1`` the block of step ``j`` gives
+    ``r = j + min(floor(U(w0, w1) (n - j)), n - j - 1)`` and entries ``j`` and ``r`` are exchanged.  Duplicate-free by construction."""
+    if not 0 <= m <= n <= 65535:
+        raise ValueError("0 <= m <= n <= 65535")
+    perm = list(range(n))
+    for j in range(m):
+        w = draw(seed, j, stream_id, SITE_POPULATE)
+        r = j + min(int(math.floor(uniform(w[0], w[1]) * float(n - j))), n - j - 1)
+        perm[j], perm[r] = perm[r], perm[j]
+    return np.array(perm[:m], dtype=np.uint16)

@@ -1,0 +1,365 @@
+"""Site hopping on the device (``ceg_site_group_*``, ``csrc/ceg_site.hip``): the reference's second Monte-Carlo model
+(``src/sitehopping.jl``), in which a mobile species hops between a finite set of sites and all physics is folded into two tables,
+``frameworkenergies[n]`` and ``interactions[n, n]``.
+
+:class:`SiteHopping` holds the tables, a population and the tail correction; :class:`DeviceSiteHoppingGroup` keeps K chains on one
+copy of the tables on the device and runs whole cycles of all of them inside one kernel; :func:`run_montecarlo` and
+:func:`run_random_quenching` are ``run_montecarlo!(::SiteHopping, ...)`` (simulation.jl:863-1010, ``groupcycles = nothing``) and
+``run_random_quenching`` on top of it.  Sites are 0-based here (the reference's are 1-based).  The step itself is specified in
+``include/ceg_hip.h`` and restated in :mod:`ceg_hip.mcrng` (``site_step``, ``site_replay``).
+
+:func:`build_site_tables` is the reference's constructor (sitehopping.jl:41-82): both tables from a guest-free
+:class:`ceg_hip.energy.DeviceMonteCarlo` of the mobile species in three launches (``ceg_site_tables``)."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple, Optional
+
+import numpy as np
+
+from . import _abi, mcrng
+
+
+class SiteHopping:
+    """``SiteHopping`` of the reference, without the geometry: ``frameworkenergies`` float64[n] (K), ``interactions`` float64[n, n] (K,
+    symmetric, the diagonal 1e100), ``population`` uint16[m] (0-based sites, no site twice) and ``tailcorrection`` (K).
+
+    ``population`` may be an integer m: then it is ``mcrng.site_random_population(seed, stream_id, n, m)``, the ``randperm`` start of
+    sitehopping.jl:85-88 drawn from the Philox stream."""
+
+    def __init__(self, frameworkenergies, interactions, population, tailcorrection: float = 0.0, *, seed: int = 0, stream_id: int = 0):
+        self.frameworkenergies = np.ascontiguousarray(frameworkenergies, dtype=np.float64).reshape(-1)
+        n = len(self.frameworkenergies)
+        self.interactions = np.ascontiguousarray(interactions, dtype=np.float64)
+        if self.interactions.shape != (n, n):
+            raise ValueError(f"interactions must be [{n}, {n}]")
+        if n > 65535:
+            raise ValueError("Cannot handle more than 65535 different sites")                  # sitehopping.jl:25
+        if isinstance(population, (int, np.integer)):
+            population = mcrng.site_random_population(seed, stream_id, n, int(population))
+        self.population = check_population(population, n)
+        self.tailcorrection = float(tailcorrection)
+
+    @classmethod
+    def from_setup(cls, mc, sites, population, *, species: int = 0, tailcorrection: Optional[float] = None, device: int = 0, seed: int = 0,
+                   stream_id: int = 0) -> "SiteHopping":
+        """``SiteHopping(sites, framework, forcefield, syst_mol, population)`` (sitehopping.jl:23-96): ``mc`` is the
+        ``MonteCarloSetup`` of the mobile species alone WITHOUT molecules (``setup_montecarlo(..., [(molecule, 0)], blockfiles=[False])``),
+        or a guest-free ``DeviceMonteCarlo`` of it; the tables are built on the device (:func:`build_site_tables`).  The tail
+        correction depends on the number of molecules and is the caller's (default: the setup's own)."""
+        from .energy import DeviceMonteCarlo
+        dev = mc if isinstance(mc, DeviceMonteCarlo) else DeviceMonteCarlo(mc, device, upload_guests=False)
+        try:
+            fw, _rec, it = build_site_tables(dev, sites, species)
+        finally:
+            if dev is not mc:
+                dev.close()
+        tail = float(getattr(dev.mc, "tailcorrection", 0.0)) if tailcorrection is None else float(tailcorrection)
+        sh = cls(fw, it, population, tail, seed=seed, stream_id=stream_id)
+        sh.sites = np.ascontiguousarray(sites, dtype=np.float64).reshape(len(fw), -1, 3)
+        return sh
+
+    @property
+    def nsites(self) -> int:
+        return len(self.frameworkenergies)
+
+    def baseline_energy(self) -> float:
+        """``baseline_energy(sh)`` (sitehopping.jl:105-112) on the host, in extended precision."""
+        return float(mcrng.site_baseline(self.frameworkenergies, self.interactions, self.population, self.tailcorrection))
+
+    def __repr__(self):
+        return f"SiteHopping setup with {len(self.population)} molecules among {self.nsites} sites"
+
+
+def ewald_offsets(mc, species: int, shape):
+    """The count-dependent constants of the ``EwaldContext`` (ewald.jl:497-544) that the tables carry: with
+    ``c(N) = 2 energy_net_charges(N) + static_contribution(N)`` for N molecules of ``species`` alone, ``(c(1), c(2) - 2 c(1))``;
+    ``shape`` float64[m_atoms, 3]: the rigid molecule (any site).  ``(0.0, 0.0)`` without Ewald summation."""
+    from .hostmirror.ewald import ewald_context_constants
+    from .hostmirror.raspa import RASPASystem
+    if mc.ewald.alpha == 0.0:
+        return 0.0, 0.0
+    shape = np.asarray(shape, dtype=np.float64).reshape(-1, 3)
+    m = len(shape)
+    q = np.array([mc.charges[ix] for ix in mc.ffidx[species]], dtype=np.float64)
+    one = RASPASystem(mc.mat, shape, [""] * m, np.zeros(m), q, True)
+
+    def c(count):
+        enc, static = ewald_context_constants(mc.ewald, [[one] * count])
+        return 2.0 * enc + static
+    return c(1), c(2) - 2.0 * c(1)
+
+
+def build_site_tables(dev, sites, species: int = 0, on_device: bool = False):
+    """``ceg_site_tables``: (framework[n], recip[n], interactions[n, n]) in K for the ``sites`` float64[n, m_atoms, 3] (Cartesian A) of
+    species ``species`` of ``dev``, a :class:`ceg_hip.energy.DeviceMonteCarlo` that holds no guest (``upload_guests=False`` on a setup
+    without molecules).  ``framework[i] = Number(baseline_energy({s_i}).er)``, ``recip[i]`` its inter + reciprocal part
+    (``ewaldenergies[i]``), ``interactions[i, j]`` = inter + reciprocal of ``baseline_energy({s_i, s_j}).er`` minus ``recip[i]`` minus
+    ``recip[j]``, the diagonal 1e100.  ``on_device``: three float64 torch tensors on the handle's device (``ceg_site_tables_device``),
+    which :class:`DeviceSiteHoppingGroup` reads in place."""
+    mc = dev.mc
+    kinds = np.ascontiguousarray([ix - 1 for ix in mc.ffidx[species]], dtype=np.int32)
+    pos = np.ascontiguousarray(sites, dtype=np.float64).reshape(-1, len(kinds), 3)
+    n = len(pos)
+    off1, off2 = ewald_offsets(mc, species, pos[0]) if n else (0.0, 0.0)
+    lib = dev._lib
+    if on_device:
+        import torch
+        fw, rec = (torch.empty(n, dtype=torch.float64, device="cuda") for _ in range(2))
+        it = torch.empty((n, n), dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        _abi.check(lib, lib.ceg_site_tables_device(dev._h, _abi.i32ptr(kinds), len(kinds), _abi.dptr(pos.reshape(-1)), n, off1, off2,
+                                                   C.c_void_p(fw.data_ptr()), C.c_void_p(rec.data_ptr()), C.c_void_p(it.data_ptr())))
+        return fw, rec, it
+    fw, rec, it = np.empty(n), np.empty(n), np.empty((n, n))
+    _abi.check(lib, lib.ceg_site_tables(dev._h, _abi.i32ptr(kinds), len(kinds), _abi.dptr(pos.reshape(-1)), n, off1, off2, _abi.dptr(fw),
+                                        _abi.dptr(rec), _abi.dptr(it.reshape(-1))))
+    return fw, rec, it
+
+
+def check_population(population, n: int) -> np.ndarray:
+    """-> uint16[m]; raises where a site is outside ``0..n-1`` or used twice."""
+    p = np.asarray(population)
+    if p.ndim != 1 or (p.size and (p.min() < 0 or p.max() >= n)):
+        raise ValueError(f"Cannot populate site {int(p.max()) if p.size else -1} among {n} sites")   # sitehopping.jl:93
+    if len(np.unique(p)) != len(p):
+        raise ValueError("a site is populated twice")
+    return np.ascontiguousarray(p, dtype=np.uint16)
+
+
+class DeviceSiteHoppingGroup:
+    """K chains of m molecules on one copy of the tables, resident on ``device`` (``ceg_site_group_t``).
+
+    ``populations``: integer [K, m] (0-based sites).  ``frameworkenergies`` / ``interactions`` may be torch tensors on that device
+    (float64, contiguous): the group then reads them in place and keeps a reference."""
+
+    def __init__(self, frameworkenergies, interactions, populations, tailcorrection: float = 0.0, device: int = 0):
+        self._lib = _abi.load_library()
+        self._h = None
+        pops = np.ascontiguousarray(populations)
+        if pops.ndim != 2:
+            raise ValueError("populations must be [K, m]")
+        if pops.size and (pops.min() < 0 or pops.max() > 65535):
+            raise ValueError("sites must fit UInt16")
+        pops = np.ascontiguousarray(pops, dtype=np.uint16)
+        self.k, self.m = (int(x) for x in pops.shape)
+        on_device = hasattr(frameworkenergies, "data_ptr")
+        if on_device != hasattr(interactions, "data_ptr"):
+            raise ValueError("both tables on the device or both on the host")
+        if on_device:
+            import torch
+            for t in (frameworkenergies, interactions):
+                if t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda or (t.device.index or 0) != device:
+                    raise ValueError("device tables must be contiguous float64 tensors on the group's device")
+            self.n = int(frameworkenergies.numel())
+            if tuple(interactions.shape) != (self.n, self.n):
+                raise ValueError(f"interactions must be [{self.n}, {self.n}]")
+            torch.cuda.synchronize(device)
+            self._keep = (frameworkenergies, interactions)
+            fw, it = C.c_void_p(frameworkenergies.data_ptr()), C.c_void_p(interactions.data_ptr())
+        else:
+            f = np.ascontiguousarray(frameworkenergies, dtype=np.float64).reshape(-1)
+            i = np.ascontiguousarray(interactions, dtype=np.float64)
+            self.n = len(f)
+            if i.shape != (self.n, self.n):
+                raise ValueError(f"interactions must be [{self.n}, {self.n}]")
+            self._keep = (f, i)
+            fw, it = C.c_void_p(f.ctypes.data), C.c_void_p(i.ctypes.data)
+        self.tailcorrection = float(tailcorrection)
+        h = C.c_void_p()
+        _abi.check(self._lib, self._lib.ceg_site_group_create(int(device), self.n, self.m, self.k, fw, it, 1 if on_device else 0,
+                                                              C.c_void_p(pops.ctypes.data), self.tailcorrection, C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_setups(cls, setups, device: int = 0) -> "DeviceSiteHoppingGroup":
+        """One chain per :class:`SiteHopping`; all must share the tables of the first."""
+        first = setups[0]
+        for sh in setups[1:]:
+            if sh.frameworkenergies is not first.frameworkenergies and not (
+                    np.array_equal(sh.frameworkenergies, first.frameworkenergies) and np.array_equal(sh.interactions, first.interactions)):
+                raise ValueError("the chains of a group share one pair of tables")
+            if sh.tailcorrection != first.tailcorrection or len(sh.population) != len(first.population):
+                raise ValueError("the chains of a group share the tail correction and the number of molecules")
+        return cls(first.frameworkenergies, first.interactions, np.stack([sh.population for sh in setups]), first.tailcorrection, device)
+
+    def sweep_cycles(self, ncycles: int, seed: int, first_step: int = 0, *, temperature, steps_per_cycle: Optional[int] = None, cycle0: int = 0,
+                     stream_id=None, log: bool = False):
+        """``ceg_site_group_sweep_cycles``: ``ncycles`` cycles of ``steps_per_cycle`` (default m, as the reference) steps of every chain.
+        ``temperature``: a scalar, [K] or [ncycles, K].  -> (stats [K] ``_abi.SITE_STATS_DTYPE``, cycle records [ncycles, K]
+        ``_abi.SITE_CYCLE_RECORD_DTYPE``, log [ncycles * steps_per_cycle, K] ``_abi.SITE_RECORD_DTYPE`` or None)."""
+        ncycles = int(ncycles)
+        spc = self.m if steps_per_cycle is None else int(steps_per_cycle)
+        T = np.asarray(temperature, dtype=np.float64)
+        T = np.ascontiguousarray(np.broadcast_to(T if T.ndim == 2 else T.reshape(1, -1), (max(ncycles, 0), self.k)), dtype=np.float64)
+        ids = None if stream_id is None else np.ascontiguousarray(stream_id, dtype=np.uint32)
+        if ids is not None and ids.shape != (self.k,):
+            raise ValueError("stream_id must be [K]")
+        params = _abi.SiteParams(int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_step), ids.ctypes.data if ids is not None else None)
+        cycles = _abi.SiteCycles(ncycles, spc, int(cycle0), T.ctypes.data if T.size else None)
+        stats = np.zeros(self.k, dtype=_abi.SITE_STATS_DTYPE)
+        recs = np.zeros((max(ncycles, 0), self.k), dtype=_abi.SITE_CYCLE_RECORD_DTYPE)
+        steps = np.zeros((max(ncycles, 0) * spc, self.k), dtype=_abi.SITE_RECORD_DTYPE) if log else None
+        _abi.check(self._lib, self._lib.ceg_site_group_sweep_cycles(self._h, C.byref(params), C.byref(cycles), stats.ctypes.data,
+                                                                    recs.ctypes.data if recs.size else None,
+                                                                    steps.ctypes.data if (steps is not None and steps.size) else None))
+        return stats, recs, steps
+
+    def stats(self) -> np.ndarray:
+        """The counters, ``delta`` and the running energy of every chain now (a call of no cycles)."""
+        return self.sweep_cycles(0, 0, temperature=1.0)[0]
+
+    def baseline_energies(self) -> np.ndarray:
+        """``baseline_energy`` (sitehopping.jl:105-112) of every chain, one launch -> float64[K]."""
+        out = np.empty(self.k, dtype=np.float64)
+        _abi.check(self._lib, self._lib.ceg_site_group_baseline(self._h, _abi.dptr(out)))
+        return out
+
+    def rebase(self) -> None:
+        """Every chain's running energy becomes its baseline (the reference's ``idx_cycle == 0`` step)."""
+        _abi.check(self._lib, self._lib.ceg_site_group_rebase(self._h))
+
+    def populations(self) -> np.ndarray:
+        out = np.empty((self.k, self.m), dtype=np.uint16)
+        _abi.check(self._lib, self._lib.ceg_site_group_get_populations(self._h, out.ctypes.data))
+        return out
+
+    def set_populations(self, populations) -> None:
+        """Replaces every chain's population (validated as at creation) and rebases."""
+        p = np.asarray(populations)
+        if p.shape != (self.k, self.m) or (p.size and (p.min() < 0 or p.max() > 65535)):
+            raise ValueError("populations must be [K, m] of sites that fit UInt16")
+        p = np.ascontiguousarray(p, dtype=np.uint16)
+        _abi.check(self._lib, self._lib.ceg_site_group_set_populations(self._h, p.ctypes.data))
+
+    def set_recorder(self, every: Optional[int], origin: int = 0, capacity: int = 1024, track_min: bool = False) -> None:
+        """Frames of every chain's population and energy at the cycle ends where ``mcrng.snapshot_due(cc, origin, every)`` holds, and
+        with ``track_min`` the population of the lowest cycle-end energy (``RMinimumEnergy``), both written inside the sweep kernel.
+        ``every=None`` removes the recorder; ``every=0`` with ``track_min`` keeps the minimum only."""
+        if every is None:
+            _abi.check(self._lib, self._lib.ceg_site_group_set_recorder(self._h, None))
+            return
+        spec = _abi.SiteRecorder(int(every), int(origin), int(capacity), 1 if track_min else 0, 0)
+        _abi.check(self._lib, self._lib.ceg_site_group_set_recorder(self._h, C.byref(spec)))
+
+    def recorder_read(self, first_frame: int = 0, nframes: Optional[int] = None):
+        """-> (records [nframes, K] ``_abi.SITE_FRAME_RECORD_DTYPE``, populations uint16[nframes, K, m])"""
+        held = C.c_int64(0)
+        _abi.check(self._lib, self._lib.ceg_site_group_recorder_read(self._h, 0, 0, None, None, C.byref(held)))
+        if nframes is None:
+            nframes = held.value - int(first_frame)
+        recs = np.zeros((max(int(nframes), 0), self.k), dtype=_abi.SITE_FRAME_RECORD_DTYPE)
+        pops = np.zeros((max(int(nframes), 0), self.k, self.m), dtype=np.uint16)
+        _abi.check(self._lib, self._lib.ceg_site_group_recorder_read(self._h, int(first_frame), int(nframes), recs.ctypes.data if recs.size else None,
+                                                                     pops.ctypes.data if pops.size else None, C.byref(held)))
+        return recs, pops
+
+    def recorder_minimum(self):
+        """-> (mink int64[K] (-1: the state at installation), mine float64[K], populations uint16[K, m])"""
+        mink, mine = np.zeros(self.k, dtype=np.int64), np.zeros(self.k, dtype=np.float64)
+        pops = np.zeros((self.k, self.m), dtype=np.uint16)
+        _abi.check(self._lib, self._lib.ceg_site_group_recorder_min(self._h, _abi.i64ptr(mink), _abi.dptr(mine), pops.ctypes.data))
+        return mink, mine, pops
+
+    def close(self) -> None:
+        if self._h is not None:
+            self._lib.ceg_site_group_destroy(self._h)
+            self._h = None
+            self._keep = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SiteHoppingDrift(RuntimeError):
+    """The running energy of a chain left its baseline by more than the tolerance (simulation.jl:1003-1007)."""
+
+
+class SiteHoppingRun(NamedTuple):
+    energies: np.ndarray          # float64[nframes, K] (K): the baseline at idx_cycle 0, then every printevery cycles
+    populations: np.ndarray       # uint16[nframes, K, m]
+    cycles: np.ndarray            # int64[nframes] idx_cycle of the frames (0, printevery, 2 printevery, ...)
+    initial_energy: np.ndarray    # float64[K] baseline before the first cycle
+    final_energy: np.ndarray      # float64[K] baseline after the last cycle
+    records: np.ndarray           # [ninit + ncycles, K] _abi.SITE_CYCLE_RECORD_DTYPE
+    stats: np.ndarray             # [K] _abi.SITE_STATS_DTYPE
+    minimum: Optional[tuple]      # track_min: (idx_cycle int64[K] (0: the start of production), energy float64[K], populations uint16[K, m])
+
+
+def run_montecarlo(group: DeviceSiteHoppingGroup, temperatures, ncycles: int, ninit: int = 0, *, printevery: int = 1, seed: int = 0,
+                   first_step: int = 0, stream_id=None, drift_rtol: float = 1e-9, track_min: bool = False) -> SiteHoppingRun:
+    """``run_montecarlo!(::SiteHopping, simu)`` (simulation.jl:863-1010, ``groupcycles = nothing``) for every chain of ``group``:
+    baseline, ``ninit`` initialisation cycles, a rebase (the reference's precise energy at ``idx_cycle == 0``), ``ncycles``
+    production cycles of m steps with a frame every ``printevery`` cycles, then the drift check: ``|energy - baseline| <=
+    drift_rtol max(|baseline|, 1)`` per chain, else :class:`SiteHoppingDrift`.
+
+    ``temperatures``: [ninit + ncycles] or [ninit + ncycles, K].  The frames are ``idx_cycle`` 0 (the state after the
+    initialisation), then ``printevery``, ``2 printevery``, ...; ``printevery == 0``: frame 0 and, if ``ncycles > 0``, the last cycle.
+    The device counts cycles from 0: the initialisation cycles are 0..ninit-1, production cycle ``idx_cycle`` is
+    ``ninit - 1 + idx_cycle``.  The absolute steps run on from ``first_step``.  ``track_min``: ``RMinimumEnergy`` over the production
+    cycle ends, from the state at ``idx_cycle == 0`` on (strict <: a tie keeps the earlier cycle)."""
+    ncycles, ninit = int(ncycles), int(ninit)
+    T = np.asarray(temperatures, dtype=np.float64)
+    if T.ndim == 0:
+        T = np.full(ninit + ncycles, float(T))
+    T = np.broadcast_to(T.reshape(ninit + ncycles, -1), (ninit + ncycles, group.k))
+    e0 = group.baseline_energies()
+    recs = []
+    if ninit:
+        _s, r, _l = group.sweep_cycles(ninit, seed, first_step, temperature=T[:ninit], cycle0=0, stream_id=stream_id)
+        recs.append(r)
+    group.rebase()
+    every = int(printevery) if printevery > 0 else max(ncycles, 1)
+    nframes = ncycles // every
+    frames_e, frames_p, frames_c = [group.baseline_energies()], [group.populations()], [0]
+    stats = minimum = None
+    if track_min and not ncycles:
+        minimum = (np.zeros(group.k, dtype=np.int64), frames_e[0].copy(), frames_p[0].copy())
+    if ncycles:
+        group.set_recorder(every, origin=ninit - 1 + every, capacity=nframes, track_min=track_min)
+        stats, r, _l = group.sweep_cycles(ncycles, seed, first_step + ninit * group.m, temperature=T[ninit:], cycle0=ninit, stream_id=stream_id)
+        recs.append(r)
+        fr, fp = group.recorder_read()
+        if track_min:
+            mink, mine, best = group.recorder_minimum()
+            minimum = (np.where(mink < 0, 0, mink - (ninit - 1)), mine, best)
+        group.set_recorder(None)
+        for f in range(len(fr)):
+            frames_e.append(fr[f]["energy"].copy())
+            frames_p.append(fp[f])
+            frames_c.append(int(fr[f]["cycle"][0]) - (ninit - 1))
+    if stats is None:
+        stats = group.stats()
+    final = group.baseline_energies()
+    drift = np.abs(stats["energy"] - final)
+    bad = np.nonzero(~(drift <= drift_rtol * np.maximum(np.abs(final), 1.0)))[0]
+    if len(bad):
+        c = int(bad[0])
+        raise SiteHoppingDrift(f"chain {c}: running energy {stats['energy'][c]!r} against baseline {final[c]!r}")
+    records = np.concatenate(recs) if recs else np.zeros((0, group.k), dtype=_abi.SITE_CYCLE_RECORD_DTYPE)
+    return SiteHoppingRun(np.array(frames_e), np.array(frames_p, dtype=np.uint16), np.array(frames_c, dtype=np.int64), e0, final, records, stats, minimum)
+
+
+class QuenchingRun(NamedTuple):
+    start: np.ndarray             # uint16[N, m] the random populations the quenches began from
+    run: SiteHoppingRun           # run.minimum: the lowest cycle-end energy of each quench (RMinimumEnergy)
+
+
+def run_random_quenching(sh: SiteHopping, N: int, temperatures, ncycles: int, *, seed: int = 0, printevery: int = 0, device: int = 0) -> QuenchingRun:
+    """``run_random_quenching``: N independent quenches of ``sh``'s tables from random populations, as the chains of one group.
+    Chain c starts from ``mcrng.site_random_population(seed, c, n, m)`` (purpose 11 of stream c) and runs on stream c.
+    ``temperatures`` [ncycles] (the quench's schedule, shared) or [ncycles, N]."""
+    n, m = sh.nsites, len(sh.population)
+    start = np.stack([mcrng.site_random_population(seed, c, n, m) for c in range(int(N))])
+    with DeviceSiteHoppingGroup(sh.frameworkenergies, sh.interactions, start, sh.tailcorrection, device) as g:
+        run = run_montecarlo(g, temperatures, int(ncycles), 0, printevery=printevery, seed=seed, track_min=True)
+    return QuenchingRun(start, run)

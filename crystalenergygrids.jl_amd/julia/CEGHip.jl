@@ -1194,6 +1194,195 @@ function mc_group_baseline(g::Ptr{Cvoid}, k::Integer; refresh::Bool=false)
     out
 end
 
+# ------------------------------------------------------------------ site hopping (src/sitehopping.jl) on the device
+# `ceg_site_*` of include/ceg_hip.h: the two tables from a guest-free handle, and whole runs of K chains on them.
+# Sites are 0-based on the device: the wrappers below take and return the reference's 1-based `UInt16` sites.
+struct SiteParams                    # ceg_site_params_t (24 bytes)
+    seed::UInt64
+    first_step::UInt64
+    stream_id::Ptr{UInt32}           # [K] or C_NULL
+end
+
+struct SiteCycles                    # ceg_site_cycles_t (32 bytes)
+    ncycles::Int64
+    steps_per_cycle::Int64
+    cycle0::Int64
+    temperature::Ptr{Float64}        # [ncycles][K]
+end
+
+struct SiteStats                     # ceg_site_stats_t (32 bytes)
+    attempted::Int64
+    accepted::Int64
+    delta::Float64
+    energy::Float64
+end
+
+struct SiteCycleRecord               # ceg_site_cycle_record_t (56 bytes)
+    cycle::Int64
+    temperature::Float64
+    energy::Float64
+    delta::Float64
+    attempted::Int64
+    accepted::Int64
+    flags::Int32                     # 1: frame taken, 2: frame dropped (store full), 4: new minimum
+    _pad::Int32
+end
+
+struct SiteRecord                    # ceg_site_record_t (40 bytes)
+    molecule::Int32
+    old_site::Int32
+    new_site::Int32
+    accepted::Int32
+    before::Float64
+    after::Float64
+    u::Float64
+end
+
+struct SiteRecorder                  # ceg_site_recorder_t (32 bytes)
+    every::Int64
+    origin::Int64
+    frame_capacity::Int64
+    track_min::Int32
+    _pad::Int32
+end
+
+struct SiteFrameRecord               # ceg_site_frame_record_t (16 bytes)
+    cycle::Int64
+    energy::Float64
+end
+
+"""
+`ceg_site_tables`: `(frameworkenergies, ewaldenergies, interactions)` in K of the constructor of `SiteHopping`
+(src/sitehopping.jl:41-82) for `sites` (`3 x m_atoms x n`, Å) of a molecule with the 0-based `kinds`, from the guest-free handle `h`.
+`offset_one` = c(1) and `offset_pair` = c(2) - 2c(1) with c(N) = 2 `energy_net_charges` + `static_contribution` of an `EwaldContext`
+of N such molecules, in K.  UNVERIFIED: never executed.
+"""
+function site_tables(h::Ptr{Cvoid}, kinds::Vector{Int32}, sites::Array{Float64,3}, offset_one::Float64, offset_pair::Float64)
+    n = size(sites, 3)
+    fw = zeros(Float64, n); rec = zeros(Float64, n); inter = zeros(Float64, n, n)
+    GC.@preserve kinds sites fw rec inter begin
+        _check(ccall((:ceg_site_tables, LIB[]), Cint,
+                     (Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Float64}, Int32, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                     h, kinds, Int32(length(kinds)), sites, Int32(n), offset_one, offset_pair, fw, rec, inter))
+    end
+    fw, rec, inter
+end
+
+"`ceg_site_tables_device`: the same into device memory of the handle's device (three `Ptr{Cvoid}`).  UNVERIFIED: never executed."
+function site_tables_device!(d_fw::Ptr{Cvoid}, d_rec::Ptr{Cvoid}, d_inter::Ptr{Cvoid}, h::Ptr{Cvoid}, kinds::Vector{Int32}, sites::Array{Float64,3},
+                             offset_one::Float64, offset_pair::Float64)
+    GC.@preserve kinds sites begin
+        _check(ccall((:ceg_site_tables_device, LIB[]), Cint,
+                     (Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Float64}, Int32, Float64, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     h, kinds, Int32(length(kinds)), sites, Int32(size(sites, 3)), offset_one, offset_pair, d_fw, d_rec, d_inter))
+    end
+    nothing
+end
+
+"""
+`ceg_site_group_create`: K chains on one copy of the tables (K); `populations` is `m x K`, 1-based as `sh.population`.
+UNVERIFIED: never executed.
+"""
+function site_group_create(frameworkenergies::Vector{Float64}, interactions::Matrix{Float64}, populations::Matrix{UInt16}, tailcorrection::Float64;
+                           device::Integer=0)
+    pops = UInt16.(populations .- 0x0001)
+    g = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve frameworkenergies interactions pops begin
+        _check(ccall((:ceg_site_group_create, LIB[]), Cint,
+                     (Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Cvoid}, Float64, Ref{Ptr{Cvoid}}),
+                     Int32(device), Int32(length(frameworkenergies)), Int32(size(pops, 1)), Int32(size(pops, 2)), frameworkenergies, interactions,
+                     Int32(0), pointer(pops), tailcorrection, g))
+    end
+    g[]
+end
+
+"`ceg_site_group_destroy`.  UNVERIFIED: never executed."
+function site_group_destroy!(g::Ptr{Cvoid})
+    _check(ccall((:ceg_site_group_destroy, LIB[]), Cint, (Ptr{Cvoid},), g))
+    nothing
+end
+
+"""
+`ceg_site_group_sweep_cycles`: the main loop of `run_montecarlo!(::SiteHopping, simu)` (src/simulation.jl:922-966, `groupcycles = nothing`)
+for the `k` chains of `g`: `temperatures` is `K x ncycles` in K.  -> (stats `k`, cycle records `k x ncycles`, log `k x steps` or nothing).
+UNVERIFIED: never executed.
+"""
+function site_group_sweep_cycles!(g::Ptr{Cvoid}, k::Integer, temperatures::Matrix{Float64}, steps_per_cycle::Integer; seed::UInt64=UInt64(0),
+                                  first_step::UInt64=UInt64(0), cycle0::Integer=0, log::Bool=false)
+    ncycles = size(temperatures, 2)
+    stats = Vector{SiteStats}(undef, k)
+    records = Matrix{SiteCycleRecord}(undef, k, ncycles)
+    steps = log ? Matrix{SiteRecord}(undef, k, ncycles * steps_per_cycle) : nothing
+    GC.@preserve temperatures stats records steps begin
+        params = Ref(SiteParams(seed, first_step, C_NULL))
+        cycles = Ref(SiteCycles(Int64(ncycles), Int64(steps_per_cycle), Int64(cycle0), pointer(temperatures)))
+        _check(ccall((:ceg_site_group_sweep_cycles, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     g, params, cycles, pointer(stats), pointer(records), log ? pointer(steps) : C_NULL))
+    end
+    stats, records, steps
+end
+
+"`ceg_site_group_baseline`: `baseline_energy(sh)` (src/sitehopping.jl:105-112) of every chain, in K.  UNVERIFIED: never executed."
+function site_group_baseline(g::Ptr{Cvoid}, k::Integer)
+    out = zeros(Float64, k)
+    _check(ccall((:ceg_site_group_baseline, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}), g, out))
+    out
+end
+
+"`ceg_site_group_rebase`: every running energy becomes the baseline (the `idx_cycle == 0` step).  UNVERIFIED: never executed."
+function site_group_rebase!(g::Ptr{Cvoid})
+    _check(ccall((:ceg_site_group_rebase, LIB[]), Cint, (Ptr{Cvoid},), g))
+    nothing
+end
+
+"`ceg_site_group_get_populations` -> `m x k`, 1-based.  UNVERIFIED: never executed."
+function site_group_populations(g::Ptr{Cvoid}, m::Integer, k::Integer)
+    pops = zeros(UInt16, m, k)
+    GC.@preserve pops _check(ccall((:ceg_site_group_get_populations, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), g, pointer(pops)))
+    pops .+ 0x0001
+end
+
+"`ceg_site_group_set_populations` (`m x k`, 1-based); rebases.  UNVERIFIED: never executed."
+function site_group_set_populations!(g::Ptr{Cvoid}, populations::Matrix{UInt16})
+    pops = UInt16.(populations .- 0x0001)
+    GC.@preserve pops _check(ccall((:ceg_site_group_set_populations, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), g, pointer(pops)))
+    nothing
+end
+
+"`ceg_site_group_set_recorder`; `every === nothing` removes it.  UNVERIFIED: never executed."
+function site_group_set_recorder!(g::Ptr{Cvoid}, every::Union{Nothing,Integer}; origin::Integer=0, capacity::Integer=1024, track_min::Bool=false)
+    if every === nothing
+        _check(ccall((:ceg_site_group_set_recorder, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), g, C_NULL))
+        return nothing
+    end
+    spec = Ref(SiteRecorder(Int64(every), Int64(origin), Int64(capacity), Int32(track_min), Int32(0)))
+    _check(ccall((:ceg_site_group_set_recorder, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), g, spec))
+    nothing
+end
+
+"`ceg_site_group_recorder_read` -> (records `k x frames`, populations `m x k x frames`, 1-based).  UNVERIFIED: never executed."
+function site_group_recorder_read(g::Ptr{Cvoid}, m::Integer, k::Integer)
+    n = Ref{Int64}(0)
+    _check(ccall((:ceg_site_group_recorder_read, LIB[]), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}),
+                 g, Int64(0), Int64(0), C_NULL, C_NULL, n))
+    records = Matrix{SiteFrameRecord}(undef, k, n[])
+    pops = zeros(UInt16, m, k, n[])
+    GC.@preserve records pops begin
+        _check(ccall((:ceg_site_group_recorder_read, LIB[]), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}),
+                     g, Int64(0), n[], pointer(records), pointer(pops), n))
+    end
+    records, pops .+ 0x0001
+end
+
+"`ceg_site_group_recorder_min` -> (mink, mine (K), populations `m x k`, 1-based): `RMinimumEnergy` per chain.  UNVERIFIED: never executed."
+function site_group_recorder_min(g::Ptr{Cvoid}, m::Integer, k::Integer)
+    mink = zeros(Int64, k); mine = zeros(Float64, k); pops = zeros(UInt16, m, k)
+    GC.@preserve pops begin
+        _check(ccall((:ceg_site_group_recorder_min, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Ptr{Cvoid}), g, mink, mine, pointer(pops)))
+    end
+    mink, mine, pops .+ 0x0001
+end
+
 """
 `baseline_energy(mc)` (src/montecarlo.jl:530-542) from the device state behind `h` (`mc_handle(mc, ...)`): the sums come from
 `ceg_mc_baseline`, the two constants of the Ewald context (`energy_net_charges`, `static_contribution`, src/ewald.jl:555-577) and

@@ -1270,6 +1270,147 @@ typedef struct ceg_mc_baseline {
 CEG_API int ceg_mc_baseline(ceg_mc_t* handle, int32_t flags, ceg_mc_baseline_t* out);
 CEG_API int ceg_mc_group_baseline(ceg_mc_group_t* group, int32_t flags, ceg_mc_baseline_t* out /* [K] */);
 
+/* ---- site hopping: whole Monte-Carlo runs of K chains on two tables (src/sitehopping.jl, src/simulation.jl:863-1010) ----
+ * The reference's second Monte-Carlo model: a mobile species hops between n sites; all physics sits in frameworkenergies[n] and
+ * interactions[n][n] (K; symmetric, the diagonal 1e100).  A group holds one copy of the tables and K chains of m molecules each
+ * (population[c][j]: the 0-based site of molecule j of chain c), all resident on one device.  ceg_site_group_sweep_cycles runs the main
+ * loop of run_montecarlo!(::SiteHopping) with groupcycles = nothing for every chain: one wave per chain, all steps of all cycles inside
+ * the kernel (k_site_sweep), no launch per step.  A group knows no ceg_mc_t and no ceg_mc_group_t; only the table build, at the end of
+ * this section, reads one.
+ *
+ * The step of chain c at the absolute step s (stream = stream_id[c]; Philox and U as for ceg_mc_group_sweep, above):
+ *  draws     purpose 10 (SITE_SELECT): molecule i = min(floor(U(w0, w1) m), m - 1), site new = min(floor(U(w2, w3) n), n - 1);
+ *            purpose 3: u = U(w0, w1).  old = population[i].
+ *  energies  before = framework[old] + R(old), after = framework[new] + R(new) (movement_energy, sitehopping.jl:114-121), with the
+ *            row sum R(r) = sum over j != i of interactions[r][population[j]] in this order, a fixed function of m alone: lane
+ *            l = 0..63 adds its terms j = l, l + 64, l + 128, ... (< m) in rising order onto +0.0, with +0.0 in the place of the term
+ *            j == i (the same bits as leaving it out: such a sum is never -0.0); then for o = 32, 16, 8, 4, 2, 1 every lane replaces
+ *            its sum by (its sum) + (the sum of lane l ^ o); R is what lane 0 then holds.  Plain FP64 adds, nothing contracted.
+ *            before is recomputed at every step, which equals the reference's old_i cache: the population changes only at i itself.
+ *  rule      compute_accept_move (montecarlo.jl:702-712): accepted iff after < before, or else u < exp((before - after) / T) with the
+ *            device library's FP64 exp and an IEEE division.  A hop onto an occupied site meets the 1e100 of that pair and is rejected
+ *            by the rule itself; a hop onto the molecule's own site has after == before, bit for bit, and is accepted as a no-op.
+ *            Neither has a special case.
+ *  accepted  energy = energy + (after - before), delta = delta + (after - before), population[i] = new.
+ * Per chain the group keeps, in device memory between launches and calls: the population, the running energy, and since creation
+ * the steps attempted, the steps accepted and `delta`, the sum of the accepted changes (ceg_site_stats_t).
+ *
+ * create: n in 1..65535 (sites are UInt16 in the reference), m in 1..CEG_SITE_MAX_MOLECULES, K >= 1, every site < n, no site twice
+ *   within a chain (the reference's randperm never produces it, and two 1e100 terms would poison the sums), finite tailcorrection;
+ *   else CEG_ERR_INVALID.  n*n*8 bytes above CEG_HIP_SITE_TABLE_LIMIT_MB MiB (environment, default 2048) -> CEG_ERR_UNSUPPORTED.
+ *   tables_on_device == 0: framework [n] and interactions [n][n] are host memory and are copied once; != 0: they are device memory
+ *   of `device`, which the group reads in place and never writes or frees: the caller keeps them alive until destroy.  The running
+ *   energy starts as the baseline (below).  Synchronous.
+ * sweep_cycles: cycles cc = cycle0 + 0 .. cycle0 + ncycles - 1 of steps_per_cycle steps each (the reference: m), the absolute steps
+ *   first_step, first_step + 1, ...; temperature [ncycles][K], stream_id [K] (NULL: the chain's index), all host memory.  At the end of
+ *   every cycle the chain's record goes to cycles_out [ncycles][K]; with log_out != NULL every step's record goes to
+ *   log_out [ncycles * steps_per_cycle][K]; stats_out [K] receives the state after the call.  Every output may be NULL.  Synchronous.
+ *   The call is cut into launches of at most CEG_HIP_SITE_STEPS_PER_LAUNCH steps per chain (environment, 1..2^30, default 4096:
+ *   6 ms per launch at m = 64 and 0.11 s at m = 4096, n = 8192, K = 256, the largest shape measured), which follow each other on the
+ *   group's stream with the state in device memory between them.  A run does not depend on how it is cut, by that limit or by the caller into several calls that continue
+ *   first_step and cycle0: outputs and state are the same bytes.
+ *   CEG_ERR_INVALID before anything is launched or changed: a missing group / params / cycles / temperature, ncycles < 0,
+ *   steps_per_cycle < 1, a temperature that is not finite and > 0, cycle0 + ncycles or first_step + the steps beyond 2^63 - 1,
+ *   more than CEG_MC_CYCLES_MAX_RECORDS log or cycle records.  ncycles == 0: stats only.
+ * baseline: baseline_energy (sitehopping.jl:105-112) of every chain in one launch, out [K] host memory:
+ *   (tailcorrection + sum_j framework[population[j]]) + sum_{i<j} interactions[population[i]][population[j]], partial sums combined in
+ *   a fixed order.  rebase: sets every chain's running energy to exactly those bytes (the reference's idx_cycle == 0 step; the caller
+ *   compares energy and baseline for the final drift check); the counters and delta stay.
+ * set_populations: validated as at creation, replaces every chain's population and rebases.  get_populations: [K][m].
+ * recorder (run_montecarlo!'s frames every printevery cycles, and RMinimumEnergy for SiteHopping, parameterinputs.jl:109), written by
+ *   the chain's own wave inside k_site_sweep, no extra launch: at the end of cycle cc with every > 0, cc >= origin and
+ *   (cc - origin) % every == 0 the chain's population and energy go into the next frame of the store ([frame_capacity][K]); once the
+ *   store is full the frame is dropped and the chain's cycle record carries CEG_SITE_FRAME_DROPPED.  With track_min, the population
+ *   of the lowest cycle-end energy so far is kept per chain, strict <, so a tie keeps the earlier cycle; installation takes the
+ *   state and energy at that moment as the minimum to beat (mink = -1).  set_recorder(NULL) removes it; installing synchronises.
+ *   recorder_read copies frames [first_frame, first_frame + nframes) (records [nframes][K], populations [nframes][K][m]; every
+ *   pointer optional; *frames_out: the frames held); recorder_min copies mink, mine and the populations [K][m].  CEG_ERR_INVALID:
+ *   every, origin or frame_capacity < 0, a store above CEG_MC_RECORDER_MAX_BYTES, a window outside the frames held, no recorder, no
+ *   track_min.
+ * A HIP failure once a launch has been enqueued marks the group inconsistent: every later call but destroy returns CEG_ERR_HIP.
+ * Out of scope: groupcycles / restartgroupcycle; replica exchange between site-hopping chains (the reference draws it per step with
+ *   randsubseq; the running energies stay on the device between the launches of a call, so a later change can put an exchange launch
+ *   between them); extremal_placements; ShootingStarMinimizer; the serialised caches and output files.
+ *
+ * The two tables (the reference's constructor, sitehopping.jl:41-82, telescoped): ceg_site_tables (host arrays out) and
+ * ceg_site_tables_device (device arrays of the handle's device out, e.g. for ceg_site_group_create with tables_on_device).
+ *  handle     a ceg_mc_t of the mobile species that holds NO guest (as ceg_mc_create leaves it, or after ceg_mc_set_guests with
+ *             nmol = 0) and belongs to no chain group; with guests -> CEG_ERR_UNSUPPORTED.  Nothing of the handle is written.
+ *  kinds      [m_atoms] the kinds of the species' atoms, m_atoms in 1..16, as for ceg_mc_trial_insert
+ *  positions  [n][m_atoms][3] Cartesian A, host memory, finite; n in 1..65535
+ *  With {...} a system of exactly those placements and .er its energy report without tail correction:
+ *   recip[i]           = inter + reciprocal of baseline_energy({s_i}).er                      (ewaldenergies[i]; optional, may be NULL)
+ *   framework[i]       = Number(baseline_energy({s_i}).er) = framework VdW + framework direct + recip[i]
+ *   interactions[i][j] = inter + reciprocal of baseline_energy({s_i, s_j}).er - recip[i] - recip[j];  [i][i] = 1e100 exactly;
+ *                        [i][j] and [j][i] hold the same bits.  A site the framework grids block keeps framework[i] >= 1e90.
+ *  Nothing large is subtracted on the device: with S_i the structure factor of site i over the handle's k-vectors, F the framework's,
+ *   recip[i] = (2 sum_k kf Re(conj(F) S_i) + sum_k kf |S_i|^2) + offset_one and
+ *   interactions[i][j] = (P_ij + 2 sum_k kf_k Re(S_i conj(S_j))) + offset_pair, P_ij the pair sum of the two molecules with the
+ *   minimum image, cutoff and rule energies of row column 2 of ceg_mc_trial.  The count-dependent constants of the EwaldContext stay
+ *   with the caller: with c(N) = 2 energy_net_charges(N) + static_contribution(N) for N molecules of the species (ewald.jl:497-544),
+ *   offset_one = c(1) and offset_pair = c(2) - 2 c(1); both 0 without Ewald summation.
+ *  Three launches for any n, on the handle's stream, then a synchronisation: k_site_points (one workgroup per site: the grids atom by
+ *   atom, S_i), k_site_recip_pairs (v_mfma_f64_16x16x4 over the 16 x 16 site tiles of the upper triangle) and k_site_real_pairs (the
+ *   molecule-pair sums over the same tiles, which also mirrors the triangle and sets the diagonal).
+ *  CEG_ERR_UNSUPPORTED, with the figures in ceg_last_error(): n*n*8 bytes, or the structure factors (nk * n * 16 bytes), above
+ *   CEG_HIP_SITE_TABLE_LIMIT_MB MiB (environment, default 2048); k-space tables of the molecule that do not fit in LDS.
+ *   CEG_ERR_INVALID: a missing pointer, n or m_atoms out of range, a kind outside the pair table, a position or offset that is not
+ *   finite, a handle inside a chain group. */
+#define CEG_SITE_MAX_MOLECULES 4096
+#define CEG_SITE_FRAME_TAKEN   1
+#define CEG_SITE_FRAME_DROPPED 2
+#define CEG_SITE_NEW_MINIMUM   4
+typedef struct ceg_site_group ceg_site_group_t;
+typedef struct ceg_site_params {        /* 24 bytes */
+    uint64_t seed, first_step;
+    const uint32_t* stream_id;          /* [K] or NULL */
+} ceg_site_params_t;
+typedef struct ceg_site_cycles {        /* 32 bytes */
+    int64_t ncycles, steps_per_cycle, cycle0;
+    const double* temperature;          /* [ncycles][K] */
+} ceg_site_cycles_t;
+typedef struct ceg_site_stats {         /* 32 bytes */
+    int64_t attempted, accepted;        /* since creation */
+    double delta, energy;               /* the sum of the accepted changes since creation; the running energy */
+} ceg_site_stats_t;
+typedef struct ceg_site_cycle_record {  /* 56 bytes */
+    int64_t cycle;
+    double temperature, energy, delta;
+    int64_t attempted, accepted;        /* cumulative, as in the stats */
+    int32_t flags, _pad;                /* CEG_SITE_FRAME_TAKEN | CEG_SITE_FRAME_DROPPED | CEG_SITE_NEW_MINIMUM */
+} ceg_site_cycle_record_t;
+typedef struct ceg_site_record {        /* 40 bytes */
+    int32_t molecule, old_site, new_site, accepted;
+    double before, after, u;
+} ceg_site_record_t;
+typedef struct ceg_site_recorder {      /* 32 bytes */
+    int64_t every, origin, frame_capacity;
+    int32_t track_min, _pad;
+} ceg_site_recorder_t;
+typedef struct ceg_site_frame_record {  /* 16 bytes */
+    int64_t cycle;
+    double energy;
+} ceg_site_frame_record_t;
+CEG_API int ceg_site_tables(ceg_mc_t* handle, const int32_t* kinds, int32_t m_atoms, const double* positions, int32_t n, double offset_one,
+                            double offset_pair, double* framework /*[n]*/, double* recip /*[n] or NULL*/, double* interactions /*[n][n]*/);
+CEG_API int ceg_site_tables_device(ceg_mc_t* handle, const int32_t* kinds, int32_t m_atoms, const double* positions, int32_t n, double offset_one,
+                                   double offset_pair, double* d_framework, double* d_recip, double* d_interactions);
+CEG_API int ceg_site_group_create(int32_t device, int32_t n, int32_t m, int32_t k, const double* framework, const double* interactions,
+                                  int32_t tables_on_device, const uint16_t* populations /*[K][m]*/, double tailcorrection,
+                                  ceg_site_group_t** group);
+CEG_API int ceg_site_group_destroy(ceg_site_group_t* group);
+CEG_API int ceg_site_group_sweep_cycles(ceg_site_group_t* group, const ceg_site_params_t* params, const ceg_site_cycles_t* cycles,
+                                        ceg_site_stats_t* stats_out, ceg_site_cycle_record_t* cycles_out, ceg_site_record_t* log_out);
+CEG_API int ceg_site_group_baseline(ceg_site_group_t* group, double* out /*[K]*/);
+CEG_API int ceg_site_group_rebase(ceg_site_group_t* group);
+CEG_API int ceg_site_group_get_populations(ceg_site_group_t* group, uint16_t* populations_out /*[K][m]*/);
+CEG_API int ceg_site_group_set_populations(ceg_site_group_t* group, const uint16_t* populations /*[K][m]*/);
+CEG_API int ceg_site_group_set_recorder(ceg_site_group_t* group, const ceg_site_recorder_t* recorder);   /* NULL removes it */
+CEG_API int ceg_site_group_recorder_read(ceg_site_group_t* group, int64_t first_frame, int64_t nframes, ceg_site_frame_record_t* records_out,
+                                         uint16_t* populations_out, int64_t* frames_out);
+CEG_API int ceg_site_group_recorder_min(ceg_site_group_t* group, int64_t* mink_out /*[K]*/, double* mine_out /*[K]*/,
+                                        uint16_t* populations_out /*[K][m]*/);
+
 /* ---- blocking masks on the grid lattice ----------------------------- */
 /*
  * BlockFile(g::EnergyGrid), src/grids.jl:188-204: a lattice cell (i, j, k), i < dims[0] etc., whose
