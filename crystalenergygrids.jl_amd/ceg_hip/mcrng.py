@@ -1,6 +1,6 @@
 """The random stream and the move proposals of the Monte-Carlo sweeps (``ceg_mc_group_sweep``), restated in NumPy.
 
-Needs no device.  The sweep kernels of ``csrc/ceg_mc_group.hip`` (through ``csrc/ceg_philox.h``) and this module follow the
+Needs no device.  The sweep kernels of ``csrc/ceg_mc_sweep.hip`` (through ``csrc/ceg_philox.h``) and this module follow the
 specification in ``include/ceg_hip.h`` word for word: Philox4x32-10, one block per (step, stream, purpose), nothing random
 stored.  A caller uses it to audit a sweep's log, to replay a chain on the host, or to predict what a chain will propose.
 

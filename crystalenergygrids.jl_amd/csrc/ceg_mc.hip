@@ -15,7 +15,7 @@
 // all threads stride over the guest atoms for the pair sum; block 0 evaluates the molecule where it currently is
 // (with its stored structure factor, like the reference's `positions === nothing` branch).  Small batches travel
 // through a pinned, device-mapped host buffer: a batch-1 trial is ONE kernel launch and one stream synchronisation.
-// The MC driver stays on the host, as in SURVEY 8f, except for the sweeps of the chain groups (ceg_mc_group.hip); what the two files
+// The MC driver stays on the host, as in SURVEY 8f, except for the sweeps of the chain groups (ceg_mc_sweep.hip); what these files
 // share is in ceg_mc_state.h.
 #include "ceg_mc_state.h"
 

@@ -39,7 +39,7 @@ __global__ void k_mcc_book_fill(McCellBook B, int32_t cap)
     if (c >= 0 && c < B.ncells && i >= 0 && i < cap) B.owner[(size_t)c * cap + i] = s;
 }
 
-// as k_mcg_sweep_trial (ceg_mc_group.hip), for the chains with cells
+// as k_mcg_sweep_trial (ceg_mc_sweep.hip), for the chains with cells
 template <bool FAST>
 __global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mcc_sweep_trial(const McView* __restrict__ views, const McSweepChain* __restrict__ params,
                                                                  const int32_t* __restrict__ bead, const int32_t* __restrict__ list, int table_ok,
@@ -238,7 +238,7 @@ __device__ __forceinline__ void mcc_commit(const McCellBook& B, const MccStage& 
         for (int q = 0; q < S.nforeign; ++q) B.idx_of[S.fslot[q]] = S.fidx[q];
 }
 
-// as k_mcg_sweep_accept (ceg_mc_group.hip); a chain with cells replays its cell operations before anything of the step is written
+// as k_mcg_sweep_accept (ceg_mc_sweep.hip); a chain with cells replays its cell operations before anything of the step is written
 __global__ __launch_bounds__(MC_THREADS) void k_mcc_sweep_accept(const McView* __restrict__ views, const McSweepChain* __restrict__ params,
                                                                  const McCellBook* __restrict__ books, uint64_t seed, uint64_t step,
                                                                  const McPositions* __restrict__ prop, const double* __restrict__ rows,
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(MC_THREADS) void k_mcc_sweep_accept(const McView* _
     }
 }
 
-// ---- GCMC sweeps on chains with cells.  As k_mcg_gcmc_trial (ceg_mc_group.hip) with the cell walk; a halted or stopped chain's workgroups
+// ---- GCMC sweeps on chains with cells.  As k_mcg_gcmc_trial (ceg_mc_sweep.hip) with the cell walk; a halted or stopped chain's workgroups
 // return at once
 template <bool FAST>
 __global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mcc_gcmc_trial(const McView* __restrict__ views, const McGcmcChain* __restrict__ params,
@@ -350,7 +350,7 @@ __global__ __launch_bounds__(MC_THREADS, MC_TRIAL_WAVES) void k_mcc_gcmc_trial(c
     else mc_trial_row<FAST, false, true>(v, mv.molecule, s_L, mine->xyz, rows, P.stride, nullptr, nullptr, 0ull, at);
 }
 
-// as k_mcg_gcmc_accept (ceg_mc_group.hip); a chain with cells replays the cell operations of an accepted step -- displacement, insertion
+// as k_mcg_gcmc_accept (ceg_mc_sweep.hip); a chain with cells replays the cell operations of an accepted step -- displacement, insertion
 // or deletion -- before anything of the step is written
 __global__ __launch_bounds__(MC_THREADS) void k_mcc_gcmc_accept(const McView* __restrict__ views, const McGcmcChain* __restrict__ params,
                                                                 const ceg_mc_gcmc_species_t* __restrict__ spec, int nspecies, McGcmcTable* tables,

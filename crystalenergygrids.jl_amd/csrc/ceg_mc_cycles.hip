@@ -1,6 +1,6 @@
 // ceg_mc_cycles.hip -- the cycle end of ceg_mc_group_sweep_cycles / ceg_mc_group_sweep_gcmc_cycles: the end-of-cycle block of
 // run_montecarlo! (src/simulation.jl:727-728, 818-827) as one small launch per cycle (k_mcg_cycle_end) on the group's stream.  The
-// sweeps of ceg_mc_group.hip enqueue it behind the accept launch (and the sampler frame) of a cycle's last step; it writes the cycle's
+// sweeps of ceg_mc_sweep.hip enqueue it behind the accept launch (and the sampler frame) of a cycle's last step; it writes the cycle's
 // record and the next cycle's temperature, dmax and thetamax into the chain's parameter slot, which the next step's launches read.
 #include "ceg_mc_state.h"
 

@@ -1,4 +1,4 @@
-// ceg_mc_gcmc.h -- what the GCMC sweep kernels of ceg_mc_group.hip (chains with the exhaustive pair loop) and of ceg_mc_cells.hip
+// ceg_mc_gcmc.h -- what the GCMC sweep kernels of ceg_mc_sweep.hip (chains with the exhaustive pair loop) and of ceg_mc_cells.hip
 // (chains with neighbour cells) share: the per-chain parameters and the device's molecule table of ceg_mc_group_sweep_gcmc, the
 // selection of a step's move, its proposal, and the block pockets with the retry loop of choose_step!.
 #pragma once

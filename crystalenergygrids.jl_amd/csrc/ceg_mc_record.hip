@@ -1,7 +1,7 @@
 // ceg_mc_record.hip -- the recorder of a chain group (ceg_mc_group_set_recorder / _snapshot / _recorder_rebase / _recorder_read /
 // _recorder_min): the trajectory of run_montecarlo! (put!(output, o) every printevery cycles, src/simulation.jl:784-799) and
 // RMinimumEnergy (src/parameterinputs.jl:86-108), taken from the resident state by one launch per cycle end (k_mcg_snapshot) on the
-// group's stream.  The *_cycles sweeps of ceg_mc_group.hip enqueue it behind k_mcg_cycle_end / k_mcg_exchange; nothing here writes
+// group's stream.  The *_cycles sweeps of ceg_mc_sweep.hip enqueue it behind k_mcg_cycle_end / k_mcg_exchange; nothing here writes
 // chain state.
 #include "ceg_mc_state.h"
 

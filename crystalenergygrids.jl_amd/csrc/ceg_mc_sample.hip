@@ -1,7 +1,7 @@
 // ceg_mc_sample.hip -- the sampler of a chain group (ceg_mc_group_set_sampler / _sample / _sampler_read / _sampler_reset): the counts
 // of bin_trajectory (src/averageclusters.jl:154-202) and the per-cycle series of GCMCRecorder / run_montecarlo!
 // (src/parameterinputs.jl:232-249, src/simulation.jl:784-799), taken from the resident state by one launch per frame (k_mcg_sample).
-// The sweeps of ceg_mc_group.hip enqueue that launch behind the accept launch of a frame step; nothing here writes chain state.
+// The sweeps of ceg_mc_sweep.hip enqueue that launch behind the accept launch of a frame step; nothing here writes chain state.
 #include "ceg_mc_state.h"
 
 using namespace ceg_mcs;

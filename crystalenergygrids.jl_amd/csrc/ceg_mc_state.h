@@ -1,4 +1,4 @@
-// ceg_mc_state.h -- what ceg_mc.hip (ceg_mc_*), ceg_mc_group.hip (ceg_mc_group_*) and ceg_mc_baseline.hip (ceg_mc_baseline,
+// ceg_mc_state.h -- what ceg_mc.hip (ceg_mc_*), ceg_mc_group.hip and ceg_mc_sweep.hip (ceg_mc_group_*) and ceg_mc_baseline.hip (ceg_mc_baseline,
 // ceg_mc_group_baseline) share: the kernel-side view of a handle, the bodies of the trial row, of the three updates and of the
 // structure-factor rebuild, and the host-side handle with its cell mirror.  Several translation units include this, so the names live
 // in namespace ceg_mcs; the kernels stay in the anonymous namespaces of the files.

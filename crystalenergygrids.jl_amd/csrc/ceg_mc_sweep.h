@@ -1,4 +1,4 @@
-// ceg_mc_sweep.h -- what the sweep kernels of ceg_mc_group.hip (chains with the exhaustive pair loop) and of ceg_mc_cells.hip (chains
+// ceg_mc_sweep.h -- what the sweep kernels of ceg_mc_sweep.hip (chains with the exhaustive pair loop) and of ceg_mc_cells.hip (chains
 // with neighbour cells) share: the per-chain parameters of ceg_mc_group_sweep, the selection and the proposal of a step, the
 // Metropolis rule of a displacement, and the device's book of the cell lists (McCellBook) with its launchers.
 #pragma once

@@ -1,7 +1,7 @@
 // ceg_mc_temper.hip -- tempering of a chain group (ceg_mc_group_set_tempering / _tempering_read): replica exchange between the chains
 // on neighbouring rungs of a temperature ladder at the end of a cycle (run_parallel_tempering, src/simulation.jl:461-622; the rule is
 // :533, compute_accept_move(E_i, E_{i+1}, inv(inv(T_i) - inv(T_{i+1})))) as one small launch per cycle (k_mcg_exchange) on the group's
-// stream.  The *_cycles sweeps of ceg_mc_group.hip enqueue it behind k_mcg_cycle_end; it exchanges temperatures, not configurations:
+// stream.  The *_cycles sweeps of ceg_mc_sweep.hip enqueue it behind k_mcg_cycle_end; it exchanges temperatures, not configurations:
 // it writes the chains' rungs, energies and records and the next cycle's temperature into the chain's parameter slot.
 #include "ceg_mc_state.h"
 

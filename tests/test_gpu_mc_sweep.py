@@ -409,3 +409,33 @@ def test_sweep_refusals_leave_the_state_alone(setup, monkeypatch):
         assert st["translation_trials"] + st["rotation_trials"] == 3
     cells.close()
     plain.close()
+
+
+def test_of_two_faults_the_first_is_reported(setup):
+    """The order of the refusals: the cycles before the chains, then chain by chain, and within a chain temperature / dmax / thetamax,
+    p_rotation, stream id, beads.  Each call carries two faults; the one that the order puts first is the one reported, and nothing
+    is launched or changed."""
+    from ceg_hip.energy import DeviceMonteCarloGroup
+    K = 2
+    devs, _ = _chains(setup, K)
+    good = dict(temperature=300.0, dmax=0.5, thetamax=1.0, p_rotation=0.5)
+    nan = float("nan")
+    two = [(dict(p_rotation=[1.01, 0.5], temperature=[300.0, nan]), "chain 0: p_rotation"),
+           (dict(temperature=[300.0, 0.0], stream_id=[6, 6]), "chain 1: the temperature"),
+           (dict(bead=[[1, 1], [0, 1]], dmax=[0.5, -0.1]), "chain 0: a bead lies outside")]
+    with DeviceMonteCarloGroup(devs) as group:
+        before = [d.state() for d in devs]
+
+        def refused(call, what):
+            with pytest.raises(_abi.CegError) as ei:
+                call()
+            assert ei.value.code == -1 and what in str(ei.value), (what, str(ei.value))
+            for d, (p, sf) in zip(devs, before):
+                p2, sf2 = d.state()
+                assert np.array_equal(p, p2) and np.array_equal(sf, sf2)
+
+        for change, what in two:
+            refused(lambda: group.sweep(5, SEED, 0, **{**good, **change}), what)
+        # a cycle description that cycles_check refuses (cycle0 < 1) together with a dmax that is not finite
+        refused(lambda: group.sweep_cycles(2, 3, SEED, 0, cycle0=0, **{**good, "dmax": [nan, 0.5]}), "cycles: ncycles >= 0")
+    _close(devs)

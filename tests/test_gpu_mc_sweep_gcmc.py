@@ -627,3 +627,37 @@ def test_gcmc_refusals_leave_the_state_alone(setup, monkeypatch):
             assert np.array_equal(p, p2) and np.array_equal(sf, sf2)
     cells.close()
     plain.close()
+
+
+def test_of_two_faults_the_first_is_reported(setup):
+    """The order of the refusals: the species table before the cycles, the cycles before the chains, then chain by chain, and within
+    a chain temperature / dmax / thetamax, stream id, kinds, max_molecules.  Each call carries two faults; the one that the order
+    puts first is the one reported, and nothing is launched or changed."""
+    from ceg_hip.energy import DeviceMonteCarloGroup
+    K = 2
+    devs, _ = _chains(setup, K)
+    good = dict(temperature=300.0, dmax=0.5, thetamax=1.0, max_molecules=8)
+    nan = float("nan")
+    with DeviceMonteCarloGroup(devs) as group:
+        table = _tail(group.gcmc_species([NA_MOVES, CO2_MOVES], [1000.0, 1000.0]))
+        bead = table.copy()
+        bead["bead"][1] = 3                                          # (CO2 has three atoms)
+        before = [d.state() for d in devs]
+        slots = [copy.deepcopy(d._slot) for d in devs]
+
+        def refused(call, what):
+            with pytest.raises(_abi.CegError) as ei:
+                call()
+            assert ei.value.code == -1 and what in str(ei.value), (what, str(ei.value))
+            for d, (p, sf), sl in zip(devs, before, slots):
+                p2, sf2 = d.state()
+                assert np.array_equal(p, p2) and np.array_equal(sf, sf2) and d._slot == sl
+
+        refused(lambda: group.sweep_gcmc(5, SEED, 0, species=bead, **{**good, "dmax": [nan, 0.5]}), "species 1: the bead lies outside")
+        # the same species together with a cycle description that cycles_check refuses (cycle0 < 1)
+        refused(lambda: group.sweep_gcmc_cycles(2, 3, SEED, 0, cycle0=0, species=bead, **good), "species 1: the bead lies outside")
+        # every chain of the fixture holds five molecules
+        refused(lambda: group.sweep_gcmc(5, SEED, 0, species=table, **{**good, "dmax": [nan, 0.5], "max_molecules": [4, 8]}), "chain 0: dmax")
+        refused(lambda: group.sweep_gcmc(5, SEED, 0, species=table, **{**good, "max_molecules": [4, 8], "temperature": [300.0, nan]}),
+                "chain 0: max_molecules")
+    _close(devs)
