@@ -153,6 +153,14 @@ class SiteRecorder(C.Structure):
     _fields_ = [("every", C.c_int64), ("origin", C.c_int64), ("frame_capacity", C.c_int64), ("track_min", C.c_int32), ("_pad", C.c_int32)]
 
 
+class SiteTempering(C.Structure):
+    """``ceg_site_tempering_t`` (``pair_cdf`` [R-1] float64 and ``ladder_stream`` [K/R] uint32 in host memory, the latter or NULL)"""
+    _fields_ = [("rungs", C.c_int32), ("_pad", C.c_int32), ("pair_cdf", C.c_void_p), ("ladder_stream", C.c_void_p), ("_reserved", C.c_int64)]
+
+
+assert C.sizeof(SiteTempering) == 32
+SITE_MAX_RUNGS = 16          # a ladder is one workgroup of 16 waves at the most
+
 SITE_STATS_DTYPE = np.dtype([('attempted', '<i8'), ('accepted', '<i8'), ('delta', '<f8'), ('energy', '<f8')], align=True)
 SITE_CYCLE_RECORD_DTYPE = np.dtype([('cycle', '<i8'), ('temperature', '<f8'), ('energy', '<f8'), ('delta', '<f8'), ('attempted', '<i8'),
                                     ('accepted', '<i8'), ('flags', '<i4'), ('_pad', '<i4')], align=True)
@@ -343,6 +351,8 @@ PROTOTYPES = {
     "ceg_site_group_set_recorder": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ceg_site_group_recorder_read": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, c_int64_p]),
     "ceg_site_group_recorder_min": (C.c_int, [C.c_void_p, c_int64_p, c_double_p, C.c_void_p]),
+    "ceg_site_group_set_tempering": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ceg_site_group_tempering_read": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_int32_p]),
     "ceg_recip_energy_device": (C.c_int, [C.c_void_p, C.c_void_p, c_double_p, C.c_int32, C.c_int64, C.c_double, C.c_double,
                                           C.c_void_p, C.c_void_p]),
 }

@@ -43,6 +43,9 @@ Site hopping (``ceg_site_group_sweep_cycles``, ``csrc/ceg_site.hip``): purpose 1
 acceptance; :func:`site_propose`, :func:`site_row_sum` (the device's summation order), :func:`site_movement_energy`, :func:`site_step`
 and :func:`site_replay` restate ``k_site_sweep``, :func:`site_baseline` is ``baseline_energy(::SiteHopping)`` in extended precision, and
 :func:`site_random_population` (purpose 11, host only) draws the ``randperm`` start of a quench.  The section at the end of this file.
+Purpose 12 is the per-step exchange draw of a tempering ladder (``ceg_site_group_set_tempering``, ``k_site_sweep_pt``):
+:func:`site_exchange_cdf`, :func:`site_exchange_draw`, :func:`site_exchange_threshold` and :func:`site_ladder_replay`, with the rule
+restated above them.
 """
 from __future__ import annotations
 
@@ -912,6 +915,136 @@ def site_replay(framework, interactions, population, energy: float, seed: int, f
     m = len(pop)
     return SiteReplay(steps, pop.astype(np.uint16), float(e), float(d), np.array(ce, dtype=np.float64),
                       np.array(cp, dtype=np.uint16).reshape(len(ce), m), acc)
+
+
+# ---- tempering of site-hopping ladders (ceg_site_group_set_tempering, k_site_sweep_pt; run_parallel_tempering, simulation.jl:461-634)
+# The rule, as include/ceg_hip.h states it:
+# Layout.  A group of K chains with tempering installed is L = K / R ladders of R rungs.  Chain ``l*R + r`` is rung r of ladder l.
+#   A chain index means a rung from then on.  Temperatures, streams, hop counters, cycle records, frames and the minimum belong to
+#   the rung.  Population, running ``energy`` and ``delta`` belong to the configuration and travel with it.  So ``energy - delta``
+#   stays the baseline that the configuration started from.
+# Temperatures.  The temperature table ``[ncycles][K]`` gives the rung temperatures.  Inside every ladder and every cycle they must
+#   be strictly increasing with the rung, because the reference sorts ``Ts``.
+# Exchange draw.  At the absolute step ``s``, every ladder takes one Philox block.  The purpose is ``SITE_EXCHANGE = 12``.  The
+#   stream is the ladder's (``ladder_stream[l]``, or ``l``).  ``v = U(w0, w1)`` chooses the pair.  ``u = U(w2, w3)`` is the
+#   acceptance draw.
+# Pair table.  The pair is the first ``j`` in ``0..R-2`` with ``v < pair_cdf[j]``.  If there is none, the step has no exchange.
+#   Each entry must be finite, in [0, 1] and non-decreasing.  The reference attempts at most the first element of
+#   ``randsubseq(1:(Npt-1), 0.1)`` (:528-529).  That is ``pair_cdf[j] = 1 - q_(j+1)`` with ``q_0 = 1`` and
+#   ``q_(i+1) = q_i * (1 - p)``, computed by repeated multiplication (:func:`site_exchange_cdf`).
+# Exchange attempt.  A step whose pair is ``j`` attempts the exchange of rungs ``j`` and ``j+1`` (:531-543).  ``E_a`` and ``E_b``
+#   are the running energies of the two rungs at the start of the step.  ``Tx = 1.0 / (1.0 / T_j - 1.0 / T_(j+1))``, with IEEE
+#   divisions in this order.  The exchange is accepted iff ``E_b < E_a``, or else ``u < exp((E_a - E_b) / Tx)``.
+# After the attempt.  ``pt_attempted[l][j]`` goes up by 1.  On acceptance ``pt_accepted[l][j]`` goes up by 1.  On acceptance the
+#   populations of the two rungs are exchanged, and their ``energy`` and ``delta`` with them.  The two rungs make no hop at this
+#   step.  ``attempted`` does not move.  Rung ``j`` logs ``molecule = -1``, ``old_site = new_site = -1``, ``before = E_a``,
+#   ``after = E_b``, ``u``, ``accepted``.  Rung ``j+1`` logs ``molecule = -2`` and the same values.  Every other rung of the ladder
+#   makes the ordinary step (:func:`site_step`).  It uses its own stream and the same bits as without tempering.
+# Cycle ends.  Cycle records, frames and ``track_min`` work per rung.  They use the population and energy that sit on the rung at
+#   that moment.
+# Replica map.  ``replica[K]`` holds, per rung, the rung (0..R-1) on which the configuration now there sat when tempering was
+#   installed.  It is a permutation inside every ladder.
+SITE_EXCHANGE = 12
+
+
+def site_exchange_cdf(rungs: int, p: float = 0.1) -> np.ndarray:
+    """The pair table of the reference's schedule, float64[R-1]: the first element of ``randsubseq(1:(R-1), p)`` is pair ``j`` with
+    probability ``p (1 - p)^j``, so ``cdf[j] = 1 - q_(j+1)`` with ``q_0 = 1`` and ``q_(i+1) = q_i * (1 - p)`` by repeated
+    multiplication in FP64."""
+    rungs, p = int(rungs), float(p)
+    if rungs < 2 or not 0.0 <= p <= 1.0:
+        raise ValueError("rungs >= 2 and p in [0, 1]")
+    out, q = np.empty(rungs - 1, dtype=np.float64), np.float64(1.0)
+    for j in range(rungs - 1):
+        q = q * (np.float64(1.0) - np.float64(p))
+        out[j] = np.float64(1.0) - q
+    return out
+
+
+def site_exchange_draw(seed: int, step: int, ladder_stream: int, cdf):
+    """-> (pair ``j`` or -1, ``u``) of the ladder at the absolute step ``step``: the first ``j`` with ``U(w0, w1) < cdf[j]``;
+    ``u = U(w2, w3)``."""
+    w = draw(seed, step, ladder_stream, SITE_EXCHANGE)
+    v, u = uniform(w[0], w[1]), uniform(w[2], w[3])
+    for j, top in enumerate(cdf):
+        if v < float(top):
+            return j, u
+    return -1, u
+
+
+def site_exchange_threshold(E_a: float, E_b: float, T_a: float, T_b: float) -> float:
+    """``exp((E_a - E_b) / Tx)`` with ``Tx = 1.0 / (1.0 / T_a - 1.0 / T_b)`` for rung ``a`` below rung ``b``, every operation rounded
+    to FP64 in this order (the arithmetic of :func:`exchange_threshold`)."""
+    return exchange_threshold(E_a, E_b, T_a, T_b)
+
+
+class SiteLadderReplay(NamedTuple):
+    steps: list               # [R] lists of SiteStep per rung; an exchange record has molecule -1 (lower rung) or -2, before = E_a, after = E_b
+    population: np.ndarray    # uint16[R, m] by rung at the end
+    energy: np.ndarray        # float64[R] by rung at the end
+    delta: np.ndarray         # float64[R]
+    cycle_energy: np.ndarray  # float64[ncycles, R] at the cycle ends, by rung
+    cycle_population: np.ndarray   # uint16[ncycles, R, m]
+    attempted: np.ndarray     # int64[R] hops attempted by the rung
+    accepted: np.ndarray      # int64[R] hops accepted
+    pt_attempted: np.ndarray  # int64[R-1] per pair
+    pt_accepted: np.ndarray   # int64[R-1]
+    replica: np.ndarray       # int32[R]
+
+
+def site_ladder_replay(framework, interactions, populations, energies, seed: int, first_step: int, stream_ids, ladder_stream: int,
+                       temperatures, steps_per_cycle: int, cdf, log=None, deltas=None, replica=None) -> SiteLadderReplay:
+    """One ladder of R rungs through ``len(temperatures)`` cycles as ``k_site_sweep_pt`` runs it.  ``populations`` [R, m],
+    ``energies`` [R], ``stream_ids`` [R], ``temperatures`` [ncycles, R] (rising with the rung).  ``log`` [steps, R] (the ladder's
+    columns of the device log, with a field ``accepted``): its decisions are followed, for hops and exchanges."""
+    fw = np.asarray(framework, dtype=np.float64)
+    it = np.asarray(interactions, dtype=np.float64)
+    pops = [np.array(p, dtype=np.int64) for p in populations]
+    R, m = len(pops), len(pops[0])
+    T = np.asarray(temperatures, dtype=np.float64).reshape(-1, R)
+    e = [np.float64(x) for x in energies]
+    d = [np.float64(0.0)] * R if deltas is None else [np.float64(x) for x in deltas]
+    rep = list(range(R)) if replica is None else [int(x) for x in replica]
+    att, acc = np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64)
+    pa, pc = np.zeros(R - 1, dtype=np.int64), np.zeros(R - 1, dtype=np.int64)
+    steps, ce, cp = [[] for _ in range(R)], [], []
+    t = 0
+    for Tc in T:
+        for _ in range(int(steps_per_cycle)):
+            s = int(first_step) + t
+            pair, u = site_exchange_draw(seed, s, ladder_stream, cdf)
+            for r in range(R):
+                if pair >= 0 and r in (pair, pair + 1):
+                    continue
+                dec = None if log is None else bool(log["accepted"][t, r])
+                st = site_step(fw, it, pops[r], seed, s, int(stream_ids[r]), float(Tc[r]), dec)
+                att[r] += 1
+                if st.accepted:
+                    diff = np.float64(st.after) - np.float64(st.before)
+                    e[r], d[r] = e[r] + diff, d[r] + diff
+                    acc[r] += 1
+                steps[r].append(st)
+            if pair >= 0:
+                a, b = pair, pair + 1
+                E_a, E_b = float(e[a]), float(e[b])
+                thr = site_exchange_threshold(E_a, E_b, float(Tc[a]), float(Tc[b]))
+                ok = bool(E_b < E_a or u < thr)
+                if log is not None:
+                    ok = bool(log["accepted"][t, a])
+                pa[a] += 1
+                if ok:
+                    pc[a] += 1
+                    pops[a], pops[b] = pops[b], pops[a]
+                    e[a], e[b], d[a], d[b] = e[b], e[a], d[b], d[a]
+                    rep[a], rep[b] = rep[b], rep[a]
+                steps[a].append(SiteStep(-1, -1, -1, E_a, E_b, u, thr, ok))
+                steps[b].append(SiteStep(-2, -1, -1, E_a, E_b, u, thr, ok))
+            t += 1
+        ce.append([float(x) for x in e])
+        cp.append([p.astype(np.uint16) for p in pops])
+    return SiteLadderReplay(steps, np.array([p.astype(np.uint16) for p in pops], dtype=np.uint16).reshape(R, m), np.array(e, dtype=np.float64),
+                            np.array(d, dtype=np.float64), np.array(ce, dtype=np.float64).reshape(len(ce), R),
+                            np.array(cp, dtype=np.uint16).reshape(len(cp), R, m), att, acc, pa, pc, np.array(rep, dtype=np.int32))
 
 
 def site_baseline(framework, interactions, population, tailcorrection: float = 0.0):

@@ -6,7 +6,9 @@
 copy of the tables on the device and runs whole cycles of all of them inside one kernel; :func:`run_montecarlo` and
 :func:`run_random_quenching` are ``run_montecarlo!(::SiteHopping, ...)`` (simulation.jl:863-1010, ``groupcycles = nothing``) and
 ``run_random_quenching`` on top of it.  Sites are 0-based here (the reference's are 1-based).  The step itself is specified in
-``include/ceg_hip.h`` and restated in :mod:`ceg_hip.mcrng` (``site_step``, ``site_replay``).
+``include/ceg_hip.h`` and restated in :mod:`ceg_hip.mcrng` (``site_step``, ``site_replay``).  :func:`run_parallel_tempering` is the
+reference's routine of that name (simulation.jl:461-634) on ``DeviceSiteHoppingGroup.set_tempering``: ladders of rungs that exchange
+configurations per step inside the sweep kernel (``mcrng.site_ladder_replay``).
 
 :func:`build_site_tables` is the reference's constructor (sitehopping.jl:41-82): both tables from a guest-free
 :class:`ceg_hip.energy.DeviceMonteCarlo` of the mobile species in three launches (``ceg_site_tables``)."""
@@ -136,6 +138,7 @@ class DeviceSiteHoppingGroup:
     def __init__(self, frameworkenergies, interactions, populations, tailcorrection: float = 0.0, device: int = 0):
         self._lib = _abi.load_library()
         self._h = None
+        self.rungs = None                 # set_tempering
         pops = np.ascontiguousarray(populations)
         if pops.ndim != 2:
             raise ValueError("populations must be [K, m]")
@@ -261,6 +264,41 @@ class DeviceSiteHoppingGroup:
         _abi.check(self._lib, self._lib.ceg_site_group_recorder_min(self._h, _abi.i64ptr(mink), _abi.dptr(mine), pops.ctypes.data))
         return mink, mine, pops
 
+    def set_tempering(self, rungs: Optional[int], p: float = 0.1, pair_cdf=None, ladder_stream=None) -> None:
+        """``ceg_site_group_set_tempering``: the K chains become K / ``rungs`` ladders (chain ``l * rungs + r`` is rung r of ladder
+        l) that exchange configurations per step inside the sweep kernel, by the rule of ``include/ceg_hip.h`` restated in
+        :mod:`ceg_hip.mcrng`.  ``pair_cdf`` float64[rungs - 1] (default ``mcrng.site_exchange_cdf(rungs, p)``, the reference's
+        ``randsubseq(1:(Npt-1), 0.1)``), ``ladder_stream`` uint32[K / rungs] (default: the ladder's index).  The temperatures of
+        later sweeps must rise strictly with the rung inside every ladder.  ``rungs=None`` removes the tempering."""
+        if rungs is None:
+            _abi.check(self._lib, self._lib.ceg_site_group_set_tempering(self._h, None))
+            self.rungs = None
+            return
+        rungs = int(rungs)
+        valid = 2 <= rungs <= _abi.SITE_MAX_RUNGS and self.k % rungs == 0          # (else the library refuses, whatever the tables)
+        if pair_cdf is None:
+            cdf = mcrng.site_exchange_cdf(rungs, p) if valid else np.zeros(0)
+        else:
+            cdf = np.ascontiguousarray(pair_cdf, dtype=np.float64).reshape(-1)
+        ls = None if ladder_stream is None else np.ascontiguousarray(ladder_stream, dtype=np.uint32).reshape(-1)
+        if valid and (len(cdf) != rungs - 1 or (ls is not None and len(ls) != self.k // rungs)):
+            raise ValueError("pair_cdf must be [rungs - 1] and ladder_stream [K / rungs]")
+        spec = _abi.SiteTempering(rungs, 0, cdf.ctypes.data if cdf.size else None, ls.ctypes.data if ls is not None else None, 0)
+        _abi.check(self._lib, self._lib.ceg_site_group_set_tempering(self._h, C.byref(spec)))
+        self.rungs = rungs
+
+    def tempering_read(self):
+        """-> (attempted int64[K / R, R - 1], accepted int64[K / R, R - 1] per pair of rungs, replica int32[K]: per rung, the rung on
+        which the configuration now there sat when tempering was installed)"""
+        R = getattr(self, "rungs", None)
+        if not R:
+            _abi.check(self._lib, self._lib.ceg_site_group_tempering_read(self._h, None, None, None))     # raises: nothing installed
+            raise RuntimeError("the group has no tempering")
+        att, acc = (np.zeros((self.k // R, R - 1), dtype=np.int64) for _ in range(2))
+        rep = np.zeros(self.k, dtype=np.int32)
+        _abi.check(self._lib, self._lib.ceg_site_group_tempering_read(self._h, _abi.i64ptr(att.reshape(-1)), _abi.i64ptr(acc.reshape(-1)), _abi.i32ptr(rep)))
+        return att, acc, rep
+
     def close(self) -> None:
         if self._h is not None:
             self._lib.ceg_site_group_destroy(self._h)
@@ -363,3 +401,45 @@ def run_random_quenching(sh: SiteHopping, N: int, temperatures, ncycles: int, *,
     with DeviceSiteHoppingGroup(sh.frameworkenergies, sh.interactions, start, sh.tailcorrection, device) as g:
         run = run_montecarlo(g, temperatures, int(ncycles), 0, printevery=printevery, seed=seed, track_min=True)
     return QuenchingRun(start, run)
+
+
+class ParallelTemperingRun(NamedTuple):
+    temperatures: np.ndarray      # float64[Npt] sorted: the rungs
+    energies: np.ndarray          # float64[N_print, K] by rung (K = ladders * Npt; chain l * Npt + r is rung r of ladder l): the matrix the reference returns
+    populations: np.ndarray       # uint16[N_print, K, m] by rung
+    cycles: np.ndarray            # int64[N_print] idx_cycle of the frames
+    hops_attempted: np.ndarray    # int64[K] per rung, initialisation included
+    hops_accepted: np.ndarray     # int64[K]
+    pairs_attempted: np.ndarray   # int64[ladders, Npt - 1] exchanges of rungs j and j + 1
+    pairs_accepted: np.ndarray    # int64[ladders, Npt - 1]
+    replica: np.ndarray           # int32[K] per rung: the rung its configuration started on
+    run: SiteHoppingRun           # everything run_montecarlo returns, by rung
+
+
+def run_parallel_tempering(sh: SiteHopping, temperatures, ncycles: int, ninit: int = 0, *, printevery: int = 1, seed: int = 0, device: int = 0,
+                           ladders: int = 1, p: float = 0.1) -> ParallelTemperingRun:
+    """``run_parallel_tempering(sh0, simu, temperatures)`` (simulation.jl:461-634): ``Npt = len(temperatures)`` copies of ``sh`` at the
+    sorted temperatures; at every step the first pair of ``randsubseq(1:(Npt-1), p)`` may exchange configurations
+    (``DeviceSiteHoppingGroup.set_tempering``; the rule is restated in :mod:`ceg_hip.mcrng`), every other rung hops.  ``ladders``
+    independent ladders run side by side: ladder l draws its exchanges from stream l, its rung r hops on stream ``l * Npt + r``.
+
+    Every rung starts from ``sh``'s population and baseline.  The frames follow the reference's ``report_now``: ``idx_cycle`` 0, then
+    every ``printevery`` cycles (``printevery == 0``: frame 0 and the last cycle), ``N_print`` rows in all.  At the end the drift
+    check of :612-616 is applied per rung at rtol 1e-9 (:class:`SiteHoppingDrift`).
+
+    The reference's own routine appears to fail for ``ninit > 0`` (:512 and :567 read ``energy`` and ``sh`` outside their scope), so
+    this wrapper runs the ``ninit`` cycles (with exchanges) and rebases every rung at ``idx_cycle`` 0, as
+    ``run_montecarlo!(::SiteHopping)`` does.  Not covered: ``groupcycles``, a schedule that attempts more than the first pair, and
+    the output files."""
+    Ts = np.sort(np.asarray(temperatures, dtype=np.float64).reshape(-1))
+    npt, ladders = len(Ts), int(ladders)
+    if ladders < 1:
+        raise ValueError("ladders >= 1")
+    k = ladders * npt
+    start = np.tile(np.asarray(sh.population, dtype=np.uint16), (k, 1))
+    with DeviceSiteHoppingGroup(sh.frameworkenergies, sh.interactions, start, sh.tailcorrection, device) as g:
+        g.set_tempering(npt, p)
+        run = run_montecarlo(g, np.tile(Ts, (int(ninit) + int(ncycles), ladders)), int(ncycles), int(ninit), printevery=printevery, seed=seed,
+                             drift_rtol=1e-9)
+        att, acc, rep = g.tempering_read()
+    return ParallelTemperingRun(Ts, run.energies, run.populations, run.cycles, run.stats["attempted"].copy(), run.stats["accepted"].copy(), att, acc, rep, run)

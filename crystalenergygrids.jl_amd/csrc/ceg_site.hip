@@ -4,7 +4,9 @@
 // (k_site_sweep), the population in LDS, the two table rows read from global memory where the population points.  The state that
 // outlives a launch -- population, running energy, counters -- sits in device memory, so a call can be cut into launches anywhere.
 // The step is specified word for word in include/ceg_hip.h and restated in ceg_hip/mcrng.py (site_step).  The group knows no
-// ceg_mc_t: it is self-contained.
+// ceg_mc_t: it is self-contained.  With tempering installed (ceg_site_group_set_tempering) the chains are ladders of R rungs and the
+// same call launches k_site_sweep_pt instead: one workgroup per ladder, one wave per rung, the exchange of run_parallel_tempering
+// (src/simulation.jl:461-634) drawn per step inside the kernel (mcrng.site_ladder_replay).
 // The second half of the file builds the two tables (ceg_site_tables / ceg_site_tables_device) from a guest-free ceg_mc_t of the
 // mobile species in three launches for any number of sites: k_site_points (framework terms and structure factor per site),
 // k_site_recip_pairs (the reciprocal pair term, v_mfma_f64_16x16x4 over 16 x 16 site tiles of the upper triangle) and
@@ -24,10 +26,12 @@ namespace {
 
 static_assert(sizeof(ceg_site_params_t) == 24 && sizeof(ceg_site_cycles_t) == 32 && sizeof(ceg_site_stats_t) == 32 &&
               sizeof(ceg_site_cycle_record_t) == 56 && sizeof(ceg_site_record_t) == 40 && sizeof(ceg_site_recorder_t) == 32 &&
-              sizeof(ceg_site_frame_record_t) == 16, "layouts the bindings restate");
+              sizeof(ceg_site_frame_record_t) == 16 && sizeof(ceg_site_tempering_t) == 32, "layouts the bindings restate");
 
 constexpr uint32_t SITE_SELECT = 10;             // the purpose of the (molecule, site) draw; 3 (ceg_philox::ACCEPT) gives u
+constexpr uint32_t SITE_EXCHANGE = 12;           // the purpose of a ladder's exchange draw (11 is the host's SITE_POPULATE)
 constexpr int BASE_THREADS = 256;
+constexpr int PT_MAX_RUNGS = 16;                 // 16 waves: one workgroup of 1024 threads
 
 struct SiteRecorderView {                        // every == 0 and track_min == 0: no recorder
     int64_t every, origin, capacity;
@@ -178,6 +182,189 @@ __global__ __launch_bounds__(64) void k_site_sweep(const SiteSweep S)
     }
 }
 
+struct SiteLadders {                             // by value (kernarg): the tempering of the group, include/ceg_hip.h "tempering"
+    const double* pair_cdf;                      // [R-1]
+    const uint32_t* ladder_stream;               // [K/R]
+    int64_t *pt_attempted, *pt_accepted;         // [K/R][R-1]
+    int32_t* replica;                            // [K]
+    int32_t rungs, pop_stride;                   // R; the uint16 entries between two populations in LDS (pop_lds(m) / 2)
+};
+
+struct SiteHop {
+    int i, old, nw;
+    double before, after, u;
+    bool ok;
+};
+
+// The step of k_site_sweep on the population `pop` (LDS), operation for operation: the lane stride, the xor butterfly and the rule.
+// Wave-uniform but for the lane's share of the two sums; on acceptance lane 0 writes pop[i] and the caller adds after - before.
+__device__ __forceinline__ SiteHop site_hop(const SiteSweep& S, uint16_t* pop, uint64_t s, uint32_t stream, double T, int lane)
+{
+    const int m = S.m;
+    const size_t n = (size_t)S.n;
+    const ceg_philox::Block a = ceg_philox::draw(S.seed, s, stream, SITE_SELECT);
+    const ceg_philox::Block b = ceg_philox::draw(S.seed, s, stream, ceg_philox::ACCEPT);
+    SiteHop h;
+    h.i = min((int)floor(ceg_philox::uniform(a.w[0], a.w[1]) * (double)m), m - 1);
+    h.nw = min((int)floor(ceg_philox::uniform(a.w[2], a.w[3]) * (double)S.n), S.n - 1);
+    h.u = ceg_philox::uniform(b.w[0], b.w[1]);
+    h.old = (int)pop[h.i];
+    const double* __restrict__ row_old = S.interactions + (size_t)h.old * n;
+    const double* __restrict__ row_new = S.interactions + (size_t)h.nw * n;
+    const double f_old = S.framework[h.old], f_new = S.framework[h.nw];
+    double so = 0.0, sn = 0.0;
+    for (int j = lane; j < m; j += 64) {
+        const size_t p = (size_t)pop[j];
+        double x = row_old[p], y = row_new[p];
+        if (j == h.i) { x = 0.0; y = 0.0; }
+        so += x;
+        sn += y;
+    }
+    so += __shfl_xor(so, 32); sn += __shfl_xor(sn, 32);
+    so += __shfl_xor(so, 16); sn += __shfl_xor(sn, 16);
+    so += from_lane_xor<8>(so); sn += from_lane_xor<8>(sn);
+    so += from_lane_xor<4>(so); sn += from_lane_xor<4>(sn);
+    so += from_lane_xor<2>(so); sn += from_lane_xor<2>(sn);
+    so += from_lane_xor<1>(so); sn += from_lane_xor<1>(sn);
+    h.before = f_old + so;
+    h.after = f_new + sn;
+    h.ok = h.after < h.before;
+    if (!h.ok) h.ok = h.u < exp((h.before - h.after) / T);
+    if (h.ok && lane == 0) pop[h.i] = (uint16_t)h.nw;
+    return h;
+}
+
+// Workgroup l = ladder l, wave r = rung r = chain l R + r (blockDim = 64 R).  The R populations sit in dynamic LDS, `slot` says
+// which one the rung owns; energy, delta, slot and the replica entry belong to the configuration and change hands in an exchange,
+// everything else in the wave's registers belongs to the rung.  The counters of pair j live in wave j.
+// Protocol, ONE workgroup barrier per step, double-buffered by the step's parity p = t & 1: lane 0 of every wave publishes
+// (energy, delta, slot, replica) into s_pub*[p][r], then the barrier, then the step.  The two waves of an attempted pair read the
+// partner's entry of s_pub*[p] and come to the same decision from the same bits; nobody writes s_pub*[p] again before the barrier
+// of step t + 1 has passed, which every reader of step t reaches only after its reads, so a late reader never meets step t + 2's
+// values.  The same barrier orders a lane-0 population write of step t before every read of step t + 1, whichever wave owns the
+// slot by then.  The barrier is the first statement of the loop body and the one after the loop: no branch that depends on the
+// rung, the pair or the cycle contains one, and the end-of-cycle code has none -- it patches this step's hop into what it copies
+// (pop_at) instead of waiting for lane 0's write.
+// Indices: as k_site_sweep; slot < R as published by waves of this workgroup; pair < R - 1, so pair + 1 is a rung; the counters
+// inside [K/R][R-1].
+__global__ __launch_bounds__(1024) void k_site_sweep_pt(const SiteSweep S, const SiteLadders P)
+{
+    extern __shared__ uint16_t s_pop[];
+    __shared__ double s_pub_e[2][PT_MAX_RUNGS], s_pub_d[2][PT_MAX_RUNGS], s_cdf[PT_MAX_RUNGS];
+    __shared__ int32_t s_pub_slot[2][PT_MAX_RUNGS], s_pub_rep[2][PT_MAX_RUNGS];
+    const int R = P.rungs, l = (int)blockIdx.x, r = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    const int c = l * R + r, m = S.m;
+    const size_t K = (size_t)S.k;
+    uint16_t* gpop = S.pop + (size_t)c * (size_t)m;
+    int slot = r;                                // between launches the populations lie by rung
+    for (int j = lane; j < m; j += 64) s_pop[(size_t)slot * P.pop_stride + j] = gpop[j];
+    if ((int)threadIdx.x < R - 1) s_cdf[threadIdx.x] = P.pair_cdf[threadIdx.x];
+    double energy = S.energy[c], delta = S.delta[c];
+    int32_t rep = P.replica[c];
+    int64_t attempted = S.attempted[c], accepted = S.accepted[c];
+    int64_t pt_att = 0, pt_acc = 0;              // of the pair (r, r + 1)
+    if (r < R - 1) { pt_att = P.pt_attempted[(size_t)l * (R - 1) + r]; pt_acc = P.pt_accepted[(size_t)l * (R - 1) + r]; }
+    const uint32_t stream = S.stream[c], lstream = P.ladder_stream[l];
+    int64_t cyc = S.t0 / S.spc, in = S.t0 - cyc * S.spc;
+    double T = S.temperature[(size_t)cyc * K + c];
+    double mine = S.rec.track_min ? S.rec.mine[c] : 0.0;
+    for (int64_t t = S.t0; t < S.t1; ++t) {
+        const int p = (int)(t & 1);
+        if (lane == 0) { s_pub_e[p][r] = energy; s_pub_d[p][r] = delta; s_pub_slot[p][r] = slot; s_pub_rep[p][r] = rep; }
+        __syncthreads();                         // the step's only barrier
+        const uint64_t s = S.first_step + (uint64_t)t;
+        const ceg_philox::Block x = ceg_philox::draw(S.seed, s, lstream, SITE_EXCHANGE);
+        const double v = ceg_philox::uniform(x.w[0], x.w[1]);
+        int pair = 0;                            // the first j with v < pair_cdf[j] (non-decreasing: the entries <= v come first)
+        while (pair < R - 1 && !(v < s_cdf[pair])) ++pair;
+        int hop_i = -1, hop_nw = 0;              // this step's accepted hop, for the copies at the cycle's end
+        if (pair < R - 1 && (r == pair || r == pair + 1)) {
+            const int q = r == pair ? pair + 1 : pair;
+            const double u = ceg_philox::uniform(x.w[2], x.w[3]);
+            const double E_a = s_pub_e[p][pair], E_b = s_pub_e[p][pair + 1];
+            const double T_a = S.temperature[(size_t)cyc * K + (size_t)(l * R + pair)], T_b = S.temperature[(size_t)cyc * K + (size_t)(l * R + pair + 1)];
+            bool ok = E_b < E_a;
+            if (!ok) {
+                const double Tx = 1.0 / (1.0 / T_a - 1.0 / T_b);
+                ok = u < exp((E_a - E_b) / Tx);
+            }
+            if (r == pair) { ++pt_att; if (ok) ++pt_acc; }
+            if (ok) {
+                energy = s_pub_e[p][q];
+                delta = s_pub_d[p][q];
+                slot = s_pub_slot[p][q];
+                rep = s_pub_rep[p][q];
+            }
+            if (S.log && lane == 0) {
+                ceg_site_record_t rec;
+                rec.molecule = r == pair ? -1 : -2; rec.old_site = -1; rec.new_site = -1; rec.accepted = ok ? 1 : 0;
+                rec.before = E_a; rec.after = E_b; rec.u = u;
+                S.log[(size_t)t * K + c] = rec;
+            }
+        } else {
+            const SiteHop h = site_hop(S, s_pop + (size_t)slot * P.pop_stride, s, stream, T, lane);
+            ++attempted;
+            if (h.ok) {
+                const double d = h.after - h.before;
+                energy = energy + d;
+                delta = delta + d;
+                ++accepted;
+                hop_i = h.i;
+                hop_nw = h.nw;
+            }
+            if (S.log && lane == 0) {
+                ceg_site_record_t rec;
+                rec.molecule = h.i; rec.old_site = h.old; rec.new_site = h.nw; rec.accepted = h.ok ? 1 : 0;
+                rec.before = h.before; rec.after = h.after; rec.u = h.u;
+                S.log[(size_t)t * K + c] = rec;
+            }
+        }
+        if (++in == S.spc) {                     // ---- the end of cycle cc, by rung, with what sits on the rung now (no barrier here)
+            const uint16_t* pop = s_pop + (size_t)slot * P.pop_stride;
+            auto pop_at = [&](int j) { return j == hop_i ? (uint16_t)hop_nw : pop[j]; };
+            const int64_t cc = S.cycle0 + cyc;
+            int32_t flags = 0;
+            const SiteRecorderView& V = S.rec;
+            if (V.every > 0 && cc >= V.origin && (cc - V.origin) % V.every == 0) {
+                const int64_t fs = V.frame0 + (cc - V.first_due) / V.every;
+                if (fs >= 0 && fs < V.capacity) {
+                    uint16_t* f = V.frames + ((size_t)fs * K + c) * (size_t)m;
+                    for (int j = lane; j < m; j += 64) f[j] = pop_at(j);
+                    if (lane == 0) V.frec[(size_t)fs * K + c] = ceg_site_frame_record_t{cc, energy};
+                    flags |= CEG_SITE_FRAME_TAKEN;
+                } else {
+                    flags |= CEG_SITE_FRAME_DROPPED;
+                }
+            }
+            if (V.track_min && energy < mine) {
+                mine = energy;
+                uint16_t* f = V.best + (size_t)c * (size_t)m;
+                for (int j = lane; j < m; j += 64) f[j] = pop_at(j);
+                if (lane == 0) { V.mine[c] = energy; V.mink[c] = cc; }
+                flags |= CEG_SITE_NEW_MINIMUM;
+            }
+            if (S.cyc && lane == 0) {
+                ceg_site_cycle_record_t rec;
+                rec.cycle = cc; rec.temperature = T; rec.energy = energy; rec.delta = delta;
+                rec.attempted = attempted; rec.accepted = accepted; rec.flags = flags; rec._pad = 0;
+                S.cyc[(size_t)cyc * K + c] = rec;
+            }
+            ++cyc;
+            in = 0;
+            if (t + 1 < S.t1) T = S.temperature[(size_t)cyc * K + c];
+        }
+    }
+    __syncthreads();                             // the last step's population writes, before any wave copies a slot out
+    const uint16_t* pop = s_pop + (size_t)slot * P.pop_stride;
+    for (int j = lane; j < m; j += 64) gpop[j] = pop[j];
+    if (lane == 0) {
+        S.energy[c] = energy; S.delta[c] = delta;
+        S.attempted[c] = attempted; S.accepted[c] = accepted;
+        P.replica[c] = rep;
+        if (r < R - 1) { P.pt_attempted[(size_t)l * (R - 1) + r] = pt_att; P.pt_accepted[(size_t)l * (R - 1) + r] = pt_acc; }
+    }
+}
+
 // Workgroup c: baseline_energy (sitehopping.jl:105-112) of chain c.  Thread t takes the rows i = t, t + 256, ... and in each the
 // pairs j = i + 1 .. m - 1 in rising order; the partial sums meet by an xor butterfly per wave and then wave by wave.
 __global__ __launch_bounds__(BASE_THREADS) void k_site_baseline(const double* __restrict__ framework, const double* __restrict__ interactions,
@@ -231,6 +418,22 @@ void recorder_free(SiteRecorder* r)
     delete r;
 }
 
+struct SiteTempering {                           // ceg_site_group_set_tempering: L = K / rungs ladders
+    int rungs = 0;
+    double* d_cdf = nullptr;                     // [R-1]
+    uint32_t* d_lstream = nullptr;               // [L]
+    int64_t *d_attempted = nullptr, *d_accepted = nullptr;   // [L][R-1]
+    int32_t* d_replica = nullptr;                // [K]
+};
+
+void tempering_free(SiteTempering* t)
+{
+    if (!t) return;
+    for (void* p : {(void*)t->d_cdf, (void*)t->d_lstream, (void*)t->d_attempted, (void*)t->d_accepted, (void*)t->d_replica})
+        if (p) (void)hipFree(p);
+    delete t;
+}
+
 // the first cycle >= from at whose end a frame is due (every > 0)
 int64_t first_due(const SiteRecorder* r, int64_t from)
 {
@@ -281,6 +484,7 @@ struct ceg_site_group {
     int64_t *d_attempted = nullptr, *d_accepted = nullptr;
     hipStream_t stream = nullptr;
     SiteRecorder* rec = nullptr;
+    SiteTempering* pt = nullptr;
 };
 
 namespace {
@@ -289,6 +493,7 @@ void group_free(ceg_site_group* g)
 {
     if (!g) return;
     recorder_free(g->rec);
+    tempering_free(g->pt);
     if (g->own_tables)
         for (const void* p : {(const void*)g->d_fw, (const void*)g->d_inter})
             if (p) (void)hipFree(const_cast<void*>(p));
@@ -312,6 +517,27 @@ int poisoned(ceg_site_group* g, const char* what)
 {
     g->poisoned = true;
     return fail(CEG_ERR_HIP, "site group: %s failed: %s; the group is inconsistent", what, hipGetErrorString(hipGetLastError()));
+}
+
+// replica[l R + r] = r: every configuration sits on its own rung (the stream is idle: a synchronous copy)
+bool identity_replica(ceg_site_group* g)
+{
+    std::vector<int32_t> id((size_t)g->k);
+    for (int c = 0; c < g->k; ++c) id[(size_t)c] = c % g->pt->rungs;
+    return hipMemcpy(g->pt->d_replica, id.data(), sizeof(int32_t) * id.size(), hipMemcpyHostToDevice) == hipSuccess;
+}
+
+// dynamic LDS of k_site_sweep_pt beside its static tables; false with the figures in *need / *have where it does not fit
+bool ladder_lds_fits(const ceg_site_group* g, int rungs, size_t* need, size_t* have)
+{
+    hipFuncAttributes fa{};
+    int limit = 0;
+    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_site_sweep_pt)) != hipSuccess ||
+        hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, g->device) != hipSuccess)
+        limit = 0;
+    *need = (size_t)rungs * pop_lds(g->m) + fa.sharedSizeBytes;
+    *have = (size_t)std::max(limit, 0);
+    return *need <= *have;
 }
 
 #define SITE_ENTER(g)                                                                                                     \
@@ -412,6 +638,7 @@ extern "C" int ceg_site_group_set_populations(ceg_site_group_t* g, const uint16_
     HIP_TRY(hipStreamSynchronize(g->stream));
     if (hipMemcpy(g->d_pop, populations, (size_t)g->k * (size_t)g->m * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) return poisoned(g, "the upload of the populations");
     if (launch_baseline(g, nullptr, g->d_energy) != hipSuccess || hipStreamSynchronize(g->stream) != hipSuccess) return poisoned(g, "the baseline launch");
+    if (g->pt && !identity_replica(g)) return poisoned(g, "the reset of the replica map");
     return CEG_OK;
 }
 
@@ -434,6 +661,11 @@ extern "C" int ceg_site_group_sweep_cycles(ceg_site_group_t* g, const ceg_site_p
         for (size_t e = 0; e < (size_t)cy->ncycles * K; ++e)
             if (!(std::isfinite(cy->temperature[e]) && cy->temperature[e] > 0.0))
                 return fail(CEG_ERR_INVALID, "site sweep: the temperature of cycle %lld, chain %lld is not finite and > 0", (long long)(e / K), (long long)(e % K));
+        if (g->pt)                               // the reference sorts Ts: inside a ladder the rungs' temperatures rise strictly
+            for (size_t e = 0; e < (size_t)cy->ncycles * K; ++e)
+                if (e % K % (size_t)g->pt->rungs != 0 && !(cy->temperature[e - 1] < cy->temperature[e]))
+                    return fail(CEG_ERR_INVALID, "site sweep: cycle %lld, chain %lld: the temperatures of a ladder must rise strictly with the rung",
+                                (long long)(e / K), (long long)(e % K));
     }
     const int64_t per_launch = env_int("CEG_HIP_SITE_STEPS_PER_LAUNCH", 4096, 1, (int64_t)1 << 30);
 
@@ -473,7 +705,11 @@ extern "C" int ceg_site_group_sweep_cycles(ceg_site_group_t* g, const ceg_site_p
         for (int64_t t0 = 0; t0 < total; t0 += per_launch) {
             S.t0 = t0;
             S.t1 = std::min(total, t0 + per_launch);
-            hipLaunchKernelGGL(k_site_sweep, dim3((unsigned)g->k), dim3(64), pop_lds(g->m), g->stream, S);
+            if (const SiteTempering* pt = g->pt) {
+                const SiteLadders P{pt->d_cdf, pt->d_lstream, pt->d_attempted, pt->d_accepted, pt->d_replica, pt->rungs, (int32_t)(pop_lds(g->m) / sizeof(uint16_t))};
+                hipLaunchKernelGGL(k_site_sweep_pt, dim3((unsigned)(g->k / pt->rungs)), dim3(64u * (unsigned)pt->rungs), (size_t)pt->rungs * pop_lds(g->m), g->stream, S, P);
+            } else
+                hipLaunchKernelGGL(k_site_sweep, dim3((unsigned)g->k), dim3(64), pop_lds(g->m), g->stream, S);
             if (hipGetLastError() != hipSuccess) {
                 release();
                 return poisoned(g, "a sweep launch");
@@ -565,6 +801,69 @@ extern "C" int ceg_site_group_recorder_min(ceg_site_group_t* g, int64_t* mink_ou
     if (mink_out) HIP_TRY(hipMemcpy(mink_out, r->d_mink, sizeof(int64_t) * K, hipMemcpyDeviceToHost));
     if (mine_out) HIP_TRY(hipMemcpy(mine_out, r->d_mine, sizeof(double) * K, hipMemcpyDeviceToHost));
     if (populations_out) HIP_TRY(hipMemcpy(populations_out, r->d_best, K * (size_t)g->m * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return CEG_OK;
+}
+
+extern "C" int ceg_site_group_set_tempering(ceg_site_group_t* g, const ceg_site_tempering_t* spec)
+{
+    SITE_ENTER(g);
+    if (!spec) {
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        tempering_free(g->pt);
+        g->pt = nullptr;
+        return CEG_OK;
+    }
+    const int R = spec->rungs;
+    if (R < 2 || R > PT_MAX_RUNGS) return fail(CEG_ERR_INVALID, "site tempering: %d rungs, outside 2..%d", R, PT_MAX_RUNGS);
+    if (g->k % R != 0) return fail(CEG_ERR_INVALID, "site tempering: K = %d chains are no whole number of ladders of %d rungs", g->k, R);
+    if (spec->_reserved != 0) return fail(CEG_ERR_INVALID, "site tempering: _reserved must be 0");
+    if (!spec->pair_cdf) return fail(CEG_ERR_INVALID, "site tempering: the pair table is missing");
+    for (int j = 0; j < R - 1; ++j) {
+        const double v = spec->pair_cdf[j];
+        if (!(std::isfinite(v) && v >= 0.0 && v <= 1.0) || (j > 0 && v < spec->pair_cdf[j - 1]))
+            return fail(CEG_ERR_INVALID, "site tempering: pair_cdf[%d] is not finite, outside [0, 1] or below the entry before it", j);
+    }
+    size_t need = 0, have = 0;
+    if (!ladder_lds_fits(g, R, &need, &have))
+        return fail(CEG_ERR_UNSUPPORTED, "site tempering: %d populations of %d molecules take %zu bytes of LDS, the device gives a workgroup %zu", R, g->m, need, have);
+    const size_t K = (size_t)g->k, L = K / (size_t)R, npairs = L * (size_t)(R - 1);
+    std::vector<uint32_t> ls(L);
+    for (size_t l = 0; l < L; ++l) ls[l] = spec->ladder_stream ? spec->ladder_stream[l] : (uint32_t)l;
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    SiteTempering* t = new SiteTempering();
+    t->rungs = R;
+    SiteTempering* old = g->pt;
+    g->pt = t;                                   // (identity_replica writes the group's)
+    const bool ok = hipMalloc((void**)&t->d_cdf, sizeof(double) * (size_t)(R - 1)) == hipSuccess && hipMalloc((void**)&t->d_lstream, sizeof(uint32_t) * L) == hipSuccess &&
+                    hipMalloc((void**)&t->d_attempted, sizeof(int64_t) * npairs) == hipSuccess && hipMalloc((void**)&t->d_accepted, sizeof(int64_t) * npairs) == hipSuccess &&
+                    hipMalloc((void**)&t->d_replica, sizeof(int32_t) * K) == hipSuccess &&
+                    hipMemcpy(t->d_cdf, spec->pair_cdf, sizeof(double) * (size_t)(R - 1), hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(t->d_lstream, ls.data(), sizeof(uint32_t) * L, hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemset(t->d_attempted, 0, sizeof(int64_t) * npairs) == hipSuccess && hipMemset(t->d_accepted, 0, sizeof(int64_t) * npairs) == hipSuccess &&
+                    identity_replica(g) && hipDeviceSynchronize() == hipSuccess &&
+                    // (above 64 KiB of dynamic LDS the runtime wants to be told; the size was checked against the device's limit)
+                    ((size_t)R * pop_lds(g->m) <= 64 * 1024 ||
+                     hipFuncSetAttribute(reinterpret_cast<const void*>(k_site_sweep_pt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)R * pop_lds(g->m))) == hipSuccess);
+    if (!ok) {
+        const int rc = fail(CEG_ERR_HIP, "site tempering: could not set up the device buffers: %s", hipGetErrorString(hipGetLastError()));
+        g->pt = old;
+        tempering_free(t);
+        return rc;
+    }
+    tempering_free(old);
+    return CEG_OK;
+}
+
+extern "C" int ceg_site_group_tempering_read(ceg_site_group_t* g, int64_t* attempted, int64_t* accepted, int32_t* replica)
+{
+    SITE_ENTER(g);
+    const SiteTempering* t = g->pt;
+    if (!t) return fail(CEG_ERR_INVALID, "site tempering: the group has no tempering (ceg_site_group_set_tempering)");
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    const size_t K = (size_t)g->k, npairs = K / (size_t)t->rungs * (size_t)(t->rungs - 1);
+    if (attempted) HIP_TRY(hipMemcpy(attempted, t->d_attempted, sizeof(int64_t) * npairs, hipMemcpyDeviceToHost));
+    if (accepted) HIP_TRY(hipMemcpy(accepted, t->d_accepted, sizeof(int64_t) * npairs, hipMemcpyDeviceToHost));
+    if (replica) HIP_TRY(hipMemcpy(replica, t->d_replica, sizeof(int32_t) * K, hipMemcpyDeviceToHost));
     return CEG_OK;
 }
 

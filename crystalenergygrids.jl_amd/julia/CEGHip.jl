@@ -1383,6 +1383,53 @@ function site_group_recorder_min(g::Ptr{Cvoid}, m::Integer, k::Integer)
     mink, mine, pops .+ 0x0001
 end
 
+struct SiteTempering                 # ceg_site_tempering_t (32 bytes)
+    rungs::Int32
+    _pad::Int32
+    pair_cdf::Ptr{Float64}
+    ladder_stream::Ptr{UInt32}
+    _reserved::Int64
+end
+
+"""
+`ceg_site_group_set_tempering`: the K chains become `K ÷ rungs` ladders whose neighbouring rungs exchange configurations per step
+inside the sweep kernel, as `run_parallel_tempering` (src/simulation.jl:461-634) does; the rule is stated in include/ceg_hip.h.
+`pair_cdf` defaults to the reference's schedule, the first element of `randsubseq(1:(Npt-1), p)`: `1 - q` with `q` multiplied by
+`1 - p` once per pair.  The temperatures of later sweeps must rise strictly with the rung.  `rungs === nothing` removes it.
+UNVERIFIED: never executed.
+"""
+function site_group_set_tempering!(g::Ptr{Cvoid}, rungs::Union{Nothing,Integer}; p::Float64=0.1, pair_cdf::Union{Nothing,Vector{Float64}}=nothing,
+                                   ladder_stream::Union{Nothing,Vector{UInt32}}=nothing)
+    if rungs === nothing
+        _check(ccall((:ceg_site_group_set_tempering, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), g, C_NULL))
+        return nothing
+    end
+    cdf = pair_cdf
+    if cdf === nothing
+        cdf = Vector{Float64}(undef, max(rungs - 1, 0))
+        q = 1.0
+        for j in 1:length(cdf)
+            q = q * (1.0 - p)
+            cdf[j] = 1.0 - q
+        end
+    end
+    GC.@preserve cdf ladder_stream begin
+        spec = Ref(SiteTempering(Int32(rungs), Int32(0), pointer(cdf), ladder_stream === nothing ? Ptr{UInt32}(C_NULL) : pointer(ladder_stream), Int64(0)))
+        _check(ccall((:ceg_site_group_set_tempering, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), g, spec))
+    end
+    nothing
+end
+
+"""
+`ceg_site_group_tempering_read` -> (attempted `(rungs-1) x ladders`, accepted `(rungs-1) x ladders`, replica `k`: per rung, the
+1-based rung on which the configuration now there sat when tempering was installed).  UNVERIFIED: never executed.
+"""
+function site_group_tempering_read(g::Ptr{Cvoid}, rungs::Integer, k::Integer)
+    attempted = zeros(Int64, rungs - 1, k ÷ rungs); accepted = zeros(Int64, rungs - 1, k ÷ rungs); replica = zeros(Int32, k)
+    _check(ccall((:ceg_site_group_tempering_read, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}), g, attempted, accepted, replica))
+    attempted, accepted, replica .+ Int32(1)
+end
+
 """
 `baseline_energy(mc)` (src/montecarlo.jl:530-542) from the device state behind `h` (`mc_handle(mc, ...)`): the sums come from
 `ceg_mc_baseline`, the two constants of the Ewald context (`energy_net_charges`, `static_contribution`, src/ewald.jl:555-577) and

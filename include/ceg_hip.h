@@ -1328,9 +1328,48 @@ CEG_API int ceg_mc_group_baseline(ceg_mc_group_t* group, int32_t flags, ceg_mc_b
  *   every, origin or frame_capacity < 0, a store above CEG_MC_RECORDER_MAX_BYTES, a window outside the frames held, no recorder, no
  *   track_min.
  * A HIP failure once a launch has been enqueued marks the group inconsistent: every later call but destroy returns CEG_ERR_HIP.
- * Out of scope: groupcycles / restartgroupcycle; replica exchange between site-hopping chains (the reference draws it per step with
- *   randsubseq; the running energies stay on the device between the launches of a call, so a later change can put an exchange launch
- *   between them); extremal_placements; ShootingStarMinimizer; the serialised caches and output files.
+ * tempering (run_parallel_tempering, src/simulation.jl:461-634; ceg_site_group_set_tempering): the exchange of configurations between
+ *   neighbouring rungs of a temperature ladder, drawn per step inside the sweep kernel (k_site_sweep_pt: one workgroup per ladder,
+ *   one wave per rung, the R populations in LDS, one workgroup barrier per step).
+ *   Layout.  A group of K chains with tempering installed is L = K / R ladders of R rungs.  Chain l*R + r is rung r of ladder l.
+ *     A chain index means a rung from then on.  Temperatures, streams, hop counters, cycle records, frames and the minimum belong to
+ *     the rung.  Population, running `energy` and `delta` belong to the configuration and travel with it.  So energy - delta stays
+ *     the baseline that the configuration started from.
+ *   Temperatures.  The temperature table [ncycles][K] of ceg_site_group_sweep_cycles gives the rung temperatures.  Inside every
+ *     ladder and every cycle they must be strictly increasing with the rung, because the reference sorts Ts.  Otherwise the call
+ *     returns CEG_ERR_INVALID before anything is launched.
+ *   Exchange draw.  At the absolute step s, every ladder takes one Philox block.  The purpose is new: SITE_EXCHANGE = 12.  The
+ *     stream is the ladder's (ladder_stream[l], or l when the pointer is NULL).  v = U(w0, w1) chooses the pair.  u = U(w2, w3) is
+ *     the acceptance draw.
+ *   Pair table.  The pair is the first j in 0..R-2 with v < pair_cdf[j].  If there is none, the step has no exchange.
+ *     pair_cdf[R-1] is host memory given by the caller.  Each entry must be finite, in [0, 1] and non-decreasing.  Otherwise the
+ *     call returns CEG_ERR_INVALID.  The reference attempts at most the first element of randsubseq(1:(Npt-1), 0.1) (:528-529).
+ *     That is pair_cdf[j] = 1 - q_(j+1) with q_0 = 1 and q_(i+1) = q_i * (1 - p), computed by repeated multiplication
+ *     (mcrng.site_exchange_cdf).  Taking the table as input, rather than p, keeps a log off the device.  It also lets a caller
+ *     or a test reach the upper pairs.
+ *   Exchange attempt.  A step whose pair is j attempts the exchange of rungs j and j+1 (:531-543).  E_a and E_b are the running
+ *     energies of the two rungs at the start of the step.  Tx = 1.0 / (1.0 / T_j - 1.0 / T_(j+1)), with IEEE divisions in this
+ *     order.  The exchange is accepted iff E_b < E_a, or else u < exp((E_a - E_b) / Tx).  This is
+ *     compute_accept_move(energypt[ipt], energypt[ipt+1], inv(inv(T) - inv(Ts[ipt+1])), sh).
+ *   After the attempt.  pt_attempted[l][j] goes up by 1.  On acceptance pt_accepted[l][j] goes up by 1.  On acceptance the
+ *     populations of the two rungs are exchanged, and their `energy` and `delta` with them.  The two rungs make no hop at this
+ *     step.  `attempted` does not move.  Rung j logs molecule = -1, old_site = new_site = -1, before = E_a, after = E_b, u,
+ *     accepted.  Rung j+1 logs molecule = -2 and the same values.  Every other rung of the ladder makes the ordinary step of
+ *     k_site_sweep.  It uses its own stream and the same bits as today.
+ *   Cycle ends.  Cycle records, frames and track_min work as today, per rung.  They use the population and energy that sit on
+ *     the rung at that moment.  This is what the reference's simu.record(sh, energypt[ipt], ...) sees.
+ *   Replica map.  The group also keeps replica[K].  It holds, per rung, the rung (0..R-1) on which the configuration now there
+ *     sat when tempering was installed.  It is a permutation inside every ladder.
+ *   set_tempering: rungs R in 2..16 with K % R == 0, pair_cdf as above, _reserved == 0, else CEG_ERR_INVALID with the state
+ *     untouched; R populations that do not fit the LDS a workgroup may take (hipDeviceAttributeMaxSharedMemoryPerBlock) ->
+ *     CEG_ERR_UNSUPPORTED with the figures.  Installing synchronises, zeroes the pair counters and sets replica to the identity;
+ *     NULL removes the tempering.  set_populations resets replica as well; rebase leaves it.  While tempering is installed,
+ *     sweep_cycles launches k_site_sweep_pt and takes params->stream_id per rung; without it the call is what it was.  A run does
+ *     not depend on how it is cut, as above: populations (by rung), energy, delta, replica and the pair counters are in device
+ *     memory between launches.  tempering_read copies the pair counters [K/R][R-1] and replica [K] (every pointer optional);
+ *     CEG_ERR_INVALID with nothing installed.
+ * Out of scope: groupcycles / restartgroupcycle; a tempering schedule that attempts more than the first pair of randsubseq;
+ *   extremal_placements; ShootingStarMinimizer; the serialised caches and output files.
  *
  * The two tables (the reference's constructor, sitehopping.jl:41-82, telescoped): ceg_site_tables (host arrays out) and
  * ceg_site_tables_device (device arrays of the handle's device out, e.g. for ceg_site_group_create with tables_on_device).
@@ -1391,6 +1430,12 @@ typedef struct ceg_site_frame_record {  /* 16 bytes */
     int64_t cycle;
     double energy;
 } ceg_site_frame_record_t;
+typedef struct ceg_site_tempering {     /* 32 bytes */
+    int32_t rungs, _pad;                /* R in 2..16, K % R == 0 */
+    const double*   pair_cdf;           /* [R-1] host */
+    const uint32_t* ladder_stream;      /* [K/R] host, or NULL: the ladder's index */
+    int64_t _reserved;                  /* 0 */
+} ceg_site_tempering_t;
 CEG_API int ceg_site_tables(ceg_mc_t* handle, const int32_t* kinds, int32_t m_atoms, const double* positions, int32_t n, double offset_one,
                             double offset_pair, double* framework /*[n]*/, double* recip /*[n] or NULL*/, double* interactions /*[n][n]*/);
 CEG_API int ceg_site_tables_device(ceg_mc_t* handle, const int32_t* kinds, int32_t m_atoms, const double* positions, int32_t n, double offset_one,
@@ -1410,6 +1455,9 @@ CEG_API int ceg_site_group_recorder_read(ceg_site_group_t* group, int64_t first_
                                          uint16_t* populations_out, int64_t* frames_out);
 CEG_API int ceg_site_group_recorder_min(ceg_site_group_t* group, int64_t* mink_out /*[K]*/, double* mine_out /*[K]*/,
                                         uint16_t* populations_out /*[K][m]*/);
+CEG_API int ceg_site_group_set_tempering(ceg_site_group_t* group, const ceg_site_tempering_t* tempering);   /* NULL removes it */
+CEG_API int ceg_site_group_tempering_read(ceg_site_group_t* group, int64_t* attempted /*[K/R][R-1]*/, int64_t* accepted /*[K/R][R-1]*/,
+                                          int32_t* replica /*[K]*/);                       /* every pointer optional */
 
 /* ---- blocking masks on the grid lattice ----------------------------- */
 /*
