@@ -136,6 +136,7 @@ assert (C.sizeof(McRecorder), MC_SNAPSHOT_RECORD_DTYPE.itemsize) == (48, 40)
 
 SITE_MAX_MOLECULES = 4096    # CEG_SITE_MAX_MOLECULES
 SITE_FRAME_TAKEN, SITE_FRAME_DROPPED, SITE_NEW_MINIMUM = 1, 2, 4      # flags of a site cycle record
+SITE_GROUP_ACCEPTED, SITE_GROUP_RESTARTED = 8, 16                     # and those a grouped cycle adds (ceg_site_group_sweep_grouped)
 
 
 class SiteParams(C.Structure):
@@ -169,6 +170,9 @@ SITE_RECORD_DTYPE = np.dtype([('molecule', '<i4'), ('old_site', '<i4'), ('new_si
 SITE_FRAME_RECORD_DTYPE = np.dtype([('cycle', '<i8'), ('energy', '<f8')], align=True)
 assert (C.sizeof(SiteParams), C.sizeof(SiteCycles), C.sizeof(SiteRecorder), SITE_STATS_DTYPE.itemsize, SITE_CYCLE_RECORD_DTYPE.itemsize,
         SITE_RECORD_DTYPE.itemsize, SITE_FRAME_RECORD_DTYPE.itemsize) == (24, 32, 32, 32, 56, 40, 16)
+SITE_GROUPED_RECORD_DTYPE = np.dtype([('before', '<f8'), ('restart_energy', '<f8'), ('after', '<f8'), ('u', '<f8'), ('accepted', '<i4'),
+                                      ('restarted', '<i4'), ('hops_accepted', '<i8')], align=True)       # ceg_site_grouped_record_t
+assert SITE_GROUPED_RECORD_DTYPE.itemsize == 48
 
 c_double_p = C.POINTER(C.c_double)
 c_float_p = C.POINTER(C.c_float)
@@ -344,6 +348,7 @@ PROTOTYPES = {
                                         C.POINTER(C.c_void_p)]),
     "ceg_site_group_destroy": (C.c_int, [C.c_void_p]),
     "ceg_site_group_sweep_cycles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ceg_site_group_sweep_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ceg_site_group_baseline": (C.c_int, [C.c_void_p, c_double_p]),
     "ceg_site_group_rebase": (C.c_int, [C.c_void_p]),
     "ceg_site_group_get_populations": (C.c_int, [C.c_void_p, C.c_void_p]),

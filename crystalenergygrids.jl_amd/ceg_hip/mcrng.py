@@ -50,7 +50,7 @@ restated above them.
 from __future__ import annotations
 
 import math
-from typing import NamedTuple, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -1068,3 +1068,163 @@ def site_random_population(seed: int, stream_id: int, n: int, m: int) -> np.ndar
         r = j + min(int(math.floor(uniform(w[0], w[1]) * float(n - j))), n - j - 1)
         perm[j], perm[r] = perm[r], perm[j]
     return np.array(perm[:m], dtype=np.uint16)
+
+
+# ---- grouped cycles (ceg_site_group_sweep_grouped, k_site_sweep_grouped; run_montecarlo!(::SiteHopping; groupcycles, restartgroupcycle),
+# simulation.jl:917-939, 941, 970-982).  The rule, as include/ceg_hip.h states it:
+# A grouped cycle of chain c runs on stream ``stream_id[c]`` at temperature T.  Its absolute steps are s0 .. s0 + spc - 1, where
+#   ``spc = steps_per_cycle`` (G m for the reference's ``groupcycles = G``).
+# 1. Save.  (P0, E0, D0) is the population, running ``energy`` and ``delta`` at the start of the cycle.
+# 2. Restart (only when asked for).  The population becomes the first m entries of a Fisher-Yates shuffle of 0..n-1.  Entry
+#    j = 0..m-1 takes the Philox block of (seed, step s0, stream, counter word 3 = ``14 | (j << 8)``), purpose ``SITE_RESTART = 14``.
+#    ``r = j + min(floor(U(w0, w1) (n - j)), n - j - 1)``, and entries j and r are exchanged (:func:`site_restart_population`).
+#    Then ``energy = baseline_energy`` of that population in the wave's order (:func:`site_baseline_wave`).  Call it Er.  Without a
+#    restart, Er = E0.
+# 3. Hops.  spc ordinary steps follow, :func:`site_step` bit for bit.  ``energy`` moves with every accepted hop.  The group's
+#    ``attempted`` / ``accepted`` counters do not move.  The hops accepted inside the cycle are counted separately.
+# 4. Decision.  The block of (seed, s0 + spc - 1, stream, purpose ``SITE_GROUP = 13``) gives ``u = U(w0, w1)``.  With E1 the energy
+#    after the hops, the cycle is accepted iff ``E1 < E0``, or else ``u < exp((E0 - E1) / T)``.  A NaN E1 is rejected by the rule
+#    itself.  ``attempted += 1``.  Accepted: ``accepted += 1`` and ``delta = D0 + (E1 - E0)``.  Rejected: population, ``energy`` and
+#    ``delta`` become P0, E0, D0 again.
+# 5. Cycle end.  As without groups, on the state after the decision.
+SITE_GROUP = 13
+SITE_RESTART = 14
+
+
+def site_restart_draws(seed: int, step: int, stream_id: int, n: int, m: int) -> list:
+    """``r_j`` for j = 0..m-1 of a restart at the absolute step ``step``: the block of counter word 3 = ``14 | (j << 8)`` gives
+    ``r_j = j + min(floor(U(w0, w1) (n - j)), n - j - 1)``."""
+    if not 0 <= m <= n <= 65535:
+        raise ValueError("0 <= m <= n <= 65535")
+    out = []
+    for j in range(m):
+        w = draw(seed, step, stream_id, SITE_RESTART | (j << 8))
+        out.append(j + min(int(math.floor(uniform(w[0], w[1]) * float(n - j))), n - j - 1))
+    return out
+
+
+def site_restart_population(seed: int, step: int, stream_id: int, n: int, m: int) -> np.ndarray:
+    """The population a restart at the absolute step ``step`` puts in place: the first ``m`` entries of the Fisher-Yates shuffle of
+    ``0..n-1`` that exchanges entries j and ``r_j`` (:func:`site_restart_draws`) for j rising.  Found as the device finds it, without
+    the n entries: entry j ends as the value that position ``r_j`` held just before exchange j.  That value is the position itself
+    unless an earlier exchange q < j had ``r_q`` equal to it; the latest such q put there what position q held just before exchange
+    q, and so on down."""
+    r = site_restart_draws(seed, step, stream_id, n, m)
+    out = np.empty(m, dtype=np.uint16)
+    for j in range(m):
+        p, top = r[j], j
+        while True:
+            q = top - 1
+            while q >= 0 and r[q] != p:
+                q -= 1
+            if q < 0:
+                break
+            p = top = q
+        out[j] = p
+    return out
+
+
+def site_baseline_wave(framework, interactions, population, tailcorrection: float = 0.0) -> float:
+    """``baseline_energy`` in the order of ``k_site_sweep_grouped``'s restart, a fixed function of m alone.  F: lane ``l`` of 64 adds
+    ``framework[pop[j]]`` for ``j = l, l + 64, ...`` in rising order onto +0.0.  E: for the rows ``i = 0 .. m - 2`` in rising order
+    lane ``l`` adds ``interactions[pop[i], pop[j]]`` for ``j = i + 1 + l, i + 1 + l + 64, ...`` in rising order onto one accumulator
+    per lane that starts at +0.0 and runs through all rows.  F and E each meet by the xor butterfly of :func:`site_row_sum`; the
+    result is ``(tailcorrection + F) + E``."""
+    pop = np.asarray(population, dtype=np.int64)
+    fw = np.asarray(framework, dtype=np.float64)
+    it = np.asarray(interactions, dtype=np.float64)
+    m = len(pop)
+    F = np.float64(site_row_sum(fw[pop]))
+    lanes = np.zeros(64, dtype=np.float64)
+    for i in range(m - 1):
+        t = it[pop[i], pop[i + 1:]]
+        rows = -(-len(t) // 64)
+        padded = np.zeros(rows * 64, dtype=np.float64)     # (+0.0 where a lane has no term: bit-neutral, a sum from +0.0 is never -0.0)
+        padded[:len(t)] = t
+        for r in padded.reshape(rows, 64):
+            lanes = lanes + r
+    for o in (32, 16, 8, 4, 2, 1):
+        lanes = lanes + lanes[_LANES ^ o]
+    return float((np.float64(tailcorrection) + F) + lanes[0])
+
+
+class SiteGroupedCycle(NamedTuple):
+    before: float             # E0
+    restart_energy: float     # Er (E0 without a restart)
+    after: float              # E1
+    u: float
+    threshold: float          # exp((E0 - E1) / T), what u is compared with when E1 >= E0
+    accepted: bool
+    restarted: bool
+    hops_accepted: int
+    restart_population: Optional[np.ndarray]      # uint16[m] what the restart put in place, or None
+
+
+class SiteGroupedReplay(NamedTuple):
+    steps: list               # [ncycles * steps_per_cycle] SiteStep
+    cycles: list              # [ncycles] SiteGroupedCycle
+    population: np.ndarray    # uint16[m] at the end
+    energy: float
+    delta: float
+    cycle_energy: np.ndarray  # float64[ncycles] at the cycle ends, after the decision
+    cycle_delta: np.ndarray   # float64[ncycles]
+    cycle_population: np.ndarray   # uint16[ncycles, m]
+    attempted: int            # cycles
+    accepted: int             # cycles accepted
+
+
+def site_grouped_replay(framework, interactions, population, energy: float, seed: int, first_step: int, stream_id: int, temperatures,
+                        steps_per_cycle: int, restart: bool = False, tailcorrection: float = 0.0, log=None, grouped=None,
+                        delta: float = 0.0) -> SiteGroupedReplay:
+    """One chain through ``len(temperatures)`` grouped cycles of ``steps_per_cycle`` steps from the absolute step ``first_step``, as
+    ``ceg_site_group_sweep_grouped`` runs it.  ``log`` (the chain's column of the device log) and ``grouped`` (its column of the
+    grouped records), each with a field ``accepted``: their decisions are followed, for the hops and for the cycles."""
+    fw = np.asarray(framework, dtype=np.float64)
+    it = np.asarray(interactions, dtype=np.float64)
+    pop = np.array(population, dtype=np.int64)
+    n, m, spc = len(fw), len(pop), int(steps_per_cycle)
+    e, d = np.float64(energy), np.float64(delta)
+    att = acc = 0
+    steps, cycles, ce, cd, cp = [], [], [], [], []
+    t = 0
+    for cyc, T in enumerate(temperatures):
+        s0 = int(first_step) + t
+        P0, E0, D0 = pop.copy(), e, d
+        fresh = None
+        if restart:
+            fresh = site_restart_population(seed, s0, stream_id, n, m)
+            pop[:] = fresh
+            e = np.float64(site_baseline_wave(fw, it, pop, tailcorrection))
+        Er, hops = e, 0
+        for _ in range(spc):
+            dec = None if log is None else bool(log["accepted"][t])
+            st = site_step(fw, it, pop, seed, int(first_step) + t, stream_id, float(T), dec)
+            if st.accepted:
+                e = e + (np.float64(st.after) - np.float64(st.before))
+                hops += 1
+            steps.append(st)
+            t += 1
+        w = draw(seed, s0 + spc - 1, stream_id, SITE_GROUP)
+        u, E1 = uniform(w[0], w[1]), e
+        with np.errstate(over="ignore", invalid="ignore"):
+            x = float((E0 - E1) / np.float64(T))
+        try:
+            thr = math.exp(x)
+        except OverflowError:
+            thr = math.inf
+        ok = bool(E1 < E0 or u < thr)
+        if grouped is not None:
+            ok = bool(grouped["accepted"][cyc])
+        att += 1
+        if ok:
+            acc += 1
+            d = D0 + (E1 - E0)
+        else:
+            pop[:] = P0
+            e, d = E0, D0
+        cycles.append(SiteGroupedCycle(float(E0), float(Er), float(E1), u, thr, ok, bool(restart), hops, fresh))
+        ce.append(float(e))
+        cd.append(float(d))
+        cp.append(pop.astype(np.uint16))
+    return SiteGroupedReplay(steps, cycles, pop.astype(np.uint16), float(e), float(d), np.array(ce, dtype=np.float64), np.array(cd, dtype=np.float64),
+                             np.array(cp, dtype=np.uint16).reshape(len(ce), m), att, acc)

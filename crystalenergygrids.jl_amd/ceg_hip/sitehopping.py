@@ -4,8 +4,10 @@
 
 :class:`SiteHopping` holds the tables, a population and the tail correction; :class:`DeviceSiteHoppingGroup` keeps K chains on one
 copy of the tables on the device and runs whole cycles of all of them inside one kernel; :func:`run_montecarlo` and
-:func:`run_random_quenching` are ``run_montecarlo!(::SiteHopping, ...)`` (simulation.jl:863-1010, ``groupcycles = nothing``) and
-``run_random_quenching`` on top of it.  Sites are 0-based here (the reference's are 1-based).  The step itself is specified in
+:func:`run_random_quenching` are ``run_montecarlo!(::SiteHopping, ...; groupcycles, restartgroupcycle)`` (simulation.jl:863-1010) and
+``run_random_quenching`` on top of it.  With ``groupcycles = G`` a cycle is G m hops accepted or rejected as one move, and with
+``restartgroupcycle`` it first restarts from a fresh random population (basin hopping): ``DeviceSiteHoppingGroup.sweep_grouped``,
+every cycle, decision, restore and restart inside one kernel (``mcrng.site_grouped_replay``).  Sites are 0-based here (the reference's are 1-based).  The step itself is specified in
 ``include/ceg_hip.h`` and restated in :mod:`ceg_hip.mcrng` (``site_step``, ``site_replay``).  :func:`run_parallel_tempering` is the
 reference's routine of that name (simulation.jl:461-634) on ``DeviceSiteHoppingGroup.set_tempering``: ladders of rungs that exchange
 configurations per step inside the sweep kernel (``mcrng.site_ladder_replay``).
@@ -186,11 +188,8 @@ class DeviceSiteHoppingGroup:
                 raise ValueError("the chains of a group share the tail correction and the number of molecules")
         return cls(first.frameworkenergies, first.interactions, np.stack([sh.population for sh in setups]), first.tailcorrection, device)
 
-    def sweep_cycles(self, ncycles: int, seed: int, first_step: int = 0, *, temperature, steps_per_cycle: Optional[int] = None, cycle0: int = 0,
-                     stream_id=None, log: bool = False):
-        """``ceg_site_group_sweep_cycles``: ``ncycles`` cycles of ``steps_per_cycle`` (default m, as the reference) steps of every chain.
-        ``temperature``: a scalar, [K] or [ncycles, K].  -> (stats [K] ``_abi.SITE_STATS_DTYPE``, cycle records [ncycles, K]
-        ``_abi.SITE_CYCLE_RECORD_DTYPE``, log [ncycles * steps_per_cycle, K] ``_abi.SITE_RECORD_DTYPE`` or None)."""
+    def _sweep(self, ncycles, seed, first_step, temperature, steps_per_cycle, cycle0, stream_id, log, restart=None):
+        """The arguments and buffers that ``sweep_cycles`` and ``sweep_grouped`` (``restart`` not None) share, and the call."""
         ncycles = int(ncycles)
         spc = self.m if steps_per_cycle is None else int(steps_per_cycle)
         T = np.asarray(temperature, dtype=np.float64)
@@ -203,10 +202,30 @@ class DeviceSiteHoppingGroup:
         stats = np.zeros(self.k, dtype=_abi.SITE_STATS_DTYPE)
         recs = np.zeros((max(ncycles, 0), self.k), dtype=_abi.SITE_CYCLE_RECORD_DTYPE)
         steps = np.zeros((max(ncycles, 0) * spc, self.k), dtype=_abi.SITE_RECORD_DTYPE) if log else None
-        _abi.check(self._lib, self._lib.ceg_site_group_sweep_cycles(self._h, C.byref(params), C.byref(cycles), stats.ctypes.data,
-                                                                    recs.ctypes.data if recs.size else None,
-                                                                    steps.ctypes.data if (steps is not None and steps.size) else None))
-        return stats, recs, steps
+        out = (stats.ctypes.data, recs.ctypes.data if recs.size else None, steps.ctypes.data if (steps is not None and steps.size) else None)
+        if restart is None:
+            _abi.check(self._lib, self._lib.ceg_site_group_sweep_cycles(self._h, C.byref(params), C.byref(cycles), *out))
+            return stats, recs, steps
+        grouped = np.zeros((max(ncycles, 0), self.k), dtype=_abi.SITE_GROUPED_RECORD_DTYPE)
+        _abi.check(self._lib, self._lib.ceg_site_group_sweep_grouped(self._h, C.byref(params), C.byref(cycles), int(restart), *out,
+                                                                     grouped.ctypes.data if grouped.size else None))
+        return stats, recs, steps, grouped
+
+    def sweep_cycles(self, ncycles: int, seed: int, first_step: int = 0, *, temperature, steps_per_cycle: Optional[int] = None, cycle0: int = 0,
+                     stream_id=None, log: bool = False):
+        """``ceg_site_group_sweep_cycles``: ``ncycles`` cycles of ``steps_per_cycle`` (default m, as the reference) steps of every chain.
+        ``temperature``: a scalar, [K] or [ncycles, K].  -> (stats [K] ``_abi.SITE_STATS_DTYPE``, cycle records [ncycles, K]
+        ``_abi.SITE_CYCLE_RECORD_DTYPE``, log [ncycles * steps_per_cycle, K] ``_abi.SITE_RECORD_DTYPE`` or None)."""
+        return self._sweep(ncycles, seed, first_step, temperature, steps_per_cycle, cycle0, stream_id, log)
+
+    def sweep_grouped(self, ncycles: int, seed: int, first_step: int = 0, *, temperature, steps_per_cycle: Optional[int] = None, cycle0: int = 0,
+                      stream_id=None, restart: int = 0, log: bool = False):
+        """``ceg_site_group_sweep_grouped``: ``ncycles`` grouped cycles of ``steps_per_cycle`` (default m; ``groupcycles = G`` of the
+        reference is G m) steps of every chain: the hops of a cycle are accepted or rejected as one move against the energy at its
+        start, and with ``restart`` (0 or 1, as the library takes it) every cycle begins from a fresh random population (the rule:
+        ``include/ceg_hip.h``, restated as ``mcrng.site_grouped_replay``).  Arguments as :meth:`sweep_cycles`.  -> (stats, cycle
+        records, log or None, grouped records [ncycles, K] ``_abi.SITE_GROUPED_RECORD_DTYPE``).  Refused while tempering is installed."""
+        return self._sweep(ncycles, seed, first_step, temperature, steps_per_cycle, cycle0, stream_id, log, restart=restart)
 
     def stats(self) -> np.ndarray:
         """The counters, ``delta`` and the running energy of every chain now (a call of no cycles)."""
@@ -331,11 +350,13 @@ class SiteHoppingRun(NamedTuple):
     records: np.ndarray           # [ninit + ncycles, K] _abi.SITE_CYCLE_RECORD_DTYPE
     stats: np.ndarray             # [K] _abi.SITE_STATS_DTYPE
     minimum: Optional[tuple]      # track_min: (idx_cycle int64[K] (0: the start of production), energy float64[K], populations uint16[K, m])
+    grouped: Optional[np.ndarray] = None      # groupcycles: [ninit + ncycles, K] _abi.SITE_GROUPED_RECORD_DTYPE
 
 
 def run_montecarlo(group: DeviceSiteHoppingGroup, temperatures, ncycles: int, ninit: int = 0, *, printevery: int = 1, seed: int = 0,
-                   first_step: int = 0, stream_id=None, drift_rtol: float = 1e-9, track_min: bool = False) -> SiteHoppingRun:
-    """``run_montecarlo!(::SiteHopping, simu)`` (simulation.jl:863-1010, ``groupcycles = nothing``) for every chain of ``group``:
+                   first_step: int = 0, stream_id=None, drift_rtol: float = 1e-9, track_min: bool = False, groupcycles: Optional[int] = None,
+                   restartgroupcycle: bool = False) -> SiteHoppingRun:
+    """``run_montecarlo!(::SiteHopping, simu; groupcycles, restartgroupcycle)`` (simulation.jl:863-1010) for every chain of ``group``:
     baseline, ``ninit`` initialisation cycles, a rebase (the reference's precise energy at ``idx_cycle == 0``), ``ncycles``
     production cycles of m steps with a frame every ``printevery`` cycles, then the drift check: ``|energy - baseline| <=
     drift_rtol max(|baseline|, 1)`` per chain, else :class:`SiteHoppingDrift`.
@@ -344,17 +365,42 @@ def run_montecarlo(group: DeviceSiteHoppingGroup, temperatures, ncycles: int, ni
     initialisation), then ``printevery``, ``2 printevery``, ...; ``printevery == 0``: frame 0 and, if ``ncycles > 0``, the last cycle.
     The device counts cycles from 0: the initialisation cycles are 0..ninit-1, production cycle ``idx_cycle`` is
     ``ninit - 1 + idx_cycle``.  The absolute steps run on from ``first_step``.  ``track_min``: ``RMinimumEnergy`` over the production
-    cycle ends, from the state at ``idx_cycle == 0`` on (strict <: a tie keeps the earlier cycle)."""
+    cycle ends, from the state at ``idx_cycle == 0`` on (strict <: a tie keeps the earlier cycle).
+
+    ``groupcycles = G``: the initialisation and the production cycles are grouped cycles of G m steps
+    (:meth:`DeviceSiteHoppingGroup.sweep_grouped`), each accepted or rejected as one move; ``restartgroupcycle`` restarts every one
+    of them from a fresh random population.  The counters of the records and stats then count cycles, and ``run.grouped`` holds the
+    grouped records.  Not on a tempered group (the reference's ``run_parallel_tempering`` has no group cycles)."""
     ncycles, ninit = int(ncycles), int(ninit)
+    if groupcycles is None:
+        if restartgroupcycle:
+            raise ValueError("restartgroupcycle needs groupcycles")
+        spc = group.m
+
+        def sweep(count, first, temps, cycle0):
+            s, r, _l = group.sweep_cycles(count, seed, first, temperature=temps, cycle0=cycle0, stream_id=stream_id)
+            return s, r, None
+    else:
+        if int(groupcycles) < 1:
+            raise ValueError("groupcycles >= 1")
+        if group.rungs:
+            raise ValueError("group cycles on a tempered group: run_parallel_tempering has none")
+        spc = int(groupcycles) * group.m
+
+        def sweep(count, first, temps, cycle0):
+            s, r, _l, g = group.sweep_grouped(count, seed, first, temperature=temps, steps_per_cycle=spc, cycle0=cycle0, stream_id=stream_id,
+                                              restart=bool(restartgroupcycle))
+            return s, r, g
     T = np.asarray(temperatures, dtype=np.float64)
     if T.ndim == 0:
         T = np.full(ninit + ncycles, float(T))
     T = np.broadcast_to(T.reshape(ninit + ncycles, -1), (ninit + ncycles, group.k))
     e0 = group.baseline_energies()
-    recs = []
+    recs, grecs = [], []
     if ninit:
-        _s, r, _l = group.sweep_cycles(ninit, seed, first_step, temperature=T[:ninit], cycle0=0, stream_id=stream_id)
+        _s, r, gr = sweep(ninit, first_step, T[:ninit], 0)
         recs.append(r)
+        grecs.append(gr)
     group.rebase()
     every = int(printevery) if printevery > 0 else max(ncycles, 1)
     nframes = ncycles // every
@@ -364,8 +410,9 @@ def run_montecarlo(group: DeviceSiteHoppingGroup, temperatures, ncycles: int, ni
         minimum = (np.zeros(group.k, dtype=np.int64), frames_e[0].copy(), frames_p[0].copy())
     if ncycles:
         group.set_recorder(every, origin=ninit - 1 + every, capacity=nframes, track_min=track_min)
-        stats, r, _l = group.sweep_cycles(ncycles, seed, first_step + ninit * group.m, temperature=T[ninit:], cycle0=ninit, stream_id=stream_id)
+        stats, r, gr = sweep(ncycles, first_step + ninit * spc, T[ninit:], ninit)
         recs.append(r)
+        grecs.append(gr)
         fr, fp = group.recorder_read()
         if track_min:
             mink, mine, best = group.recorder_minimum()
@@ -384,7 +431,11 @@ def run_montecarlo(group: DeviceSiteHoppingGroup, temperatures, ncycles: int, ni
         c = int(bad[0])
         raise SiteHoppingDrift(f"chain {c}: running energy {stats['energy'][c]!r} against baseline {final[c]!r}")
     records = np.concatenate(recs) if recs else np.zeros((0, group.k), dtype=_abi.SITE_CYCLE_RECORD_DTYPE)
-    return SiteHoppingRun(np.array(frames_e), np.array(frames_p, dtype=np.uint16), np.array(frames_c, dtype=np.int64), e0, final, records, stats, minimum)
+    grouped = None
+    if groupcycles is not None:
+        grouped = np.concatenate(grecs) if grecs else np.zeros((0, group.k), dtype=_abi.SITE_GROUPED_RECORD_DTYPE)
+    return SiteHoppingRun(np.array(frames_e), np.array(frames_p, dtype=np.uint16), np.array(frames_c, dtype=np.int64), e0, final, records, stats, minimum,
+                          grouped)
 
 
 class QuenchingRun(NamedTuple):
@@ -392,14 +443,17 @@ class QuenchingRun(NamedTuple):
     run: SiteHoppingRun           # run.minimum: the lowest cycle-end energy of each quench (RMinimumEnergy)
 
 
-def run_random_quenching(sh: SiteHopping, N: int, temperatures, ncycles: int, *, seed: int = 0, printevery: int = 0, device: int = 0) -> QuenchingRun:
+def run_random_quenching(sh: SiteHopping, N: int, temperatures, ncycles: int, *, seed: int = 0, printevery: int = 0, device: int = 0,
+                         groupcycles: Optional[int] = None, restartgroupcycle: bool = False) -> QuenchingRun:
     """``run_random_quenching``: N independent quenches of ``sh``'s tables from random populations, as the chains of one group.
     Chain c starts from ``mcrng.site_random_population(seed, c, n, m)`` (purpose 11 of stream c) and runs on stream c.
-    ``temperatures`` [ncycles] (the quench's schedule, shared) or [ncycles, N]."""
+    ``temperatures`` [ncycles] (the quench's schedule, shared) or [ncycles, N].  ``groupcycles`` / ``restartgroupcycle`` are passed
+    through to :func:`run_montecarlo` (simulation.jl:450)."""
     n, m = sh.nsites, len(sh.population)
     start = np.stack([mcrng.site_random_population(seed, c, n, m) for c in range(int(N))])
     with DeviceSiteHoppingGroup(sh.frameworkenergies, sh.interactions, start, sh.tailcorrection, device) as g:
-        run = run_montecarlo(g, temperatures, int(ncycles), 0, printevery=printevery, seed=seed, track_min=True)
+        run = run_montecarlo(g, temperatures, int(ncycles), 0, printevery=printevery, seed=seed, track_min=True, groupcycles=groupcycles,
+                             restartgroupcycle=restartgroupcycle)
     return QuenchingRun(start, run)
 
 
@@ -429,8 +483,8 @@ def run_parallel_tempering(sh: SiteHopping, temperatures, ncycles: int, ninit: i
 
     The reference's own routine appears to fail for ``ninit > 0`` (:512 and :567 read ``energy`` and ``sh`` outside their scope), so
     this wrapper runs the ``ninit`` cycles (with exchanges) and rebases every rung at ``idx_cycle`` 0, as
-    ``run_montecarlo!(::SiteHopping)`` does.  Not covered: ``groupcycles``, a schedule that attempts more than the first pair, and
-    the output files."""
+    ``run_montecarlo!(::SiteHopping)`` does.  Not covered: a schedule that attempts more than the first pair, and the output files
+    (the reference's routine has no ``groupcycles``)."""
     Ts = np.sort(np.asarray(temperatures, dtype=np.float64).reshape(-1))
     npt, ladders = len(Ts), int(ladders)
     if ladders < 1:

@@ -6,7 +6,10 @@
 // The step is specified word for word in include/ceg_hip.h and restated in ceg_hip/mcrng.py (site_step).  The group knows no
 // ceg_mc_t: it is self-contained.  With tempering installed (ceg_site_group_set_tempering) the chains are ladders of R rungs and the
 // same call launches k_site_sweep_pt instead: one workgroup per ladder, one wave per rung, the exchange of run_parallel_tempering
-// (src/simulation.jl:461-634) drawn per step inside the kernel (mcrng.site_ladder_replay).
+// (src/simulation.jl:461-634) drawn per step inside the kernel (mcrng.site_ladder_replay).  ceg_site_group_sweep_grouped is the
+// groupcycles / restartgroupcycle mode of the same loop (src/simulation.jl:917-982): k_site_sweep_grouped, one wave per chain again,
+// accepts or rejects the hops of a cycle as one move and can restart every cycle from a fresh random population, all inside the
+// kernel (mcrng.site_grouped_replay).
 // The second half of the file builds the two tables (ceg_site_tables / ceg_site_tables_device) from a guest-free ceg_mc_t of the
 // mobile species in three launches for any number of sites: k_site_points (framework terms and structure factor per site),
 // k_site_recip_pairs (the reciprocal pair term, v_mfma_f64_16x16x4 over 16 x 16 site tiles of the upper triangle) and
@@ -365,6 +368,189 @@ __global__ __launch_bounds__(1024) void k_site_sweep_pt(const SiteSweep S, const
     }
 }
 
+// ---- grouped cycles (ceg_site_group_sweep_grouped; run_montecarlo!(::SiteHopping; groupcycles, restartgroupcycle), simulation.jl:917-982)
+static_assert(sizeof(ceg_site_grouped_record_t) == 48, "a layout the bindings restate");
+
+constexpr uint32_t SITE_GROUP = 13;              // the purpose of a grouped cycle's decision draw
+constexpr uint32_t SITE_RESTART = 14;            // entry j of a restart's shuffle: counter word 3 = 14 | (j << 8)
+
+struct SiteGrouped {                             // by value (kernarg): what a grouped call adds to SiteSweep
+    uint16_t* p0;                                // [K][m] P0, the population at the start of the cycle in flight
+    double *e0, *d0, *er;                        // [K] E0, D0 and Er of the cycle in flight
+    int64_t* hops;                               // [K] the hops accepted in it so far
+    ceg_site_grouped_record_t* out;              // [ncycles][K] or nullptr
+    double tail;
+    int32_t restart, pop_stride;                 // pop_stride: the uint16 entries between s_pop and the r_j of a restart in LDS
+};
+
+// baseline_energy of the population `pop` (LDS) by one wave, in the order include/ceg_hip.h writes down ("grouped cycles", restart):
+// lane l adds framework[pop[j]] for j = l, l + 64, ... onto +0.0 (F); row by row, i = 0 .. m - 2, lane l adds
+// interactions[pop[i]][pop[j]] for j = i + 1 + l, i + 1 + l + 64, ... onto ONE accumulator that starts at +0.0 (E); both meet by the xor
+// butterfly of the row sum; the result is (tail + F) + E.  Every lane returns it.
+__device__ __forceinline__ double site_baseline_wave(const SiteSweep& S, const uint16_t* pop, double tail, int lane)
+{
+    const int m = S.m;
+    const size_t n = (size_t)S.n;
+    double f = 0.0, e = 0.0;
+    for (int j = lane; j < m; j += 64) f += S.framework[pop[j]];
+    int i = 0;
+    for (; m - (i + 1) > 64; ++i) {
+        const double* __restrict__ row = S.interactions + (size_t)pop[i] * n;
+        for (int j = i + 1 + lane; j < m; j += 64) e += row[pop[j]];
+    }
+    // the last rows hold one term per lane at the most: eight rows' gathers in flight, added in the rows' order, +0.0 where the lane
+    // has no term (the same bits: e is never -0.0)
+    for (; i + 1 < m; i += 8) {
+        double t[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int j = i + r + 1 + lane;
+            t[r] = j < m ? S.interactions[(size_t)pop[i + r] * n + (size_t)pop[j]] : 0.0;
+        }
+#pragma unroll
+        for (int r = 0; r < 8; ++r) e += t[r];
+    }
+    f += __shfl_xor(f, 32); e += __shfl_xor(e, 32);
+    f += __shfl_xor(f, 16); e += __shfl_xor(e, 16);
+    f += from_lane_xor<8>(f); e += from_lane_xor<8>(e);
+    f += from_lane_xor<4>(f); e += from_lane_xor<4>(e);
+    f += from_lane_xor<2>(f); e += from_lane_xor<2>(e);
+    f += from_lane_xor<1>(f); e += from_lane_xor<1>(e);
+    return (tail + f) + e;
+}
+
+// Workgroup = wave c = chain c, as k_site_sweep; the hop is site_hop.  What a grouped cycle adds happens at its first step (save,
+// restart) and after its last (decision, restore), by the rule of include/ceg_hip.h "grouped cycles".  A launch may end inside a
+// cycle: P0 sits in device memory from the cycle's start on, E0, D0 and Er are written there at the start and the hop count at the
+// end of every launch, and a launch that begins inside a cycle reads them back.
+// The restart never builds the n-entry permutation.  Pass 1, lane-strided: r_j of entry j from its own Philox block, into s_r.
+// Pass 2, lane-strided: entry j ends as the value that position r_j held just before exchange j.  That value is p itself unless an
+// earlier exchange q < j had r_q == p; the latest such q put there what position q held just before exchange q, and so on down
+// (q falls strictly, so the walk ends).  Positions >= j are touched by earlier exchanges only as their r_q, which is all the walk
+// looks at.
+// Indices: as k_site_sweep; s_r[j] and the walk's q stay inside [0, m); p0 inside [K][m]; the grouped record inside [ncycles][K].
+__global__ __launch_bounds__(64) void k_site_sweep_grouped(const SiteSweep S, const SiteGrouped G)
+{
+    extern __shared__ uint16_t s_pop[];
+    const int c = (int)blockIdx.x, lane = (int)threadIdx.x;
+    const int m = S.m;
+    const size_t K = (size_t)S.k;
+    uint16_t* s_r = s_pop + G.pop_stride;
+    uint16_t* gpop = S.pop + (size_t)c * (size_t)m;
+    uint16_t* gp0 = G.p0 + (size_t)c * (size_t)m;
+    for (int j = lane; j < m; j += 64) s_pop[j] = gpop[j];
+    double energy = S.energy[c], delta = S.delta[c];
+    int64_t attempted = S.attempted[c], accepted = S.accepted[c];
+    const uint32_t stream = S.stream[c];
+    int64_t cyc = S.t0 / S.spc, in = S.t0 - cyc * S.spc;
+    double T = S.temperature[(size_t)cyc * K + c];
+    double mine = S.rec.track_min ? S.rec.mine[c] : 0.0;
+    double E0 = 0.0, D0 = 0.0, Er = 0.0;
+    int64_t hops = 0;
+    if (in != 0) { E0 = G.e0[c]; D0 = G.d0[c]; Er = G.er[c]; hops = G.hops[c]; }      // the launch begins inside a cycle
+    __syncthreads();
+    for (int64_t t = S.t0; t < S.t1; ++t) {
+        const uint64_t s = S.first_step + (uint64_t)t;
+        if (in == 0) {                           // ---- the start of a cycle: save, restart
+            E0 = energy; D0 = delta; hops = 0;
+            for (int j = lane; j < m; j += 64) gp0[j] = s_pop[j];
+            if (G.restart) {
+                for (int j = lane; j < m; j += 64) {
+                    const ceg_philox::Block b = ceg_philox::draw(S.seed, s, stream, ceg_philox::attempt_purpose(SITE_RESTART, (uint32_t)j));
+                    const int left = S.n - j;
+                    s_r[j] = (uint16_t)(j + min((int)floor(ceg_philox::uniform(b.w[0], b.w[1]) * (double)left), left - 1));
+                }
+                __syncthreads();
+                for (int j = lane; j < m; j += 64) {
+                    int p = (int)s_r[j], top = j;
+                    for (;;) {
+                        int q = top - 1;
+                        while (q >= 0 && (int)s_r[q] != p) --q;
+                        if (q < 0) break;
+                        p = q;
+                        top = q;
+                    }
+                    s_pop[j] = (uint16_t)p;
+                }
+                __syncthreads();
+                energy = site_baseline_wave(S, s_pop, G.tail, lane);
+            }
+            Er = energy;
+            if (lane == 0) { G.e0[c] = E0; G.d0[c] = D0; G.er[c] = Er; }
+        }
+        const SiteHop h = site_hop(S, s_pop, s, stream, T, lane);
+        if (h.ok) {
+            energy = energy + (h.after - h.before);
+            ++hops;
+        }
+        if (S.log && lane == 0) {
+            ceg_site_record_t r;
+            r.molecule = h.i; r.old_site = h.old; r.new_site = h.nw; r.accepted = h.ok ? 1 : 0;
+            r.before = h.before; r.after = h.after; r.u = h.u;
+            S.log[(size_t)t * K + c] = r;
+        }
+        __syncthreads();
+        if (++in == S.spc) {                     // ---- the decision, then the end of cycle cc on what it leaves
+            const ceg_philox::Block g = ceg_philox::draw(S.seed, s, stream, SITE_GROUP);
+            const double u = ceg_philox::uniform(g.w[0], g.w[1]), E1 = energy;
+            bool ok = E1 < E0;
+            if (!ok) ok = u < exp((E0 - E1) / T);
+            ++attempted;
+            if (ok) {
+                ++accepted;
+                delta = D0 + (E1 - E0);
+            } else {
+                for (int j = lane; j < m; j += 64) s_pop[j] = gp0[j];
+                energy = E0;
+                delta = D0;
+            }
+            __syncthreads();
+            if (G.out && lane == 0) {
+                ceg_site_grouped_record_t r;
+                r.before = E0; r.restart_energy = Er; r.after = E1; r.u = u;
+                r.accepted = ok ? 1 : 0; r.restarted = G.restart ? 1 : 0; r.hops_accepted = hops;
+                G.out[(size_t)cyc * K + c] = r;
+            }
+            const int64_t cc = S.cycle0 + cyc;
+            int32_t flags = (ok ? CEG_SITE_GROUP_ACCEPTED : 0) | (G.restart ? CEG_SITE_GROUP_RESTARTED : 0);
+            const SiteRecorderView& R = S.rec;
+            if (R.every > 0 && cc >= R.origin && (cc - R.origin) % R.every == 0) {
+                const int64_t slot = R.frame0 + (cc - R.first_due) / R.every;
+                if (slot >= 0 && slot < R.capacity) {
+                    uint16_t* f = R.frames + ((size_t)slot * K + c) * (size_t)m;
+                    for (int j = lane; j < m; j += 64) f[j] = s_pop[j];
+                    if (lane == 0) R.frec[(size_t)slot * K + c] = ceg_site_frame_record_t{cc, energy};
+                    flags |= CEG_SITE_FRAME_TAKEN;
+                } else {
+                    flags |= CEG_SITE_FRAME_DROPPED;
+                }
+            }
+            if (R.track_min && energy < mine) {
+                mine = energy;
+                uint16_t* f = R.best + (size_t)c * (size_t)m;
+                for (int j = lane; j < m; j += 64) f[j] = s_pop[j];
+                if (lane == 0) { R.mine[c] = energy; R.mink[c] = cc; }
+                flags |= CEG_SITE_NEW_MINIMUM;
+            }
+            if (S.cyc && lane == 0) {
+                ceg_site_cycle_record_t r;
+                r.cycle = cc; r.temperature = T; r.energy = energy; r.delta = delta;
+                r.attempted = attempted; r.accepted = accepted; r.flags = flags; r._pad = 0;
+                S.cyc[(size_t)cyc * K + c] = r;
+            }
+            ++cyc;
+            in = 0;
+            if (t + 1 < S.t1) T = S.temperature[(size_t)cyc * K + c];
+        }
+    }
+    for (int j = lane; j < m; j += 64) gpop[j] = s_pop[j];
+    if (lane == 0) {
+        S.energy[c] = energy; S.delta[c] = delta;
+        S.attempted[c] = attempted; S.accepted[c] = accepted;
+        G.hops[c] = hops;
+    }
+}
+
 // Workgroup c: baseline_energy (sitehopping.jl:105-112) of chain c.  Thread t takes the rows i = t, t + 256, ... and in each the
 // pairs j = i + 1 .. m - 1 in rising order; the partial sums meet by an xor butterfly per wave and then wave by wave.
 __global__ __launch_bounds__(BASE_THREADS) void k_site_baseline(const double* __restrict__ framework, const double* __restrict__ interactions,
@@ -642,10 +828,20 @@ extern "C" int ceg_site_group_set_populations(ceg_site_group_t* g, const uint16_
     return CEG_OK;
 }
 
-extern "C" int ceg_site_group_sweep_cycles(ceg_site_group_t* g, const ceg_site_params_t* params, const ceg_site_cycles_t* cy, ceg_site_stats_t* stats_out,
-                                           ceg_site_cycle_record_t* cycles_out, ceg_site_record_t* log_out)
+namespace {
+
+struct GroupedCall {                             // what ceg_site_group_sweep_grouped adds to a sweep
+    int32_t restart;
+    ceg_site_grouped_record_t* out;              // [ncycles][K] host, or nullptr
+};
+
+// ceg_site_group_sweep_cycles (grouped == nullptr) and ceg_site_group_sweep_grouped: one validation, one staging, one launch loop
+int sweep_call(ceg_site_group_t* g, const ceg_site_params_t* params, const ceg_site_cycles_t* cy, ceg_site_stats_t* stats_out,
+               ceg_site_cycle_record_t* cycles_out, ceg_site_record_t* log_out, const GroupedCall* grouped)
 {
     SITE_ENTER(g);
+    if (grouped && g->pt) return fail(CEG_ERR_UNSUPPORTED, "site sweep: grouped cycles while tempering is installed (run_parallel_tempering has no group cycles)");
+    if (grouped && grouped->restart != 0 && grouped->restart != 1) return fail(CEG_ERR_INVALID, "site sweep: restart = %d, outside {0, 1}", grouped->restart);
     if (!params || !cy) return fail(CEG_ERR_INVALID, "site sweep: params or cycles are missing");
     if (cy->ncycles < 0 || cy->steps_per_cycle < 1) return fail(CEG_ERR_INVALID, "site sweep: ncycles >= 0 and steps_per_cycle >= 1");
     const size_t K = (size_t)g->k;
@@ -673,8 +869,12 @@ extern "C" int ceg_site_group_sweep_cycles(ceg_site_group_t* g, const ceg_site_p
     uint32_t* d_stream = nullptr;
     ceg_site_cycle_record_t* d_cyc = nullptr;
     ceg_site_record_t* d_log = nullptr;
+    uint16_t* d_p0 = nullptr;                    // grouped: the cycle in flight (SiteGrouped)
+    double* d_saved = nullptr;                   // grouped: [3][K] E0, D0, Er
+    int64_t* d_hops = nullptr;
+    ceg_site_grouped_record_t* d_grouped = nullptr;
     auto release = [&]() {
-        for (void* p : {(void*)d_temp, (void*)d_stream, (void*)d_cyc, (void*)d_log})
+        for (void* p : {(void*)d_temp, (void*)d_stream, (void*)d_cyc, (void*)d_log, (void*)d_p0, (void*)d_saved, (void*)d_hops, (void*)d_grouped})
             if (p) (void)hipFree(p);
     };
     if (total > 0) {
@@ -686,6 +886,10 @@ extern "C" int ceg_site_group_sweep_cycles(ceg_site_group_t* g, const ceg_site_p
                   (!log_out || hipMalloc((void**)&d_log, sizeof(ceg_site_record_t) * (size_t)total * K) == hipSuccess) &&
                   hipMemcpy(d_temp, cy->temperature, sizeof(double) * ncyc * K, hipMemcpyHostToDevice) == hipSuccess &&
                   hipMemcpy(d_stream, ids.data(), sizeof(uint32_t) * K, hipMemcpyHostToDevice) == hipSuccess;
+        if (grouped)
+            ok = ok && hipMalloc((void**)&d_p0, K * (size_t)g->m * sizeof(uint16_t)) == hipSuccess && hipMalloc((void**)&d_saved, sizeof(double) * 3 * K) == hipSuccess &&
+                 hipMalloc((void**)&d_hops, sizeof(int64_t) * K) == hipSuccess &&
+                 (!grouped->out || hipMalloc((void**)&d_grouped, sizeof(ceg_site_grouped_record_t) * ncyc * K) == hipSuccess);
         if (!ok) {
             const int rc = fail(CEG_ERR_HIP, "site sweep: could not stage the call: %s", hipGetErrorString(hipGetLastError()));
             release();
@@ -705,7 +909,10 @@ extern "C" int ceg_site_group_sweep_cycles(ceg_site_group_t* g, const ceg_site_p
         for (int64_t t0 = 0; t0 < total; t0 += per_launch) {
             S.t0 = t0;
             S.t1 = std::min(total, t0 + per_launch);
-            if (const SiteTempering* pt = g->pt) {
+            if (grouped) {
+                const SiteGrouped G{d_p0, d_saved, d_saved + K, d_saved + 2 * K, d_hops, d_grouped, g->tail, grouped->restart, (int32_t)(pop_lds(g->m) / sizeof(uint16_t))};
+                hipLaunchKernelGGL(k_site_sweep_grouped, dim3((unsigned)g->k), dim3(64), 2 * pop_lds(g->m), g->stream, S, G);
+            } else if (const SiteTempering* pt = g->pt) {
                 const SiteLadders P{pt->d_cdf, pt->d_lstream, pt->d_attempted, pt->d_accepted, pt->d_replica, pt->rungs, (int32_t)(pop_lds(g->m) / sizeof(uint16_t))};
                 hipLaunchKernelGGL(k_site_sweep_pt, dim3((unsigned)(g->k / pt->rungs)), dim3(64u * (unsigned)pt->rungs), (size_t)pt->rungs * pop_lds(g->m), g->stream, S, P);
             } else
@@ -721,7 +928,8 @@ extern "C" int ceg_site_group_sweep_cycles(ceg_site_group_t* g, const ceg_site_p
         }
         if (g->rec) g->rec->frames = std::min(g->rec->capacity, g->rec->frames + frames_due(g->rec, cy->cycle0, cy->ncycles));
         ok = (!cycles_out || hipMemcpy(cycles_out, d_cyc, sizeof(ceg_site_cycle_record_t) * ncyc * K, hipMemcpyDeviceToHost) == hipSuccess) &&
-             (!log_out || hipMemcpy(log_out, d_log, sizeof(ceg_site_record_t) * (size_t)total * K, hipMemcpyDeviceToHost) == hipSuccess);
+             (!log_out || hipMemcpy(log_out, d_log, sizeof(ceg_site_record_t) * (size_t)total * K, hipMemcpyDeviceToHost) == hipSuccess) &&
+             (!d_grouped || hipMemcpy(grouped->out, d_grouped, sizeof(ceg_site_grouped_record_t) * ncyc * K, hipMemcpyDeviceToHost) == hipSuccess);
         release();
         if (!ok) return fail(CEG_ERR_HIP, "site sweep: D2H of the records failed");
     }
@@ -736,6 +944,22 @@ extern "C" int ceg_site_group_sweep_cycles(ceg_site_group_t* g, const ceg_site_p
         for (size_t c = 0; c < K; ++c) stats_out[c] = ceg_site_stats_t{at[c], ac[c], d[c], e[c]};
     }
     return CEG_OK;
+}
+
+}  // namespace
+
+extern "C" int ceg_site_group_sweep_cycles(ceg_site_group_t* g, const ceg_site_params_t* params, const ceg_site_cycles_t* cy, ceg_site_stats_t* stats_out,
+                                           ceg_site_cycle_record_t* cycles_out, ceg_site_record_t* log_out)
+{
+    return sweep_call(g, params, cy, stats_out, cycles_out, log_out, nullptr);
+}
+
+extern "C" int ceg_site_group_sweep_grouped(ceg_site_group_t* g, const ceg_site_params_t* params, const ceg_site_cycles_t* cy, int32_t restart,
+                                            ceg_site_stats_t* stats_out, ceg_site_cycle_record_t* cycles_out, ceg_site_record_t* log_out,
+                                            ceg_site_grouped_record_t* grouped_out)
+{
+    const GroupedCall call{restart, grouped_out};
+    return sweep_call(g, params, cy, stats_out, cycles_out, log_out, &call);
 }
 
 extern "C" int ceg_site_group_set_recorder(ceg_site_group_t* g, const ceg_site_recorder_t* spec)

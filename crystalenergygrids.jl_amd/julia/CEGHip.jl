@@ -1224,7 +1224,7 @@ struct SiteCycleRecord               # ceg_site_cycle_record_t (56 bytes)
     delta::Float64
     attempted::Int64
     accepted::Int64
-    flags::Int32                     # 1: frame taken, 2: frame dropped (store full), 4: new minimum
+    flags::Int32                     # 1: frame taken, 2: frame dropped (store full), 4: new minimum, 8: grouped cycle accepted, 16: restarted
     _pad::Int32
 end
 
@@ -1236,6 +1236,16 @@ struct SiteRecord                    # ceg_site_record_t (40 bytes)
     before::Float64
     after::Float64
     u::Float64
+end
+
+struct SiteGroupedRecord             # ceg_site_grouped_record_t (48 bytes)
+    before::Float64                  # E0, the energy at the start of the cycle
+    restart_energy::Float64          # Er, the baseline of the restart's population (E0 without a restart)
+    after::Float64                   # E1, the energy after the hops
+    u::Float64
+    accepted::Int32
+    restarted::Int32
+    hops_accepted::Int64
 end
 
 struct SiteRecorder                  # ceg_site_recorder_t (32 bytes)
@@ -1320,6 +1330,29 @@ function site_group_sweep_cycles!(g::Ptr{Cvoid}, k::Integer, temperatures::Matri
                      g, params, cycles, pointer(stats), pointer(records), log ? pointer(steps) : C_NULL))
     end
     stats, records, steps
+end
+
+"""
+`ceg_site_group_sweep_grouped`: the main loop of `run_montecarlo!(::SiteHopping, simu; groupcycles, restartgroupcycle)`
+(src/simulation.jl:917-982) for the `k` chains of `g`: every cycle of `steps_per_cycle` (`groupcycles * m`) hops is accepted or rejected
+as one move, after a restart from a fresh random population if `restart`.  `temperatures` is `K x ncycles` in K.
+-> (stats `k`, cycle records `k x ncycles`, log `k x steps` or nothing, grouped records `k x ncycles`).  UNVERIFIED: never executed.
+"""
+function site_group_sweep_grouped!(g::Ptr{Cvoid}, k::Integer, temperatures::Matrix{Float64}, steps_per_cycle::Integer; restart::Bool=false,
+                                   seed::UInt64=UInt64(0), first_step::UInt64=UInt64(0), cycle0::Integer=0, log::Bool=false)
+    ncycles = size(temperatures, 2)
+    stats = Vector{SiteStats}(undef, k)
+    records = Matrix{SiteCycleRecord}(undef, k, ncycles)
+    grouped = Matrix{SiteGroupedRecord}(undef, k, ncycles)
+    steps = log ? Matrix{SiteRecord}(undef, k, ncycles * steps_per_cycle) : nothing
+    GC.@preserve temperatures stats records steps grouped begin
+        params = Ref(SiteParams(seed, first_step, C_NULL))
+        cycles = Ref(SiteCycles(Int64(ncycles), Int64(steps_per_cycle), Int64(cycle0), pointer(temperatures)))
+        _check(ccall((:ceg_site_group_sweep_grouped, LIB[]), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     g, params, cycles, Int32(restart), pointer(stats), pointer(records), log ? pointer(steps) : C_NULL, pointer(grouped)))
+    end
+    stats, records, steps, grouped
 end
 
 "`ceg_site_group_baseline`: `baseline_energy(sh)` (src/sitehopping.jl:105-112) of every chain, in K.  UNVERIFIED: never executed."

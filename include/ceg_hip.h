@@ -1368,7 +1368,47 @@ CEG_API int ceg_mc_group_baseline(ceg_mc_group_t* group, int32_t flags, ceg_mc_b
  *     not depend on how it is cut, as above: populations (by rung), energy, delta, replica and the pair counters are in device
  *     memory between launches.  tempering_read copies the pair counters [K/R][R-1] and replica [K] (every pointer optional);
  *     CEG_ERR_INVALID with nothing installed.
- * Out of scope: groupcycles / restartgroupcycle; a tempering schedule that attempts more than the first pair of randsubseq;
+ * grouped cycles (run_montecarlo!(::SiteHopping, simu; groupcycles, restartgroupcycle), src/simulation.jl:917-939, 941, 970-982;
+ *   ceg_site_group_sweep_grouped): the hops of a cycle are accepted or rejected as ONE move, and with `restart` every cycle first
+ *   replaces the population by a fresh randperm start (basin hopping, what run_random_quenching drives).  One kernel,
+ *   k_site_sweep_grouped: one wave per chain, the population in LDS, all steps and decisions of all cycles of a launch inside it.
+ *   A grouped cycle of chain c runs on stream stream_id[c] at temperature T.  Its absolute steps are s0 .. s0 + spc - 1, where
+ *   spc = steps_per_cycle (G*m for the reference's groupcycles = G).  The device needs no G of its own.
+ *   1. Save.  (P0, E0, D0) is the population, running `energy` and `delta` at the start of the cycle.
+ *   2. Restart (only when asked for).  The population becomes the first m entries of a Fisher-Yates shuffle of 0..n-1.
+ *      Entry j = 0..m-1 takes the Philox block of (seed, step s0, stream, counter word 3 = 14 | (j << 8)).  Purpose
+ *      SITE_RESTART = 14 is new.  It is keyed the way the retried proposals of ceg_mc_group_sweep_gcmc key their attempts.
+ *      r = j + min(floor(U(w0, w1) (n - j)), n - j - 1), and entries j and r are exchanged, for j rising.  This is the arithmetic
+ *      of mcrng.site_random_population.  The device never builds the n entries: entry j ends as the value that position r_j held
+ *      just before exchange j, which is found by walking down the earlier (q, r_q) pairs (mcrng.site_restart_population).
+ *      Then energy = baseline_energy of that population, computed by the chain's own wave in this order, a function of m alone:
+ *      F: lane l = 0..63 adds framework[pop[j]] for j = l, l + 64, ... (< m) in rising order onto +0.0.  E: for the rows
+ *      i = 0, 1, .., m - 2 in rising order lane l adds interactions[pop[i]][pop[j]] for j = i + 1 + l, i + 1 + l + 64, ... (< m) in
+ *      rising order onto ONE accumulator per lane that starts at +0.0 and runs through all rows.  Then F and E each meet by the xor
+ *      butterfly of the row sum R (o = 32, 16, 8, 4, 2, 1), and the baseline is (tailcorrection + F) + E (mcrng.site_baseline_wave).
+ *      Call this energy Er.  Without a restart, Er = E0.
+ *   3. Hops.  spc ordinary steps follow, and they are the step above bit for bit: the draws, row sums, rule and log record of
+ *      sweep_cycles.  `energy` moves with every accepted hop.  The group's attempted / accepted counters do not move (:946, :962).
+ *      The hops accepted inside the cycle are counted separately.
+ *   4. Decision.  Draw the block of (seed, s0 + spc - 1, stream, purpose SITE_GROUP = 13), and take u = U(w0, w1).  With E1 the
+ *      energy after the hops, the cycle is accepted iff E1 < E0, or else u < exp((E0 - E1) / T).  This is
+ *      compute_accept_move(group_energy, energy, temperature, sh) (:972), with the device library's FP64 exp and an IEEE division.
+ *      A NaN E1 is rejected by the rule itself, with no special case.  attempted += 1.
+ *      Accepted: accepted += 1 and delta = D0 + (E1 - E0), with or without a restart, so energy - delta stays the baseline the
+ *      chain began from.  Rejected: population, `energy` and `delta` become P0, E0, D0 again.
+ *   5. Cycle end.  It is as for sweep_cycles, on the state AFTER the decision: frame, strict-< minimum and the cycle record are
+ *      unchanged.  `flags` gains CEG_SITE_GROUP_ACCEPTED = 8 and CEG_SITE_GROUP_RESTARTED = 16.
+ *   The reference's old_i / before / after cache (:926-927, :975-980) needs no device state: `before` is recomputed at every hop,
+ *   and the cache is reset wherever the population changes other than at old_i (restart, rejection).
+ *   sweep_grouped is sweep_cycles plus `restart` (0 or 1) and grouped_out [ncycles][K] (optional): per cycle and chain E0, Er, E1,
+ *   u, the decision, whether the cycle restarted and the hops accepted inside it.  Nothing is installed in the group, and
+ *   sweep_cycles is what it was.  Validation, limits and the synchronous contract are those of sweep_cycles; in addition
+ *   CEG_ERR_UNSUPPORTED while tempering is installed (run_parallel_tempering has no group cycles) and CEG_ERR_INVALID for a
+ *   `restart` outside {0, 1}; in both cases nothing is launched and nothing changes.  The call is cut into launches as sweep_cycles
+ *   is, and a cut may fall inside a cycle: P0, E0, D0, Er and the cycle's hop count live in device memory between launches, so
+ *   outputs and state are the same bytes however the call is cut, and however the caller cuts a run into calls of whole cycles.
+ *   Between calls nothing is pending.
+ * Out of scope: a tempering schedule that attempts more than the first pair of randsubseq;
  *   extremal_placements; ShootingStarMinimizer; the serialised caches and output files.
  *
  * The two tables (the reference's constructor, sitehopping.jl:41-82, telescoped): ceg_site_tables (host arrays out) and
@@ -1399,6 +1439,8 @@ CEG_API int ceg_mc_group_baseline(ceg_mc_group_t* group, int32_t flags, ceg_mc_b
 #define CEG_SITE_FRAME_TAKEN   1
 #define CEG_SITE_FRAME_DROPPED 2
 #define CEG_SITE_NEW_MINIMUM   4
+#define CEG_SITE_GROUP_ACCEPTED  8      /* sweep_grouped: the cycle was accepted as one move */
+#define CEG_SITE_GROUP_RESTARTED 16     /* sweep_grouped: the cycle began from a fresh random population */
 typedef struct ceg_site_group ceg_site_group_t;
 typedef struct ceg_site_params {        /* 24 bytes */
     uint64_t seed, first_step;
@@ -1416,7 +1458,7 @@ typedef struct ceg_site_cycle_record {  /* 56 bytes */
     int64_t cycle;
     double temperature, energy, delta;
     int64_t attempted, accepted;        /* cumulative, as in the stats */
-    int32_t flags, _pad;                /* CEG_SITE_FRAME_TAKEN | CEG_SITE_FRAME_DROPPED | CEG_SITE_NEW_MINIMUM */
+    int32_t flags, _pad;                /* CEG_SITE_FRAME_TAKEN | CEG_SITE_FRAME_DROPPED | CEG_SITE_NEW_MINIMUM | CEG_SITE_GROUP_* */
 } ceg_site_cycle_record_t;
 typedef struct ceg_site_record {        /* 40 bytes */
     int32_t molecule, old_site, new_site, accepted;
@@ -1430,6 +1472,11 @@ typedef struct ceg_site_frame_record {  /* 16 bytes */
     int64_t cycle;
     double energy;
 } ceg_site_frame_record_t;
+typedef struct ceg_site_grouped_record { /* 48 bytes */
+    double before, restart_energy, after, u;   /* E0, Er, E1 and the decision's draw */
+    int32_t accepted, restarted;
+    int64_t hops_accepted;              /* inside the cycle, whatever the decision */
+} ceg_site_grouped_record_t;
 typedef struct ceg_site_tempering {     /* 32 bytes */
     int32_t rungs, _pad;                /* R in 2..16, K % R == 0 */
     const double*   pair_cdf;           /* [R-1] host */
@@ -1446,6 +1493,9 @@ CEG_API int ceg_site_group_create(int32_t device, int32_t n, int32_t m, int32_t 
 CEG_API int ceg_site_group_destroy(ceg_site_group_t* group);
 CEG_API int ceg_site_group_sweep_cycles(ceg_site_group_t* group, const ceg_site_params_t* params, const ceg_site_cycles_t* cycles,
                                         ceg_site_stats_t* stats_out, ceg_site_cycle_record_t* cycles_out, ceg_site_record_t* log_out);
+CEG_API int ceg_site_group_sweep_grouped(ceg_site_group_t* group, const ceg_site_params_t* params, const ceg_site_cycles_t* cycles, int32_t restart,
+                                         ceg_site_stats_t* stats_out, ceg_site_cycle_record_t* cycles_out, ceg_site_record_t* log_out,
+                                         ceg_site_grouped_record_t* grouped_out /*[ncycles][K] or NULL*/);
 CEG_API int ceg_site_group_baseline(ceg_site_group_t* group, double* out /*[K]*/);
 CEG_API int ceg_site_group_rebase(ceg_site_group_t* group);
 CEG_API int ceg_site_group_get_populations(ceg_site_group_t* group, uint16_t* populations_out /*[K][m]*/);
