@@ -360,7 +360,17 @@ PROTOTYPES = {
     "ceg_site_group_tempering_read": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_int32_p]),
     "ceg_recip_energy_device": (C.c_int, [C.c_void_p, C.c_void_p, c_double_p, C.c_int32, C.c_int64, C.c_double, C.c_double,
                                           C.c_void_p, C.c_void_p]),
+    "ceg_grid_local_minima": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_int64,
+                                        c_int64_p, c_double_p, C.c_void_p]),
+    "ceg_grid_components": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_double, C.c_double, C.c_void_p,
+                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, c_int64_p, C.c_void_p]),
+    "ceg_grid_site_proximity": (C.c_int, [C.c_int32, c_int32_p, c_double_p, c_double_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.c_void_p]),
+    "ceg_grid_site_density": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_void_p]),
 }
+COMPONENTS_NONZERO, COMPONENTS_BAND = 0, 1      # CEG_COMPONENTS_*
+SITE_PROXIMITY_MAX_SITES = 2048                  # CEG_SITE_PROXIMITY_MAX_SITES
 
 ALGO_AUTO, ALGO_BRUTEFORCE, ALGO_CULLED = 0, 1, 2
 EGRID_MAX_TEMPS = 8          # CEG_EGRID_MAX_TEMPS

@@ -1689,4 +1689,118 @@ function create_grid_vdw_streamed(file, framework::AbstractSystem{3}, forcefield
     grid
 end
 
+# ------------------------------------------------------------------ grid analysis (src/basins.jl)
+# 1-based at this boundary; the library is 0-based.  A grid is an Array{T,3} (host) or a `Ptr{Cvoid}` to device memory in the same
+# memory order together with its `dims`.  UNVERIFIED: never executed.
+_dims32(dims) = Int32[dims...]
+
+"""
+    local_minima(grid::Array{Float64,3}, tolerance=1e-2; lt=(<), device=0) -> Vector{CartesianIndex{3}}
+
+`CrystalEnergyGrids.local_minima` (src/basins.jl:40-99) with the scan on the device (`ceg_grid_local_minima`), sorted.  `lt` is `<`
+or `>`.  The reference's `@assert min_energy < 0` arrives as an error of the library; a grid without any local extremum gives an
+empty list where the reference throws.
+"""
+function local_minima(grid::Array{Float64,3}, tolerance=1e-2; lt=(<), device=0)
+    lt === (<) || lt === (>) || error("lt must be < or >")
+    _local_minima(grid, 0, size(grid), tolerance, lt === (>), device)
+end
+"the same for a grid in device memory (e.g. a `min` lattice of `ceg_energy_grid_reduced`)"
+local_minima(d_grid::Ptr{Cvoid}, dims::NTuple{3,Int}, tolerance=1e-2; lt=(<), device=0) =
+    _local_minima(d_grid, 1, dims, tolerance, lt === (>), device)
+
+function _local_minima(grid, on_device::Int, dims, tolerance, maxima::Bool, device)
+    d = _dims32(dims)
+    count = Int64[0]; ext = Float64[0.0]
+    cap = 4096
+    while true
+        ijk = Matrix{Int32}(undef, 3, max(cap, 1))
+        GC.@preserve grid d ijk count ext _check(ccall((:ceg_grid_local_minima, LIB[]), Cint,
+            (Int32, Ptr{Cvoid}, Int32, Ptr{Int32}, Int32, Float64, Ptr{Int32}, Int32, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Cvoid}),
+            device, grid, on_device, d, maxima ? 1 : 0, Float64(tolerance), ijk, 0, cap, count, ext, C_NULL))
+        count[1] <= cap && return [CartesianIndex(Int(ijk[1, n]) + 1, Int(ijk[2, n]) + 1, Int(ijk[3, n]) + 1) for n in 1:count[1]]
+        cap = Int(count[1])
+    end
+end
+
+"""
+    grid_components(grid::Array{T,3}; band=nothing, device=0) -> (labels, seeds, sizes, sums)
+
+The periodic 6-connected components of the non-zero points of `grid` (`T` = Int64 or Float64: `local_components`, src/basins.jl:279-313)
+or, with `band = (mine, maxe)`, of the points with `mine < value < maxe` of a Float64 lattice (`compute_levels`, :842-869; strict on
+both sides).  `labels[i,j,k]` is 0 for an inactive point, else the 1-based rank of its component in the order in which the reference's
+scan finds them; `seeds` are `CartesianIndex`es (the first point of each component in that scan), `sums` the exact Int64 sums (empty
+for Float64).  The unwrapped coordinates of the reference's lists, Float64 sums and the atol / rtol / ntol cut are not covered.
+"""
+function grid_components(grid::Array{T,3}; band=nothing, device=0) where {T<:Union{Int64,Float64}}
+    a, b, c = size(grid)
+    d = _dims32(size(grid))
+    isint = T === Int64
+    mode = band === nothing ? 0 : 1
+    lo, hi = band === nothing ? (0.0, 0.0) : Float64.(band)
+    labels = Array{Int32,3}(undef, a, b, c)
+    count = Int64[0]
+    cap = 4096
+    while true
+        seed = zeros(Int32, max(cap, 1)); sz = zeros(Int32, max(cap, 1)); sm = zeros(Int64, max(cap, 1))
+        GC.@preserve grid d labels seed sz sm count _check(ccall((:ceg_grid_components, LIB[]), Cint,
+            (Int32, Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Int32, Float64, Float64, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int64},
+             Int32, Int64, Ptr{Int64}, Ptr{Cvoid}),
+            device, grid, isint ? 1 : 0, 0, d, mode, lo, hi, labels, 0, seed, sz, isint ? pointer(sm) : Ptr{Int64}(C_NULL), 0, cap, count, C_NULL))
+        if count[1] <= cap
+            n = Int(count[1])
+            seeds = [CartesianIndex(Int(s % a) + 1, Int((s ÷ a) % b) + 1, Int(s ÷ (a*b)) + 1) for s in seed[1:n]]
+            return labels .+ Int32(1), seeds, Int.(sz[1:n]), isint ? sm[1:n] : Int64[]
+        end
+        cap = Int(count[1])
+    end
+end
+
+"""
+    site_proximity_map(sites, dims, mat, maxdist=2.0; device=0) -> (map, deleted)
+
+`site_proximity_map!` (src/basins.jl:466-578): `map[i,j,k] == (s, ofs)` as the reference returns it.  `sites` (fractional) is NOT
+mutated: the indices the reference would delete (sites that snap to the voxel of an earlier one, :471-484) are returned, and `s`
+indexes the kept ones.  `mat` in Å, unitless.  Refused when a ball of `maxdist` plus the skin would meet its own periodic image.
+"""
+function site_proximity_map(sites::AbstractVector, dims::NTuple{3,Int}, mat::AbstractMatrix, maxdist=2.0; device=0)
+    a, b, c = dims
+    known = Set{NTuple{3,Int}}(); deleted = Int[]
+    for (idx, (i, j, k)) in enumerate(sites)
+        ijk = (1 + round(Int, a*i), 1 + round(Int, b*j), 1 + round(Int, c*k))
+        ijk in known ? push!(deleted, idx) : push!(known, ijk)
+    end
+    kept = [Float64(x) for (idx, s) in enumerate(sites) if !(idx in deleted) for x in s]
+    m = Vector{Float64}(vec(Matrix{Float64}(mat)))
+    d = _dims32(dims)
+    site = Array{Int32,3}(undef, a, b, c)
+    ofs = Array{Int8,4}(undef, 3, a, b, c)
+    GC.@preserve d m kept site ofs _check(ccall((:ceg_grid_site_proximity, LIB[]), Cint,
+        (Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Int32, Float64, Ptr{Int32}, Ptr{Cvoid}, Int32, Ptr{Cvoid}),
+        device, d, m, kept, length(kept) ÷ 3, Float64(maxdist), site, ofs, 0, C_NULL))
+    [(site[i, j, k], SVector{3,Int8}(ofs[1, i, j, k], ofs[2, i, j, k], ofs[3, i, j, k])) for i in 1:a, j in 1:b, k in 1:c], deleted
+end
+
+"""
+    site_density(bins::Array{Int64,3}, proximity, numsites; device=0) -> Vector{Tuple{Float64,SVector{3,Float64}}}
+
+`closest_from_proximity(bins, proximity, numsites)` (src/basins.jl:580-597) for the Int64 bins of a density map: the sums are exact
+integers on the device, `pos` is one division of them.  `first.(site_density(...))` is `proximal_map`.
+"""
+function site_density(bins::Array{Int64,3}, proximity::Array{<:Tuple,3}, numsites::Int; device=0)
+    a, b, c = size(bins)
+    size(proximity) == (a, b, c) || error("the proximity map and the bins differ in size")
+    site = Int32[p[1] for p in proximity]
+    ofs = Array{Int8,4}(undef, 3, a, b, c)
+    for k in 1:c, j in 1:b, i in 1:a, q in 1:3
+        ofs[q, i, j, k] = proximity[i, j, k][2][q]
+    end
+    d = _dims32((a, b, c))
+    rho = zeros(Int64, numsites + 1); mom = zeros(Int64, 3, numsites + 1)
+    GC.@preserve bins site ofs d rho mom _check(ccall((:ceg_grid_site_density, LIB[]), Cint,
+        (Int32, Ptr{Int64}, Int32, Ptr{Int32}, Ptr{Cvoid}, Int32, Ptr{Int32}, Int32, Ptr{Int64}, Ptr{Int64}, Int32, Ptr{Cvoid}),
+        device, bins, 0, site, ofs, 0, d, numsites, rho, mom, 0, C_NULL))
+    [(Float64(rho[s]), SVector{3,Float64}(mom[1, s] / (a*rho[s]), mom[2, s] / (b*rho[s]), mom[3, s] / (c*rho[s]))) for s in 1:numsites+1]
+end
+
 end # module

@@ -1529,6 +1529,98 @@ CEG_API int ceg_block_spheres(int32_t device, const int32_t dims[3], const doubl
                               const double mat[9], const double invmat[9], int32_t ortho, double safemin2,
                               const double* centers, const double* radius2, int32_t nspheres, uint8_t* block);
 
+/* ---- grid analysis: minima, components, site proximity maps (src/basins.jl) -------------- */
+/*
+ * What the reference does between an energy grid or a density map and the site model.  Common to the four entry points:
+ *  - a grid is an Array{T,3} in Julia's memory order, first axis fastest: element (i, j, k), 0-based, at i + a*(j + b*k), dims =
+ *    (a, b, c); a*b*c must fit int32 (CEG_ERR_INVALID otherwise);
+ *  - every array marked "host or device" lives where its *_on_device flag says, device meaning `device`.  With device arrays the
+ *    work is asynchronous on `stream` (a hipStream_t, NULL = the null stream) except where a count has to reach the caller:
+ *    ceg_grid_local_minima and ceg_grid_components synchronise the stream, the two site calls do so only when an array of theirs is
+ *    in host memory;
+ *  - neighbours are periodic (mod1) as in the reference: an axis of length 1 makes a point its own neighbour, an axis of length 2
+ *    makes both neighbours the same point; both come out as the reference's loops give them;
+ *  - nothing is launched on a bad argument; no float atomics: every result is independent of the order in which waves arrive.
+ *
+ * ceg_grid_local_minima: local_minima(grid, tolerance; lt), basins.jl:40-99.
+ *  maxima      0: lt = <;  1: lt = >.  A point is kept iff lt(value, neighbour) for all 26 periodic neighbours: strict, a NaN
+ *              anywhere in the cube fails it, 1e100 and +-Inf are ordinary values.
+ *  tolerance   < 0: every kept point.  >= 0: extremum = the MINIMUM of the grid over the kept points (also for maxima: :89 takes
+ *              `minimum`), threshold = extremum + abs(extremum*tolerance) in FP64 in this order, and a kept point survives iff
+ *              !(value > threshold) (also for maxima, :95).  The reference's `@assert min_energy < 0` (:91) is CEG_ERR_INVALID.
+ *  count_out   the full count (host).  No local extremum at all, where the reference throws on an empty `minimum`: count 0, CEG_OK,
+ *              extremum +Inf.
+ *  ijk_out     [min(count, capacity)][3] int32, 0-based, sorted by linear index (Julia's sort! of the CartesianIndex list); host or
+ *              device.  A count above the capacity is no error: compare and call again.  capacity 0: ijk_out may be NULL.
+ *  extremum_out  host, optional: the minimum over the kept points (before the threshold).
+ * One pass over the grid (the 3x3x3 cube of a point comes from an LDS tile with a periodic halo), then the flags are compacted in
+ * linear-index order: counts per 2048 points, an exclusive scan, an emit.
+ */
+CEG_API int ceg_grid_local_minima(int32_t device, const double* grid, int32_t grid_on_device, const int32_t dims[3], int32_t maxima,
+                                  double tolerance, int32_t* ijk_out, int32_t ijk_on_device, int64_t capacity, int64_t* count_out,
+                                  double* extremum_out, void* stream);
+
+/*
+ * ceg_grid_components: the periodic 6-connected components of the ACTIVE points of a grid.
+ *  mode  CEG_COMPONENTS_NONZERO  active iff value != 0 (a NaN is active, as with iszero): local_components, basins.jl:279-313.
+ *                                grid_is_int64 = 1: an int64 grid (the bins of ceg_mc_group_set_sampler), 0: FP64.  lo, hi ignored.
+ *        CEG_COMPONENTS_BAND     active iff lo < value < hi, FP64 only: compute_levels, basins.jl:842-869, on a mean lattice of
+ *                                ceg_energy_grid_reduced.  STRICT on both sides: the reference admits == for the point a scan starts
+ *                                from and not for a neighbour, which for a value equal to a bound depends on its scan order.
+ *  labels_out  [a*b*c] int32, optional, host or device: -1 for an inactive point, else the rank of the point's component when the
+ *              components are ordered by their smallest linear index -- the order in which the reference's k, j, i scan finds them.
+ *  count_out   the number of components (host).
+ *  seed_out, size_out, sum_out   [min(count, capacity)], each optional, all host or all device (lists_on_device): the smallest linear
+ *              index of the component, its number of points, the int64 sum of its values.  sum_out is for an int64 grid only
+ *              (CEG_ERR_INVALID with an FP64 grid): an FP64 sum depends on the order of the additions, and the reference's is its
+ *              queue's; the caller sums by label where it needs one.
+ * Union-find over a parent array int32[a*b*c] (each active point united with its +i, +j, +k neighbours, the larger root hung under
+ * the smaller with atomicMin until it holds), a flatten pass, ranks from the flagged roots and an exclusive scan; sizes and sums
+ * by integer atomics, runs of equal labels inside a wave combined first.
+ * Not covered: the unwrapped coordinates the reference's point lists carry, FP64 sums, the atol / rtol / ntol cut and the sort by
+ * decreasing sum (a few numbers per component: the bindings do them from seed / size / sum).
+ */
+#define CEG_COMPONENTS_NONZERO 0
+#define CEG_COMPONENTS_BAND    1
+CEG_API int ceg_grid_components(int32_t device, const void* grid, int32_t grid_is_int64, int32_t grid_on_device, const int32_t dims[3],
+                                int32_t mode, double lo, double hi, int32_t* labels_out, int32_t labels_on_device, int32_t* seed_out,
+                                int32_t* size_out, int64_t* sum_out, int32_t lists_on_device, int64_t capacity, int64_t* count_out,
+                                void* stream);
+
+/*
+ * ceg_grid_site_proximity: the map of site_proximity_map!, basins.jl:466-578.  For every grid point w = (i, j, k): the site s and the
+ * cell offset o in {-1, 0, 1}^3 that minimise d2 = |mat * (site_s - ((w + o.*dims) ./ dims))|^2 (:526-528); the lowest site index
+ * wins among equal d2; the point is assigned iff d2 < maxdist^2.
+ *  mat       3x3 column-major, the cell;  sites  [nsites][3] FRACTIONAL, host memory, 0 <= nsites <= CEG_SITE_PROXIMITY_MAX_SITES.
+ *            The reference first deletes the sites that snap to the voxel of an earlier one (1 + round(dims*x), :471-484): that is
+ *            the caller's business (the bindings do it and return the deleted indices).
+ *  site_out  [a*b*c] int32: 0 = none, else the 1-based site, as the reference's map;  offset_out  [a*b*c][3] int8, (0, 0, 0) where
+ *            site_out is 0; both host or both device (out_on_device).
+ * The reference reaches this map by two breadth-first passes per site with a skin of one voxel diagonal; it is the same map as long
+ * as a ball does not meet its own image.  Hence CEG_ERR_INVALID unless 2*(maxdist + |mat*(1 ./ dims)|) is below the smallest
+ * perpendicular width of the cell.  Under that condition an assigned point lies within half a cell of its site along every axis, so
+ * the kernel tests one offset per site and axis, round(site - w/dims) clamped to {-1, 0, 1}, not 27.  (The reference also gives the
+ * voxel a site snaps to to that site whatever the distances; that differs from the rule above only where maxdist, or the distance
+ * to another site, is below a voxel diagonal.)
+ * A gather: one thread per point, the sites in LDS.  Synchronises `stream` (the sites are read from host memory).
+ */
+#define CEG_SITE_PROXIMITY_MAX_SITES 2048
+CEG_API int ceg_grid_site_proximity(int32_t device, const int32_t dims[3], const double mat[9], const double* sites, int32_t nsites,
+                                    double maxdist, int32_t* site_out, int8_t* offset_out, int32_t out_on_device, void* stream);
+
+/*
+ * ceg_grid_site_density: the sums of closest_from_proximity, basins.jl:580-597, of an int64 density map over a proximity map, exact.
+ *  bins        [a*b*c] int64, host or device;  site / offset  the map of ceg_grid_site_proximity, both host or both device
+ *              (map_on_device); an entry of `site` outside 0 .. nsites is ignored
+ *  rho_out     [nsites+1] int64: rho_s = the sum of the bins of the points of site s+1; entry nsites = the unattributed rest
+ *  moment_out  [nsites+1][3] int64: M_c = sum of bins * (o_c*dims_c + w_c); the reference's centre is pos_c = M_c / (dims_c * rho)
+ *              both host or both device (out_on_device), overwritten.
+ * Integer atomics, runs of equal sites inside a wave combined first.
+ */
+CEG_API int ceg_grid_site_density(int32_t device, const int64_t* bins, int32_t bins_on_device, const int32_t* site, const int8_t* offset,
+                                  int32_t map_on_device, const int32_t dims[3], int32_t nsites, int64_t* rho_out, int64_t* moment_out,
+                                  int32_t out_on_device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
