@@ -166,8 +166,10 @@ class GpuEnergySetup:
         """``energy_grid(setup, step, num_rotate)`` for a polyatomic guest (grids.jl:346-424) in ONE device pass
         (``ceg_energy_grid``): float64[nrot, numA, numB, numC] of ``sum(energy_point)`` with the molecule turned by
         ``rotations[k]`` (3x3, applied as ``r @ p``, grids.jl:389; e.g. from :func:`ceg_hip.hostmirror.lebedev.rotation_matrices`)
-        on the lattice of :meth:`energy_grid`.  The array is a view of the buffer in Julia's memory order of ``allvals``
-        (rotation fastest).  With ``out_device_ptr`` (device memory for nrot*numA*numB*numC doubles) the result stays on the
+        on the lattice of :meth:`energy_grid`.  At the reference's default ``num_rotate = 40`` its ``get_rotation_matrices``
+        (lebedev.jl:109-123) yields 43 orientations for a linear symmetric guest such as CO2 (the 86-point Lebedev grid halved)
+        and 70 for a non-linear one (5 z-rotations x 14 points).  The array is a view of the buffer in Julia's memory order of
+        ``allvals`` (rotation fastest).  With ``out_device_ptr`` (device memory for nrot*numA*numB*numC doubles) the result stays on the
         device, the call is asynchronous on ``stream`` and the lattice shape is returned instead."""
         lib = _abi.load_library()
         args, keep, nrot, (numA, numB, numC) = self._egrid_arguments(step, rotations)
