@@ -10,7 +10,7 @@ is not built.
 PRODUCT (bindings of the C ABI): ``_abi``, ``plan`` (resident-plan API, device buffers), ``grids`` (the reference's grid
 functions on top of the one-shot entry points), ``interp`` / ``energy`` (batched GPU consumers of the grids: interpolation,
 reciprocal Ewald, pair energies, ``GpuEnergySetup``, ``GpuMonteCarloEnergy``, ``DeviceMonteCarlo``), ``distributed`` (x-slab /
-block-cyclic sharding over ranks), ``basins`` (grid analysis of ``src/basins.jl`` on the device: minima, components, site proximity maps).
+block-cyclic sharding over ranks), ``basins`` (grid analysis of ``src/basins.jl`` on the device: minima, components, site proximity maps, attraction basins).
 
 HARNESS (``hostmirror/``, see its docstring): Python restatements of the reference's host code around the path -- RASPA parsers,
 force fields, ProbeSystem, Ewald set-up, the Monte-Carlo energy functions, ``setup_RASPA`` -- which build the inputs of the C ABI
@@ -28,4 +28,5 @@ from .hostmirror.raspa import (setdir_RASPA, getdir_RASPA, parse_pseudoatoms_RAS
 from .grids import (EnergyGrid, CrystalEnergySetup, create_grid_vdw, create_grid_coulomb, parse_grid,
                     interpolate_grid, energy_point, build_vdw_array, build_coulomb_array)
 from .hostmirror.setup_raspa import setup_RASPA, retrieve_or_create_grid
-from .basins import (local_minima, local_components, compute_levels, site_proximity_map, closest_from_proximity, proximal_map)
+from .basins import (local_minima, local_components, compute_levels, site_proximity_map, closest_from_proximity, proximal_map,
+                     local_basins, decompose_basins)

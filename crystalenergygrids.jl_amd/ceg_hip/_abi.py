@@ -368,7 +368,11 @@ PROTOTYPES = {
                                           C.c_void_p]),
     "ceg_grid_site_density": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_int32, C.c_void_p]),
+    "ceg_grid_basins": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, c_int32_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_double,
+                                  C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, c_int64_p, C.c_void_p,
+                                  C.c_int32, C.c_void_p]),
 }
+BASINS_MAX_OWNERS = 16                           # CEG_BASINS_MAX_OWNERS
 COMPONENTS_NONZERO, COMPONENTS_BAND = 0, 1      # CEG_COMPONENTS_*
 SITE_PROXIMITY_MAX_SITES = 2048                  # CEG_SITE_PROXIMITY_MAX_SITES
 

@@ -1,14 +1,19 @@
 """Grid analysis of the reference's ``src/basins.jl`` on the device: ``local_minima`` (:40-99), ``local_components`` (:279-313),
-``compute_levels`` (:842-869), ``site_proximity_map!`` (:466-578), ``closest_from_proximity`` (:580-597), ``proximal_map`` (:607-610),
-on top of ``ceg_grid_local_minima`` / ``ceg_grid_components`` / ``ceg_grid_site_proximity`` / ``ceg_grid_site_density``.
+``compute_levels`` (:842-869), ``site_proximity_map!`` (:466-578), ``closest_from_proximity`` (:580-597), ``proximal_map`` (:607-610), ``local_basins`` (:195-264), ``decompose_basins`` (:765-797),
+on top of ``ceg_grid_local_minima`` / ``ceg_grid_components`` / ``ceg_grid_site_proximity`` / ``ceg_grid_site_density`` /
+``ceg_grid_basins``.
 
 Everything is 0-based.  A grid argument is a NumPy array ``g[i, j, k]`` (any memory order; it is handed over in Julia's, first axis
 fastest) or ``(device_ptr, (a, b, c))`` -- ``(device_ptr, (a, b, c), dtype)`` where both int64 and float64 are legal -- for an array that
 is already in device memory in that order (a lattice of ``ceg_energy_grid_reduced``, the bins of the MC sampler).
 
 The ``*_host`` functions are vectorised NumPy restatements of the same definitions, for where no device is wanted; they never touch
-the library.  Not covered: ``local_basins`` / ``decompose_basins``, ``coalescing_basins`` / ``average_clusters``,
-``closest_to_sites``, ``energy_levels``, the unwrapped coordinates of the reference's component lists.
+the library.  Not covered: ``coalescing_basins`` / ``average_clusters``, ``closest_to_sites``, ``energy_levels``,
+the unwrapped coordinates of the reference's component lists and basin sets (a point is its wrapped index here).
+
+The basins follow the definition (``x`` belongs to basin ``i`` iff no start reaches ``x`` at an earlier breadth-first level than
+``i`` does); the reference as written departs from it at the sole last-level point of a basin (basins.jl:153), see
+``ceg_grid_basins`` in the header.
 """
 from __future__ import annotations
 
@@ -23,7 +28,9 @@ from . import _abi
 __all__ = ["local_minima", "grid_components", "local_components", "compute_levels", "site_proximity_map", "site_density",
            "closest_from_proximity", "proximal_map", "snap_sites", "check_maxdist", "Components",
            "local_minima_host", "grid_components_host", "local_components_host", "compute_levels_host", "site_proximity_map_host",
-           "site_density_host", "closest_from_proximity_host", "proximal_map_host"]
+           "site_density_host", "closest_from_proximity_host", "proximal_map_host",
+           "Basins", "local_basins", "basin_points", "decompose_basins", "local_basins_host", "decompose_basins_host",
+           "circular_distance"]
 
 
 class Components(NamedTuple):
@@ -411,3 +418,236 @@ def proximal_map_host(bins, sites, mat, maxdist=2.0):
     nk = len(np.asarray(sites).reshape(-1, 3)) - len(deleted)
     rho, _ = site_density_host(bins, site, off, nk)
     return rho.astype(np.float64), deleted
+
+
+# ---------------------------------------------------------------------------------------------------------------- basins
+class Basins(NamedTuple):
+    """``level[i, j, k]``: the breadth-first level at which the nearest start reaches the point, -1 where none does.  ``owner[i, j, k]``:
+    the smallest index (into the list of starts) of a basin the point belongs to, -1 for none; ``nowners[i, j, k]`` (uint8): how many
+    basins it belongs to.  ``shared`` (m, 2) int32: ``(linear index i + a*(j + b*k), owner)`` for every owner of every point with more
+    than one, sorted by index then owner.  ``size[n]``: the points of each basin (0 for a start that was skipped or merged away by
+    ``cluster``).  ``kept``: the indices of the starts that have a basin, ascending -- the reference's ``basinsets`` is
+    ``[basin_points(b, i) for i in b.kept]``.  The start of basin ``i`` is its one point of level 0."""
+    level: np.ndarray
+    owner: np.ndarray
+    nowners: np.ndarray
+    shared: np.ndarray
+    size: np.ndarray
+    kept: np.ndarray
+
+
+def circular_distance(a, m, n):
+    """:108-113 as written, on 1-based coordinates: the wrapped distance is taken only when ``min(m, n) < a // 2 < max(m, n)``"""
+    b = a // 2
+    i, j = (m, n) if m <= n else (n, m)
+    if i < b < j:
+        return min(j - i, i - j + a)
+    return j - i
+
+
+def _cluster_reps(minima, cluster, dims):
+    """``clean_cluster!`` (:116-128) over a list of 0-based minima -> ``unions`` (0-based positions in that list)"""
+    m = np.asarray(minima, dtype=np.int64).reshape(-1, 3) + 1                    # the reference's coordinates are 1-based
+    unions = np.arange(len(m))
+    if not cluster > 0:
+        return unions
+    half = [d // 2 for d in dims]
+    for i1 in range(len(m) - 1):
+        dist = np.zeros(len(m) - i1 - 1, dtype=np.int64)
+        for q in range(3):
+            lo, hi = np.minimum(m[i1, q], m[i1 + 1:, q]), np.maximum(m[i1, q], m[i1 + 1:, q])
+            dist += np.where((lo < half[q]) & (half[q] < hi), np.minimum(hi - lo, lo - hi + dims[q]), hi - lo)
+        unions[i1 + 1:][dist <= cluster] = unions[i1]
+    return unions
+
+
+def _basins_from_pairs(level, pt, ow, nstarts, kept, dims):
+    """the maps and lists from the (point, owner) pairs, duplicates allowed"""
+    n = dims[0] * dims[1] * dims[2]
+    key = np.unique(pt.astype(np.int64) * max(nstarts, 1) + ow.astype(np.int64))
+    pt, ow = key // max(nstarts, 1), key % max(nstarts, 1)
+    cnt = np.bincount(pt, minlength=n)
+    if cnt.size and cnt.max(initial=0) > 255:
+        raise ValueError("a point with more than 255 owners")
+    owner = np.full(n, -1, dtype=np.int32)
+    first = np.ones(pt.size, dtype=bool)
+    first[1:] = pt[1:] != pt[:-1]
+    owner[pt[first]] = ow[first]
+    multi = cnt[pt] > 1
+    shared = np.stack([pt[multi], ow[multi]], axis=1).astype(np.int32).reshape(-1, 2)
+    size = np.bincount(ow, minlength=nstarts).astype(np.int32)
+    return Basins(np.asarray(level, dtype=np.int32).reshape(dims, order="F"), owner.reshape(dims, order="F"),
+                  cnt.astype(np.uint8).reshape(dims, order="F"), shared, size, np.asarray(kept, dtype=np.int64))
+
+
+def _pairs(b: Basins):
+    own, cnt = b.owner.ravel(order="F"), b.nowners.ravel(order="F")
+    single = np.flatnonzero(cnt == 1)
+    return np.concatenate([single, b.shared[:, 0].astype(np.int64)]), np.concatenate([own[single].astype(np.int64), b.shared[:, 1].astype(np.int64)])
+
+
+def _apply_cluster(b: Basins, minima, cluster) -> Basins:
+    """:250 over the kept minima: the owners relabelled to the basin they are merged into, duplicates removed"""
+    if not cluster > 0 or not len(b.kept):
+        return b
+    dims = b.level.shape
+    unions = _cluster_reps(np.asarray(minima).reshape(-1, 3)[b.kept], cluster, dims)
+    rep = np.arange(len(b.size), dtype=np.int64)
+    rep[b.kept] = b.kept[unions]
+    pt, ow = _pairs(b)
+    return _basins_from_pairs(b.level.ravel(order="F"), pt, rep[ow], len(b.size), np.unique(rep[b.kept]), dims)
+
+
+def _starts_arg(minima):
+    m = np.ascontiguousarray(np.asarray(minima, dtype=np.int64).reshape(-1, 3))
+    if m.size and (m.min() < -2**31 or m.max() > 2**31 - 1):
+        raise ValueError("a start does not fit int32")
+    return m.astype(np.int32)
+
+
+def local_basins(grid, minima=None, tolerance=-math.inf, *, maxima=False, cluster=0, skip_above=math.inf, maxdist=0, device=0,
+                 stream=None) -> Basins:
+    """``local_basins(grid, minima; lt, cluster, skip, maxdist)`` / ``local_basins(grid, tolerance; ...)`` on the device.  ``minima``:
+    (n, 3) 0-based starts (distinct, inside the grid; they need not be minima), or ``None``: ``local_minima(grid, tolerance)`` runs
+    first, on the device, and its list goes from device memory into ``ceg_grid_basins`` (this route allocates through torch).
+    ``skip_above``: the reference's ``skip`` as ``v -> v > skip_above``.  ``cluster`` is applied on the host, over the list of kept
+    minima.  A point with more than ``_abi.BASINS_MAX_OWNERS`` owners raises ``CegError`` (code -5)."""
+    lib = _abi.load_library()
+    ptr, on_dev, dims, _, keep = _grid_arg(grid, (np.float64,))
+    n = dims[0] * dims[1] * dims[2]
+    d32 = _dims_arg(dims)
+    hold = []
+    if minima is None:
+        import torch
+        dev = torch.device("cuda", device)
+        if not on_dev:
+            tg = torch.from_numpy(keep.ravel(order="F")).to(dev)
+            torch.cuda.synchronize(dev)
+            hold.append(tg)
+            ptr, on_dev = C.c_void_p(tg.data_ptr()), 1
+        count, cap = C.c_int64(0), 4096
+        while True:
+            tm = torch.empty((max(cap, 1), 3), dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)
+            _abi.check(lib, lib.ceg_grid_local_minima(device, ptr, on_dev, _abi.i32ptr(d32), int(bool(maxima)), float(tolerance),
+                                                      C.c_void_p(tm.data_ptr()), 1, cap, C.byref(count), None, _stream(stream)))
+            if count.value <= cap:
+                break
+            cap = int(count.value)
+        hold.append(tm)
+        ns, sptr, s_dev = int(count.value), C.c_void_p(tm.data_ptr()), 1
+        starts = None
+    else:
+        starts = _starts_arg(minima)
+        ns, sptr, s_dev = len(starts), C.c_void_p(starts.ctypes.data if len(starts) else 0), 0
+    level, owner = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+    nown, size = np.empty(n, dtype=np.uint8), np.zeros(max(ns, 1), dtype=np.int32)
+    count = C.c_int64(0)
+    cap = n // 2 + 4096
+    shared = np.empty((cap, 2), dtype=np.int32)
+
+    def call(maps, cap, shared):
+        _abi.check(lib, lib.ceg_grid_basins(device, ptr, on_dev, _abi.i32ptr(d32), sptr, s_dev, ns, int(bool(maxima)), float(skip_above),
+                                            int(maxdist), C.c_void_p(level.ctypes.data if maps else 0), C.c_void_p(owner.ctypes.data if maps else 0),
+                                            C.c_void_p(nown.ctypes.data if maps else 0), 0, C.c_void_p(shared.ctypes.data), cap, C.byref(count),
+                                            C.c_void_p(size.ctypes.data if maps else 0), 0, _stream(stream)))
+
+    call(True, cap, shared)
+    if count.value > cap:                                            # the pairs alone, with the room they need
+        cap = int(count.value)
+        shared = np.empty((cap, 2), dtype=np.int32)
+        call(False, cap, shared)
+    size = size[:ns]
+    b = Basins(level.reshape(dims, order="F"), owner.reshape(dims, order="F"), nown.reshape(dims, order="F"), shared[:count.value].copy(),
+               size, np.flatnonzero(size > 0))
+    if cluster > 0:
+        if starts is None:
+            starts = hold[-1][:ns].cpu().numpy()
+        b = _apply_cluster(b, starts, cluster)
+    return b
+
+
+def basin_points(b: Basins, i):
+    """the wrapped 0-based points (m, 3) of basin ``i`` (an index into the list of starts), in linear-index order"""
+    a, bb, _ = b.level.shape
+    lin = np.flatnonzero((b.owner.ravel(order="F") == i) & (b.nowners.ravel(order="F") == 1))
+    lin = np.sort(np.concatenate([lin, b.shared[b.shared[:, 1] == i, 0].astype(np.int64)]))
+    return np.stack([lin % a, (lin // a) % bb, lin // (a * bb)], axis=1).astype(np.int32)
+
+
+def _decompose(b: Basins):
+    a, bb, _ = b.level.shape
+    pt, ow = _pairs(b)
+    order = np.lexsort((ow, pt))
+    pt, ow = pt[order], ow[order]
+    lin, counts = np.unique(pt, return_counts=True)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    points = np.stack([lin % a, (lin // a) % bb, lin // (a * bb)], axis=1).astype(np.int32)
+    return points, offsets, np.searchsorted(b.kept, ow).astype(np.int32)
+
+
+def decompose_basins(grid, minima=None, tolerance=-math.inf, **kw):
+    """``decompose_basins(grid, basinsets)`` / ``decompose_basins(grid, tolerance; ...)`` (:765-797) -> ``(points, offsets, owners)``:
+    ``points`` (m, 3) the 0-based points that belong to a basin, sorted as :790 sorts them (k, then j, then i); the reference's
+    ``nodes[points[p]]`` is ``owners[offsets[p]:offsets[p + 1]]``, ascending 0-based positions in the list of kept basins (``Basins.kept``).
+    ``grid`` may be a ``Basins`` already computed; otherwise the arguments are those of ``local_basins``."""
+    return _decompose(grid if isinstance(grid, Basins) else local_basins(grid, minima, tolerance, **kw))
+
+
+def _lin_neighbour(lin, q, dims):
+    a, b, c = dims
+    i, j, k = lin % a, (lin // a) % b, lin // (a * b)
+    step = 1 if q % 2 == 0 else -1
+    if q // 2 == 0:
+        i = (i + step) % a
+    elif q // 2 == 1:
+        j = (j + step) % b
+    else:
+        k = (k + step) % c
+    return i + a * (j + b * k)
+
+
+def local_basins_host(grid, minima=None, tolerance=-math.inf, *, maxima=False, cluster=0, skip_above=math.inf, maxdist=0) -> Basins:
+    """The definition in NumPy, level by level over (point, owner) pairs: the pairs of level L + 1 are the pairs of level L moved
+    along every edge to a point that no earlier level reached, duplicates removed."""
+    g = np.asarray(grid, dtype=np.float64)
+    if g.ndim != 3:
+        raise ValueError("a grid has three axes")
+    dims = g.shape
+    a, b, c = dims
+    n = a * b * c
+    gf = g.ravel(order="F")
+    starts = local_minima_host(g, tolerance, maxima=maxima) if minima is None else _starts_arg(minima)
+    ns = len(starts)
+    s64 = starts.astype(np.int64).reshape(-1, 3)
+    if ns and (s64.min() < 0 or np.any(s64 >= np.asarray(dims))):
+        raise ValueError("a start is outside the grid")
+    lin0 = s64[:, 0] + a * (s64[:, 1] + b * s64[:, 2])
+    if len(np.unique(lin0)) != ns:
+        raise ValueError("a start repeats an earlier start")
+    alive = ~(gf[lin0] > skip_above)
+    level = np.full(n, -1, dtype=np.int32)
+    pt, ow = lin0[alive], np.flatnonzero(alive)
+    level[pt] = 0
+    all_pt, all_ow = [pt], [ow]
+    L = 0
+    while pt.size and (maxdist == 0 or L + 1 <= maxdist - 1):
+        cv, co = [], []
+        for q in range(6):
+            v = _lin_neighbour(pt, q, dims)
+            with np.errstate(invalid="ignore"):
+                edge = ((gf[pt] > gf[v]) if maxima else (gf[pt] < gf[v])) & ~(gf[v] > skip_above) & (level[v] < 0)
+            cv.append(v[edge])
+            co.append(ow[edge])
+        key = np.unique(np.concatenate(cv) * max(ns, 1) + np.concatenate(co))
+        pt, ow = key // max(ns, 1), key % max(ns, 1)
+        L += 1
+        level[pt] = L
+        all_pt.append(pt)
+        all_ow.append(ow)
+    out = _basins_from_pairs(level, np.concatenate(all_pt), np.concatenate(all_ow), ns, np.flatnonzero(alive), dims)
+    return _apply_cluster(out, starts, cluster)
+
+
+def decompose_basins_host(grid, minima=None, tolerance=-math.inf, **kw):
+    return _decompose(grid if isinstance(grid, Basins) else local_basins_host(grid, minima, tolerance, **kw))

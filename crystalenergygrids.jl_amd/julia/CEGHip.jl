@@ -1803,4 +1803,101 @@ function site_density(bins::Array{Int64,3}, proximity::Array{<:Tuple,3}, numsite
     [(Float64(rho[s]), SVector{3,Float64}(mom[1, s] / (a*rho[s]), mom[2, s] / (b*rho[s]), mom[3, s] / (c*rho[s]))) for s in 1:numsites+1]
 end
 
+# circular_distance (src/basins.jl:108-113) as written: the wrapped distance only when min < a ÷ 2 < max
+function _circular_distance(a::Int, m::Int, n::Int)
+    b = a ÷ 2
+    i, j = minmax(m, n)
+    i < b < j && return min(j - i, i - j + a)
+    j - i
+end
+
+"""
+    local_basins(grid::Array{Float64,3}, minima::Vector{CartesianIndex{3}}; lt=(<), cluster=0, skip_above=Inf, maxdist=0, device=0)
+    local_basins(grid::Array{Float64,3}, tolerance::Float64=-Inf; kwargs...)
+
+`CrystalEnergyGrids.local_basins` (src/basins.jl:195-264) with one levelled pass for all minima on the device (`ceg_grid_basins`).
+Returns `Vector{Set{NTuple{3,Int}}}`, 1-based.  Differences from the reference: `skip` is `v -> v > skip_above`; the sets hold WRAPPED
+coordinates, where the reference's hold whichever periodic image its queue met first; and the result follows the definition of the
+reference's docstring, where the reference as written skips the last level of a basin when that level holds exactly one point
+(:153).  `cluster` is `clean_cluster!` (:116-138) over the kept minima.  More than 16 basins at one point is an error of the library.
+"""
+function local_basins(grid::Array{Float64,3}, minima::Vector{CartesianIndex{3}}; lt=(<), cluster=0, skip_above=Inf, maxdist=0, device=0)
+    lt === (<) || lt === (>) || error("lt must be < or >")
+    a, b, c = size(grid)
+    n = length(minima)
+    d = _dims32(size(grid))
+    starts = Matrix{Int32}(undef, 3, max(n, 1))
+    for (s, m) in enumerate(minima), q in 1:3
+        starts[q, s] = m[q] - 1
+    end
+    owner = Array{Int32,3}(undef, a, b, c); nown = Array{UInt8,3}(undef, a, b, c)
+    sz = zeros(Int32, max(n, 1)); count = Int64[0]
+    cap = a*b*c ÷ 2 + 4096
+    shared = Matrix{Int32}(undef, 2, cap)
+    while true
+        GC.@preserve grid d starts owner nown shared count sz _check(ccall((:ceg_grid_basins, LIB[]), Cint,
+            (Int32, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int32}, Int32, Int64, Int32, Float64, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{UInt8}, Int32,
+             Ptr{Int32}, Int64, Ptr{Int64}, Ptr{Int32}, Int32, Ptr{Cvoid}),
+            device, grid, 0, d, starts, 0, n, lt === (>) ? 1 : 0, Float64(skip_above), Int64(maxdist), Ptr{Int32}(C_NULL), owner, nown, 0,
+            shared, cap, count, sz, 0, C_NULL))
+        count[1] <= cap && break
+        cap = Int(count[1])
+        shared = Matrix{Int32}(undef, 2, cap)
+    end
+    sets = [Set{NTuple{3,Int}}() for _ in 1:n]
+    for k in 1:c, j in 1:b, i in 1:a
+        nown[i, j, k] == 1 && push!(sets[owner[i, j, k] + 1], (i, j, k))
+    end
+    for p in 1:Int(count[1])
+        lin = Int(shared[1, p])
+        push!(sets[shared[2, p] + 1], (lin % a + 1, (lin ÷ a) % b + 1, lin ÷ (a*b) + 1))
+    end
+    kept = [s for s in 1:n if sz[s] > 0]
+    sets = sets[kept]
+    if cluster > 0
+        km = minima[kept]
+        unions = collect(1:length(km))
+        for i1 in 1:length(km), i2 in (i1+1):length(km)
+            if _circular_distance(a, km[i1][1], km[i2][1]) + _circular_distance(b, km[i1][2], km[i2][2]) +
+               _circular_distance(c, km[i1][3], km[i2][3]) ≤ cluster
+                unions[i2] = unions[i1]
+            end
+        end
+        todelete = Int[]
+        for i in 1:length(km)
+            j = unions[i]
+            i == j && continue
+            union!(sets[j], sets[i])
+            push!(todelete, i)
+        end
+        deleteat!(sets, todelete)
+    end
+    sets
+end
+local_basins(grid::Array{Float64,3}, tolerance::Float64=-Inf; lt=(<), device=0, kwargs...) =
+    local_basins(grid, local_minima(grid, tolerance; lt, device); lt, device, kwargs...)
+
+"""
+    decompose_basins(grid::Array{Float64,3}, basinsets::Vector{Set{NTuple{3,Int}}}) -> (points, nodes)
+    decompose_basins(grid::Array{Float64,3}, tolerance::Float64=-Inf; kwargs...)
+
+`CrystalEnergyGrids.decompose_basins` (src/basins.jl:765-797) on the sets of `local_basins` above: `points` sorted as :790 sorts them,
+`nodes[i,j,k]` the ascending list of the basins the point belongs to.  Host work: the device pass is the one behind `local_basins`.
+"""
+function decompose_basins(grid::Array{Float64,3}, basinsets::Vector{Set{NTuple{3,Int}}})
+    a, b, c = size(grid)
+    nodes = [Int[] for _ in 1:a, _ in 1:b, _ in 1:c]
+    pointsset = Set{NTuple{3,Int}}()
+    for (iset, set) in enumerate(basinsets)
+        union!(pointsset, set)
+        for (i, j, k) in set
+            push!(nodes[mod1(i, a), mod1(j, b), mod1(k, c)], iset)
+        end
+    end
+    points = collect(pointsset)
+    sort!(points; by = p -> (p[3], p[2], p[1]))
+    points, nodes
+end
+decompose_basins(grid::Array{Float64,3}, tolerance::Float64=-Inf; kwargs...) = decompose_basins(grid, local_basins(grid, tolerance; kwargs...))
+
 end # module

@@ -1531,7 +1531,8 @@ CEG_API int ceg_block_spheres(int32_t device, const int32_t dims[3], const doubl
 
 /* ---- grid analysis: minima, components, site proximity maps (src/basins.jl) -------------- */
 /*
- * What the reference does between an energy grid or a density map and the site model.  Common to the four entry points:
+ * What the reference does between an energy grid or a density map and the site model.  Common to the entry points of this section
+ * (ceg_grid_basins, the last of them, says itself when it synchronises):
  *  - a grid is an Array{T,3} in Julia's memory order, first axis fastest: element (i, j, k), 0-based, at i + a*(j + b*k), dims =
  *    (a, b, c); a*b*c must fit int32 (CEG_ERR_INVALID otherwise);
  *  - every array marked "host or device" lives where its *_on_device flag says, device meaning `device`.  With device arrays the
@@ -1620,6 +1621,52 @@ CEG_API int ceg_grid_site_proximity(int32_t device, const int32_t dims[3], const
 CEG_API int ceg_grid_site_density(int32_t device, const int64_t* bins, int32_t bins_on_device, const int32_t* site, const int8_t* offset,
                                   int32_t map_on_device, const int32_t dims[3], int32_t nsites, int64_t* rho_out, int64_t* moment_out,
                                   int32_t out_on_device, void* stream);
+
+/*
+ * ceg_grid_basins: the attraction basins of local_basins(grid, minima; lt, skip, maxdist), basins.jl:195-252, as the maps from which
+ * decompose_basins (:765-792) follows: for every grid point its level and the starts that own it.
+ *  Definition.  u -> v is an edge when v is one of the six periodic GridNeighbors of u, lt(grid[u], grid[v]) and !skip(grid[v]).
+ *    d_i(x) is the breadth-first level of x from start i along edges, D(x) = min_i d_i(x), and x belongs to basin i iff
+ *    d_i(x) = D(x): the reference runs one search per start and then deletes from basin i every point that another basin reached at
+ *    an earlier level (keep_shortest_distance!, :140-172).  Equal values give no edge; a NaN fails lt both ways.
+ *  The one corner.  basins.jl:153 (`start == length(Q) && continue`) skips the last level of a basin when that level holds exactly
+ *    one point: the point is neither checked against the earlier levels nor recorded for the later ones.  As written the reference
+ *    therefore differs from the definition at points that are the sole last-level point of some basin, and only there.  This entry
+ *    point follows the definition, which is what the reference's docstring promises.
+ *  grid        [a*b*c] FP64, host or device, Julia's order.
+ *  starts      [nstarts][3] int32, 0-based (i, j, k), host or device (starts_on_device): the list of ceg_grid_local_minima as it
+ *              stands in device memory, or any other distinct points; they need not be minima.  An entry outside the grid or equal
+ *              to an earlier one -> CEG_ERR_INVALID with its index in ceg_last_error().  nstarts == 0: starts may be NULL.
+ *  maxima      0: lt = <;  1: lt = >.
+ *  skip_above  skip(v) = v > skip_above; +Inf: nothing is skipped; a NaN value is never skipped (and never entered: it fails lt).
+ *              A start whose value is skipped is dropped (:204-207): it owns nothing and its size is 0.  skip_above NaN -> INVALID.
+ *  maxdist     0: no bound; > 0: levels 0 .. maxdist - 1 (the reference pushes only while current_dist < maxdist, and current_dist
+ *              is 1 while the start itself is expanded, :214-226).
+ *  level_out   [a*b*c] int32, optional: D(x), -1 where no basin reaches.
+ *  owner_out   [a*b*c] int32, optional: the smallest index of a start that owns x, -1 for none.
+ *  nowners_out [a*b*c] uint8, optional: the number of owners.        The three maps are all host or all device (maps_on_device).
+ *  shared_out  [min(count, shared_capacity)][2] int32: the pairs (linear index, owner) for every owner of every point with more than
+ *              one owner, sorted by index, then owner.  shared_count_out (host, optional) is the full count of pairs; a count above
+ *              the capacity is no error: compare and call again.  shared_capacity 0: shared_out may be NULL.
+ *  size_out    [nstarts] int32, optional: the number of points of each basin, a shared point counted once for each of its owners.
+ *              shared_out and size_out are both host or both device (lists_on_device).
+ *  A point with more than CEG_BASINS_MAX_OWNERS owners -> CEG_ERR_UNSUPPORTED, the linear index and the number of owners in
+ *  ceg_last_error(); nothing is truncated and no output is to be used.
+ * One levelled pass serves all the starts: per level one launch that claims the next frontier (compare-and-swap on the level map;
+ * the claimer shows in no output) and, afterwards, one launch that pulls the owners of the level's points from their predecessors
+ * one level down.  A single owner is one int32; lists of 2 .. 16 owners live in a pool and are merged in registers.  Sizes by integer
+ * atomics; the pairs by counts per 2048 points, an exclusive scan and an emit.  Synchronises `stream` once per 16 levels and once
+ * after the owner pass (the counts have to reach the host), and once more when an output is in host memory.  The pool starts with
+ * max(a*b*c, 4096) entries (CEG_HIP_BASINS_POOL in the environment: another first size); if that is short the owner pass runs once
+ * more with the bound, 16 a*b*c entries.
+ * Not covered: the unwrapped coordinates of the reference's sets (a point is its wrapped index here; the reference holds whichever
+ * periodic image its queue met first), clean_cluster! (a relabelling over the list of starts: the bindings do it).
+ */
+#define CEG_BASINS_MAX_OWNERS 16
+CEG_API int ceg_grid_basins(int32_t device, const double* grid, int32_t grid_on_device, const int32_t dims[3], const int32_t* starts,
+                            int32_t starts_on_device, int64_t nstarts, int32_t maxima, double skip_above, int64_t maxdist,
+                            int32_t* level_out, int32_t* owner_out, uint8_t* nowners_out, int32_t maps_on_device, int32_t* shared_out,
+                            int64_t shared_capacity, int64_t* shared_count_out, int32_t* size_out, int32_t lists_on_device, void* stream);
 
 #ifdef __cplusplus
 }
