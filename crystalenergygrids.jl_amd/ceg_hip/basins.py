@@ -8,8 +8,8 @@ fastest) or ``(device_ptr, (a, b, c))`` -- ``(device_ptr, (a, b, c), dtype)`` wh
 is already in device memory in that order (a lattice of ``ceg_energy_grid_reduced``, the bins of the MC sampler).
 
 The ``*_host`` functions are vectorised NumPy restatements of the same definitions, for where no device is wanted; they never touch
-the library.  Not covered: ``coalescing_basins`` / ``average_clusters``, ``closest_to_sites``, ``energy_levels``,
-the unwrapped coordinates of the reference's component lists and basin sets (a point is its wrapped index here).
+the library.  The last section goes from a density map to the list of sites: ``average_clusters``, ``coalescing_basins``,
+``closest_to_sites`` (see there).  Not covered: ``energy_levels``, ``output_sites``, the unwrapped coordinates of the reference's component lists and basin sets (a point is its wrapped index here).
 
 The basins follow the definition (``x`` belongs to basin ``i`` iff no start reaches ``x`` at an earlier breadth-first level than
 ``i`` does); the reference as written departs from it at the sole last-level point of a basin (basins.jl:153), see
@@ -30,7 +30,11 @@ __all__ = ["local_minima", "grid_components", "local_components", "compute_level
            "local_minima_host", "grid_components_host", "local_components_host", "compute_levels_host", "site_proximity_map_host",
            "site_density_host", "closest_from_proximity_host", "proximal_map_host",
            "Basins", "local_basins", "basin_points", "decompose_basins", "local_basins_host", "decompose_basins_host",
-           "circular_distance"]
+           "circular_distance",
+           "ClosestSites", "gaussian_taps", "smoothing_sigmas", "smooth_grid", "ranked_above", "site_nearest", "coalesce_ranked",
+           "cluster_closer_than", "closest_to_sites", "updated_sites_with_closest", "coalescing_basins", "average_clusters",
+           "smooth_grid_host", "ranked_above_host", "site_nearest_host", "coalesce_ranked_host", "cluster_closer_than_host",
+           "closest_to_sites_host", "updated_sites_with_closest_host", "coalescing_basins_host", "average_clusters_host"]
 
 
 class Components(NamedTuple):
@@ -651,3 +655,561 @@ def local_basins_host(grid, minima=None, tolerance=-math.inf, *, maxima=False, c
 
 def decompose_basins_host(grid, minima=None, tolerance=-math.inf, **kw):
     return _decompose(grid if isinstance(grid, Basins) else local_basins_host(grid, minima, tolerance, **kw))
+
+
+# ---------------------------------------------------------------------------------------------------------------- site extraction
+# From a density map to the list of sites: average_clusters (averageclusters.jl:280-294), coalescing_basins (basins.jl:661-731),
+# closest_to_sites (:324-437), updated_sites_with_closest (:447-456), cluster_closer_than! (:613-642), on top of ceg_grid_smooth /
+# ceg_grid_ranked / ceg_grid_site_nearest (device) and ceg_coalesce_ranked (host, in the library).
+#
+# A density map is an FP64 grid, or the sampler's int64 bins with the number of frames ``counter``: its values are then
+# ``bins * (1.0 / counter)`` -- one multiplication per voxel, the form the device applies; the reference's ``bins ./ counter`` can differ
+# from it in the last bit.
+class ClosestSites(NamedTuple):
+    """``sums[s]``: the density attributed to kept site ``s``; ``centres[s]``: the value-weighted centre of its voxels, fractional, with the
+    cell offsets applied (NaN where ``sums`` is 0); ``deleted``: the 0-based indices of the input sites that snapped to the voxel of an
+    earlier one; ``cap_bound``: whether the cap ``s + rho > 1`` (basins.jl:430) skipped a voxel."""
+    sums: np.ndarray
+    centres: np.ndarray
+    deleted: np.ndarray
+    cap_bound: bool
+
+
+def _mat_arg(mat):
+    m = np.asarray(mat, dtype=np.float64).reshape(3, 3)
+    return m, np.ascontiguousarray(m.T).ravel()                                  # column-major for the library
+
+
+def _periodic_setup(m):
+    from .hostmirror.utils import prepare_periodic_distance_computations
+    ortho, safemin = prepare_periodic_distance_computations(m)
+    return bool(ortho), float(safemin)
+
+
+def _as_density(grid):
+    """a host array of any integer dtype is a map of counts: handed on as int64 (the library's bins); everything else as it is"""
+    if isinstance(grid, tuple):
+        return grid
+    arr = np.asarray(grid)
+    if arr.dtype.kind in "iu" and arr.dtype != np.int64:
+        if arr.dtype == np.uint64 and arr.size and arr.max() >= 2**63:
+            raise ValueError("a bin does not fit int64")
+        arr = arr.astype(np.int64)
+    return arr
+
+
+def _is_bins(grid, counter):
+    if isinstance(grid, tuple):
+        return np.dtype(grid[2] if len(grid) > 2 else (np.int64 if counter is not None else np.float64)) == np.int64
+    return np.asarray(grid).dtype.kind in "iu"
+
+
+def _density_values(grid, counter, device=0, stream=None):
+    """-> (flat FP64 values in Julia's order, dims).  A map in device memory comes back through ``ceg_grid_smooth`` with the one tap
+    1.0 per axis: ``fma(1.0, x, 0.0)`` is ``x``, and int64 bins arrive scaled as every other stage sees them."""
+    grid = _as_density(grid)
+    bins = _is_bins(grid, counter)
+    if bins and counter is None:
+        raise ValueError("integer bins need their counter")
+    scale = 1.0 / float(counter) if bins else 1.0
+    if isinstance(grid, tuple):
+        dims = tuple(int(d) for d in grid[1])
+        one = np.ones(1)
+        src = (grid[0], dims, np.int64 if bins else np.float64)
+        return smooth_grid(src, (one, one, one), scale=scale, device=device, stream=stream).ravel(order="F"), dims
+    flat = grid.ravel(order="F")
+    if bins:
+        if flat.size and np.abs(flat).max() >= 2**53:
+            raise ValueError("a bin with |value| >= 2^53")
+        return flat.astype(np.float64) * scale, tuple(grid.shape)
+    return np.ascontiguousarray(flat, dtype=np.float64), tuple(grid.shape)
+
+
+def _device_mask(grid, counter, values, dims, device):
+    """what ``site_nearest`` takes as ``bins`` for this map, made once per pipeline call: the bins themselves where they already lie in
+    device memory, else one uploaded int64 mask of the non-zero voxels.  -> (bins argument, keepalive)"""
+    if isinstance(grid, tuple) and _is_bins(grid, counter):
+        return (grid[0], dims), None
+    import torch
+    dev = torch.device("cuda", device)
+    t = torch.from_numpy((values != 0).astype(np.int64)).to(dev)
+    torch.cuda.synchronize(dev)
+    return (t.data_ptr(), dims), t
+
+
+def gaussian_taps(sigma):
+    """The taps of one axis: ``[1.0]`` for ``sigma == 0``, else ``w = 2*ceil(sigma)`` and ``g[x] = exp(-x^2/(2 sigma^2))`` for
+    ``x = -w..w`` divided by their sum.  This definition is this package's (what ImageFiltering's ``KernelFactors.gaussian`` computes
+    as far as its documentation goes; the package was not at hand to compare)."""
+    sigma = float(sigma)
+    if not (sigma >= 0 and math.isfinite(sigma)):
+        raise ValueError("sigma must be a finite number >= 0")
+    if sigma == 0:
+        return np.ones(1)
+    w = 2 * int(math.ceil(sigma))
+    x = np.arange(-w, w + 1, dtype=np.float64)
+    g = np.exp(-(x * x) / (2.0 * sigma * sigma))
+    return g / g.sum()
+
+
+def smoothing_sigmas(dims, mat, smooth=None):
+    """:667-668: ``sigma_c = smooth * dims[c] / |column c of mat|``; ``smooth=None`` is the voxel diagonal ``|mat * (1 ./ dims)|``"""
+    m = np.asarray(mat, dtype=np.float64).reshape(3, 3)
+    d = np.asarray(dims, dtype=np.float64)
+    if smooth is None:
+        smooth = float(np.linalg.norm(m @ (1.0 / d)))
+    return tuple(float(smooth) * d[c] / float(np.linalg.norm(m[:, c])) for c in range(3))
+
+
+def _taps_arg(taps):
+    if len(taps) != 3:
+        raise ValueError("three tap arrays, one per axis")
+    return [np.ascontiguousarray(t, dtype=np.float64).ravel() for t in taps]
+
+
+def smooth_grid(grid, taps, *, scale=1.0, device=0, stream=None, out_ptr=None):
+    """``ceg_grid_smooth``: the circular separable filter of ``grid`` (FP64, or int64 bins times ``scale``) with ``taps = (t0, t1, t2)``,
+    one odd-length array per axis (``gaussian_taps``).  ``y[p] = sum_t taps[t + w] * x[(p + t) mod n]`` with ``t`` ascending and one fma per
+    tap, along axis 0, then 1, then 2.  -> the FP64 array, or ``None`` with ``out_ptr`` (a device address that receives it)."""
+    lib = _abi.load_library()
+    ptr, on_dev, dims, dt, keep = _grid_arg(_as_density(grid), (np.float64, np.int64))
+    t0, t1, t2 = _taps_arg(taps)
+    out = None if out_ptr is not None else np.empty(dims[0] * dims[1] * dims[2], dtype=np.float64)
+    _abi.check(lib, lib.ceg_grid_smooth(device, ptr, int(dt == np.int64), on_dev, float(scale), _abi.i32ptr(_dims_arg(dims)), _abi.dptr(t0),
+                                        len(t0), _abi.dptr(t1), len(t1), _abi.dptr(t2), len(t2),
+                                        C.c_void_p(int(out_ptr) if out_ptr is not None else out.ctypes.data), int(out_ptr is not None),
+                                        _stream(stream)))
+    return None if out is None else out.reshape(dims, order="F")
+
+
+def smooth_grid_host(grid, taps, *, scale=1.0, dtype=np.float64):
+    """The same three passes in NumPy, in ``dtype`` (``np.longdouble`` for a reference).  A multiplication and an addition per tap where
+    the device has one fma: the two agree to within the bound of the rounding analysis, not to the bit."""
+    g = np.asarray(grid)
+    x = g.astype(np.float64) * np.float64(scale) if g.dtype.kind in "iu" else g.astype(np.float64)
+    x = x.astype(dtype)
+    for axis, t in enumerate(_taps_arg(taps)):
+        w = len(t) // 2
+        acc = np.zeros_like(x)
+        for q in range(len(t)):
+            acc = acc + t[q].astype(dtype) * np.roll(x, -(q - w), axis=axis)
+        x = acc
+    return x
+
+
+def ranked_above(grid, crop, *, device=0, stream=None, capacity=None):
+    """``ceg_grid_ranked``: ``(lin, values)`` -- the 0-based linear indices (``i + a*(j + b*k)``) of the voxels with a value ``> crop``,
+    by decreasing value, equal values by ascending index (``sortperm(vec(grid), rev=true)`` cut at ``<= crop``), and those values.
+    A NaN is dropped (the reference would visit it first); ``crop >= 0``."""
+    lib = _abi.load_library()
+    ptr, on_dev, dims, _, keep = _grid_arg(grid, (np.float64,))
+    n = dims[0] * dims[1] * dims[2]
+    cap = n if capacity is None else max(int(capacity), 0)
+    count = C.c_int64(0)
+    while True:
+        idx, val = np.empty(max(cap, 1), dtype=np.int32), np.empty(max(cap, 1), dtype=np.float64)
+        _abi.check(lib, lib.ceg_grid_ranked(device, ptr, on_dev, _abi.i32ptr(_dims_arg(dims)), float(crop), C.c_void_p(idx.ctypes.data),
+                                            C.c_void_p(val.ctypes.data), 0, cap, C.byref(count), _stream(stream)))
+        if count.value <= cap:
+            break
+        cap = int(count.value)
+    return idx[:count.value].copy(), val[:count.value].copy()
+
+
+def ranked_above_host(grid, crop):
+    if not crop >= 0:
+        raise ValueError("crop must be a number >= 0")
+    flat = np.asarray(grid, dtype=np.float64).ravel(order="F")
+    with np.errstate(invalid="ignore"):
+        sel = np.flatnonzero(flat > crop)
+    order = sel[np.argsort(-flat[sel], kind="stable")]
+    return order.astype(np.int32), flat[order]
+
+
+def _sites_arg(sites):
+    s = np.ascontiguousarray(np.asarray(sites, dtype=np.float64).reshape(-1, 3))
+    if not len(s):
+        raise ValueError("at least one site")
+    if not np.all(np.abs(s) <= 64.0):
+        raise ValueError("fractional site coordinates must be finite with |x| <= 64")
+    return s
+
+
+def site_nearest(sites, dims, mat, *, bins=None, origin=0, device=0, stream=None, capacity=None, want_dist=True):
+    """``ceg_grid_site_nearest``: for every active voxel (``bins != 0``; every voxel without ``bins``) the site at the smallest
+    ``periodic_distance_with_ofs!`` of ``site - (w + origin) ./ dims``, the lowest index among equals, at any distance (phase 2 of
+    ``closest_to_sites``).  ``bins``: an int64 grid, host array or ``(device_ptr, dims)``.  -> ``(lin, site, offset, dist)`` in
+    linear-index order: int32 0-based linear indices, int32 0-based sites, int8 (n, 3) cell offsets, FP64 distances (``None``
+    without ``want_dist``)."""
+    lib = _abi.load_library()
+    dims = tuple(int(d) for d in dims)
+    m, mcol = _mat_arg(mat)
+    ortho, safemin = _periodic_setup(m)
+    s = _sites_arg(sites)
+    n = dims[0] * dims[1] * dims[2]
+    if bins is None:
+        bptr, b_dev, keep = C.c_void_p(0), 0, None
+    else:
+        bptr, b_dev, bdims, _, keep = _grid_arg(bins, (np.int64,))
+        if tuple(bdims) != dims:
+            raise ValueError("bins and dims differ")
+    cap = n if capacity is None else max(int(capacity), 0)
+    count = C.c_int64(0)
+    while True:
+        k = max(cap, 1)
+        lin, site, off = np.empty(k, dtype=np.int32), np.empty(k, dtype=np.int32), np.empty((k, 3), dtype=np.int8)
+        dist = np.empty(k, dtype=np.float64) if want_dist else None
+        _abi.check(lib, lib.ceg_grid_site_nearest(device, _abi.i32ptr(_dims_arg(dims)), _abi.dptr(mcol), int(ortho), safemin, _abi.dptr(s.ravel()),
+                                                  len(s), int(origin), bptr, b_dev, C.c_void_p(lin.ctypes.data), C.c_void_p(site.ctypes.data),
+                                                  C.c_void_p(off.ctypes.data), C.c_void_p(dist.ctypes.data if want_dist else 0), 0, cap,
+                                                  C.byref(count), _stream(stream)))
+        if count.value <= cap:
+            break
+        cap = int(count.value)
+    k = int(count.value)
+    return lin[:k].copy(), site[:k].copy(), off[:k].copy(), (dist[:k].copy() if want_dist else None)
+
+
+def _pdwo_many(m, ortho, safemin, buf):
+    """``periodic_distance_with_ofs!`` (utils.jl:257-280) over the rows of ``buf`` (n, 3), vectorised, operation by operation
+    -> (d, ofs int64 (n, 3))"""
+    def norm(v):
+        x = m[0, 0] * v[:, 0] + m[0, 1] * v[:, 1] + m[0, 2] * v[:, 2]
+        y = m[1, 0] * v[:, 0] + m[1, 1] * v[:, 1] + m[1, 2] * v[:, 2]
+        z = m[2, 0] * v[:, 0] + m[2, 1] * v[:, 1] + m[2, 2] * v[:, 2]
+        return np.sqrt(x * x + y * y + z * z)
+
+    diff = buf + 0.5
+    fl = np.floor(diff)
+    ofs = fl.astype(np.int64)
+    v = diff - fl - 0.5
+    d = norm(v)
+    if ortho:
+        return d, ofs
+    ref = d.copy()
+    live = ~(ref <= safemin)                                  # rows still in the search
+    for q in range(3):
+        v[:, q] = v[:, q] + 1
+        nn = norm(v)
+        hit = live & (nn < ref)
+        d[hit], ofs[hit, q], live = nn[hit], ofs[hit, q] - 1, live & ~hit
+        v[:, q] = v[:, q] - 2
+        nn = norm(v)
+        hit = live & (nn < ref)
+        d[hit], ofs[hit, q], live = nn[hit], ofs[hit, q] + 1, live & ~hit
+        v[:, q] = v[:, q] + 1
+    return d, ofs
+
+
+def site_nearest_host(sites, dims, mat, *, bins=None, origin=0, want_dist=True):
+    """The same in NumPy, one site at a time over all the active voxels."""
+    dims = tuple(int(d) for d in dims)
+    if origin not in (0, 1):
+        raise ValueError("origin is 0 or 1")
+    m, _ = _mat_arg(mat)
+    ortho, safemin = _periodic_setup(m)
+    s = _sites_arg(sites)
+    a, b, c = dims
+    if bins is None:
+        lin = np.arange(a * b * c, dtype=np.int64)
+    else:
+        lin = np.flatnonzero(np.asarray(bins).ravel(order="F") != 0)
+    w = np.stack([lin % a, (lin // a) % b, lin // (a * b)], axis=1) + origin
+    frac = w.astype(np.float64) / np.asarray(dims, dtype=np.float64)
+    best = np.full(len(lin), np.inf)
+    site = np.zeros(len(lin), dtype=np.int32)
+    off = np.zeros((len(lin), 3), dtype=np.int8)
+    for idx, x in enumerate(s):
+        d, o = _pdwo_many(m, ortho, safemin, x[None, :] - frac)
+        better = d < best
+        best = np.where(better, d, best)
+        site[better] = idx
+        off[better] = o[better]
+    return lin.astype(np.int32), site, off, (best if want_dist else None)
+
+
+def _pdwo_one(m, ortho, safemin, buf):
+    """``periodic_distance_with_ofs!`` on one difference, plain floats -> (d, ofs list of float)"""
+    def norm(v):
+        x = m[0][0] * v[0] + m[0][1] * v[1] + m[0][2] * v[2]
+        y = m[1][0] * v[0] + m[1][1] * v[1] + m[1][2] * v[2]
+        z = m[2][0] * v[0] + m[2][1] * v[1] + m[2][2] * v[2]
+        return math.sqrt(x * x + y * y + z * z)
+
+    v, ofs = [0.0, 0.0, 0.0], [0.0, 0.0, 0.0]
+    for q in range(3):
+        diff = buf[q] + 0.5
+        ofs[q] = float(math.floor(diff))
+        v[q] = diff - ofs[q] - 0.5
+    ref = norm(v)
+    if ortho or ref <= safemin:
+        return ref, ofs
+    for q in range(3):
+        v[q] += 1
+        nn = norm(v)
+        if nn < ref:
+            ofs[q] -= 1
+            return nn, ofs
+        v[q] -= 2
+        nn = norm(v)
+        if nn < ref:
+            ofs[q] += 1
+            return nn, ofs
+        v[q] += 1
+    return ref, ofs
+
+
+def coalesce_ranked(lin, smoothed, values, dims, mat, maxdist, atol=0.1, maxbasins=math.inf):
+    """``ceg_coalesce_ranked``: the greedy pass of ``coalescing_basins`` (:677-719) over a ranking already cut at the crop, in the
+    library (host code, no device).  ``lin`` / ``smoothed``: what ``ranked_above`` returns; ``values``: the unsmoothed map at ``lin``.
+    -> list of ``(value, centre)``, ``centre`` a length-3 array."""
+    lib = _abi.load_library()
+    lin = np.ascontiguousarray(lin, dtype=np.int32)
+    sm = np.ascontiguousarray(smoothed, dtype=np.float64)
+    va = np.ascontiguousarray(values, dtype=np.float64)
+    if not (len(lin) == len(sm) == len(va)):
+        raise ValueError("lin, smoothed and values differ in length")
+    m, mcol = _mat_arg(mat)
+    ortho, safemin = _periodic_setup(m)
+    cap, count = max(len(lin), 1), C.c_int64(0)
+    val, cen = np.empty(cap, dtype=np.float64), np.empty((cap, 3), dtype=np.float64)
+    _abi.check(lib, lib.ceg_coalesce_ranked(_abi.i32ptr(lin), _abi.dptr(sm), _abi.dptr(va), len(lin), _abi.i32ptr(_dims_arg(dims)),
+                                            _abi.dptr(mcol), int(ortho), safemin, float(maxdist), float(atol), float(maxbasins),
+                                            _abi.dptr(val), _abi.dptr(cen.ravel()), cap, C.byref(count)))
+    return [(float(val[q]), cen[q].copy()) for q in range(int(count.value))]
+
+
+def coalesce_ranked_host(lin, smoothed, values, dims, mat, maxdist, atol=0.1, maxbasins=math.inf):
+    """The same loop in plain Python floats: the same IEEE operations in the same order, so the same bits."""
+    m, _ = _mat_arg(mat)
+    ortho, safemin = _periodic_setup(m)
+    ml = m.tolist()
+    a, b, c = (int(d) for d in dims)
+    ret = []
+    for x, smval, val in zip(np.asarray(lin).tolist(), np.asarray(smoothed, dtype=np.float64).tolist(),
+                             np.asarray(values, dtype=np.float64).tolist()):
+        i, j, k = x % a + 1, (x // a) % b + 1, x // (a * b) + 1
+        pos = [i / a, j / b, k / c]
+        in_distance = []
+        for idx, (_, center) in enumerate(ret):
+            d, ofs = _pdwo_one(ml, ortho, safemin, [pos[q] - center[q] for q in range(3)])
+            if d > maxdist:
+                continue
+            in_distance.append((idx, ofs, d))
+        if not in_distance and smval >= atol:
+            ret.append((val, pos))
+            if len(ret) >= maxbasins:
+                break
+            continue
+        if len(in_distance) > 1:
+            in_distance.sort(key=lambda e: (math.isnan(e[2]), e[2]))
+            submid = 1 if val < atol else next((q + 1 for q, e in enumerate(in_distance) if e[2] < maxdist / 2), 1)
+            del in_distance[submid:]
+        newcenter = [pos[q] * val for q in range(3)]
+        newval = val
+        for j2, o2, _ in in_distance:
+            val2, center2 = ret[j2]
+            for q in range(3):
+                newcenter[q] += (center2[q] + o2[q]) * val2
+            newval += val2
+        if newval == 0:
+            continue
+        newcenter = [x / newval for x in newcenter]
+        if len(in_distance) == 1:
+            ret[in_distance[0][0]] = (newval, newcenter)
+        else:
+            for j2 in sorted((e[0] for e in in_distance), reverse=True):
+                del ret[j2]
+            ret.append((newval, newcenter))
+    return [(float(v), np.asarray(p, dtype=np.float64)) for v, p in ret]
+
+
+def cluster_closer_than(ret, mat, maxdist):
+    """``cluster_closer_than!`` (:613-642) on a list of ``(rho, pos)``: a later entry within ``maxdist`` of an earlier one is merged into
+    it (value-weighted centre, the offset applied) unless the two together exceed 1.  -> the new list.  Host arithmetic only."""
+    m, _ = _mat_arg(mat)
+    ortho, safemin = _periodic_setup(m)
+    ml = m.tolist()
+    ret = [(float(r), [float(x) for x in p]) for r, p in ret]
+    n = len(ret)
+    todelete = [False] * n
+    for i1 in range(n):
+        if todelete[i1]:
+            continue
+        rho1, pos1 = ret[i1]
+        for i2 in range(i1 + 1, n):
+            if todelete[i2]:
+                continue
+            rho2, pos2 = ret[i2]
+            rho = rho1 + rho2
+            if rho > 1:
+                continue
+            d, ofs = _pdwo_one(ml, ortho, safemin, [pos1[q] - pos2[q] for q in range(3)])
+            if d >= maxdist:
+                continue
+            todelete[i2] = True
+            pos1 = [(rho1 * pos1[q] + rho2 * (pos2[q] + ofs[q])) / rho for q in range(3)]
+            rho1 = rho
+            ret[i1] = (rho1, pos1)
+    return [(r, np.asarray(p, dtype=np.float64)) for (r, p), dead in zip(ret, todelete) if not dead]
+
+
+cluster_closer_than_host = cluster_closer_than
+
+
+def _accumulate_closest(values, dims, nsites, lin, site, off, deleted) -> ClosestSites:
+    """stage 3 of ``closest_to_sites``: the voxels in linear-index order, each added to its nearest site unless that takes the site's
+    sum above 1 (:425-434), and the centres of ``updated_sites_with_closest`` (:454): ``sum(((ijk + ofs.*dims) ./ dims) .* w) / s`` on
+    0-based ``ijk``"""
+    a, b, c = dims
+    sums = [0.0] * nsites
+    acc = [[0.0, 0.0, 0.0] for _ in range(nsites)]
+    cap_bound = False
+    vals = values[lin].tolist()
+    for x, s, o, rho in zip(np.asarray(lin).tolist(), np.asarray(site).tolist(), np.asarray(off).tolist(), vals):
+        if sums[s] + rho > 1:
+            cap_bound = True
+            continue
+        sums[s] = sums[s] + rho
+        w = (x % a, (x // a) % b, x // (a * b))
+        for q in range(3):
+            acc[s][q] += (w[q] + o[q] * dims[q]) / dims[q] * rho
+    with np.errstate(invalid="ignore", divide="ignore"):
+        centres = np.asarray(acc, dtype=np.float64).reshape(nsites, 3) / np.asarray(sums, dtype=np.float64)[:, None]
+    return ClosestSites(np.asarray(sums, dtype=np.float64), centres, np.asarray(deleted, dtype=np.int64), cap_bound)
+
+
+def _closest_to_sites(grid, sites, mat, counter, on_device, device=0, stream=None, prepared=None) -> ClosestSites:
+    """``prepared = (values, dims, mask)``: the map's values and the ``bins`` argument of ``site_nearest``, where a caller that runs
+    several rounds on one map has them already"""
+    if prepared is None:
+        values, dims = _density_values(grid, counter, device, stream)
+        if not on_device:
+            mask = None
+        elif isinstance(grid, tuple) and _is_bins(grid, counter):
+            mask = (grid[0], dims)                                               # the bins as they lie in device memory
+        else:
+            mask = (values != 0).astype(np.int64).reshape(dims, order="F")       # one call: uploaded by the library
+    else:
+        values, dims, mask = prepared
+    kept, deleted = snap_sites(sites, dims)
+    if on_device:
+        lin, site, off, _ = site_nearest(kept, dims, mat, bins=mask, origin=0, device=device, stream=stream, want_dist=False)
+    else:
+        lin, site, off, _ = site_nearest_host(kept, dims, mat, bins=(values != 0).reshape(dims, order="F"), origin=0, want_dist=False)
+    return _accumulate_closest(values, dims, len(kept), lin, site, off, deleted)
+
+
+def closest_to_sites(grid, sites, mat, *, counter=None, device=0, stream=None) -> ClosestSites:
+    """The partition of the non-zero voxels of a density map among ``sites`` (fractional, (n, 3)), device-backed: the sites are
+    snapped and deduplicated (``snap_sites``), every non-zero voxel gets its nearest kept site from ``ceg_grid_site_nearest`` with
+    ``origin = 0``, and the host adds the voxels up in linear-index order under the reference's cap (a voxel that would take its
+    site's sum above 1 is skipped, :430).  ``grid``: an FP64 map, or int64 bins with ``counter``; host array or ``(device_ptr, dims[,
+    dtype])``.
+
+    Where this differs from ``closest_to_sites`` of the reference as written (:324-437): the reference first gives each site the
+    voxels inside half its nearest-site distance, in breadth-first order, and breaks off when the running sum passes 1 (:347-382);
+    and it measures the phase-2 distances one voxel off (``Tuple(tovisit) ./ dims`` on 1-based indices, ``origin = 1``).  The two
+    agree whenever the cap does not bind, except at voxels whose two nearest sites differ in distance by at most
+    ``2*|mat*(1 ./ dims)|``."""
+    return _closest_to_sites(grid, sites, mat, counter, True, device, stream)
+
+
+def closest_to_sites_host(grid, sites, mat, *, counter=None) -> ClosestSites:
+    return _closest_to_sites(grid, sites, mat, counter, False)
+
+
+def updated_sites_with_closest(closest: ClosestSites):
+    """``updated_sites_with_closest`` (:447-456) -> list of ``(sum, centre)``; an empty site raises like the reference's ``error``"""
+    if np.any(closest.sums == 0):
+        raise ValueError("Encountered empty weight: please use a non-zero atol value.")
+    return [(float(s), c.copy()) for s, c in zip(closest.sums, closest.centres)]
+
+
+updated_sites_with_closest_host = updated_sites_with_closest
+
+
+def _coalescing_basins(grid, maxdist, mat, counter, smooth, atol, crop, maxbasins, on_device, device=0, stream=None):
+    """-> (the list of ``(value, centre)``, the sum of the map).  The map is read back once; the refinement rounds share one mask in
+    device memory (the bins themselves where they are device-resident)."""
+    grid = _as_density(grid)
+    values, dims = _density_values(grid, counter, device, stream)
+    total = float(values.sum())
+    n = values.size
+    vgrid = values.reshape(dims, order="F")
+    _crop = atol * float(values.max()) / 100 if crop is None else float(crop)                  # :676
+    taps = None if smooth == 0 else [gaussian_taps(s) for s in smoothing_sigmas(dims, mat, smooth)]
+    mask = keep = None
+    if on_device:
+        if taps is None:
+            lin, smval = ranked_above(vgrid, _crop, device=device, stream=stream)
+        else:
+            import torch
+            dev = torch.device("cuda", device)
+            tmp = torch.empty(n, dtype=torch.float64, device=dev)
+            torch.cuda.synchronize(dev)
+            bins = _is_bins(grid, counter)
+            smooth_grid(grid, taps, scale=(1.0 / float(counter)) if bins else 1.0, device=device, stream=stream, out_ptr=tmp.data_ptr())
+            lin, smval = ranked_above((tmp.data_ptr(), dims), _crop, device=device, stream=stream)
+            del tmp
+        ret = coalesce_ranked(lin, smval, values[lin], dims, mat, maxdist, atol, maxbasins)
+        if ret:
+            mask, keep = _device_mask(grid, counter, values, dims, device)
+    else:
+        smoothed = vgrid if taps is None else smooth_grid_host(vgrid, taps)
+        lin, smval = ranked_above_host(smoothed, _crop)
+        ret = coalesce_ranked_host(lin, smval, values[lin], dims, mat, maxdist, atol, maxbasins)
+    n1 = -1
+    while len(ret) != n1:                                                                      # :720-729
+        n1 = len(ret)
+        if not ret:
+            break
+        pts = np.asarray([p for _, p in ret], dtype=np.float64).reshape(-1, 3)
+        closest = _closest_to_sites(None, pts, mat, None, on_device, device, stream, prepared=(values, dims, mask))
+        ret = updated_sites_with_closest(closest)
+        ret = cluster_closer_than(ret, mat, maxdist)
+        newret = [e for e in ret if e[0] >= atol]
+        if not newret:
+            break
+        ret = newret
+    del keep
+    return ret, total
+
+
+def coalescing_basins(grid, maxdist, mat, *, counter=None, smooth=None, atol=0.1, crop=None, maxbasins=math.inf, device=0, stream=None):
+    """``coalescing_basins(grid, maxdist, mat; smooth, atol, crop, maxbasins)`` (:661-731) -> list of ``(value, centre)``.  Smoothing
+    (``smooth=None``: the voxel diagonal; 0: none), ranking and the nearest-site partition of every refinement round run on the
+    device; the greedy pass runs in the library on the host; the cap, the centres and ``cluster_closer_than`` in Python.  ``grid``: an
+    FP64 map or int64 bins with ``counter``, host array or ``(device_ptr, dims[, dtype])``.  ``closest_to_sites`` is this package's
+    (see its docstring for where it departs from the reference as written)."""
+    return _coalescing_basins(grid, maxdist, mat, counter, smooth, atol, crop, maxbasins, True, device, stream)[0]
+
+
+def coalescing_basins_host(grid, maxdist, mat, *, counter=None, smooth=None, atol=0.1, crop=None, maxbasins=math.inf):
+    """The same composition from the ``*_host`` forms; never touches the library."""
+    return _coalescing_basins(grid, maxdist, mat, counter, smooth, atol, crop, maxbasins, False)[0]
+
+
+def _average_clusters(ret, total, rtol, ntol):
+    ret = sorted(ret, key=lambda e: (e[0], *e[1]), reverse=True)                               # sort!(ret; rev=true), :282
+    if rtol == 1:
+        return ret
+    max_total = rtol * total
+    run = 0.0
+    for i, (p, _) in enumerate(ret, start=1):                                                  # :286-292
+        run += p
+        if run >= max_total or i + 1 > ntol:
+            return ret[:i]
+    return ret
+
+
+def average_clusters(grid, dist, mat, *, counter=None, smooth=None, crop=None, atol=0.0, rtol=1, ntol=math.inf, device=0, stream=None):
+    """``average_clusters(bins, dist, mat; smooth, crop, atol, rtol, ntol)`` (averageclusters.jl:280-294): ``coalescing_basins`` with
+    ``maxbasins = 2*ntol``, sorted by decreasing probability, cut by ``rtol`` and ``ntol``."""
+    ret, total = _coalescing_basins(grid, dist, mat, counter, smooth, atol, crop, 2 * ntol, True, device, stream)
+    return _average_clusters(ret, total, rtol, ntol)
+
+
+def average_clusters_host(grid, dist, mat, *, counter=None, smooth=None, crop=None, atol=0.0, rtol=1, ntol=math.inf):
+    ret, total = _coalescing_basins(grid, dist, mat, counter, smooth, atol, crop, 2 * ntol, False)
+    return _average_clusters(ret, total, rtol, ntol)

@@ -1900,4 +1900,103 @@ function decompose_basins(grid::Array{Float64,3}, basinsets::Vector{Set{NTuple{3
 end
 decompose_basins(grid::Array{Float64,3}, tolerance::Float64=-Inf; kwargs...) = decompose_basins(grid, local_basins(grid, tolerance; kwargs...))
 
+# ---- from a density map to the sites: ceg_grid_smooth / ceg_grid_ranked / ceg_grid_site_nearest / ceg_coalesce_ranked ----------
+"""
+    gaussian_taps(sigma) -> Vector{Float64}
+
+The taps of one axis as `ceg_hip.basins.gaussian_taps` defines them: `[1.0]` for `sigma == 0`, else `w = 2ceil(sigma)`,
+`exp(-x^2/(2sigma^2))` for `x = -w:w`, divided by their sum.  The definition is this package's.
+"""
+function gaussian_taps(sigma::Real)
+    sigma == 0 && return [1.0]
+    w = 2 * ceil(Int, sigma)
+    g = [exp(-(x * x) / (2.0 * sigma * sigma)) for x in -w:w]
+    g ./ sum(g)
+end
+
+"""
+    smooth_grid(grid::Array{<:Union{Float64,Int64},3}, taps::NTuple{3,Vector{Float64}}; scale=1.0, device=0) -> Array{Float64,3}
+
+`imfilter(grid, kernel, "circular")` (src/basins.jl:668) with the separable kernel given as three tap vectors of odd length (at most
+129), on the device: `y[p] = sum_t taps[t+w] * x[mod(p+t, n)]`, `t` ascending, one fma per tap, along axis 1, 2, then 3.  Int64 bins are
+multiplied by `scale` first (`1/counter`).
+"""
+function smooth_grid(grid::Array{T,3}, taps::NTuple{3,Vector{Float64}}; scale::Float64=1.0, device=0) where {T<:Union{Int64,Float64}}
+    d = _dims32(size(grid))
+    out = Array{Float64,3}(undef, size(grid))
+    t1, t2, t3 = taps
+    GC.@preserve grid d t1 t2 t3 out _check(ccall((:ceg_grid_smooth, LIB[]), Cint,
+        (Int32, Ptr{Cvoid}, Int32, Int32, Float64, Ptr{Int32}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Cvoid}),
+        device, grid, T === Int64 ? 1 : 0, 0, scale, d, t1, length(t1), t2, length(t2), t3, length(t3), out, 0, C_NULL))
+    out
+end
+
+"""
+    ranked_above(grid::Array{Float64,3}, crop; device=0) -> (idx::Vector{Int}, values::Vector{Float64})
+
+`sortperm(vec(grid), rev=true)` cut where the value is `<= crop` (src/basins.jl:670, 679): 1-based linear indices by decreasing value,
+equal values by increasing index.  A NaN is dropped; `crop >= 0`.
+"""
+function ranked_above(grid::Array{Float64,3}, crop::Real; device=0)
+    d = _dims32(size(grid))
+    cap = length(grid)
+    idx = Vector{Int32}(undef, max(cap, 1)); val = Vector{Float64}(undef, max(cap, 1))
+    count = Int64[0]
+    GC.@preserve grid d idx val count _check(ccall((:ceg_grid_ranked, LIB[]), Cint,
+        (Int32, Ptr{Float64}, Int32, Ptr{Int32}, Float64, Ptr{Int32}, Ptr{Float64}, Int32, Int64, Ptr{Int64}, Ptr{Cvoid}),
+        device, grid, 0, d, Float64(crop), idx, val, 0, cap, count, C_NULL))
+    n = Int(count[1])
+    Int.(idx[1:n]) .+ 1, val[1:n]
+end
+
+"""
+    site_nearest(sites, dims, mat; bins=nothing, origin=1, device=0) -> (points, site, ofs, dist)
+
+Phase 2 of `closest_to_sites` (src/basins.jl:400-422) for every voxel with a non-zero bin (every voxel without `bins`): the site at
+the smallest `periodic_distance_with_ofs!` of `site .- (ijk .- 1 .+ origin) ./ dims`, the lowest index among equals, and its cell
+offset.  `origin = 1` is the reference as written, `origin = 0` the convention of `site_proximity_map!`.  `points`: 1-based linear
+indices in increasing order; `site`: 1-based.
+"""
+function site_nearest(sites::AbstractVector, dims::NTuple{3,Int}, mat::AbstractMatrix; bins::Union{Nothing,Array{Int64,3}}=nothing,
+                      origin::Integer=1, device=0)
+    m = Vector{Float64}(vec(Matrix{Float64}(mat)))
+    _, ortho, safemin = CEG.prepare_periodic_distance_computations(mat)
+    flat = [Float64(x) for s in sites for x in s]
+    d = _dims32(dims)
+    cap = prod(dims)
+    lin = Vector{Int32}(undef, cap); site = Vector{Int32}(undef, cap); ofs = Matrix{Int8}(undef, 3, cap); dist = Vector{Float64}(undef, cap)
+    count = Int64[0]
+    bptr = bins === nothing ? Ptr{Int64}(C_NULL) : pointer(bins)
+    GC.@preserve bins d m flat lin site ofs dist count _check(ccall((:ceg_grid_site_nearest, LIB[]), Cint,
+        (Int32, Ptr{Int32}, Ptr{Float64}, Int32, Float64, Ptr{Float64}, Int32, Int32, Ptr{Int64}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Cvoid},
+         Ptr{Float64}, Int32, Int64, Ptr{Int64}, Ptr{Cvoid}),
+        device, d, m, ortho ? 1 : 0, Float64(ustrip(safemin)), flat, length(flat) ÷ 3, origin, bptr, 0, lin, site, ofs, dist, 0, cap, count, C_NULL))
+    n = Int(count[1])
+    Int.(lin[1:n]) .+ 1, Int.(site[1:n]) .+ 1, [SVector{3,Int}(ofs[1, q], ofs[2, q], ofs[3, q]) for q in 1:n], dist[1:n]
+end
+
+"""
+    coalesce_ranked(idx, smoothed, values, dims, mat, maxdist; atol=0.1, maxbasins=Inf) -> Vector{Tuple{Float64,SVector{3,Float64}}}
+
+The greedy pass of `coalescing_basins` (src/basins.jl:677-719) in the library's host code: `idx` the 1-based ranking of `ranked_above`,
+`smoothed` and `values` the smoothed and the unsmoothed grid at those indices.  The same IEEE operations in the same order as the
+reference's loop.
+"""
+function coalesce_ranked(idx::Vector{Int}, smoothed::Vector{Float64}, values::Vector{Float64}, dims::NTuple{3,Int}, mat::AbstractMatrix,
+                         maxdist::Real; atol::Real=0.1, maxbasins::Real=Inf)
+    m = Vector{Float64}(vec(Matrix{Float64}(mat)))
+    _, ortho, safemin = CEG.prepare_periodic_distance_computations(mat)
+    lin = Int32.(idx .- 1)
+    d = _dims32(dims)
+    cap = max(length(lin), 1)
+    val = Vector{Float64}(undef, cap); cen = Matrix{Float64}(undef, 3, cap)
+    count = Int64[0]
+    GC.@preserve lin smoothed values d m val cen count _check(ccall((:ceg_coalesce_ranked, LIB[]), Cint,
+        (Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Float64}, Int32, Float64, Float64, Float64, Float64, Ptr{Float64},
+         Ptr{Float64}, Int64, Ptr{Int64}),
+        lin, smoothed, values, length(lin), d, m, ortho ? 1 : 0, Float64(ustrip(safemin)), Float64(maxdist), Float64(atol), Float64(maxbasins),
+        val, cen, cap, count))
+    [(val[q], SVector{3,Float64}(cen[1, q], cen[2, q], cen[3, q])) for q in 1:Int(count[1])]
+end
+
 end # module

@@ -1668,6 +1668,69 @@ CEG_API int ceg_grid_basins(int32_t device, const double* grid, int32_t grid_on_
                             int32_t* level_out, int32_t* owner_out, uint8_t* nowners_out, int32_t maps_on_device, int32_t* shared_out,
                             int64_t shared_capacity, int64_t* shared_count_out, int32_t* size_out, int32_t lists_on_device, void* stream);
 
+/* ---- from a density map to the sites: smoothing, ranking, nearest-site partition (src/basins.jl:324-456, 613-731) -------------- */
+/*
+ * The device stages of coalescing_basins / average_clusters, and the greedy pass between them as a host function.  The conventions
+ * of the grid-analysis section hold: Julia's memory order, a*b*c within int32, *_on_device flags, a full count when a capacity is
+ * short (no error), nothing launched on an argument that can be refused from the host, no float atomics.  All three device entry
+ * points synchronise `stream` before they return (taps, sites and counts cross the host).
+ *
+ * ceg_grid_smooth: imfilter(grid, Kernel.gaussian(sigma), "circular"), basins.jl:668, with the taps as an argument.
+ *  grid        [a*b*c], host or device: FP64 (grid_is_int64 = 0; `scale` is ignored, x = value), or the int64 bins of the MC sampler
+ *              (grid_is_int64 = 1): x = fl(scale * value), the first rounding; scale must be finite.  A bin with |value| >= 2^53
+ *              -> CEG_ERR_INVALID (found by the first pass: the output is then not to be used).
+ *  tapsC, lenC host arrays, lenC = 2 wC + 1 odd, 1 <= lenC <= 129; an even or non-positive length is CEG_ERR_INVALID, a longer one
+ *              CEG_ERR_UNSUPPORTED with the figure in ceg_last_error().  What a Gaussian is is the caller's business.
+ *  out         [a*b*c] FP64, host or device; not `grid` itself.
+ *  Definition: three passes, along axis 0, then 1, then 2; y[p] = sum over t = -w .. w of taps[t + w] * x[(p + t) mod n] along the axis,
+ *  t ascending, the accumulator starting at 0.0 and updated by fma(tap, x, acc); mod is the true modulus, so an axis shorter than w
+ *  (or of length 1) wraps as often as needed.  Every element is that one sequence of operations whatever tile it falls in.
+ *
+ * ceg_grid_ranked: sortperm(vec(smoothed), rev=true) cut at `smval <= crop`, basins.jl:670, 679.
+ *  Every linear index whose value is > crop, by value descending, equal values by ascending index (Julia's sortperm is stable and
+ *  rev=true keeps the order of ties).  A NaN is not above anything and is dropped; the reference would visit it first.  crop >= 0 is
+ *  required (CEG_ERR_INVALID otherwise, also for a NaN): it keeps -0.0 out of the keys.
+ *  idx_out     [min(count, capacity)] int32;  val_out  optional, the values in the same order; both host or both device.
+ *  count_out   the full count (host).
+ *
+ * ceg_grid_site_nearest: phase 2 of closest_to_sites, basins.jl:400-422, for every ACTIVE point and at any distance.
+ *  For a point w = (i, j, k), 0-based, and a site s: buffer = site_s - (w + origin) ./ dims (an FP64 division, then a subtraction,
+ *  per component), then periodic_distance_with_ofs! (utils.jl:257-280) as written: diff = buffer + 0.5, ofs = floor(diff), buffer =
+ *  diff - ofs - 0.5; ref = sqrt(x*x + y*y + z*z) of mat*buffer (rows summed left to right, no contraction, correctly rounded square
+ *  root); ref is returned if ortho or ref <= safemin, otherwise the first-improvement search over +1 / -1 per axis runs in the
+ *  reference's order with its updates of ofs.  The point gets the site of smallest distance, the lowest index among equal ones
+ *  (findmin), and that site's ofs.
+ *  ortho, safemin   prepare_periodic_distance_computations(mat) (utils.jl:146-155), from the host as in the grid builds.
+ *  origin      1: the reference as written (`Tuple(tovisit) ./ dims` on 1-based indices);  0: the convention of site_proximity_map!
+ *              and updated_sites_with_closest.  Anything else is CEG_ERR_INVALID.
+ *  sites       [nsites][3] fractional, host memory, 1 <= nsites <= CEG_SITE_PROXIMITY_MAX_SITES, finite with |x| <= 64 (so an
+ *              offset fits int8).
+ *  bins        optional [a*b*c] int64, host or device: a point is active iff its bin != 0.  NULL: every point is active.
+ *  lin_out     [min(count, capacity)] int32, the active points in linear-index order;  site_out  int32, 0-based;  offset_out  [][3]
+ *              int8;  dist_out  optional FP64.  All host or all device (out_on_device).  count_out: the full count (host).
+ *
+ * ceg_coalesce_ranked: the greedy pass of coalescing_basins, basins.jl:677-719, on the host (no device work, no device needed).
+ *  lin, smoothed, values   [nranked]: the ranking of ceg_grid_ranked (already cut at the crop), the smoothed values and the
+ *              unsmoothed grid values at those indices.
+ *  maxbasins   the loop ends once that many basins exist; +Inf for no bound.
+ *  value_out   [min(count, capacity)], centre_out [..][3]: the reference's `ret` at the end of the loop.  count_out: the full count.
+ *  Plain IEEE FP64 in the reference's order with contraction off: pos = (i/a, j/b, k/c) on 1-based indices, the in-distance list
+ *  sorted stably by distance, the submid rule, (val, pos*val/val) appended for a voxel with nothing in range and smval < atol
+ *  unless val == 0, merged basins deleted in place and the new one pushed at the end.
+ */
+CEG_API int ceg_grid_smooth(int32_t device, const void* grid, int32_t grid_is_int64, int32_t grid_on_device, double scale,
+                            const int32_t dims[3], const double* taps0, int32_t len0, const double* taps1, int32_t len1,
+                            const double* taps2, int32_t len2, double* out, int32_t out_on_device, void* stream);
+CEG_API int ceg_grid_ranked(int32_t device, const double* grid, int32_t grid_on_device, const int32_t dims[3], double crop, int32_t* idx_out,
+                            double* val_out, int32_t out_on_device, int64_t capacity, int64_t* count_out, void* stream);
+CEG_API int ceg_grid_site_nearest(int32_t device, const int32_t dims[3], const double mat[9], int32_t ortho, double safemin,
+                                  const double* sites, int32_t nsites, int32_t origin, const int64_t* bins, int32_t bins_on_device,
+                                  int32_t* lin_out, int32_t* site_out, int8_t* offset_out, double* dist_out, int32_t out_on_device,
+                                  int64_t capacity, int64_t* count_out, void* stream);
+CEG_API int ceg_coalesce_ranked(const int32_t* lin, const double* smoothed, const double* values, int64_t nranked, const int32_t dims[3],
+                                const double mat[9], int32_t ortho, double safemin, double maxdist, double atol, double maxbasins,
+                                double* value_out, double* centre_out, int64_t capacity, int64_t* count_out);
+
 #ifdef __cplusplus
 }
 #endif
