@@ -380,6 +380,13 @@ PROTOTYPES = {
                                         C.c_void_p]),
     "ceg_coalesce_ranked": (C.c_int, [c_int32_p, c_double_p, c_double_p, C.c_int64, c_int32_p, c_double_p, C.c_int32, C.c_double, C.c_double,
                                       C.c_double, C.c_double, c_double_p, c_double_p, C.c_int64, c_int64_p]),
+    "ceg_grid_coalesce": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_double,
+                                    c_int32_p, c_double_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_void_p,
+                                    C.c_void_p, C.c_int32, C.c_int64, c_int64_p, C.c_void_p]),
+    "ceg_grid_site_partition": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_double, c_int32_p, c_double_p, C.c_int32, C.c_double,
+                                          c_double_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_int32_p, c_int64_p,
+                                          C.c_void_p]),
+    "ceg_cluster_closer_than": (C.c_int, [c_double_p, c_double_p, C.c_int64, c_double_p, C.c_int32, C.c_double, C.c_double, c_int64_p]),
 }
 BASINS_MAX_OWNERS = 16                           # CEG_BASINS_MAX_OWNERS
 COMPONENTS_NONZERO, COMPONENTS_BAND = 0, 1      # CEG_COMPONENTS_*

@@ -32,7 +32,7 @@ __all__ = ["local_minima", "grid_components", "local_components", "compute_level
            "Basins", "local_basins", "basin_points", "decompose_basins", "local_basins_host", "decompose_basins_host",
            "circular_distance",
            "ClosestSites", "gaussian_taps", "smoothing_sigmas", "smooth_grid", "ranked_above", "site_nearest", "coalesce_ranked",
-           "cluster_closer_than", "closest_to_sites", "updated_sites_with_closest", "coalescing_basins", "average_clusters",
+           "grid_coalesce", "site_partition", "SitePartition", "cluster_closer_than", "closest_to_sites", "updated_sites_with_closest", "coalescing_basins", "average_clusters",
            "smooth_grid_host", "ranked_above_host", "site_nearest_host", "coalesce_ranked_host", "cluster_closer_than_host",
            "closest_to_sites_host", "updated_sites_with_closest_host", "coalescing_basins_host", "average_clusters_host"]
 
@@ -660,7 +660,8 @@ def decompose_basins_host(grid, minima=None, tolerance=-math.inf, **kw):
 # ---------------------------------------------------------------------------------------------------------------- site extraction
 # From a density map to the list of sites: average_clusters (averageclusters.jl:280-294), coalescing_basins (basins.jl:661-731),
 # closest_to_sites (:324-437), updated_sites_with_closest (:447-456), cluster_closer_than! (:613-642), on top of ceg_grid_smooth /
-# ceg_grid_ranked / ceg_grid_site_nearest (device) and ceg_coalesce_ranked (host, in the library).
+# ceg_grid_ranked / ceg_grid_coalesce / ceg_grid_site_partition (device) and ceg_cluster_closer_than (host, in the library);
+# ceg_grid_site_nearest and ceg_coalesce_ranked are the stages on their own.
 #
 # A density map is an FP64 grid, or the sampler's int64 bins with the number of frames ``counter``: its values are then
 # ``bins * (1.0 / counter)`` -- one multiplication per voxel, the form the device applies; the reference's ``bins ./ counter`` can differ
@@ -725,16 +726,18 @@ def _density_values(grid, counter, device=0, stream=None):
     return np.ascontiguousarray(flat, dtype=np.float64), tuple(grid.shape)
 
 
-def _device_mask(grid, counter, values, dims, device):
-    """what ``site_nearest`` takes as ``bins`` for this map, made once per pipeline call: the bins themselves where they already lie in
-    device memory, else one uploaded int64 mask of the non-zero voxels.  -> (bins argument, keepalive)"""
-    if isinstance(grid, tuple) and _is_bins(grid, counter):
-        return (grid[0], dims), None
+def _device_map(grid, counter, values, dims, device):
+    """the map as the device stages of one pipeline call take it: where it already lies in device memory, else uploaded once (bins as
+    bins, an FP64 map as it is).  -> (grid argument, FP64 view in device memory or None, keepalive)"""
+    grid, bins, _ = _map_scale(grid, counter)
+    if isinstance(grid, tuple):
+        return grid, (None if bins else grid), None
     import torch
     dev = torch.device("cuda", device)
-    t = torch.from_numpy((values != 0).astype(np.int64)).to(dev)
+    t = torch.from_numpy(np.ascontiguousarray(grid.ravel(order="F")) if bins else values).to(dev)
     torch.cuda.synchronize(dev)
-    return (t.data_ptr(), dims), t
+    arg = (t.data_ptr(), dims, np.int64 if bins else np.float64)
+    return arg, (None if bins else arg), t
 
 
 def gaussian_taps(sigma):
@@ -1024,9 +1027,93 @@ def coalesce_ranked_host(lin, smoothed, values, dims, mat, maxdist, atol=0.1, ma
     return [(float(v), np.asarray(p, dtype=np.float64)) for v, p in ret]
 
 
-def cluster_closer_than(ret, mat, maxdist):
+def _map_scale(grid, counter):
+    """-> (grid as the library takes it, is bins, scale)"""
+    grid = _as_density(grid)
+    bins = _is_bins(grid, counter)
+    if bins and counter is None:
+        raise ValueError("integer bins need their counter")
+    if isinstance(grid, tuple):
+        grid = (grid[0], tuple(int(d) for d in grid[1]), np.int64 if bins else np.float64)
+    return grid, bins, (1.0 / float(counter)) if bins else 1.0
+
+
+def grid_coalesce(lin, smoothed, grid, mat, maxdist, atol=0.1, maxbasins=math.inf, *, counter=None, nranked=None, voxels_per_launch=0,
+                  device=0, stream=None, out_ptrs=None, capacity=None):
+    """``ceg_grid_coalesce``: the greedy pass of ``coalescing_basins`` on the device, the bytes of ``coalesce_ranked``.  ``lin`` /
+    ``smoothed``: the ranking as ``ranked_above`` returns it, or two device addresses with ``nranked``.  ``grid``: the unsmoothed map, FP64
+    or int64 bins with ``counter``, host array or ``(device_ptr, dims[, dtype])``; the kernel gathers the values itself.
+    ``voxels_per_launch``: the cut of the run into launches (0: the default); the result does not depend on it.
+    -> list of ``(value, centre)``; with ``out_ptrs = (value_ptr, centre_ptr)`` and ``capacity`` the basins go to device memory and the
+    full count is returned."""
+    lib = _abi.load_library()
+    grid, bins, scale = _map_scale(grid, counter)
+    gptr, g_dev, dims, dt, keep = _grid_arg(grid, (np.float64, np.int64))
+    if isinstance(lin, (int, np.integer)):
+        if nranked is None:
+            raise ValueError("a ranking in device memory needs nranked")
+        nr, lptr, sptr, r_dev = int(nranked), C.c_void_p(int(lin)), C.c_void_p(int(smoothed)), 1
+    else:
+        lin = np.ascontiguousarray(lin, dtype=np.int32)
+        sm = np.ascontiguousarray(smoothed, dtype=np.float64)
+        if len(lin) != len(sm):
+            raise ValueError("lin and smoothed differ in length")
+        nr, lptr, sptr, r_dev = len(lin), C.c_void_p(lin.ctypes.data), C.c_void_p(sm.ctypes.data), 0
+    m, mcol = _mat_arg(mat)
+    ortho, safemin = _periodic_setup(m)
+    count = C.c_int64(0)
+    if out_ptrs is None:
+        cap = max(nr, 1) if capacity is None else max(int(capacity), 0)
+        val, cen = np.empty(max(cap, 1), dtype=np.float64), np.empty((max(cap, 1), 3), dtype=np.float64)
+        vptr, cptr, o_dev = C.c_void_p(val.ctypes.data), C.c_void_p(cen.ctypes.data), 0
+    else:
+        if capacity is None:
+            raise ValueError("device outputs need their capacity")
+        cap, vptr, cptr, o_dev = max(int(capacity), 0), C.c_void_p(int(out_ptrs[0])), C.c_void_p(int(out_ptrs[1])), 1
+    _abi.check(lib, lib.ceg_grid_coalesce(device, lptr, sptr, r_dev, nr, gptr, int(dt == np.int64), g_dev, scale, _abi.i32ptr(_dims_arg(dims)),
+                                          _abi.dptr(mcol), int(ortho), safemin, float(maxdist), float(atol), float(maxbasins),
+                                          int(voxels_per_launch), vptr, cptr, o_dev, cap, C.byref(count), _stream(stream)))
+    if out_ptrs is not None:
+        return int(count.value)
+    return [(float(val[q]), cen[q].copy()) for q in range(min(int(count.value), cap))]
+
+
+class SitePartition(NamedTuple):
+    """``sums[s]``, ``centres[s]`` (NaN for a site without a voxel), ``cap_bound``, ``count`` (the active voxels) of ``site_partition``;
+    ``sums`` and ``centres`` are ``None`` where they went to device memory"""
+    sums: np.ndarray
+    centres: np.ndarray
+    cap_bound: bool
+    count: int
+
+
+def site_partition(grid, sites, mat, *, counter=None, origin=0, device=0, stream=None, out_ptrs=None) -> SitePartition:
+    """``ceg_grid_site_partition``: stages 2 and 3 of ``closest_to_sites`` in one device call, for any number of sites: every non-zero
+    voxel of the map goes to its nearest site (``site_nearest`` with that ``origin``), and each site adds its voxels up in linear-index
+    order under the cap (``_accumulate_closest``).  ``sites`` are taken as they are (``closest_to_sites`` snaps them first).  ``grid``: FP64
+    or int64 bins with ``counter``, host array or ``(device_ptr, dims[, dtype])``.  ``out_ptrs = (sums_ptr, centres_ptr)``: device outputs."""
+    lib = _abi.load_library()
+    grid, bins, scale = _map_scale(grid, counter)
+    gptr, g_dev, dims, dt, keep = _grid_arg(grid, (np.float64, np.int64))
+    m, mcol = _mat_arg(mat)
+    ortho, safemin = _periodic_setup(m)
+    s = _sites_arg(sites)
+    cap_bound, count = C.c_int32(0), C.c_int64(0)
+    if out_ptrs is None:
+        sums, cen = np.empty(len(s), dtype=np.float64), np.empty((len(s), 3), dtype=np.float64)
+        sp, cp, o_dev = C.c_void_p(sums.ctypes.data), C.c_void_p(cen.ctypes.data), 0
+    else:
+        sums = cen = None
+        sp, cp, o_dev = C.c_void_p(int(out_ptrs[0])), C.c_void_p(int(out_ptrs[1])), 1
+    _abi.check(lib, lib.ceg_grid_site_partition(device, gptr, int(dt == np.int64), g_dev, scale, _abi.i32ptr(_dims_arg(dims)), _abi.dptr(mcol),
+                                                int(ortho), safemin, _abi.dptr(s.ravel()), len(s), int(origin), sp, cp, o_dev,
+                                                C.byref(cap_bound), C.byref(count), _stream(stream)))
+    return SitePartition(sums, cen, bool(cap_bound.value), int(count.value))
+
+
+def cluster_closer_than_host(ret, mat, maxdist):
     """``cluster_closer_than!`` (:613-642) on a list of ``(rho, pos)``: a later entry within ``maxdist`` of an earlier one is merged into
-    it (value-weighted centre, the offset applied) unless the two together exceed 1.  -> the new list.  Host arithmetic only."""
+    it (value-weighted centre, the offset applied) unless the two together exceed 1.  -> the new list.  Plain Python floats."""
     m, _ = _mat_arg(mat)
     ortho, safemin = _periodic_setup(m)
     ml = m.tolist()
@@ -1054,7 +1141,18 @@ def cluster_closer_than(ret, mat, maxdist):
     return [(r, np.asarray(p, dtype=np.float64)) for (r, p), dead in zip(ret, todelete) if not dead]
 
 
-cluster_closer_than_host = cluster_closer_than
+def cluster_closer_than(ret, mat, maxdist):
+    """``ceg_cluster_closer_than``: the same loop in the library's host code (no device needed), the same bits."""
+    lib = _abi.load_library()
+    m, mcol = _mat_arg(mat)
+    ortho, safemin = _periodic_setup(m)
+    n = len(ret)
+    rho = np.ascontiguousarray([r for r, _ in ret], dtype=np.float64).reshape(n)
+    pos = np.ascontiguousarray([p for _, p in ret], dtype=np.float64).reshape(n, 3)
+    count = C.c_int64(0)
+    _abi.check(lib, lib.ceg_cluster_closer_than(_abi.dptr(rho), _abi.dptr(pos.reshape(-1)), n, _abi.dptr(mcol), int(ortho), safemin, float(maxdist),
+                                                C.byref(count)))
+    return [(float(rho[q]), pos[q].copy()) for q in range(int(count.value))]
 
 
 def _accumulate_closest(values, dims, nsites, lin, site, off, deleted) -> ClosestSites:
@@ -1080,31 +1178,28 @@ def _accumulate_closest(values, dims, nsites, lin, site, off, deleted) -> Closes
 
 
 def _closest_to_sites(grid, sites, mat, counter, on_device, device=0, stream=None, prepared=None) -> ClosestSites:
-    """``prepared = (values, dims, mask)``: the map's values and the ``bins`` argument of ``site_nearest``, where a caller that runs
-    several rounds on one map has them already"""
-    if prepared is None:
-        values, dims = _density_values(grid, counter, device, stream)
-        if not on_device:
-            mask = None
-        elif isinstance(grid, tuple) and _is_bins(grid, counter):
-            mask = (grid[0], dims)                                               # the bins as they lie in device memory
-        else:
-            mask = (values != 0).astype(np.int64).reshape(dims, order="F")       # one call: uploaded by the library
-    else:
-        values, dims, mask = prepared
-    kept, deleted = snap_sites(sites, dims)
+    """``prepared``: what a caller that runs several rounds on one map has already -- ``(values, dims)`` for the host route, the map
+    as ``site_partition`` takes it (device-resident) and ``dims`` for the device route"""
     if on_device:
-        lin, site, off, _ = site_nearest(kept, dims, mat, bins=mask, origin=0, device=device, stream=stream, want_dist=False)
-    else:
-        lin, site, off, _ = site_nearest_host(kept, dims, mat, bins=(values != 0).reshape(dims, order="F"), origin=0, want_dist=False)
+        if prepared is None:
+            grid = _as_density(grid)
+            dims = tuple(int(d) for d in (grid[1] if isinstance(grid, tuple) else grid.shape))
+        else:
+            grid, dims = prepared
+        kept, deleted = snap_sites(sites, dims)
+        part = site_partition(grid, kept, mat, counter=counter, origin=0, device=device, stream=stream)
+        return ClosestSites(part.sums, part.centres, np.asarray(deleted, dtype=np.int64), part.cap_bound)
+    values, dims = _density_values(grid, counter, device, stream) if prepared is None else prepared
+    kept, deleted = snap_sites(sites, dims)
+    lin, site, off, _ = site_nearest_host(kept, dims, mat, bins=(values != 0).reshape(dims, order="F"), origin=0, want_dist=False)
     return _accumulate_closest(values, dims, len(kept), lin, site, off, deleted)
 
 
 def closest_to_sites(grid, sites, mat, *, counter=None, device=0, stream=None) -> ClosestSites:
     """The partition of the non-zero voxels of a density map among ``sites`` (fractional, (n, 3)), device-backed: the sites are
-    snapped and deduplicated (``snap_sites``), every non-zero voxel gets its nearest kept site from ``ceg_grid_site_nearest`` with
-    ``origin = 0``, and the host adds the voxels up in linear-index order under the reference's cap (a voxel that would take its
-    site's sum above 1 is skipped, :430).  ``grid``: an FP64 map, or int64 bins with ``counter``; host array or ``(device_ptr, dims[,
+    snapped and deduplicated (``snap_sites``), every non-zero voxel gets its nearest kept site with ``origin = 0``, and each site adds its
+    voxels up in linear-index order under the reference's cap (a voxel that would take its site's sum above 1 is skipped, :430), all in
+    one ``ceg_grid_site_partition`` call, for any number of sites.  ``grid``: an FP64 map, or int64 bins with ``counter``; host array or ``(device_ptr, dims[,
     dtype])``.
 
     Where this differs from ``closest_to_sites`` of the reference as written (:324-437): the reference first gives each site the
@@ -1130,8 +1225,8 @@ updated_sites_with_closest_host = updated_sites_with_closest
 
 
 def _coalescing_basins(grid, maxdist, mat, counter, smooth, atol, crop, maxbasins, on_device, device=0, stream=None):
-    """-> (the list of ``(value, centre)``, the sum of the map).  The map is read back once; the refinement rounds share one mask in
-    device memory (the bins themselves where they are device-resident)."""
+    """-> (the list of ``(value, centre)``, the sum of the map).  The map is read back once, for its sum and its maximum; on the device
+    route the map, its smoothed form and the ranking stay in device memory from the smoothing to the last refinement round."""
     grid = _as_density(grid)
     values, dims = _density_values(grid, counter, device, stream)
     total = float(values.sum())
@@ -1139,47 +1234,57 @@ def _coalescing_basins(grid, maxdist, mat, counter, smooth, atol, crop, maxbasin
     vgrid = values.reshape(dims, order="F")
     _crop = atol * float(values.max()) / 100 if crop is None else float(crop)                  # :676
     taps = None if smooth == 0 else [gaussian_taps(s) for s in smoothing_sigmas(dims, mat, smooth)]
-    mask = keep = None
+    dmap = None
     if on_device:
-        if taps is None:
-            lin, smval = ranked_above(vgrid, _crop, device=device, stream=stream)
-        else:
-            import torch
-            dev = torch.device("cuda", device)
-            tmp = torch.empty(n, dtype=torch.float64, device=dev)
+        import torch
+        lib = _abi.load_library()
+        dev = torch.device("cuda", device)
+        dmap, dvalues, keep = _device_map(grid, counter, values, dims, device)
+        hold = [keep]
+        if taps is None and dvalues is None:                                                   # bins, unsmoothed: their FP64 values
+            hold.append(torch.from_numpy(values).to(dev))
+            dvalues = (hold[-1].data_ptr(), dims, np.float64)
+        if taps is not None:
+            hold.append(torch.empty(n, dtype=torch.float64, device=dev))
             torch.cuda.synchronize(dev)
-            bins = _is_bins(grid, counter)
-            smooth_grid(grid, taps, scale=(1.0 / float(counter)) if bins else 1.0, device=device, stream=stream, out_ptr=tmp.data_ptr())
-            lin, smval = ranked_above((tmp.data_ptr(), dims), _crop, device=device, stream=stream)
-            del tmp
-        ret = coalesce_ranked(lin, smval, values[lin], dims, mat, maxdist, atol, maxbasins)
-        if ret:
-            mask, keep = _device_mask(grid, counter, values, dims, device)
+            smooth_grid(dmap, taps, scale=(1.0 / float(counter)) if dmap[2] == np.int64 else 1.0, device=device, stream=stream,
+                        out_ptr=hold[-1].data_ptr())
+            dvalues = (hold[-1].data_ptr(), dims, np.float64)
+        t_lin = torch.empty(n, dtype=torch.int32, device=dev)
+        t_sm = torch.empty(n, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        count = C.c_int64(0)
+        _abi.check(lib, lib.ceg_grid_ranked(device, C.c_void_p(dvalues[0]), 1, _abi.i32ptr(_dims_arg(dims)), float(_crop), C.c_void_p(t_lin.data_ptr()),
+                                            C.c_void_p(t_sm.data_ptr()), 1, n, C.byref(count), _stream(stream)))
+        ret = grid_coalesce(t_lin.data_ptr(), t_sm.data_ptr(), dmap, mat, maxdist, atol, maxbasins, counter=counter, nranked=int(count.value),
+                            device=device, stream=stream)
+        del t_lin, t_sm
     else:
         smoothed = vgrid if taps is None else smooth_grid_host(vgrid, taps)
         lin, smval = ranked_above_host(smoothed, _crop)
         ret = coalesce_ranked_host(lin, smval, values[lin], dims, mat, maxdist, atol, maxbasins)
+    cluster = cluster_closer_than if on_device else cluster_closer_than_host
     n1 = -1
     while len(ret) != n1:                                                                      # :720-729
         n1 = len(ret)
         if not ret:
             break
         pts = np.asarray([p for _, p in ret], dtype=np.float64).reshape(-1, 3)
-        closest = _closest_to_sites(None, pts, mat, None, on_device, device, stream, prepared=(values, dims, mask))
+        closest = _closest_to_sites(None, pts, mat, counter, on_device, device, stream, prepared=(dmap, dims) if on_device else (values, dims))
         ret = updated_sites_with_closest(closest)
-        ret = cluster_closer_than(ret, mat, maxdist)
+        ret = cluster(ret, mat, maxdist)
         newret = [e for e in ret if e[0] >= atol]
         if not newret:
             break
         ret = newret
-    del keep
     return ret, total
 
 
 def coalescing_basins(grid, maxdist, mat, *, counter=None, smooth=None, atol=0.1, crop=None, maxbasins=math.inf, device=0, stream=None):
     """``coalescing_basins(grid, maxdist, mat; smooth, atol, crop, maxbasins)`` (:661-731) -> list of ``(value, centre)``.  Smoothing
     (``smooth=None``: the voxel diagonal; 0: none), ranking and the nearest-site partition of every refinement round run on the
-    device; the greedy pass runs in the library on the host; the cap, the centres and ``cluster_closer_than`` in Python.  ``grid``: an
+    device, and so do the greedy pass (``ceg_grid_coalesce``) and the sums and centres of a round (``ceg_grid_site_partition``);
+    ``cluster_closer_than`` runs in the library on the host.  ``grid``: an
     FP64 map or int64 bins with ``counter``, host array or ``(device_ptr, dims[, dtype])``.  ``closest_to_sites`` is this package's
     (see its docstring for where it departs from the reference as written)."""
     return _coalescing_basins(grid, maxdist, mat, counter, smooth, atol, crop, maxbasins, True, device, stream)[0]

@@ -1,6 +1,9 @@
-// ceg_coalesce.h -- the two pieces of the site extraction that are plain sequential FP64 and are shared by the host and the device:
+// ceg_coalesce.h -- the pieces of the site extraction that are plain sequential FP64 and are shared by the host and the device:
 //   ceg_pdwo            periodic_distance_with_ofs!, utils.jl:257-280, operation by operation
 //   ceg_coalesce_greedy the greedy pass of coalescing_basins, basins.jl:677-719, line by line
+//   ceg_nearer, ceg_coalesce_lone, ceg_coalesce_absorb   the order and the two updates of that pass as the nearest-basin rule the device
+//                       follows (ceg_grid_coalesce.hip); tests/native/cluster_sanitize.cpp holds them against the loop above
+//   ceg_cluster_closer_than_inplace   cluster_closer_than!, basins.jl:613-642, line by line (host)
 // No HIP in here: the file also compiles as ordinary C++ (tests/native/coalesce_sanitize.cpp does so under the sanitizers).
 #ifndef CEG_COALESCE_H
 #define CEG_COALESCE_H
@@ -66,6 +69,76 @@ struct CegBasin {
     double val;
     double c[3];
 };
+
+// As :695-699 are written the in-distance list keeps one entry, the nearest basin (isless on d, a NaN last, the lowest index among
+// equals), so the loop body has two updates; both are :700-708 in the reference's operation order, ofs held as double.
+// isless(d1, d2) with the index as the second key: the order of the stable sort of :696
+CEG_HD inline bool ceg_isless(double p, double q) { return p < q || (q != q && p == p); }
+
+CEG_HD inline bool ceg_nearer(double d1, int64_t i1, double d2, int64_t i2)
+{
+    return ceg_isless(d1, d2) || (!ceg_isless(d2, d1) && i1 < i2);
+}
+
+// nothing in range and smval < atol: (val, pos*val/val) -- not pos.  The caller skips val == 0 (:707)
+CEG_HD inline CegBasin ceg_coalesce_lone(double val, const double (&pos)[3])
+{
+    CegBasin o;
+    o.val = val;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) o.c[q] = pos[q] * val / val;
+    return o;
+}
+
+// one basin in range: it becomes (val + v2, (pos*val + (c + ofs)*v2) / (val + v2)); false, and nothing changed, where val + v2 == 0
+CEG_HD inline bool ceg_coalesce_absorb(CegBasin& o, double val, const double (&pos)[3], const double (&ofs)[3])
+{
+    const double newval = val + o.val;
+    if (newval == 0) return false;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        double nc = pos[q] * val;
+        nc += (o.c[q] + ofs[q]) * o.val;
+        o.c[q] = nc / newval;
+    }
+    o.val = newval;
+    return true;
+}
+
+// cluster_closer_than!, basins.jl:613-642, line by line, in place: rho[n], pos[n][3].  -> the number of entries kept, moved to the front
+inline int64_t ceg_cluster_closer_than_inplace(double* rho, double* pos, int64_t n, const double* mat, bool ortho, double safemin,
+                                               double maxdist)
+{
+    std::vector<char> todelete((size_t)n, 0);
+    for (int64_t i1 = 0; i1 < n; ++i1) {
+        if (todelete[(size_t)i1]) continue;                                                   // :619
+        double rho1 = rho[i1], pos1[3] = {pos[3 * i1], pos[3 * i1 + 1], pos[3 * i1 + 2]};
+        for (int64_t i2 = i1 + 1; i2 < n; ++i2) {
+            if (todelete[(size_t)i2]) continue;                                               // :622
+            const double rho2 = rho[i2];
+            const double* pos2 = pos + 3 * i2;
+            const double r = rho1 + rho2;
+            if (r > 1) continue;                                                              // :625
+            double buffer[3] = {pos1[0] - pos2[0], pos1[1] - pos2[1], pos1[2] - pos2[2]};
+            double ofs[3];
+            const double d = ceg_pdwo(mat, ortho, safemin, buffer, ofs);
+            if (d >= maxdist) continue;                                                       // :633
+            todelete[(size_t)i2] = 1;
+            for (int q = 0; q < 3; ++q) pos1[q] = (rho1 * pos1[q] + rho2 * (pos2[q] + ofs[q])) / r;      // :635
+            rho1 = r;
+            rho[i1] = rho1;                                                                   // :637
+            for (int q = 0; q < 3; ++q) pos[3 * i1 + q] = pos1[q];
+        }
+    }
+    int64_t kept = 0;
+    for (int64_t i = 0; i < n; ++i) {                                                         // :640
+        if (todelete[(size_t)i]) continue;
+        rho[kept] = rho[i];
+        for (int q = 0; q < 3; ++q) pos[3 * kept + q] = pos[3 * i + q];
+        ++kept;
+    }
+    return kept;
+}
 
 // basins.jl:677-719 over a ranking that is already cut at the crop (:679).  lin: 0-based linear indices; smoothed / values: the smoothed
 // and the unsmoothed grid at them.  -> the basins, in the order the reference's `ret` holds them when the loop ends

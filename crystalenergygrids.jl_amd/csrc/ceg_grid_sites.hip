@@ -8,8 +8,14 @@
 //                                                          (counts per 2048 points, exclusive scan, emit), then a stable radix sort
 //   closest_to_sites, phase 2              :400-422     ceg_grid_site_nearest: the active points compacted the same way, then a gather:
 //                                                          one thread per point, the sites in LDS, periodic_distance_with_ofs! per pair
-//   the greedy pass                        :677-719     ceg_coalesce_ranked: host only (ceg_coalesce.h)
-// An output element is one fixed sequence of FP64 operations whatever the tile it falls in; no float atomics, no scratch.
+//   closest_to_sites, phases 2 and 3       :400-434     ceg_grid_site_partition, any number of sites: the same compaction (on the map's
+//                                                          value), k_gs_nearest_tiled (the sites through LDS 2048 at a time, the best carried
+//                                                          along), a stable radix sort of (site, position), k_gs_site_runs (the bounds of each
+//                                                          site's run) and k_gs_site_sums: one thread per site walks its voxels in linear-index
+//                                                          order, because the cap (:430) makes every step depend on the one before
+//   the greedy pass                        :677-719     ceg_coalesce_ranked: host only (ceg_coalesce.h); on the device: ceg_grid_coalesce.hip
+// An output element is one fixed sequence of FP64 operations whatever the tile it falls in; no float atomics (one integer atomicOr
+// for the cap flag), no scratch.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -20,19 +26,14 @@
 
 #include "../../include/ceg_hip.h"
 #include "ceg_coalesce.h"
-
-extern "C" void ceg_set_last_error_(const char* msg);
+#include "ceg_grid_common.h"
 
 // distances and the scale are the reference's expressions, operation by operation; the taps are applied by explicit fma
 #pragma clang fp contract(off)
 
 namespace {
 
-int gerr(int code, const char* msg)
-{
-    ceg_set_last_error_(msg);
-    return code;
-}
+using namespace ceg_gs;
 
 constexpr int CHUNK = 2048;             // points of one workgroup of the compaction kernels (8 per thread)
 constexpr int SEG = 64, ROWS = 4;       // k_gs_smooth_row: points of a row segment, rows per workgroup
@@ -45,15 +46,6 @@ __device__ __forceinline__ int pmod(int x, int n)
 }
 
 // ---- smoothing --------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double gs_load(const double* p, int64_t x, double, int32_t*) { return p[x]; }
-
-__device__ __forceinline__ double gs_load(const int64_t* p, int64_t x, double scale, int32_t* bad)
-{
-    const int64_t v = p[x];
-    if (v >= (1ll << 53) || v <= -(1ll << 53)) *bad = 1;            // the same value from whoever sees one
-    return scale * (double)v;                                       // the conversion is exact: one rounding
-}
-
 template <typename TIN>
 __global__ __launch_bounds__(256) void k_gs_smooth_row(const TIN* __restrict__ in, double scale, const double* __restrict__ taps, int w,
                                                        int a, int64_t nrows, int ntx, double* __restrict__ out, int32_t* __restrict__ bad)
@@ -114,13 +106,16 @@ __global__ __launch_bounds__(256) void k_gs_smooth_axis(const double* __restrict
 }
 
 // ---- compaction in linear-index order ---------------------------------------------------------------------------------------------
-enum { SEL_ABOVE = 0, SEL_NONZERO = 1, SEL_ALL = 2 };
+// SEL_VALUE_F64 / SEL_VALUE_BINS: the map value != 0, an FP64 map or int64 bins times the scale, which travels in `crop`
+enum { SEL_ABOVE = 0, SEL_NONZERO = 1, SEL_ALL = 2, SEL_VALUE_F64 = 3, SEL_VALUE_BINS = 4 };
 
 template <int SEL>
 __device__ __forceinline__ bool gs_selected(const void* __restrict__ src, int64_t x, double crop)
 {
     if (SEL == SEL_ABOVE) return static_cast<const double*>(src)[x] > crop;      // a NaN is not above anything
     if (SEL == SEL_NONZERO) return static_cast<const int64_t*>(src)[x] != 0;
+    if (SEL == SEL_VALUE_F64) return static_cast<const double*>(src)[x] != 0;
+    if (SEL == SEL_VALUE_BINS) return crop * (double)static_cast<const int64_t*>(src)[x] != 0;
     return true;
 }
 
@@ -200,74 +195,98 @@ __global__ __launch_bounds__(256) void k_gs_nearest(NearGeom G, const double* __
     if (dist_out) dist_out[e] = bestd;
 }
 
-// ---- host side --------------------------------------------------------------------------------------------------------------------
-struct DevGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DevGuard(int d)
-    {
-        (void)hipGetDevice(&prev);
-        ok = hipSetDevice(d) == hipSuccess;
-    }
-    ~DevGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
+// ---- nearest site and site sums for any number of sites ---------------------------------------------------------------------------
+constexpr int SITE_TILE = 2048;          // sites of one pass through LDS (48 KiB)
 
-// stream-ordered workspace of one call: everything it handed out is freed behind the call's last launch
-struct Workspace {
-    hipStream_t st;
-    std::vector<void*> held;
-    bool failed = false;
-    bool staged = false;          // an input came from host memory: the call synchronises before it returns
-    explicit Workspace(hipStream_t s) : st(s) {}
-    ~Workspace()
-    {
-        for (void* p : held) (void)hipFreeAsync(p, st);
-    }
-    void* get(size_t bytes)
-    {
-        void* p = nullptr;
-        if (hipMallocAsync(&p, bytes ? bytes : 1, st) != hipSuccess) {
-            failed = true;
-            return nullptr;
+// k_gs_nearest with the sites streamed through LDS SITE_TILE at a time and the best carried along: ascending sites and a strict `<`, so
+// the result is the one all sites resident would give
+__global__ __launch_bounds__(256) void k_gs_nearest_tiled(NearGeom G, const double* __restrict__ sites, const int32_t* __restrict__ lin, int64_t nout,
+                                                          int32_t* __restrict__ site_out, int8_t* __restrict__ off_out)
+{
+    __shared__ double s_sites[3 * SITE_TILE];
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = e < nout;
+    const int x = live ? lin[e] : 0;
+    const int i = x % G.a, j = (x / G.a) % G.b, k = x / (G.a * G.b);
+    const double wx = (double)(i + G.origin) / (double)G.a;
+    const double wy = (double)(j + G.origin) / (double)G.b;
+    const double wz = (double)(k + G.origin) / (double)G.c;
+    int best = 0, bo0 = 0, bo1 = 0, bo2 = 0;
+    double bestd = INFINITY;
+    for (int s0 = 0; s0 < G.ns; s0 += SITE_TILE) {
+        const int cnt = G.ns - s0 < SITE_TILE ? G.ns - s0 : SITE_TILE;
+        __syncthreads();
+        for (int t = (int)threadIdx.x; t < 3 * cnt; t += 256) s_sites[t] = sites[3 * (int64_t)s0 + t];
+        __syncthreads();
+        if (!live) continue;
+        for (int s = 0; s < cnt; ++s) {
+            double buf[3] = {s_sites[3 * s] - wx, s_sites[3 * s + 1] - wy, s_sites[3 * s + 2] - wz};
+            int o[3];
+            const double d = ceg_pdwo(G.mat, G.ortho != 0, G.safemin, buf, o);
+            if (d < bestd) {
+                bestd = d;
+                best = s0 + s;
+                bo0 = o[0]; bo1 = o[1]; bo2 = o[2];
+            }
         }
-        held.push_back(p);
-        return p;
     }
-    const void* in(const void* src, int on_device, size_t bytes)
-    {
-        if (on_device) return src;
-        staged = true;
-        void* p = get(bytes);
-        if (p && bytes && hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess) failed = true;
-        return p;
-    }
-    void* out(void* dst, int on_device, size_t bytes) { return (on_device || !dst) ? dst : get(bytes); }
-    void back(void* dst, int on_device, const void* dev, size_t bytes)
-    {
-        if (dst && !on_device && bytes && hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, st) != hipSuccess) failed = true;
-    }
-};
-
-int check_dims(const int32_t* dims, int64_t* n)
-{
-    if (!dims || dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return gerr(CEG_ERR_INVALID, "dims must be three positive numbers");
-    const int64_t ab = (int64_t)dims[0] * dims[1];
-    if (ab > std::numeric_limits<int32_t>::max() || ab * dims[2] > std::numeric_limits<int32_t>::max())
-        return gerr(CEG_ERR_INVALID, "a*b*c does not fit int32");
-    *n = ab * dims[2];
-    return CEG_OK;
+    if (!live) return;
+    site_out[e] = best;
+    off_out[3 * e] = (int8_t)bo0;
+    off_out[3 * e + 1] = (int8_t)bo1;
+    off_out[3 * e + 2] = (int8_t)bo2;
 }
 
-int check_device(int32_t device)
+__global__ __launch_bounds__(256) void k_gs_iota(int32_t* __restrict__ out, int64_t n)
 {
-    if (ceg_device_count() <= 0) return gerr(CEG_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= ceg_device_count()) return gerr(CEG_ERR_NO_DEVICE, "device not present");
-    return CEG_OK;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < n) out[e] = (int32_t)e;
 }
 
+// keys sorted by site: first[s] .. last[s] is the run of site s (both stay 0 for a site without a voxel)
+__global__ __launch_bounds__(256) void k_gs_site_runs(const int32_t* __restrict__ key, int64_t n, int32_t* __restrict__ first, int32_t* __restrict__ last)
+{
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    const int s = key[q];
+    if (q == 0 || key[q - 1] != s) first[s] = (int32_t)q;
+    if (q == n - 1 || key[q + 1] != s) last[s] = (int32_t)(q + 1);
+}
+
+// stage 3 of closest_to_sites (:425-434) and the centres of updated_sites_with_closest (:454): one thread per site walks the site's
+// voxels in linear-index order, because the cap makes every step depend on the one before
+template <typename TMAP>
+__global__ __launch_bounds__(256) void k_gs_site_sums(const TMAP* __restrict__ map, double scale, int32_t a, int32_t b, int32_t c, int32_t ns,
+                                                      const int32_t* __restrict__ first, const int32_t* __restrict__ last,
+                                                      const int32_t* __restrict__ order, const int32_t* __restrict__ lin,
+                                                      const int8_t* __restrict__ off, double* __restrict__ sums, double* __restrict__ centres,
+                                                      int32_t* __restrict__ flags)
+{
+    const int s = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (s >= ns) return;
+    const int64_t dims[3] = {a, b, c};
+    double sum = 0.0, acc[3] = {0.0, 0.0, 0.0};
+    bool capped = false;
+    for (int q = first[s]; q < last[s]; ++q) {
+        const int e = order[q];
+        const int x = lin[e];
+        const double rho = gs_load(map, (int64_t)x, scale, flags + 1);      // flags[1]: a plain store of 1 by whoever sees a bad bin
+        if (sum + rho > 1) {                                                     // :430
+            capped = true;
+            continue;
+        }
+        sum = sum + rho;
+        const int64_t w[3] = {x % a, (x / a) % b, x / (a * b)};
+#pragma unroll
+        for (int r = 0; r < 3; ++r) acc[r] += (double)(w[r] + (int64_t)off[3 * (int64_t)e + r] * dims[r]) / (double)dims[r] * rho;
+    }
+    if (capped) atomicOr(flags, 1);                                              // flags[0]: the one integer atomic of the call
+    sums[s] = sum;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) centres[3 * (int64_t)s + r] = acc[r] / sum;       // 0/0 = NaN for a site without a voxel
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------------
 // counts per chunk of the selected points -> exclusive offsets and the total (synchronises the stream)
 template <int SEL>
 int select_offsets(Workspace& ws, const void* d_src, int64_t n, double crop, int64_t* nchunk, int32_t** d_off, int64_t* total)
@@ -466,6 +485,97 @@ extern "C" int ceg_grid_site_nearest(int32_t device, const int32_t dims[3], cons
     ws.back(dist_out, out_on_device, d_dist, sizeof(double) * (size_t)nout);
     if (hipGetLastError() != hipSuccess || ws.failed || hipStreamSynchronize(ws.st) != hipSuccess)      // `sites` was read from the host
         return gerr(CEG_ERR_HIP, "the nearest-site pass failed");
+    return CEG_OK;
+}
+
+static int check_sites(const double* sites, int64_t nsites)
+{
+    for (int64_t q = 0; q < 3 * nsites; ++q)
+        if (!(std::fabs(sites[q]) <= 64.0)) {
+            char msg[128];
+            std::snprintf(msg, sizeof msg, "site %lld: fractional coordinates must be finite with |x| <= 64", (long long)(q / 3));
+            return gerr(CEG_ERR_INVALID, msg);
+        }
+    return CEG_OK;
+}
+
+extern "C" int ceg_grid_site_partition(int32_t device, const void* map, int32_t map_is_int64, int32_t map_on_device, double scale,
+                                       const int32_t dims[3], const double mat[9], int32_t ortho, double safemin, const double* sites,
+                                       int32_t nsites, int32_t origin, double* sums_out, double* centres_out, int32_t out_on_device,
+                                       int32_t* cap_bound_out, int64_t* count_out, void* stream)
+{
+    int64_t n = 0;
+    if (!map || !mat || !sites || !sums_out || !centres_out || !cap_bound_out || !count_out || safemin != safemin)
+        return gerr(CEG_ERR_INVALID, "bad argument");
+    if (map_is_int64 && !std::isfinite(scale)) return gerr(CEG_ERR_INVALID, "scale must be a finite number");
+    if (origin != 0 && origin != 1) return gerr(CEG_ERR_INVALID, "origin is 0 or 1");
+    if (nsites < 1) return gerr(CEG_ERR_INVALID, "at least one site");
+    for (int q = 0; q < 9; ++q)
+        if (!std::isfinite(mat[q])) return gerr(CEG_ERR_INVALID, "mat must be finite");
+    if (int rc = check_sites(sites, nsites)) return rc;
+    if (int rc = check_dims(dims, &n)) return rc;
+    if (int rc = check_device(device)) return rc;
+    DevGuard guard(device);
+    if (!guard.ok) return gerr(CEG_ERR_HIP, "hipSetDevice failed");
+    Workspace ws((hipStream_t)stream);
+    const void* d_map = ws.in(map, map_on_device, 8 * (size_t)n);
+    const double* d_sites = (const double*)ws.in(sites, 0, sizeof(double) * 3 * (size_t)nsites);
+    int64_t nchunk = 0, total = 0;
+    int32_t* d_off = nullptr;
+    if (int rc = map_is_int64 ? select_offsets<SEL_VALUE_BINS>(ws, d_map, n, scale, &nchunk, &d_off, &total)
+                              : select_offsets<SEL_VALUE_F64>(ws, d_map, n, 0.0, &nchunk, &d_off, &total))
+        return rc;
+    *count_out = total;
+    const size_t m = (size_t)(total ? total : 1);
+    int32_t* d_lin = (int32_t*)ws.get(sizeof(int32_t) * m);
+    int32_t* d_site = (int32_t*)ws.get(sizeof(int32_t) * m);
+    int32_t* d_site2 = (int32_t*)ws.get(sizeof(int32_t) * m);
+    int32_t* d_ord = (int32_t*)ws.get(sizeof(int32_t) * m);
+    int32_t* d_ord2 = (int32_t*)ws.get(sizeof(int32_t) * m);
+    int8_t* d_ofs = (int8_t*)ws.get(3 * m);
+    int32_t* d_runs = (int32_t*)ws.get(sizeof(int32_t) * (2 * (size_t)nsites + 2));      // first[ns], last[ns], cap flag, bad-bin flag
+    int32_t* d_flags = d_runs ? d_runs + 2 * (size_t)nsites : nullptr;
+    double* d_sums = (double*)ws.out(sums_out, out_on_device, sizeof(double) * (size_t)nsites);
+    double* d_cen = (double*)ws.out(centres_out, out_on_device, sizeof(double) * 3 * (size_t)nsites);
+    int bits = 1;
+    while (bits < 31 && (1ll << bits) < (int64_t)nsites) ++bits;
+    size_t tmp_bytes = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_site, d_site2, d_ord, d_ord2, (int)total, 0, bits, ws.st);
+    void* d_tmp = ws.get(tmp_bytes);
+    if (ws.failed) return gerr(CEG_ERR_HIP, "could not allocate the device workspace / upload the inputs");
+    if (hipMemsetAsync(d_runs, 0, sizeof(int32_t) * (2 * (size_t)nsites + 2), ws.st) != hipSuccess) return gerr(CEG_ERR_HIP, "hipMemsetAsync failed");
+    if (total > 0) {
+        NearGeom G{};
+        for (int q = 0; q < 9; ++q) G.mat[q] = mat[q];
+        G.safemin = safemin;
+        G.a = dims[0]; G.b = dims[1]; G.c = dims[2]; G.ns = nsites; G.origin = origin; G.ortho = ortho ? 1 : 0;
+        const unsigned nb = (unsigned)((total + 255) / 256);
+        if (map_is_int64)
+            hipLaunchKernelGGL(k_gs_emit<SEL_VALUE_BINS>, dim3((unsigned)nchunk), dim3(256), 0, ws.st, d_map, n, scale, d_off, total, d_lin, (double*)nullptr);
+        else
+            hipLaunchKernelGGL(k_gs_emit<SEL_VALUE_F64>, dim3((unsigned)nchunk), dim3(256), 0, ws.st, d_map, n, 0.0, d_off, total, d_lin, (double*)nullptr);
+        hipLaunchKernelGGL(k_gs_nearest_tiled, dim3(nb), dim3(256), 0, ws.st, G, d_sites, d_lin, total, d_site, d_ofs);
+        hipLaunchKernelGGL(k_gs_iota, dim3(nb), dim3(256), 0, ws.st, d_ord, total);
+        // least-significant-digit radix sort: stable, so the voxels of a site keep their linear-index order
+        if (hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_site, d_site2, d_ord, d_ord2, (int)total, 0, bits, ws.st) != hipSuccess)
+            return gerr(CEG_ERR_HIP, "the radix sort failed");
+        hipLaunchKernelGGL(k_gs_site_runs, dim3(nb), dim3(256), 0, ws.st, d_site2, total, d_runs, d_runs + nsites);
+    }
+    const unsigned nbs = (unsigned)((nsites + 255) / 256);
+    if (map_is_int64)
+        hipLaunchKernelGGL(k_gs_site_sums<int64_t>, dim3(nbs), dim3(256), 0, ws.st, (const int64_t*)d_map, scale, dims[0], dims[1], dims[2], nsites, d_runs,
+                           d_runs + nsites, d_ord2, d_lin, d_ofs, d_sums, d_cen, d_flags);
+    else
+        hipLaunchKernelGGL(k_gs_site_sums<double>, dim3(nbs), dim3(256), 0, ws.st, (const double*)d_map, scale, dims[0], dims[1], dims[2], nsites, d_runs,
+                           d_runs + nsites, d_ord2, d_lin, d_ofs, d_sums, d_cen, d_flags);
+    int32_t flags[2] = {0, 0};
+    ws.back(sums_out, out_on_device, d_sums, sizeof(double) * (size_t)nsites);
+    ws.back(centres_out, out_on_device, d_cen, sizeof(double) * 3 * (size_t)nsites);
+    if (hipGetLastError() != hipSuccess || ws.failed || hipMemcpyAsync(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost, ws.st) != hipSuccess ||
+        hipStreamSynchronize(ws.st) != hipSuccess)                                   // `sites` was read from the host
+        return gerr(CEG_ERR_HIP, "the site partition failed");
+    if (flags[1]) return gerr(CEG_ERR_INVALID, "a bin with |value| >= 2^53: its conversion to FP64 would round (the output is not to be used)");
+    *cap_bound_out = flags[0] ? 1 : 0;
     return CEG_OK;
 }
 

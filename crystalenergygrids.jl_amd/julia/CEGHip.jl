@@ -1999,4 +1999,76 @@ function coalesce_ranked(idx::Vector{Int}, smoothed::Vector{Float64}, values::Ve
     [(val[q], SVector{3,Float64}(cen[1, q], cen[2, q], cen[3, q])) for q in 1:Int(count[1])]
 end
 
+"""
+    grid_coalesce(idx, smoothed, grid, mat, maxdist; scale=1.0, atol=0.1, maxbasins=Inf, voxels_per_launch=0, device=0)
+        -> Vector{Tuple{Float64,SVector{3,Float64}}}
+
+The greedy pass of `coalescing_basins` (src/basins.jl:677-719) on the device, the bytes of `coalesce_ranked`: `idx` and `smoothed` the
+1-based ranking of `ranked_above`, `grid` the unsmoothed map (`Float64`, or `Int64` bins times `scale`), whose values the kernel gathers
+itself.  The loop runs in launches of at most `voxels_per_launch` voxels (0: the default); the result does not depend on the cut.
+"""
+function grid_coalesce(idx::Vector{Int}, smoothed::Vector{Float64}, grid::Array{T,3}, mat::AbstractMatrix, maxdist::Real;
+                       scale::Float64=1.0, atol::Real=0.1, maxbasins::Real=Inf, voxels_per_launch::Integer=0,
+                       device=0) where {T<:Union{Int64,Float64}}
+    m = Vector{Float64}(vec(Matrix{Float64}(mat)))
+    _, ortho, safemin = CEG.prepare_periodic_distance_computations(mat)
+    lin = Int32.(idx .- 1)
+    d = _dims32(size(grid))
+    cap = max(length(lin), 1)
+    val = Vector{Float64}(undef, cap); cen = Matrix{Float64}(undef, 3, cap)
+    count = Int64[0]
+    GC.@preserve lin smoothed grid d m val cen count _check(ccall((:ceg_grid_coalesce, LIB[]), Cint,
+        (Int32, Ptr{Int32}, Ptr{Float64}, Int32, Int64, Ptr{Cvoid}, Int32, Int32, Float64, Ptr{Int32}, Ptr{Float64}, Int32, Float64, Float64,
+         Float64, Float64, Int64, Ptr{Float64}, Ptr{Float64}, Int32, Int64, Ptr{Int64}, Ptr{Cvoid}),
+        device, lin, smoothed, 0, length(lin), grid, T === Int64 ? 1 : 0, 0, scale, d, m, ortho ? 1 : 0, Float64(ustrip(safemin)),
+        Float64(maxdist), Float64(atol), Float64(maxbasins), voxels_per_launch, val, cen, 0, cap, count, C_NULL))
+    [(val[q], SVector{3,Float64}(cen[1, q], cen[2, q], cen[3, q])) for q in 1:Int(count[1])]
+end
+
+"""
+    site_partition(grid, sites, mat; scale=1.0, origin=0, device=0) -> (sums, centres, cap_bound, nactive)
+
+Stages 2 and 3 of `closest_to_sites` (src/basins.jl:400-434) and the centres of `updated_sites_with_closest` (:454) in one device call,
+for any number of sites: every non-zero voxel of `grid` (`Float64`, or `Int64` bins times `scale`) goes to its nearest site, and each
+site adds its voxels up in linear-index order, skipping a voxel that would take its sum above 1 (`cap_bound`).  `centres[s]` is NaN for
+a site without a voxel.
+"""
+function site_partition(grid::Array{T,3}, sites::AbstractVector, mat::AbstractMatrix; scale::Float64=1.0, origin::Integer=0,
+                        device=0) where {T<:Union{Int64,Float64}}
+    m = Vector{Float64}(vec(Matrix{Float64}(mat)))
+    _, ortho, safemin = CEG.prepare_periodic_distance_computations(mat)
+    flat = [Float64(x) for s in sites for x in s]
+    ns = length(flat) ÷ 3
+    d = _dims32(size(grid))
+    sums = Vector{Float64}(undef, ns); cen = Matrix{Float64}(undef, 3, ns)
+    cap = Int32[0]; count = Int64[0]
+    GC.@preserve grid d m flat sums cen cap count _check(ccall((:ceg_grid_site_partition, LIB[]), Cint,
+        (Int32, Ptr{Cvoid}, Int32, Int32, Float64, Ptr{Int32}, Ptr{Float64}, Int32, Float64, Ptr{Float64}, Int32, Int32, Ptr{Float64},
+         Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Cvoid}),
+        device, grid, T === Int64 ? 1 : 0, 0, scale, d, m, ortho ? 1 : 0, Float64(ustrip(safemin)), flat, ns, origin, sums, cen, 0, cap, count,
+        C_NULL))
+    sums, [SVector{3,Float64}(cen[1, q], cen[2, q], cen[3, q]) for q in 1:ns], cap[1] != 0, Int(count[1])
+end
+
+"""
+    cluster_closer_than(ret, mat, maxdist) -> Vector{Tuple{Float64,SVector{3,Float64}}}
+
+`cluster_closer_than!` (src/basins.jl:613-642) in the library's host code, line by line; returns the new list.
+"""
+function cluster_closer_than(ret::Vector{Tuple{Float64,SVector{3,Float64}}}, mat::AbstractMatrix, maxdist::Real)
+    m = Vector{Float64}(vec(Matrix{Float64}(mat)))
+    _, ortho, safemin = CEG.prepare_periodic_distance_computations(mat)
+    n = length(ret)
+    rho = Float64[r for (r, _) in ret]
+    pos = Matrix{Float64}(undef, 3, max(n, 1))
+    for (q, (_, p)) in enumerate(ret)
+        pos[:, q] .= p
+    end
+    count = Int64[0]
+    GC.@preserve rho pos m count _check(ccall((:ceg_cluster_closer_than, LIB[]), Cint,
+        (Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Int32, Float64, Float64, Ptr{Int64}),
+        rho, pos, n, m, ortho ? 1 : 0, Float64(ustrip(safemin)), Float64(maxdist), count))
+    [(rho[q], SVector{3,Float64}(pos[1, q], pos[2, q], pos[3, q])) for q in 1:Int(count[1])]
+end
+
 end # module

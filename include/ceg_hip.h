@@ -1731,6 +1731,55 @@ CEG_API int ceg_coalesce_ranked(const int32_t* lin, const double* smoothed, cons
                                 const double mat[9], int32_t ortho, double safemin, double maxdist, double atol, double maxbasins,
                                 double* value_out, double* centre_out, int64_t capacity, int64_t* count_out);
 
+/*
+ * The same path with the sequential loops in the library: the greedy pass on the device, stages 2 and 3 of closest_to_sites for any
+ * number of sites in one call, and cluster_closer_than! on the host.  Both device entry points synchronise `stream`.
+ *
+ * ceg_grid_coalesce: ceg_coalesce_ranked on the device -- the same bytes for any nranked, any number of basins and any cut into launches.
+ *  lin, smoothed   [nranked] as ceg_grid_ranked leaves them, both host or both device (ranked_on_device).
+ *  map         [a*b*c] the unsmoothed map, host or device: FP64 (map_is_int64 = 0, `scale` ignored) or int64 bins (val = fl(scale *
+ *              bin), one rounding; scale finite).  The kernel gathers val = map[lin[r]] itself.  A bin with |value| >= 2^53 at a voxel
+ *              the loop reaches -> CEG_ERR_INVALID.
+ *  ortho, safemin, maxdist, atol, maxbasins   as ceg_coalesce_ranked; a NaN among them or a non-finite mat is CEG_ERR_INVALID.
+ *  voxels_per_launch   the loop runs in one workgroup, in launches of at most this many ranked voxels, its state (basins, count, next
+ *              rank, stop flag) kept in device memory in between; 0: the default (32768).  The result does not depend on it.
+ *  value_out   [min(count, capacity)], centre_out [..][3], both host or both device (out_on_device); count_out: the full count (host).
+ *  An index outside the grid -> CEG_ERR_INVALID, found on the device at the voxel the loop reaches: the outputs are then not to be used.
+ *  As :695-699 are written at most one entry of the in-distance list survives -- the nearest basin with !(d > maxdist), isless on d,
+ *  the lowest index among equals -- so a voxel is absorbed by that basin, or founds one (smval >= atol, counted against maxbasins), or
+ *  is pushed alone as (val, pos*val/val) (smval < atol, val != 0, not counted), or is skipped.  Every voxel is compared with every
+ *  basin: periodic_distance_with_ofs! in a triclinic cell is a first-improvement search, not a metric a cell index could reproduce.
+ *
+ * ceg_grid_site_partition: ceg_grid_site_nearest followed by stage 3 of closest_to_sites (:425-434) and the centres of
+ * updated_sites_with_closest (:454), for any nsites >= 1.
+ *  map         as above; a voxel is active iff its value != 0.
+ *  sites       [nsites][3] fractional, host memory, finite with |x| <= 64;  origin  0 or 1, as ceg_grid_site_nearest.
+ *  Every active voxel goes to its nearest site (strict <, ascending sites: the lowest index among equals).  Per site, over its voxels
+ *  in linear-index order:  if (sum + rho > 1) { cap_bound = 1; skip }  sum = sum + rho;  acc[q] += (double)(w[q] + ofs[q]*dims[q]) /
+ *  (double)dims[q] * rho  on the 0-based w = (i, j, k), no contraction.
+ *  sums_out    [nsites];  centres_out [nsites][3] = acc / sum, NaN for a site without a voxel;  both host or both device.
+ *  cap_bound_out   1 iff the cap skipped a voxel;  count_out  the number of active voxels.  Both host.
+ *  Cost: a site's voxels are walked by ONE thread, because the cap makes its sum sequential: with one site, or one that takes most of
+ *  the map, that walk is as long as the map has active voxels (307 k at 189^3), whatever the device.
+ *  Stages: compaction in linear-index order, the nearest site with the sites streamed through LDS 2048 at a time, a stable radix sort
+ *  of (site, position), the bounds of each site's run, one thread per site over its run.  Integer atomics only (the cap flag).
+ *
+ * ceg_cluster_closer_than: cluster_closer_than!, basins.jl:613-642, line by line on the host (no device needed), in place.
+ *  rho [n], pos [n][3]: the list; on return the first *count_out entries are the list after deleteat!(ret, todelete).
+ *  rho1 + rho2 > 1 is tested before the distance, d >= maxdist continues, pos1 = (rho1*pos1 + rho2*(pos2 + ofs)) / rho.
+ */
+CEG_API int ceg_grid_coalesce(int32_t device, const int32_t* lin, const double* smoothed, int32_t ranked_on_device, int64_t nranked,
+                              const void* map, int32_t map_is_int64, int32_t map_on_device, double scale, const int32_t dims[3],
+                              const double mat[9], int32_t ortho, double safemin, double maxdist, double atol, double maxbasins,
+                              int64_t voxels_per_launch, double* value_out, double* centre_out, int32_t out_on_device, int64_t capacity,
+                              int64_t* count_out, void* stream);
+CEG_API int ceg_grid_site_partition(int32_t device, const void* map, int32_t map_is_int64, int32_t map_on_device, double scale,
+                                    const int32_t dims[3], const double mat[9], int32_t ortho, double safemin, const double* sites,
+                                    int32_t nsites, int32_t origin, double* sums_out, double* centres_out, int32_t out_on_device,
+                                    int32_t* cap_bound_out, int64_t* count_out, void* stream);
+CEG_API int ceg_cluster_closer_than(double* rho, double* pos, int64_t n, const double mat[9], int32_t ortho, double safemin, double maxdist,
+                                    int64_t* count_out);
+
 #ifdef __cplusplus
 }
 #endif
